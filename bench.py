@@ -12,6 +12,7 @@ Inputs are resident in HBM when the timed region starts.
     python bench.py --gpus 1 --steps 5 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...          (no launcher: starts the same N rank processes itself, see _self_launch)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   (also writes the last timed step's outputs)
 
 Prints ONE JSON line on rank 0 (contract in the task statement): `value` is the
 whole-job images/s, `roofline` is the dominant kernel class (the ViT linear-layer
@@ -285,6 +286,32 @@ def ingest_leg(variant, n_images, device_index):
         shutil.rmtree(root, ignore_errors=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """Write ``arrays`` (name -> numpy array) as ``dirpath/<name>.npy``: floating arrays as float32, integer arrays as
+    float64 (exact for every index below 2**53).  If they would take more than ``limit_bytes`` in all, every array keeps
+    the same fixed, seeded sample of its leading-axis rows, written beside it as ``<name>_rows.npy``.  Returns what was
+    written: name -> shape."""
+    import numpy as np
+    conv = {n: a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64, copy=False)
+            for n, a in arrays.items()}
+    if sum(a.nbytes for a in conv.values()) > limit_bytes:
+        # the same fraction of every array's rows, counting the 8 bytes per kept row of its _rows file
+        frac = limit_bytes / sum(a.nbytes + 8 * a.shape[0] for a in conv.values() if a.ndim)
+        for n, a in list(conv.items()):
+            if a.ndim:
+                m = max(1, int(a.shape[0] * frac))
+                rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], m, replace=False))
+                conv[n] = np.ascontiguousarray(a[rows])
+                conv[n + "_rows"] = rows.astype(np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    for n, a in conv.items():
+        np.save(os.path.join(dirpath, n + ".npy"), a)
+    return {n: list(a.shape) for n, a in conv.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -316,7 +343,13 @@ def main():
     ap.add_argument("--search-queries", type=int, default=10000,
                     help="extra, untimed-by-the-headline measurement: a batch of this many queries against the local "
                          "gallery shard (BASELINE.json configs[3]); 0 disables it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned (its embeddings and the "
+                         "top-k scores, indices and counts of every query) as DIR/<name>.npy in float32 / float64, "
+                         "at most 64 MB in all: two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -375,19 +408,20 @@ def main():
     def step_async():
         emb = eng.embed(images)                 # [B, D] L2-normalised fp32
         q = ss.gather_queries(emb)              # [B*world, D]
-        return ss.search_async(q, args.k)       # first round enqueued; result() = certified, or re-done exactly
+        return emb, ss.search_async(q, args.k)  # first round enqueued; result() = certified, or re-done exactly
 
     def run_steps(n):
         """n steps back to back.  Every step's result is finalised (result(): the one host decision of a sharded
         search, whether any query needs the protocol's second round) -- but only after the NEXT step has been
-        enqueued, so the device does not idle while the host waits for that count (N = 1: nothing to wait for)."""
+        enqueued, so the device does not idle while the host waits for that count (N = 1: nothing to wait for).
+        Returns the last step's (embeddings, (scores, indices, counts)): what a caller of the step receives."""
         pend, out = None, None
         for _ in range(n):
             nxt = step_async()
             if pend is not None:
-                out = pend.result()
+                out = (pend[0], pend[1].result())
             pend = nxt
-        return pend.result() if pend is not None else out
+        return (pend[0], pend[1].result()) if pend is not None else out
 
     def fence():
         if world > 1:
@@ -411,6 +445,12 @@ def main():
     dt = time.perf_counter() - t0
     engine.prof_enable(False)
     prof = engine.prof_report()
+    last_outputs = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, copied to the host once the clock has stopped and before the untimed passes
+        emb, (scores, idx, counts) = out
+        last_outputs = {"embeddings": emb.cpu().numpy(), "topk_scores": scores.cpu().numpy(),
+                        "topk_indices": idx.cpu().numpy(), "topk_counts": counts.cpu().numpy()}
     # untimed pass with events around every kernel class: the per-class breakdown and the scan timing
     engine.prof_reset()
     engine.prof_enable(1)
@@ -658,6 +698,8 @@ def main():
                 res["ingest"] = {"error": repr(e)}
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, args.gallery, D, args.k, args.cpu_images, min(args.gallery, 250_000))
+        if last_outputs is not None:
+            res["dumped_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -127,3 +127,40 @@ def test_allgather_budget_field():
     assert not slow["meets_target"] and slow["allgather_budget_ms"] > 0          # compute fits, the exchange is what misses
     worse = bench.allgather_budget(18.38, 3.5, 0.1)
     assert worse["allgather_budget_ms"] < 0                                      # the compute alone misses the target
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: floating outputs land as float32, integer ones as float64 (indices stay exact); over the size limit
+    every array keeps the same fixed, seeded sample of its rows, written beside it as <name>_rows.npy."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(1)
+    arrays = {"embeddings": rng.standard_normal((64, 32), dtype=np.float32),
+              "topk_indices": rng.integers(0, 1 << 40, (64, 10)), "topk_counts": np.full(64, 10, np.int32)}
+    shapes = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert shapes == {"embeddings": [64, 32], "topk_indices": [64, 10], "topk_counts": [64]}
+    e = np.load(tmp_path / "full" / "embeddings.npy")
+    i = np.load(tmp_path / "full" / "topk_indices.npy")
+    assert e.dtype == np.float32 and np.array_equal(e, arrays["embeddings"])
+    assert i.dtype == np.float64 and np.array_equal(i.astype(np.int64), arrays["topk_indices"])
+    limit = 4096
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit_bytes=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["embeddings.npy", "embeddings_rows.npy", "topk_indices.npy", "topk_indices_rows.npy",
+                            "topk_counts.npy", "topk_counts_rows.npy"])
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= limit
+    for f in files:                                                              # the sample is the same every run
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    rows = np.load(tmp_path / "a" / "embeddings_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "embeddings.npy"), arrays["embeddings"][rows])
+
+
+def test_steps_must_be_at_least_one():
+    """--steps sets the number of timed steps (ms_per_step = their time / --steps): zero is refused before any device work."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr, p.stderr[-1500:]

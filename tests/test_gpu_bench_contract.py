@@ -38,12 +38,21 @@ def _check_contract(d, n):
     assert sq["sharded_ms"] > 0
 
 
-def test_bench_contract_one_gpu(dev):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL, cwd=ROOT, capture_output=True, text=True,
-                       timeout=600)
+def test_bench_contract_one_gpu(dev, tmp_path):
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + ["--dump-outputs", str(dump)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
     _check_contract(d, 1)
+    # --dump-outputs: the last timed step's embeddings and top-k, as float32 / float64 arrays
+    import numpy as np
+    emb = np.load(dump / "embeddings.npy")
+    s, i, cnt = (np.load(dump / f"topk_{n}.npy") for n in ("scores", "indices", "counts"))
+    assert emb.dtype == np.float32 and emb.shape[0] == 8 and np.allclose(np.linalg.norm(emb, axis=1), 1.0, atol=1e-3)
+    assert s.dtype == np.float32 and s.shape == (8, 10) and i.dtype == np.float64 and i.shape == (8, 10) and cnt.shape == (8,)
+    assert (cnt == 10).all() and (i >= 0).all() and (i < 60000).all() and (np.diff(s, axis=1) <= 0).all()
+    assert d["dumped_outputs"]["embeddings"] == list(emb.shape)
     assert d["ingest"]["ok"] and d["ingest"]["images"] == 24 and d["ingest"]["images_per_s"] > 0, d["ingest"]     # the reported ingest leg
     # the box-speed probes run right before the timed region (profiles/calibration_reference.json: the constants they are held against)
     c = d["calibration"]
