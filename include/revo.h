@@ -115,7 +115,12 @@ int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst,
  * come out in either order there and here.  tests/test_gpu_search.py therefore compares with the float64 oracle up to
  * swaps of ADJACENT results inside that band (`near_tie`) -- a tolerance of the checker's arithmetic, not of this
  * search -- and asserts that the k-th place of no query of the headline 1 M x 1024 gallery falls inside it; exact
- * duplicates (scores equal to the bit) are always returned index-ascending. */
+ * duplicates (scores equal to the bit) are always returned index-ascending.
+ * FILTERED (revo_search_set_filter): a search of a handle with a filter returns exactly what the same exhaustive scoring
+ * of the ALLOWED rows alone would -- the same scores, order, tie rule and threshold cut as an unfiltered search of a
+ * gallery holding just those rows, with indices of this gallery.  A disallowed row is never admitted by any scan, never
+ * counted towards an admission bound and never collected by the fallback; fewer than k allowed rows leave the tail of
+ * a result empty (score -inf, index -1), none at all gives counts 0. */
 int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
                          float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
                          void* stream);
@@ -147,6 +152,15 @@ int32_t revo_search_ksel(int32_t k);     /* candidates the scan keeps per query 
  * is set, revo_search_finish refuses cert = NULL after an estimating scan (status -2), and revo_topk_merge_packed with its
  * unc_* outputs plus revo_search_exact are mandatory parts of the search.  revo_search_topk ignores the setting. */
 int32_t revo_search_set_total_rows(revo_gallery* g, int64_t total_rows);
+/* Restrict the following searches of this handle (revo_search_topk, _candidates, _finish, _exact) to the rows whose
+ * bit is set: bit (r & 31) of word r >> 5.  `rows` must equal revo_gallery_size(g).  The bitmap (ceil(rows / 32)
+ * words, host or device memory) is copied into the handle on `stream`.  NULL clears the filter.
+ * The handle owns its copy (a host bitmap has been read when this returns; a device one is read on `stream`).  A search
+ * while the gallery's size differs from `rows` (rows appended after the filter was set) fails (status -2).  A filtered
+ * shard of a row-sharded search never scans against the estimate of revo_search_set_total_rows: pass the exchanged
+ * bounds (all_bounds) to revo_search_finish. */
+int32_t revo_search_set_filter(revo_gallery* g, const uint32_t* allow_bits, int64_t rows, int32_t src_on_device,
+                               void* stream);
 /* 1 if a two-phase search for the best k on shards that know the total row count scans against that estimate (then every
  * shard's list is already cut at the whole gallery's level and step 2's exchange may be skipped: pass all_bounds = NULL to
  * revo_search_finish on EVERY rank), 0 if not (k > 25: those scans run with the admission margin of revo_search_topk instead) */

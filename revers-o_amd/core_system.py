@@ -838,16 +838,21 @@ class SimpleReverso:
         return "\n".join(status_messages)
 
     # ---------------------------------------------------------------- search --
-    def search_similar(self, similarity_threshold=0.7, max_results=5):
+    def search_similar(self, similarity_threshold=0.7, max_results=5, query_filter=None):
         """core_system.py:650-717: first region embedding as the query, limit + score
-        threshold, results best first with the same text and thumbnail formatting."""
+        threshold, results best first with the same text and thumbnail formatting.  ``query_filter``: a Qdrant-style
+        payload filter (filters.Filter or its dict form) restricting the search to the points it selects."""
         if not self.region_embeddings:
             return "❌ No query embeddings available. Please detect/process an image first.", []
         if not self.vector_db or not self.current_database:
             return "❌ No database loaded. Please create or load a database first.", []
         query = self.region_embeddings[0]
         with self._lock:
-            hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold))
+            if query_filter is None:
+                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold))
+            else:
+                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold),
+                                             query_filter=query_filter)
         if not hits:
             return f"❌ No similar regions found above threshold {similarity_threshold}", []
         text = f"🎯 Found {len(hits)} similar regions:\n\n"

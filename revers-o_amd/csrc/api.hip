@@ -737,8 +737,11 @@ struct revo_gallery {
     char* xbuf = nullptr; revo::ExactWs xw{};
     int mode = 0;
     const uint32_t* seed_bounds = nullptr;   // experiment build only (revo_debug_seed_bounds): admission bounds from outside
+    // revo_search_set_filter: the handle's own copy of the allow-bitmap, zero-padded to whole 256-row tiles (filter_words
+    // words allocated); filter_rows = the gallery size it was set for, -1 = no filter
+    uint32_t* filter = nullptr; size_t filter_words = 0; int64_t filter_rows = -1;
     ~revo_gallery() {
-        (void)hipFree(gb); (void)hipFree(gf); (void)hipFree(qf); (void)hipFree(qb); (void)hipFree(part);
+        (void)hipFree(gb); (void)hipFree(gf); (void)hipFree(qf); (void)hipFree(qb); (void)hipFree(part); (void)hipFree(filter);
         (void)hipFree(tau0); (void)hipFree(marg); (void)hipFree(dropflag);
         (void)hipFree(stage);
         (void)hipFree(qstat); (void)hipFree(gstat); (void)hipFree(xbuf);
@@ -781,6 +784,60 @@ extern "C" int32_t revo_search_set_total_rows(revo_gallery* g, int64_t total_row
     g->total_rows = total_rows;
     return 0;
 }
+// the handle's copy of an allow-bitmap: dst[i] = src[i] for the `nsrc` words that hold rows, bits from row `rows` on cleared,
+// zero words up to `total` (whole 256-row tiles: the filtered scans read a wave's 64 bits of any tile they touch).  src may
+// be dst (a host bitmap is first copied into place).
+__global__ void filter_copy_kernel(uint32_t* dst, const uint32_t* src, long rows, long nsrc, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    uint32_t w = i < nsrc ? src[i] : 0u;
+    if (i == rows >> 5 && (rows & 31)) w &= (1u << (rows & 31)) - 1u;
+    dst[i] = w;
+}
+extern "C" int32_t revo_search_set_filter(revo_gallery* g, const uint32_t* allow_bits, int64_t rows, int32_t src_on_device,
+                                          void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_set_filter: null handle");
+    REVO_REQUIRE(rows >= 0, "search_set_filter: negative row count");
+    if (!allow_bits) { g->filter_rows = -1; return 0; }
+    REVO_REQUIRE(rows == g->size, "search_set_filter: rows must equal revo_gallery_size (the filter covers the whole gallery)");
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    const long nsrc = (long)((rows + 31) / 32);
+    const long total = (long)((rows + 255) / 256 * 8) > 8 ? (long)((rows + 255) / 256 * 8) : 8;
+    g->filter_rows = -1;                                  // (until the copy below has been enqueued)
+    if (g->filter_words < (size_t)total) {
+        REVO_HIP_CHECK(hipStreamSynchronize(st));         // an earlier search may still read the old copy
+        (void)hipFree(g->filter); g->filter = nullptr; g->filter_words = 0;
+        REVO_HIP_CHECK(hipMalloc((void**)&g->filter, (size_t)total * 4));
+        g->filter_words = (size_t)total;
+    }
+    const uint32_t* src = allow_bits;
+    if (!src_on_device) {
+        // the caller may free its host buffer on return: copy now
+        if (nsrc > 0) REVO_HIP_CHECK(hipMemcpyAsync(g->filter, allow_bits, (size_t)nsrc * 4, hipMemcpyHostToDevice, st));
+        src = g->filter;
+    }
+    hipLaunchKernelGGL(filter_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g->filter, src, (long)rows,
+                       nsrc, total);
+    REVO_HIP_CHECK(hipGetLastError());
+    if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));
+    g->filter_rows = rows;
+    return 0;
+    API_END
+}
+// the allow-bitmap the next search of this handle runs with (null: none) -- a filter set for another gallery size is an
+// error, never a silently unfiltered search
+static int search_filter(const revo_gallery* g, const uint32_t** out) {
+    *out = nullptr;
+    if (g->filter_rows < 0) return 0;
+    REVO_REQUIRE(g->filter_rows == g->size,
+                 "search: the filter was set for " + std::to_string(g->filter_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set it again after appending)");
+    *out = g->filter;
+    return 0;
+}
+
 extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     REVO_REQUIRE(g, "null handle");
     REVO_ON_DEVICE(g->device);
@@ -892,6 +949,8 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
     using namespace revo;
     const int D = g->D;
     const long N = g->size;
+    const uint32_t* allow = nullptr;
+    CHECK_RC(search_filter(g, &allow));
     if (g->q_cap < Q) {
         REVO_HIP_CHECK(hipStreamSynchronize(st));
         (void)hipFree(g->qf); (void)hipFree(g->qb); (void)hipFree(g->tau0); (void)hipFree(g->qstat); (void)hipFree(g->xbuf);
@@ -934,6 +993,9 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
     // the admission margin only pays where the certificate is expected to fail (see revo_search_topk) and only the
     // 256 x 256 scan has segments; it needs the fp32 rows (no certificate without them)
     margin = margin && g->keep_f32 && N >= SEARCH_SMALL_ROWS;
+    // (a filtered scan of more than 128 queries has no margin form: launch_topk_scan256; its uncertified queries take the
+    //  collect pass instead -- exact either way)
+    if (allow && Q > 128) margin = false;
     // query normalisation (+ rounding norms); the same kernel clears the certificate's counters and -- 256 x 256 scan -- the
     // score histograms (two memset launches fewer per search: a quarter of a one-query search is launches)
     auto prep = [&](uint32_t* hist, long hist_words) -> int {
@@ -998,7 +1060,9 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
             // starts from an ESTIMATE of the whole gallery's level, extrapolated from its own pre-pass scores
             // (topk_select_rows_kernel); an estimate, not a bound: the protocol's certificate and second round cover it.
             float est_z = 0.f;
-            if (bounds && !margin && g->total_rows > N) {
+            // (not under a filter: the estimate extrapolates from ALL of the whole gallery's rows, a filtered search needs the
+            //  level of the allowed ones -- the bound exchange decides instead)
+            if (bounds && !margin && g->total_rows > N && !allow) {
                 int j = 2 * ksel < 64 ? 2 * ksel : 64;
 #ifdef REVO_EXPERIMENTS
                 if (const char* e = getenv("REVO_EST_J")) j = atoi(e) > 0 ? atoi(e) : j;      // sweep of the estimate's rank (scripts/)
@@ -1007,7 +1071,7 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
                 g->cand_estimated = true;
             }
             CHECK_RC(launch_topk_select_rows(pre_scores, n_pre, (int)n_pre, Q, prelist, ksel, 0, tau_base, ksel, hist, NB,
-                                             topk_scan256_hist_shift(), st, tau_live, est_z));
+                                             topk_scan256_hist_shift(), st, tau_live, est_z, allow));
 #ifdef REVO_EXPERIMENTS
             if (g->seed_bounds) hipLaunchKernelGGL(seed_bounds_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, tau_live, g->seed_bounds, Q);
 #endif
@@ -1018,7 +1082,7 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
               CHECK_RC(launch_topk_scan256(g->qb + (size_t)pt.q0 * D, D, g->gb, D, pt.nq, N, D, n_pre, pt.splits,
                                            (uint64_t*)(wsb + pt.seg_off), (int*)(wsb + pt.cnt_off), tau_live + pt.q0,
                                            tau_base + pt.q0, hist + (size_t)pt.q0 * NB, ksel, st,
-                                           margin ? g->marg + pt.q0 : nullptr, margin ? g->dropflag + pt.q0 : nullptr));
+                                           margin ? g->marg + pt.q0 : nullptr, margin ? g->dropflag + pt.q0 : nullptr, allow));
               if (margin) g->segs[i] = SegSrc{(const uint64_t*)(wsb + pt.seg_off), (const int*)(wsb + pt.cnt_off), pt.splits, pt.q0, pt.nq};
           }
           if (margin) { g->nsegs = nparts; g->prelist = prelist; } }
@@ -1037,7 +1101,7 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
         CHECK_RC(prep(nullptr, 0));
         ScanArgs a{};
         a.Qb = g->qb; a.ldq = D; a.Gb = g->gb; a.ldg = D; a.Q = Q; a.N = N; a.D = D; a.ksel = ksel;
-        a.splits = splits; a.part = g->part;
+        a.splits = splits; a.part = g->part; a.allow = allow;
         { ProfScope ps("topk_scan", st); CHECK_RC(launch_topk_scan(a, st)); }
         { ProfScope ps("topk_reduce", st); CHECK_RC(launch_topk_reduce(g->part, Q, splits, ksel, st)); }
         g->cand = g->part; g->cand_stride = (long)splits * ksel;
@@ -1054,16 +1118,19 @@ static int search_fallback(revo_gallery* g, int max_entries, int k, int has_thr,
                            float* scores, long long* indices, int* counts, hipStream_t st) {
     using namespace revo;
     ProfScope ps("topk_exact", st);
+    const uint32_t* allow = nullptr;
+    CHECK_RC(search_filter(g, &allow));
     if (g->mode != 2) {
         Collect256Args ca{};
         ca.Qb = g->xw.qb_u; ca.ldq = g->xw.ldqb; ca.Gb = g->gb; ca.ldg = g->D; ca.N = g->size; ca.D = g->D;
         ca.n_q = g->xw.ctr; ca.lb = g->xw.unc_lb; ca.cnt = g->xw.col_cnt; ca.col = g->xw.col; ca.cap = EXACT_COL_CAP;
+        ca.allow = allow;
         CHECK_RC(launch_topk_collect256(ca, max_entries, st));
     }
     CHECK_RC(launch_topk_exact_finish(g->xw, max_entries, g->qf, g->D, g->gf, g->D, g->D, k, has_thr, thr, index_offset,
                                       g->mode == 2, out_compact, scores, indices, counts, st));
     return launch_topk_exact_bruteforce(g->xw, max_entries, g->qf, g->D, g->gf, g->D, g->size, g->D, k, has_thr, thr,
-                                        index_offset, out_compact, scores, indices, counts, st);
+                                        index_offset, out_compact, scores, indices, counts, st, allow);
 }
 
 // over-selection: the bf16 scan keeps ksel >= k + margin candidates, the fp32 re-score decides
@@ -1094,6 +1161,7 @@ extern "C" int32_t revo_search_topk(revo_gallery* g, const float* queries, int32
     REVO_REQUIRE(Q >= 0, "search: negative query count");
     REVO_REQUIRE(k >= 1 && k <= 50, "search: k must be in [1, 50]");
     if (Q == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     using namespace revo;
@@ -1133,6 +1201,7 @@ extern "C" int32_t revo_search_candidates(revo_gallery* g, const float* queries,
     const int ksel = search_ksel(k);
     REVO_REQUIRE(top_m >= 1 && top_m <= ksel, "search_candidates: top_m must be in [1, revo_search_ksel(k)]");
     if (Q == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     g->cand = nullptr; g->cand_Q = Q; g->cand_ksel = ksel;
@@ -1160,6 +1229,7 @@ extern "C" int32_t revo_search_finish(revo_gallery* g, int32_t Q, int32_t k, int
                  "search_finish: this shard scanned against an estimated admission level (revo_search_set_total_rows): cert must "
                  "be given and checked by revo_topk_merge_packed, with revo_search_exact as the second round");
     if (Q == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     using namespace revo;
@@ -1185,6 +1255,7 @@ extern "C" int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* 
     REVO_REQUIRE(k >= 1 && k <= 50 && n >= 0, "search_exact: bad k or entry count");
     REVO_REQUIRE(n <= g->cand_Q, "search_exact: more entries than queries in the last revo_search_candidates call");
     if (n == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     using namespace revo;

@@ -164,6 +164,7 @@ struct ScanArgs {
     int ksel;                     // candidates kept per query (32 or 64)
     int splits;                   // gallery splits (grid.y); part is [Q][splits][ksel]
     uint64_t* part;               // out: candidate keys, sorted best-first, 0 = empty
+    const uint32_t* allow;        // optional allow-bitmap (revo_search_set_filter; padded to whole 256-row tiles)
 };
 int topk_scan_workspace_splits(int Q, long N);
 int launch_topk_scan(const ScanArgs& a, hipStream_t st);
@@ -249,6 +250,7 @@ struct Collect256Args {
     int* cnt;                     // [entries] rows appended
     uint64_t* col;                // [entries][cap]
     int cap;
+    const uint32_t* allow;        // optional allow-bitmap (revo_search_set_filter; padded to whole 256-row tiles): rows whose bit is clear are skipped
 };
 int launch_topk_collect256(const Collect256Args& a, int max_queries, hipStream_t st);
 // Fallback passes over the entries ws.ctr[0] (device count; launches are sized for max_entries).
@@ -260,7 +262,9 @@ int launch_topk_exact_finish(const ExactWs& ws, int max_entries, const float* Qf
                              float* out_scores, long long* out_idx, int* out_counts, hipStream_t st);
 int launch_topk_exact_bruteforce(const ExactWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf,
                                  long N, int D, int k, int has_thr, float thr, long idx_offset, int out_compact,
-                                 float* out_scores, long long* out_idx, int* out_counts, hipStream_t st);
+                                 float* out_scores, long long* out_idx, int* out_counts, hipStream_t st,
+                                 const uint32_t* allow = nullptr);
+// (allow, optional: the allow-bitmap of a filtered search; the brute force skips rows whose bit is clear)
 // entries from an explicit list (the row-sharded search's second round): entry j = query q_idx[j], collect bound
 // need[j] - eps(query, this gallery); sets ws.ctr[0] = n
 int launch_topk_exact_prepare(const ExactWs& ws, const int* q_idx, const float* need, int n, const CertArgs& cert, int D,
@@ -287,7 +291,9 @@ unsigned long long* topk_scan256_stats();
 // the pre-pass bound (constant), hist [Q][buckets] zeroed and then seeded by launch_topk_select_rows
 int launch_topk_scan256(const bf16_t* Qb, long ldq, const bf16_t* Gb, long ldg, int Q, long N, int D, long n_begin,
                         int splits, uint64_t* seg, int* seg_cnt, uint32_t* tau_g, const uint32_t* tau_base, uint32_t* hist,
-                        int ksel, hipStream_t st, const float* marg = nullptr, int* dropflag = nullptr);
+                        int ksel, hipStream_t st, const float* marg = nullptr, int* dropflag = nullptr,
+                        const uint32_t* allow = nullptr);
+// allow (optional): the search's allow-bitmap, zero-padded to whole 256-row tiles; n_begin must then be a multiple of 256
 // marg / dropflag (optional, [Q]): admit every score >= max(pre-pass bound, bound - marg[q]) instead of >= bound, and flag
 // the queries whose segments a drain or a recomputed tile touched (CertArgs: the finish step's segment collect)
 // out[q][ksel] = best ksel distinct keys (sorted, best first) of prelist[q][ksel] and the query's segments;
@@ -299,7 +305,7 @@ int launch_topk_reduce_segs(const uint64_t* seg, const int* seg_cnt, int splits,
 // tau0[q] = the KSEL-th score; hist (optional): the kept scores are counted into the query's histogram
 int launch_topk_select_rows(const float* scores, long ld, int n, int Q, uint64_t* part, long part_row_stride, int slot,
                             uint32_t* tau0, int ksel, uint32_t* hist, int hist_buckets, int hist_shift, hipStream_t st,
-                            uint32_t* tau_copy = nullptr, float est_z = 0.f);
+                            uint32_t* tau_copy = nullptr, float est_z = 0.f, const uint32_t* allow = nullptr);
 // (est_z != 0: tau0[q] = max(KSEL-th best score, mean + est_z * sigma of the row's scores): an estimated admission level)
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);

@@ -38,8 +38,9 @@ __device__ __forceinline__ float list_insert(uint64_t* list, uint64_t cand, int 
 constexpr int SCAN_BM = 128, SCAN_BN = 128;
 constexpr int SCAN_GEMM_LDS = 2 * (SCAN_BM + SCAN_BN) * 128;
 
-template <int KSEL>
-__global__ __launch_bounds__(GEMM_THREADS) void topk_scan_kernel(ScanArgs p) {
+// FILTER: the scores of rows whose allow-bit is clear become -inf (never admitted), like the columns past the gallery's end
+template <int KSEL, bool FILTER>
+__device__ __forceinline__ void topk_scan_body(const ScanArgs& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MF = 2, NF = 8;   // wave tile 32 x 128
     uint64_t* lists = (uint64_t*)(smem + SCAN_GEMM_LDS);
@@ -80,6 +81,20 @@ __global__ __launch_bounds__(GEMM_THREADS) void topk_scan_kernel(ScanArgs p) {
         gemm_mainloop<SCAN_BM, SCAN_BN, MF, NF>(la, lb, smem, p.D, wave, lane, wave * 32, 0, acc);
 
         const int nvalid = (p.N - n0) < SCAN_BN ? (int)(p.N - n0) : SCAN_BN;
+        if constexpr (FILTER) {
+            // the tile's 128 allow-bits: four words (wave-uniform loads; the bitmap is padded to whole 256-row tiles)
+            uint32_t aw[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) aw[i] = p.allow[(n0 >> 5) + i];
+#pragma unroll
+            for (int n = 0; n < NF; ++n)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool off = !((aw[n >> 1] >> ((n & 1) * 16 + lq * 4 + j)) & 1u);
+#pragma unroll
+                    for (int m = 0; m < MF; ++m) acc[m][n][j] = off ? -INFINITY : acc[m][n][j];
+                }
+        }
 #pragma unroll
         for (int m = 0; m < MF; ++m) {
             float mx = -INFINITY;
@@ -118,6 +133,10 @@ __global__ __launch_bounds__(GEMM_THREADS) void topk_scan_kernel(ScanArgs p) {
         if (lane < KSEL) p.part[((long)q * p.splits + sp) * KSEL + lane] = mylists[rloc * KSEL + lane];
     }
 }
+template <int KSEL>
+__global__ __launch_bounds__(GEMM_THREADS) void topk_scan_kernel(ScanArgs p) { topk_scan_body<KSEL, false>(p); }
+template <int KSEL>
+__global__ __launch_bounds__(GEMM_THREADS) void topk_scan_filtered_kernel(ScanArgs p) { topk_scan_body<KSEL, true>(p); }
 
 // Splits chosen so that (query tiles x splits) fills the 256 CUs about once
 // or twice (one 96-128 KB workgroup per CU), while each split keeps enough
@@ -150,12 +169,22 @@ int launch_topk_scan(const ScanArgs& a, hipStream_t st) {
     dim3 grid((a.Q + SCAN_BM - 1) / SCAN_BM, a.splits), block(GEMM_THREADS);
     if (a.ksel == 32) {
         constexpr int LDS = SCAN_GEMM_LDS + SCAN_BM * 32 * 8;
-        REVO_FUNC_LDS(topk_scan_kernel<32>, LDS);
-        hipLaunchKernelGGL((topk_scan_kernel<32>), grid, block, LDS, st, a);
+        if (a.allow) {
+            REVO_FUNC_LDS(topk_scan_filtered_kernel<32>, LDS);
+            hipLaunchKernelGGL((topk_scan_filtered_kernel<32>), grid, block, LDS, st, a);
+        } else {
+            REVO_FUNC_LDS(topk_scan_kernel<32>, LDS);
+            hipLaunchKernelGGL((topk_scan_kernel<32>), grid, block, LDS, st, a);
+        }
     } else {
         constexpr int LDS = SCAN_GEMM_LDS + SCAN_BM * 64 * 8;
-        REVO_FUNC_LDS(topk_scan_kernel<64>, LDS);
-        hipLaunchKernelGGL((topk_scan_kernel<64>), grid, block, LDS, st, a);
+        if (a.allow) {
+            REVO_FUNC_LDS(topk_scan_filtered_kernel<64>, LDS);
+            hipLaunchKernelGGL((topk_scan_filtered_kernel<64>), grid, block, LDS, st, a);
+        } else {
+            REVO_FUNC_LDS(topk_scan_kernel<64>, LDS);
+            hipLaunchKernelGGL((topk_scan_kernel<64>), grid, block, LDS, st, a);
+        }
     }
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
@@ -445,13 +474,14 @@ __device__ __noinline__ void sel_flush(uint64_t& run, float& tau, int& cnt, cons
 constexpr int SEL_STRIP = 4096;     // columns per wave
 constexpr int SEL_MAXW = 16;        // waves per query: n <= 65536
 constexpr int SEL_NV = SEL_STRIP / 256;   // 16-byte loads per lane
-template <int KSEL>
-__global__ __launch_bounds__(SEL_MAXW * 64) void topk_select_rows_kernel(const float* __restrict__ scores, long lds_, int n,
-                                                                        int Q, uint64_t* __restrict__ part,
-                                                                        long part_row_stride, int slot,
-                                                                        uint32_t* __restrict__ tau0, uint32_t* __restrict__ hist,
-                                                                        int hist_buckets, int hist_shift,
-                                                                        uint32_t* __restrict__ tau_copy, float est_z) {
+// FILTER: columns whose allow-bit is clear read as -inf (column c = gallery row c): they are never kept, never counted in the
+// histogram or the moments, and a strip set with fewer than KSEL allowed columns leaves the bound at -inf
+template <int KSEL, bool FILTER>
+__device__ __forceinline__ void topk_select_rows_body(const float* __restrict__ scores, long lds_, int n, int Q,
+                                                      uint64_t* __restrict__ part, long part_row_stride, int slot,
+                                                      uint32_t* __restrict__ tau0, uint32_t* __restrict__ hist,
+                                                      int hist_buckets, int hist_shift, uint32_t* __restrict__ tau_copy,
+                                                      float est_z, const uint32_t* __restrict__ allow) {
     __shared__ uint64_t partial[SEL_MAXW][64];
     __shared__ float mom[SEL_MAXW][3];          // est_z != 0: per-wave count, sum, sum of squares of the strip's scores
     __shared__ uint64_t cand[SEL_MAXW][128];    // per wave: survivors of pass 2, compacted (up to two sorts' worth)
@@ -468,6 +498,12 @@ __global__ __launch_bounds__(SEL_MAXW * 64) void topk_select_rows_kernel(const f
         const int c = (i * 64 + lane) * 4;
         // n and the row stride are multiples of 4 (checked by the launcher): a 16-byte chunk is all in or all out
         v[i] = c < left ? *(const f32x4*)(row + c) : (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        if constexpr (FILTER) {
+            // (c0 + c is a multiple of 4: the chunk's four bits sit in one word)
+            const uint32_t bits = c < left ? allow[(c0 + c) >> 5] >> ((c0 + c) & 31) : 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] = ((bits >> e) & 1u) ? v[i][e] : -INFINITY;
+        }
     }
 #pragma unroll
     for (int i = 0; i < SEL_NV; ++i) mx = fmaxf(fmaxf(mx, fmaxf(v[i][0], v[i][1])), fmaxf(v[i][2], v[i][3]));
@@ -593,14 +629,36 @@ __global__ __launch_bounds__(SEL_MAXW * 64) void topk_select_rows_kernel(const f
         }
     }
 }
+#define SEL_ROWS_PARAMS                                                                                                     \
+    const float* __restrict__ scores, long lds_, int n, int Q, uint64_t* __restrict__ part, long part_row_stride, int slot, \
+        uint32_t* __restrict__ tau0, uint32_t* __restrict__ hist, int hist_buckets, int hist_shift,                          \
+        uint32_t* __restrict__ tau_copy, float est_z
+template <int KSEL>
+__global__ __launch_bounds__(SEL_MAXW * 64) void topk_select_rows_kernel(SEL_ROWS_PARAMS) {
+    topk_select_rows_body<KSEL, false>(scores, lds_, n, Q, part, part_row_stride, slot, tau0, hist, hist_buckets, hist_shift,
+                                       tau_copy, est_z, nullptr);
+}
+template <int KSEL>
+__global__ __launch_bounds__(SEL_MAXW * 64) void topk_select_rows_filtered_kernel(SEL_ROWS_PARAMS, const uint32_t* __restrict__ allow) {
+    topk_select_rows_body<KSEL, true>(scores, lds_, n, Q, part, part_row_stride, slot, tau0, hist, hist_buckets, hist_shift,
+                                      tau_copy, est_z, allow);
+}
+#undef SEL_ROWS_PARAMS
 int launch_topk_select_rows(const float* scores, long ld, int n, int Q, uint64_t* part, long part_row_stride, int slot,
                             uint32_t* tau0, int ksel, uint32_t* hist, int hist_buckets, int hist_shift, hipStream_t st,
-                            uint32_t* tau_copy, float est_z) {
+                            uint32_t* tau_copy, float est_z, const uint32_t* allow) {
     if (Q <= 0) return 0;
     REVO_REQUIRE(n >= 1 && n <= SEL_STRIP * SEL_MAXW, "search: the pre-pass selection takes at most 65536 columns");
     REVO_REQUIRE(n % 4 == 0 && ld % 4 == 0 && (((uintptr_t)scores) & 15) == 0, "search: pre-pass score rows must be 16-byte aligned");
     const int nw = (n + SEL_STRIP - 1) / SEL_STRIP;
-    if (ksel == 32)
+    if (allow) {
+        if (ksel == 32)
+            hipLaunchKernelGGL((topk_select_rows_filtered_kernel<32>), dim3(Q), dim3(nw * 64), 0, st, scores, ld, n, Q, part,
+                               part_row_stride, slot, tau0, hist, hist_buckets, hist_shift, tau_copy, est_z, allow);
+        else
+            hipLaunchKernelGGL((topk_select_rows_filtered_kernel<64>), dim3(Q), dim3(nw * 64), 0, st, scores, ld, n, Q, part,
+                               part_row_stride, slot, tau0, hist, hist_buckets, hist_shift, tau_copy, est_z, allow);
+    } else if (ksel == 32)
         hipLaunchKernelGGL((topk_select_rows_kernel<32>), dim3(Q), dim3(nw * 64), 0, st, scores, ld, n, Q, part,
                            part_row_stride, slot, tau0, hist, hist_buckets, hist_shift, tau_copy, est_z);
     else

@@ -110,9 +110,11 @@ int launch_topk_exact_finish(const ExactWs& ws, int max_entries, const float* Qf
 // each wave keeps its best 64 (score, row) keys sorted in one register per lane and inserts a row only if it beats
 // the 64th.  The slice's 16 lists meet in LDS; its best 64 go to slot s of the entry's (now useless) collect buffer.
 constexpr int BF_WAVES = 16;
-__global__ __launch_bounds__(BF_WAVES * 64) void topk_exact_bruteforce_kernel(ExactWs ws, const float* __restrict__ Qf,
-                                                                              long ldqf, const float* __restrict__ Gf,
-                                                                              long ldgf, long N, int D) {
+// FILTER: rows whose allow-bit is clear are skipped (the test is wave-uniform: one row per step of the insertion)
+template <bool FILTER>
+__device__ __forceinline__ void bruteforce_body(const ExactWs& ws, const float* __restrict__ Qf, long ldqf,
+                                                const float* __restrict__ Gf, long ldgf, long N, int D,
+                                                const uint32_t* __restrict__ allow) {
     __shared__ uint64_t partial[BF_WAVES][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int over = ws.ctr[1];
@@ -132,6 +134,7 @@ __global__ __launch_bounds__(BF_WAVES * 64) void topk_exact_bruteforce_kernel(Ex
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (r + u >= r1) break;                                        // wave-uniform
+            if constexpr (FILTER) { if (!((allow[(r + u) >> 5] >> ((r + u) & 31)) & 1u)) continue; }   // wave-uniform
             const uint64_t key = make_key(t[u], (uint32_t)(r + u));       // wave-uniform value
             const uint64_t worst = readlane_u64(run, 63);
             if (key <= worst) continue;
@@ -152,6 +155,17 @@ __global__ __launch_bounds__(BF_WAVES * 64) void topk_exact_bruteforce_kernel(Ex
     }
     __syncthreads();
     }
+}
+__global__ __launch_bounds__(BF_WAVES * 64) void topk_exact_bruteforce_kernel(ExactWs ws, const float* __restrict__ Qf,
+                                                                              long ldqf, const float* __restrict__ Gf,
+                                                                              long ldgf, long N, int D) {
+    bruteforce_body<false>(ws, Qf, ldqf, Gf, ldgf, N, D, nullptr);
+}
+__global__ __launch_bounds__(BF_WAVES * 64) void topk_exact_bruteforce_filtered_kernel(ExactWs ws, const float* __restrict__ Qf,
+                                                                                       long ldqf, const float* __restrict__ Gf,
+                                                                                       long ldgf, long N, int D,
+                                                                                       const uint32_t* __restrict__ allow) {
+    bruteforce_body<true>(ws, Qf, ldqf, Gf, ldgf, N, D, allow);
 }
 // one wave per overflowed entry: merge the slices' lists, write the results
 __global__ __launch_bounds__(256) void topk_exact_bruteforce_final_kernel(ExactWs ws, int k, int has_thr, float thr,
@@ -176,12 +190,17 @@ __global__ __launch_bounds__(256) void topk_exact_bruteforce_final_kernel(ExactW
 }
 int launch_topk_exact_bruteforce(const ExactWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf,
                                  long N, int D, int k, int has_thr, float thr, long idx_offset, int out_compact,
-                                 float* out_scores, long long* out_idx, int* out_counts, hipStream_t st) {
+                                 float* out_scores, long long* out_idx, int* out_counts, hipStream_t st,
+                                 const uint32_t* allow) {
     if (max_entries <= 0 || N <= 0) return 0;
     REVO_REQUIRE(Gf && k >= 1 && k <= 64 && N < (1ll << 32), "exact brute force: needs the fp32 master rows, 1 <= k <= 64, N < 2^32");
     const int ny = max_entries < 64 ? max_entries : 64;
-    hipLaunchKernelGGL(topk_exact_bruteforce_kernel, dim3(EXACT_L3_SLICES, (unsigned)ny), dim3(BF_WAVES * 64), 0, st,
-                       ws, Qf, ldqf, Gf, ldgf, N, D);
+    if (allow)
+        hipLaunchKernelGGL(topk_exact_bruteforce_filtered_kernel, dim3(EXACT_L3_SLICES, (unsigned)ny), dim3(BF_WAVES * 64), 0,
+                           st, ws, Qf, ldqf, Gf, ldgf, N, D, allow);
+    else
+        hipLaunchKernelGGL(topk_exact_bruteforce_kernel, dim3(EXACT_L3_SLICES, (unsigned)ny), dim3(BF_WAVES * 64), 0, st,
+                           ws, Qf, ldqf, Gf, ldgf, N, D);
     hipLaunchKernelGGL(topk_exact_bruteforce_final_kernel, dim3((unsigned)((ny + 3) / 4)), dim3(256), 0, st, ws, k,
                        has_thr, thr, idx_offset, out_compact, out_scores, out_idx, out_counts);
     REVO_HIP_CHECK(hipGetLastError());

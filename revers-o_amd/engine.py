@@ -8,6 +8,7 @@ the reference does at
 * ``core_system.py:596-622`` collection create + upsert     ->  :class:`Gallery`
 * ``core_system.py:650-664`` ``search_similar`` / ``vector_db.search``  ->  :meth:`Gallery.search`
 """
+import contextlib
 import ctypes as C
 import json
 import threading
@@ -234,11 +235,45 @@ class Gallery:
             _lib.check(self._lib.revo_gallery_read(self._h, start, n, _lib.ptr(out), 1), "revo_gallery_read")
         return out
 
-    def search(self, queries, k=5, score_threshold=None, index_offset=0):
+    def allow_bits(self, allow):
+        """The device allow-bitmap (int32 ``[ceil(len / 32)]``, bit ``r & 31`` of word ``r >> 5``) of ``allow``: a device
+        tensor, either ``torch.bool [len(self)]`` or that bitmap already packed."""
+        n = len(self)
+        _require_cuda(allow, "allow", self.device)
+        words = (n + 31) // 32
+        if allow.dtype == torch.bool:
+            if allow.dim() != 1 or allow.shape[0] != n:
+                raise ValueError(f"allow must be bool [{n}] (one entry per gallery row), got {tuple(allow.shape)}")
+            m = torch.zeros(words * 32, dtype=torch.int64, device=allow.device)
+            m[:n] = allow.to(torch.int64)
+            w = (m.view(words, 32) << torch.arange(32, device=allow.device, dtype=torch.int64)).sum(1)
+            return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+        if allow.dtype != torch.int32 or allow.dim() != 1 or allow.shape[0] != words:
+            raise ValueError(f"allow must be bool [{n}] or a packed int32 bitmap [{words}], got {allow.dtype} "
+                             f"{tuple(allow.shape)}")
+        return allow.contiguous()
+
+    @contextlib.contextmanager
+    def _filter(self, allow):
+        """Inside: the handle's searches see only the rows ``allow`` selects (revo_search_set_filter); the filter is
+        cleared again on the way out.  The caller holds the handle's lock."""
+        if allow is None:
+            yield
+            return
+        bits = self.allow_bits(allow)
+        _lib.check(self._lib.revo_search_set_filter(self._h, _lib.ptr(bits), len(self), 1, _lib.current_stream()),
+                   "revo_search_set_filter")
+        try:
+            yield
+        finally:
+            self._lib.revo_search_set_filter(self._h, None, 0, 0, None)
+
+    def search(self, queries, k=5, score_threshold=None, index_offset=0, allow=None):
         """queries: fp32 [Q, dim] device tensor.  Returns (scores [Q,k] fp32,
         indices [Q,k] int64, counts [Q] int32), best first, padded with -inf/-1
         past ``counts`` (the reference's ``limit`` / ``score_threshold`` semantics,
-        core_system.py:659-664)."""
+        core_system.py:659-664).  ``allow`` (device tensor, bool [len] or a packed int32 bitmap): search only those
+        rows -- exactly the result an unfiltered search of a gallery holding just the allowed rows would give."""
         _require_cuda(queries, "queries", self.device)
         q = queries.detach().to(torch.float32).contiguous()
         if q.dim() == 1:
@@ -249,7 +284,7 @@ class Gallery:
         scores = torch.empty((Q, k), dtype=torch.float32, device=q.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
         counts = torch.empty((Q,), dtype=torch.int32, device=q.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
             _lib.check(self._lib.revo_search_topk(
                 self._h, _lib.ptr(q), Q, int(k), int(score_threshold is not None),
                 float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
@@ -290,7 +325,7 @@ class Gallery:
         return {"scan256": bool(out[0]), "prepass_rows": int(out[1]), "slices": int(out[2]), "ksel": int(out[3])}
 
     # -- the same search in two phases (row-sharded gallery; see sharded.py and include/revo.h) --------------
-    def search_candidates(self, queries, k=5, top_m=8):
+    def search_candidates(self, queries, k=5, top_m=8, allow=None):
         """Phase 1: scan this shard, keep the candidates in the handle.  Returns int32 ``[Q, top_m]``: the bit
         patterns of the order-preserving uint32 scan scores of each query's best ``top_m`` candidates."""
         _require_cuda(queries, "queries", self.device)
@@ -300,12 +335,12 @@ class Gallery:
         if q.shape[1] != self.dim:
             raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
         bounds = torch.empty((q.shape[0], int(top_m)), dtype=torch.int32, device=q.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
             _lib.check(self._lib.revo_search_candidates(self._h, _lib.ptr(q), q.shape[0], int(k), int(top_m),
                                                         _lib.ptr(bounds), _lib.current_stream()), "revo_search_candidates")
         return bounds
 
-    def search_finish(self, n_queries, k, all_bounds=None, score_threshold=None, index_offset=0, out_packed=None):
+    def search_finish(self, n_queries, k, all_bounds=None, score_threshold=None, index_offset=0, out_packed=None, allow=None):
         """Phase 2: fp32 re-score of the candidates that can still be among the best of the whole gallery
         (``all_bounds``: int32 ``[parts, Q, top_m]``, the all-gathered phase-1 outputs; None = every candidate).
         Returns (scores, indices, counts); with ``out_packed`` (uint8 ``[packed_bytes(Q, k)]``) scores and indices
@@ -330,7 +365,7 @@ class Gallery:
             parts, top_m = int(all_bounds.shape[0]), int(all_bounds.shape[2])
             if all_bounds.dtype != torch.int32 or all_bounds.shape[1] != Q:
                 raise ValueError("all_bounds must be int32 [parts, Q, top_m]")
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
             _lib.check(self._lib.revo_search_finish(
                 self._h, Q, k, int(score_threshold is not None),
                 float(score_threshold if score_threshold is not None else 0.0), int(index_offset), _lib.ptr(all_bounds),
@@ -338,7 +373,7 @@ class Gallery:
                 "revo_search_finish")
         return scores, idx, counts
 
-    def search_exact(self, q_idx, need, k, index_offset=0, out_packed=None):
+    def search_exact(self, q_idx, need, k, index_offset=0, out_packed=None, allow=None):
         """Second round of a row-sharded search: exact local top-k of the queries ``q_idx`` (int32 ``[n]``, rows of the
         last :meth:`search_candidates` call) given ``need`` (fp32 ``[n]``: the score a row must reach to change the
         merged result).  Results in compact rows ``[n, k]``; with ``out_packed`` laid out for :func:`merge_topk_packed`."""
@@ -354,7 +389,7 @@ class Gallery:
             scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
             idx = torch.empty((n, k), dtype=torch.int64, device=self.device)
         counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
             _lib.check(self._lib.revo_search_exact(self._h, n, _lib.ptr(q_idx.contiguous()), _lib.ptr(need.contiguous()), k, 0,
                                                    0.0, int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts),
                                                    _lib.current_stream()), "revo_search_exact")
@@ -448,11 +483,11 @@ def embed(images, engine=None):
     return eng.embed(images)
 
 
-def search(queries, k=5, score_threshold=None, gallery=None):
+def search(queries, k=5, score_threshold=None, gallery=None, allow=None):
     gal = gallery or _default_gallery
     if gal is None:
         raise _lib.RevoError("search(): no gallery; create a Gallery and call set_default(gallery=...)")
-    return gal.search(queries, k=k, score_threshold=score_threshold)
+    return gal.search(queries, k=k, score_threshold=score_threshold, allow=allow)
 
 
 # ---- profiler ---------------------------------------------------------------

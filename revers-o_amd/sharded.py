@@ -74,16 +74,16 @@ class GalleryBackend:
     def packed_bytes(self, n_queries, k):
         return self._engine.packed_bytes(n_queries, k)
 
-    def search(self, queries, k, threshold):
-        return self.gallery.search(queries, k, threshold)
+    def search(self, queries, k, threshold, allow=None):
+        return self.gallery.search(queries, k, threshold, allow=allow)
 
-    def candidates(self, queries, k, top_m):
-        return self.gallery.search_candidates(queries, k, top_m)
+    def candidates(self, queries, k, top_m, allow=None):
+        return self.gallery.search_candidates(queries, k, top_m, allow=allow)
 
-    def finish(self, n_queries, k, all_bounds, index_offset):
+    def finish(self, n_queries, k, all_bounds, index_offset, allow=None):
         out = self._packed("finish", n_queries, k)
         # the threshold is applied after the merge (a per-element predicate: same result, one code path)
-        self.gallery.search_finish(n_queries, k, all_bounds, None, index_offset, out_packed=out)
+        self.gallery.search_finish(n_queries, k, all_bounds, None, index_offset, out_packed=out, allow=allow)
         return out
 
     def merge(self, packed_all, parts, n_queries, k, threshold, certify=False):
@@ -92,9 +92,9 @@ class GalleryBackend:
     def set_total_rows(self, total_rows):
         self.gallery.set_total_rows(total_rows)
 
-    def exact(self, q_idx, need, k, index_offset):
+    def exact(self, q_idx, need, k, index_offset, allow=None):
         out = self._packed("exact", int(q_idx.shape[0]), k)
-        self.gallery.search_exact(q_idx, need, k, index_offset, out_packed=out)
+        self.gallery.search_exact(q_idx, need, k, index_offset, out_packed=out, allow=allow)
         return out
 
 
@@ -258,11 +258,13 @@ class ShardedSearch:
         ksel = self.backend.ksel(k)
         return min(ksel, max(8, -(-min(64, 2 * ksel) // self.world)))
 
-    def search(self, queries, k, threshold=None):
-        """queries: identical [Q, D] on every rank.  Returns the global top-k triple on every rank."""
-        return self.search_async(queries, k, threshold).result()
+    def search(self, queries, k, threshold=None, allow=None):
+        """queries: identical [Q, D] on every rank.  Returns the global top-k triple on every rank.  ``allow``: this RANK'S
+        rows to search (device bool [local rows], or their packed int32 bitmap); None on every rank = all rows.  Either
+        every rank passes a mask or none does (the protocol's exchanges differ)."""
+        return self.search_async(queries, k, threshold, allow).result()
 
-    def search_async(self, queries, k, threshold=None):
+    def search_async(self, queries, k, threshold=None, allow=None):
         """The same search with its one host decision deferred: everything of the first round (scan, both exchanges,
         merge with the cross-shard certificate) is enqueued and a :class:`PendingSearch` comes back at once;
         ``result()`` waits for the count of uncertified queries and, only if there are any, runs the second round.
@@ -270,11 +272,15 @@ class ShardedSearch:
         waits for the host between searches (``search()`` = ``search_async().result()`` does, once per call).
         Every rank must issue the same calls in the same order (the collectives are matched by order).
         ``queries`` must stay unmodified until ``result()`` has returned: a pending search whose shard state has been
-        overwritten by a later one re-searches its uncertified rows from this tensor."""
+        overwritten by a later one re-searches its uncertified rows from this tensor (and ``allow``, with a filter).
+        A filtered search exchanges the shards' bounds instead of scanning against the estimate (that is the level of ALL
+        rows) and is not counted towards switching the estimate off."""
         Q = queries.shape[0]
         top_m = self.top_m(k)
+        fkw = {"allow": allow} if allow is not None else {}                      # (backends without filters: unchanged calls)
         if self.world == 1:
-            return PendingSearch(self, self.backend.search(queries, k, threshold), None, None, queries, k, threshold, 0)
+            return PendingSearch(self, self.backend.search(queries, k, threshold, **fkw), None, None, queries, k, threshold,
+                                 0, allow)
         if self._timing is not None:
             self._timed_searches += 1
         # The landing place this search will use may still belong to a search eight back that was never asked for its
@@ -286,17 +292,17 @@ class ShardedSearch:
             self._inflight[(self._gen + 1) % len(self._pinned)].result()
         self._gen += 1                                                           # the shard handle's candidates are this search's now
         gen = self._gen                                                          # (one value for the slot AND the PendingSearch)
-        mine = self.backend.candidates(queries, k, top_m)                        # [Q, top_m] int32
-        estimated = bool(self._estimating and self.backend.estimates(k))
+        mine = self.backend.candidates(queries, k, top_m, **fkw)                 # [Q, top_m] int32
+        estimated = bool(self._estimating and self.backend.estimates(k)) and allow is None
         if estimated:
             # the shard scanned against an estimate of the whole gallery's admission level and its finish step cuts its list
             # there: that is what exchange 1 would have told it, so the exchange is left out (measured: the fp32 re-score is
             # no dearer without it -- 0.075 against 0.081 ms at 10 000 queries on a 125 k-row shard)
-            packed = self.backend.finish(Q, k, None, self.offset)
+            packed = self.backend.finish(Q, k, None, self.offset, **fkw)
         else:
             allb = self._gather_buf("bounds", (self.world * Q, top_m), mine.dtype, mine.device)
             self._all_gather(allb, mine, "bounds")                               # exchange 1: admission scores
-            packed = self.backend.finish(Q, k, allb.view(self.world, Q, top_m), self.offset)
+            packed = self.backend.finish(Q, k, allb.view(self.world, Q, top_m), self.offset, **fkw)
         allp = self._gather_buf("packed", (self.world * packed.numel(),), torch.uint8, packed.device)
         self._all_gather(allp, packed, "packed")                                 # exchange 2: packed per-rank top-k
         scores, idx, counts, unc = self.backend.merge(allp, self.world, Q, k, threshold, certify=True)
@@ -309,17 +315,17 @@ class ShardedSearch:
             ev.record()
         else:
             host_n.copy_(unc[0].reshape(1))          # CPU backends (tests)
-        p = PendingSearch(self, (scores, idx, counts), unc, (host_n, ev), queries, k, threshold, gen)
+        p = PendingSearch(self, (scores, idx, counts), unc, (host_n, ev), queries, k, threshold, gen, allow)
         p._estimated = estimated
         self._inflight[slot] = p
         return p
 
-    def _second_round(self, res, unc, n, k, threshold):
+    def _second_round(self, res, unc, n, k, threshold, allow=None):
         """The uncertified queries (identical on every rank: same merged data), in one canonical order, exactly on every shard."""
         scores, idx, counts = res
         qs, order = torch.sort(unc[1][:n])
         need = unc[2][:n][order].contiguous()
-        packed2 = self.backend.exact(qs.contiguous(), need, k, self.offset)
+        packed2 = self.backend.exact(qs.contiguous(), need, k, self.offset, **({"allow": allow} if allow is not None else {}))
         allp2 = torch.empty((self.world * packed2.numel(),), dtype=torch.uint8, device=packed2.device)
         self._all_gather(allp2, packed2, "packed_second_round")                  # exchange 3 (rare)
         s2, i2, c2 = self.backend.merge(allp2, self.world, n, k, threshold)
@@ -333,9 +339,10 @@ class ShardedSearch:
 class PendingSearch:
     """A sharded search whose first round is enqueued (ShardedSearch.search_async)."""
 
-    def __init__(self, owner, res, unc, host, queries, k, threshold, gen):
+    def __init__(self, owner, res, unc, host, queries, k, threshold, gen, allow=None):
         self._owner, self._res, self._unc, self._host = owner, res, unc, host
         self._queries, self._k, self._thr, self._gen = queries, k, threshold, gen
+        self._allow = allow                         # the rank's filter of this search (None: all rows)
         self._note = True
         self._estimated = False                     # this search's scans started from the estimated admission level
         self._done = unc is None
@@ -360,7 +367,7 @@ class PendingSearch:
         if n > 0:
             if o._gen == self._gen:
                 o.second_rounds += 1
-                self._res = o._second_round(self._res, self._unc, n, self._k, self._thr)
+                self._res = o._second_round(self._res, self._unc, n, self._k, self._thr, self._allow)
             else:
                 # Another search has used the shard handle since (its candidates are gone).  Only the n uncertified queries
                 # are searched again -- a search of their own, in step on every rank (the list is the same everywhere),
@@ -374,7 +381,7 @@ class PendingSearch:
                 # cached by shape, and one shape per uncertified count would push the steady-state shapes out of the caches
                 nb = 1 << max(0, int(n) - 1).bit_length()
                 pad = torch.cat([rows, rows[-1:].expand(nb - n)]) if nb > n else rows
-                sub = o.search_async(self._queries[pad].contiguous(), self._k, self._thr)
+                sub = o.search_async(self._queries[pad].contiguous(), self._k, self._thr, self._allow)
                 sub._note = False                       # the rate of uncertified queries is counted once per query
                 s2, i2, c2 = sub.result()
                 scores[rows] = s2[:n]
@@ -452,16 +459,26 @@ class LocalShards:
         except Exception:
             pass
 
-    def search(self, queries, k, threshold=None):
+    def search(self, queries, k, threshold=None, allow=None):
+        """``allow`` (device bool [total rows], global row order): search only those rows.  Each shard gets its slice,
+        re-packed from the shard's row 0; a filtered search exchanges bounds instead of using the estimate (the estimate is
+        the level of ALL rows) and does not count towards switching the estimate off."""
         self._retell()
         P, Q = len(self.backends), queries.shape[0]
         ksel = self.backends[0].ksel(k)
         top_m = min(ksel, max(8, -(-min(64, 2 * ksel) // P)))
-        allb = torch.stack([b.candidates(queries, k, top_m) for b in self.backends])            # [P, Q, top_m]
-        estimated = bool(self.estimating and self.backends[0].estimates(k))
+        if allow is not None:
+            sizes = [nxt - off for off, nxt in zip(self.offsets, self.offsets[1:] + [int(allow.shape[0])])]
+            allows = [allow[off: off + n] for off, n in zip(self.offsets, sizes)]
+        else:
+            allows = [None] * P
+        allb = torch.stack([b.candidates(queries, k, top_m, **({"allow": a} if a is not None else {}))
+                            for b, a in zip(self.backends, allows)])                                # [P, Q, top_m]
+        estimated = bool(self.estimating and self.backends[0].estimates(k)) and allow is None
         if estimated:
             allb = None                                                                          # (see ShardedSearch.search_async)
-        allp = torch.cat([b.finish(Q, k, allb, off) for b, off in zip(self.backends, self.offsets)])
+        fkw = lambda a: {"allow": a} if a is not None else {}
+        allp = torch.cat([b.finish(Q, k, allb, off, **fkw(a)) for b, off, a in zip(self.backends, self.offsets, allows)])
         scores, idx, counts, unc = self.backends[0].merge(allp, P, Q, k, threshold, certify=True)
         n = int(unc[0].item())
         self.last_uncertified = n
@@ -470,7 +487,8 @@ class LocalShards:
         if n > 0:
             qs, order = torch.sort(unc[1][:n])
             need = unc[2][:n][order].contiguous()
-            allp2 = torch.cat([b.exact(qs.contiguous(), need, k, off) for b, off in zip(self.backends, self.offsets)])
+            allp2 = torch.cat([b.exact(qs.contiguous(), need, k, off, **fkw(a))
+                               for b, off, a in zip(self.backends, self.offsets, allows)])
             s2, i2, c2 = self.backends[0].merge(allp2, P, n, k, threshold)
             rows = qs.long()
             scores[rows] = s2

@@ -26,6 +26,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import filters as _filters
 from .engine import Gallery
 
 MANIFEST = "manifest.jsonl"
@@ -162,6 +163,8 @@ class GalleryStore:
         self._shards = 0
         self._files_pending = []     # source files whose rows were added since the last flush
         self.files_done = set()      # source files covered by the shards on disk
+        self._pindex = _filters.PayloadIndex()   # columnar payload index of query_filter, caught up lazily
+        self._filter_cache = None                # (filter key, len(store), device allow-bitmap) of the last filtered search
         if path:
             os.makedirs(path, exist_ok=True)
             open(os.path.join(path, ".lock"), "a").close()
@@ -199,11 +202,24 @@ class GalleryStore:
             self._files_pending.extend(files)
         self.complete = False
 
-    def search(self, query_vector, limit, score_threshold=None):
-        """One query, qdrant-style result list (core_system.py:659-664)."""
+    def filter_mask(self, query_filter):
+        """bool numpy [len(self)]: the points a Qdrant-style filter (filters.Filter or its dict form) selects."""
+        return self._pindex.sync(self.ids, self.payloads).evaluate(query_filter)
+
+    def _allow_bits(self, query_filter):
+        key = (_filters.filter_key(query_filter), len(self))
+        if self._filter_cache is None or self._filter_cache[0] != key:
+            bits = torch.from_numpy(_filters.pack_bits(self.filter_mask(query_filter))).to(self.gallery.device)
+            self._filter_cache = (key, bits)
+        return self._filter_cache[1]
+
+    def search(self, query_vector, limit, score_threshold=None, query_filter=None):
+        """One query, qdrant-style result list (core_system.py:659-664).  ``query_filter`` (Qdrant's ``Filter`` shape, see
+        filters.py, or its dict form): only points it selects are searched -- exactly, in the kernels, not by dropping hits."""
         q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(1, -1)
         dev = self.gallery.device
-        s, i, c = self.gallery.search(q.to(dev), k=int(limit), score_threshold=score_threshold)
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        s, i, c = self.gallery.search(q.to(dev), k=int(limit), score_threshold=score_threshold, allow=allow)
         n = int(c[0])
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
