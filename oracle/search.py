@@ -50,11 +50,15 @@ def rank_topk(scores_row, k, threshold=None):
     return order
 
 
-def search(gallery, queries, k, threshold=None, normalize=True, acc=np.float64):
+def search(gallery, queries, k, threshold=None, normalize=True, acc=np.float64, allow=None):
     """Brute-force cosine top-k.
 
     Returns (scores float32 [Q,k], indices int64 [Q,k], counts int32 [Q]) padded
     with -inf / -1 past ``counts`` — the layout of the build's ``search()``.
+
+    ``allow`` (bool [N], optional): rank only the rows whose entry is True (the
+    build's filtered search, ``revo_search_set_filter``).  Indices stay the whole
+    gallery's; a row that is not allowed is never scored.
     """
     g = normalize_rows(gallery) if normalize else np.asarray(gallery, dtype=np.float32)
     q = normalize_rows(queries) if normalize else np.asarray(queries, dtype=np.float32)
@@ -62,6 +66,14 @@ def search(gallery, queries, k, threshold=None, normalize=True, acc=np.float64):
     out_s = np.full((Q, k), -np.inf, dtype=np.float32)
     out_i = np.full((Q, k), -1, dtype=np.int64)
     out_c = np.zeros((Q,), dtype=np.int32)
+    if allow is None:
+        rows = np.arange(g.shape[0])
+    else:
+        allow = np.asarray(allow)
+        if allow.dtype != np.bool_ or allow.shape != (g.shape[0],):
+            raise ValueError(f"allow must be bool [{g.shape[0]}], got {allow.dtype} {allow.shape}")
+        rows = np.flatnonzero(allow)                     # column c of the scores below is gallery row rows[c]
+        g = g[rows]
     if g.shape[0] == 0:
         return out_s, out_i, out_c
     # block over queries so a 1M-row gallery does not materialise Q x N at once
@@ -78,12 +90,12 @@ def search(gallery, queries, k, threshold=None, normalize=True, acc=np.float64):
                 cand = np.nonzero(row >= kth)[0]
             else:
                 cand = np.arange(row.shape[0])
-            o = cand[np.lexsort((cand, -row[cand].astype(np.float64)))][:kk]
+            o = cand[np.lexsort((rows[cand], -row[cand].astype(np.float64)))][:kk]
             if threshold is not None:
                 o = o[row[o] >= np.float32(threshold)]
             c = o.shape[0]
             out_s[s + r, :c] = row[o]
-            out_i[s + r, :c] = o
+            out_i[s + r, :c] = rows[o]
             out_c[s + r] = c
     return out_s, out_i, out_c
 

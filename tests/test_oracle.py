@@ -139,6 +139,47 @@ def test_known_answer_search_cases():
     assert [r[0] for r in ref] == i0[0].tolist()
 
 
+def test_filtered_search_oracle_equals_search_of_the_allowed_rows():
+    """allow= ranks only the allowed rows, with the whole gallery's indices: the search of gal[allowed] mapped back."""
+    D, N = 64, 3000
+    rng = np.random.default_rng(7)
+    g = rng.standard_normal((N, D)).astype(np.float32)
+    g[1000:1090] = g[1000]                                     # a tie group the mask cuts through
+    q = rng.standard_normal((6, D)).astype(np.float32)
+    q[0] = g[1000]
+    q[1] = g[2999] * 2.0
+    masks = {"random": rng.random(N) < 0.3, "every_third": np.arange(N) % 3 == 0, "few": np.zeros(N, bool)}
+    masks["few"][[5, 1001, 2999]] = True                       # fewer allowed rows than k
+    for name, m in masks.items():
+        allowed = np.flatnonzero(m)
+        for k in (1, 10, 50):
+            for thr in (None, 0.1, 0.99):
+                s, i, c = osearch.search(g, q, k, thr, allow=m)
+                ws, wi, wc = osearch.search(g[allowed], q, k, thr)
+                assert np.array_equal(c, wc), (name, k, thr)
+                assert np.array_equal(i, np.where(wi >= 0, allowed[np.maximum(wi, 0)], -1)), (name, k, thr)
+                assert np.array_equal(s, ws), (name, k, thr)
+                assert m[i[i >= 0]].all()
+                if name == "few":
+                    assert np.all(c <= 3) and np.all(i[:, 3:] == -1) and np.all(np.isneginf(s[:, 3:]))
+    # the tie group: the first allowed members in index order, equal scores
+    s, i, c = osearch.search(g, q[:1], 10, allow=masks["every_third"])
+    assert i[0].tolist() == [r for r in range(1000, 1090) if r % 3 == 0][:10] and np.all(s[0] == s[0, 0])
+    # the threshold cuts the filtered list: only the scaled copy of row 2999 passes 0.99 for query 1
+    s, i, c = osearch.search(g, q, 10, 0.99, allow=masks["few"])
+    assert c[1] == 1 and i[1, 0] == 2999 and i[1, 1] == -1
+    # all-true is no mask; all-false ranks nothing
+    for k, thr in ((10, None), (10, 0.05), (50, None)):
+        for a, b in zip(osearch.search(g, q, k, thr, allow=np.ones(N, bool)), osearch.search(g, q, k, thr)):
+            assert np.array_equal(a, b)
+        s, i, c = osearch.search(g, q, k, thr, allow=np.zeros(N, bool))
+        assert np.all(c == 0) and np.all(i == -1) and np.all(np.isneginf(s))
+    with pytest.raises(ValueError):
+        osearch.search(g, q, 10, allow=np.ones(N - 1, bool))
+    with pytest.raises(ValueError):
+        osearch.search(g, q, 10, allow=np.ones(N, np.int32))
+
+
 def test_layernorm_and_softmax_known_answers():
     x = torch.full((2, 8), 3.0)
     w, b = torch.randn(8), torch.randn(8)
