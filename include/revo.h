@@ -120,7 +120,15 @@ int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst,
  * of the ALLOWED rows alone would -- the same scores, order, tie rule and threshold cut as an unfiltered search of a
  * gallery holding just those rows, with indices of this gallery.  A disallowed row is never admitted by any scan, never
  * counted towards an admission bound and never collected by the fallback; fewer than k allowed rows leave the tail of
- * a result empty (score -inf, index -1), none at all gives counts 0. */
+ * a result empty (score -inf, index -1), none at all gives counts 0.
+ * GROUPED (revo_search_groups): each row has a group id (int32 >= 0; -1 = in no group, never returned).  A group's key is
+ * its best row under the order above (fp32 score desc, row index asc), counting only rows the filter allows and that
+ * reach the threshold.  The result is the best `limit` groups in key order, each with its best `group_size` rows in the
+ * same order -- exactly what grouping an exhaustive fp32 scoring of the allowed rows gives: the same bits (every score
+ * from the one fma chain), ties and threshold cut as revo_search_topk.  A query's groups come from the certified top-50
+ * of revo_search_topk when that list decides them (it holds every allowed row at or above the threshold, or >= limit
+ * groups of which each of the first `limit` holds >= group_size of its rows: any row outside it ranks below all of
+ * them); otherwise from two fp32 passes over the gallery (best groups, then the chosen groups' best rows). */
 int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
                          float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
                          void* stream);
@@ -161,6 +169,20 @@ int32_t revo_search_set_total_rows(revo_gallery* g, int64_t total_rows);
  * bounds (all_bounds) to revo_search_finish. */
 int32_t revo_search_set_filter(revo_gallery* g, const uint32_t* allow_bits, int64_t rows, int32_t src_on_device,
                                void* stream);
+/* The group id of every row for the following grouped searches of this handle (GROUPED above): group_of_row[r] >= 0, or
+ * -1 for none; `rows` must equal revo_gallery_size(g).  Host or device memory, copied into the handle on `stream` (a host
+ * array has been read when this returns).  NULL clears them.  Lifecycle as revo_search_set_filter: a grouped search while
+ * the gallery's size differs from `rows` fails (status -2). */
+int32_t revo_search_set_groups(revo_gallery* g, const int32_t* group_of_row, int64_t rows, int32_t src_on_device,
+                               void* stream);
+/* The best `limit` groups of each query (1 <= limit <= 50, 1 <= group_size <= 50, limit * group_size <= 50), with the
+ * handle's filter and group ids; needs the fp32 master rows (keep_f32 = 1).  Device outputs: scores / indices
+ * [n_queries, limit, group_size] (row index + index_offset), hit_counts [n_queries, limit] (rows in each group's list),
+ * group_ids [n_queries, limit], group_counts [n_queries] (groups returned).  Padding: score -inf, index -1, hit count 0,
+ * group id -1.  No host round trip; revo_search_stats slot 5 counts the queries that took the fp32 passes. */
+int32_t revo_search_groups(revo_gallery* g, const float* queries, int32_t n_queries, int32_t limit, int32_t group_size,
+                           int32_t has_threshold, float threshold, int64_t index_offset, float* scores, int64_t* indices,
+                           int32_t* hit_counts, int32_t* group_ids, int32_t* group_counts, void* stream);
 /* 1 if a two-phase search for the best k on shards that know the total row count scans against that estimate (then every
  * shard's list is already cut at the whole gallery's level and step 2's exchange may be skipped: pass all_bounds = NULL to
  * revo_search_finish on EVERY rank), 0 if not (k > 25: those scans run with the admission margin of revo_search_topk instead) */
@@ -189,7 +211,8 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
 /* counters of the handle's last search, read after `stream` has drained (host array of 8): out8 = { queries the
  * certificate failed for (-1: the gallery has no fp32 rows), of those: brute-forced, queries the certificate was
  * evaluated for, rows the exact passes re-scored, of the failed queries: resolved from what the scan had kept (no second
- * pass over the gallery: searches with k > 25 scan with an admission margin for that), 0, 0, 0 } */
+ * pass over the gallery: searches with k > 25 scan with an admission margin for that), grouped search
+ * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), 0, 0 } */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */
@@ -260,8 +283,8 @@ int32_t revo_vit_read_residual(revo_vit* vit, int32_t batch, float* dst, void* s
  * output after its MLP residual, before proj (fp32 [batch, width]) */
 int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch, void* dst, void* stream);
 /* how the certificate treats the handle's searches: 0 = certificate + fallback (the product library's only behaviour),
- * 1 = every query takes the collecting pass, 2 = every query takes the brute-force pass (1 and 2: parity tests of the
- * fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
+ * 1 = every query takes the collecting pass, 2 = every query takes the brute-force pass -- and every query of a grouped
+ * search the grouped fp32 passes (1 and 2: parity tests of the fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
 int32_t revo_search_set_mode(revo_gallery* g, int32_t mode);
 /* phase groups of the persistent 256 x 256 GEMM (an experiment, measured in round 5 and not adopted): 0 / 1 = off (all
  * workgroups in step), 2..4 = that many groups, a workgroup of group g doing the first (g + 1) / groups of its first tile at the start and the

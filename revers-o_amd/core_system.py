@@ -838,17 +838,23 @@ class SimpleReverso:
         return "\n".join(status_messages)
 
     # ---------------------------------------------------------------- search --
-    def search_similar(self, similarity_threshold=0.7, max_results=5, query_filter=None):
+    def search_similar(self, similarity_threshold=0.7, max_results=5, query_filter=None, group_by=None):
         """core_system.py:650-717: first region embedding as the query, limit + score
         threshold, results best first with the same text and thumbnail formatting.  ``query_filter``: a Qdrant-style
-        payload filter (filters.Filter or its dict form) restricting the search to the points it selects."""
+        payload filter (filters.Filter or its dict form) restricting the search to the points it selects.  ``group_by``
+        (a payload key, e.g. ``"image_source"``): at most ``max_results`` distinct values of it, each by its best region
+        (a region-mode database holds several rows per image; without it one image can fill every place)."""
         if not self.region_embeddings:
             return "❌ No query embeddings available. Please detect/process an image first.", []
         if not self.vector_db or not self.current_database:
             return "❌ No database loaded. Please create or load a database first.", []
         query = self.region_embeddings[0]
         with self._lock:
-            if query_filter is None:
+            if group_by is not None:
+                res = self.vector_db.search_groups(query, group_by, limit=int(max_results),
+                                                   score_threshold=float(similarity_threshold), query_filter=query_filter)
+                hits = [grp.hits[0] for grp in res.groups]
+            elif query_filter is None:
                 hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold))
             else:
                 hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold),

@@ -740,8 +740,14 @@ struct revo_gallery {
     // revo_search_set_filter: the handle's own copy of the allow-bitmap, zero-padded to whole 256-row tiles (filter_words
     // words allocated); filter_rows = the gallery size it was set for, -1 = no filter
     uint32_t* filter = nullptr; size_t filter_words = 0; int64_t filter_rows = -1;
+    // revo_search_set_groups: the handle's copy of the rows' group ids (groups_cap rows allocated), set for groups_rows rows,
+    // -1 = none; the grouped search's workspace (grouped_q queries): top-GROUP_K1 scores | indices | counts | fallback
+    // queries | chosen groups
+    int32_t* groups = nullptr; int64_t groups_cap = 0, groups_rows = -1;
+    char* gbuf = nullptr; int grouped_q = 0;
     ~revo_gallery() {
         (void)hipFree(gb); (void)hipFree(gf); (void)hipFree(qf); (void)hipFree(qb); (void)hipFree(part); (void)hipFree(filter);
+        (void)hipFree(groups); (void)hipFree(gbuf);
         (void)hipFree(tau0); (void)hipFree(marg); (void)hipFree(dropflag);
         (void)hipFree(stage);
         (void)hipFree(qstat); (void)hipFree(gstat); (void)hipFree(xbuf);
@@ -836,6 +842,32 @@ static int search_filter(const revo_gallery* g, const uint32_t** out) {
                      std::to_string(g->size) + " (set it again after appending)");
     *out = g->filter;
     return 0;
+}
+
+extern "C" int32_t revo_search_set_groups(revo_gallery* g, const int32_t* group_of_row, int64_t rows, int32_t src_on_device,
+                                          void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_set_groups: null handle");
+    REVO_REQUIRE(rows >= 0, "search_set_groups: negative row count");
+    if (!group_of_row) { g->groups_rows = -1; return 0; }
+    REVO_REQUIRE(rows == g->size, "search_set_groups: rows must equal revo_gallery_size (one group id per gallery row)");
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    g->groups_rows = -1;                                  // (until the copy below has been enqueued)
+    if (g->groups_cap < rows || !g->groups) {
+        REVO_HIP_CHECK(hipStreamSynchronize(st));         // an earlier search may still read the old copy
+        (void)hipFree(g->groups); g->groups = nullptr; g->groups_cap = 0;
+        const int64_t cap = rows > 1 ? rows : 1;
+        REVO_HIP_CHECK(hipMalloc((void**)&g->groups, (size_t)cap * 4));
+        g->groups_cap = cap;
+    }
+    if (rows > 0)
+        REVO_HIP_CHECK(hipMemcpyAsync(g->groups, group_of_row, (size_t)rows * 4,
+                                      src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));   // the caller may free its host buffer on return
+    g->groups_rows = rows;
+    return 0;
+    API_END
 }
 
 extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
@@ -1268,6 +1300,58 @@ extern "C" int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* 
     API_END
 }
 
+// Grouped search (include/revo.h): the certified search at k = GROUP_K1 into the handle's workspace, the groups of each
+// query's list (certified, or an entry of the grouped fallback), the fallback's fp32 passes over the gallery.  Every launch
+// is sized for Q entries and reads the entry count from the device.
+extern "C" int32_t revo_search_groups(revo_gallery* g, const float* queries, int32_t Q, int32_t limit, int32_t group_size,
+                                      int32_t has_thr, float thr, int64_t index_offset, float* scores, int64_t* indices,
+                                      int32_t* hit_counts, int32_t* group_ids, int32_t* group_counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(Q >= 0, "search_groups: negative query count");
+    REVO_REQUIRE(limit >= 1 && limit <= 50 && group_size >= 1 && group_size <= 50 && limit * group_size <= 50,
+                 "search_groups: needs 1 <= limit, 1 <= group_size and limit * group_size <= 50");
+    REVO_REQUIRE(g, "search_groups: null handle");
+    REVO_REQUIRE(scores && indices && hit_counts && group_ids && group_counts && (queries || Q == 0), "search_groups: null argument");
+    REVO_REQUIRE(g->keep_f32, "search_groups: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    REVO_REQUIRE(g->groups_rows >= 0, "search_groups: no group ids set (revo_search_set_groups)");
+    REVO_REQUIRE(g->groups_rows == g->size,
+                 "search_groups: the group ids were set for " + std::to_string(g->groups_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set them again after appending)");
+    if (Q == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_i = up256((size_t)Q * GROUP_K1 * 4), o_c = o_i + up256((size_t)Q * GROUP_K1 * 8),
+                 o_q = o_c + up256((size_t)Q * 4), o_ch = o_q + up256((size_t)Q * 4), total = o_ch + (size_t)Q * 64 * 4;
+    if (g->grouped_q < Q) {
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        (void)hipFree(g->gbuf); g->gbuf = nullptr; g->grouped_q = 0;
+        REVO_HIP_CHECK(hipMalloc((void**)&g->gbuf, total));
+        g->grouped_q = Q;
+    }
+    float* s1 = (float*)g->gbuf;
+    long long* i1 = (long long*)(g->gbuf + o_i);
+    int* c1 = (int*)(g->gbuf + o_c);
+    CHECK_RC(revo_search_topk(g, queries, Q, GROUP_K1, has_thr, thr, 0, s1, (int64_t*)i1, c1, stream));
+    ProfScope ps("topk_groups", st);
+    GroupWs gw{};
+    gw.group_of_row = g->groups; gw.gq = (int*)(g->gbuf + o_q); gw.chosen = (int*)(g->gbuf + o_ch);
+    gw.has_thr = has_thr ? 1 : 0; gw.thr = thr;
+    GroupOut o{};
+    o.scores = scores; o.idx = (long long*)indices; o.hit_counts = hit_counts; o.group_ids = group_ids;
+    o.group_counts = group_counts; o.limit = limit; o.group_size = group_size; o.idx_offset = (long)index_offset;
+    // (an empty gallery: the search wrote empty lists and left the counters alone -- every query is certified)
+    if (g->size == 0) return launch_topk_group_select(s1, i1, c1, Q, g->xw, gw, 0, o, st);
+    REVO_REQUIRE(g->xbuf, "search_groups: no certificate workspace");
+    CHECK_RC(launch_topk_group_select(s1, i1, c1, Q, g->xw, gw, g->mode == 2, o, st));
+    const uint32_t* allow = nullptr;
+    CHECK_RC(search_filter(g, &allow));
+    return launch_topk_group_fallback(g->xw, gw, Q, g->qf, g->D, g->gf, g->D, g->size, g->D, allow, o, st);
+    API_END
+}
+
 #ifdef REVO_EXPERIMENTS   // librevo.so cannot be put into a non-exact mode
 extern "C" int32_t revo_search_set_mode(revo_gallery* g, int32_t mode) {
     REVO_REQUIRE(g && mode >= 0 && mode <= 3, "search_set_mode: mode must be 0..3");
@@ -1285,7 +1369,7 @@ extern "C" int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* strea
     int c[8];
     REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     REVO_HIP_CHECK(hipMemcpy(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost));
-    out4[0] = c[0] + c[4] + c[5]; out4[1] = c[1]; out4[2] = c[2]; out4[3] = c[3]; out8[4] = c[5];
+    out4[0] = c[0] + c[4] + c[5]; out4[1] = c[1]; out4[2] = c[2]; out4[3] = c[3]; out8[4] = c[5]; out8[5] = c[6];
     return 0;
     API_END
 }

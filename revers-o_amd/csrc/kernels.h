@@ -183,7 +183,8 @@ static_assert(EXACT_L3_SLICES * 64 == EXACT_COL_CAP, "the brute-force partial li
 struct ExactWs {
     int* ctr;            // [0] uncertified queries of this search, [1] of those: collect list overflowed -> brute force,
                          // [2] queries the certificate was evaluated for, [3] rows collected (all lists), [4] mode 3: failed
-                         // (counted only), [5] uncertified queries resolved from the scan's segments (numbered from the back)
+                         // (counted only), [5] uncertified queries resolved from the scan's segments (numbered from the back),
+                         // [6] grouped searches: queries sent to the grouped fallback (GroupWs)
     int* unc_q;          // [cap] query index of uncertified entry j (or the output row, see out_compact)
     float* unc_lb;       // [cap] bf16-score bound of entry j's collect pass
     bf16_t* qb_u;        // [cap][ldqb] its bf16 query row (compacted: the collect pass reads whole query tiles)
@@ -195,6 +196,29 @@ struct ExactWs {
     int cap;             // entries the arrays hold.  Entries the finish step fills from the scan's own segments (no gallery
                          // pass needed) are numbered from the BACK: cap - 1, cap - 2, ...; their count is ctr[5]
 };
+// ---- grouped search (revo_search_groups; topk_exact.hip).  The exact top-GROUP_K1 rows of the ungrouped search decide a
+// query's groups when they certify it (topk_group_select_kernel); other queries are entries of the grouped fallback:
+// pass A (bruteforce_body, group mode) finds the best groups over the whole gallery in fp32, pass B (group_size > 1) the
+// best rows of the chosen groups.  Entry count: ExactWs::ctr[6]; slice lists: ExactWs::col, as for the brute force.
+constexpr int GROUP_K1 = 50;
+struct GroupWs {
+    const int* group_of_row;   // [N] group of each row, -1 = none
+    int* gq;                   // [cap] query of fallback entry i
+    int* chosen;               // [cap][64] entry i's best groups after pass A, best first, -1 padded
+    int hits;                  // 0: pass A; group_size: pass B
+    int has_thr; float thr;
+};
+struct GroupOut {
+    float* scores; long long* idx;   // [Q][limit][group_size]
+    int* hit_counts; int* group_ids; // [Q][limit]
+    int* group_counts;               // [Q]
+    int limit, group_size;
+    long idx_offset;
+};
+int launch_topk_group_select(const float* s1, const long long* i1, const int* c1, int Q, const ExactWs& ws, const GroupWs& gw,
+                             int force_fallback, const GroupOut& o, hipStream_t st);
+int launch_topk_group_fallback(const ExactWs& ws, GroupWs gw, int max_entries, const float* Qf, long ldqf, const float* Gf,
+                               long ldgf, long N, int D, const uint32_t* allow, const GroupOut& o, hipStream_t st);
 // The scan's segments of one launch part (queries [q0, q0 + nq) of the search): every survivor the scan appended
 struct SegSrc { const uint64_t* seg; const int* cnt; int splits, q0, nq; };
 struct CertArgs {

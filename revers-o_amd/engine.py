@@ -291,13 +291,57 @@ class Gallery:
                 _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_topk")
         return scores, idx, counts
 
+    @contextlib.contextmanager
+    def _groups(self, groups):
+        """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.
+        The caller holds the handle's lock."""
+        n = len(self)
+        _require_cuda(groups, "groups", self.device)
+        if groups.dtype != torch.int32 or groups.dim() != 1 or groups.shape[0] != n:
+            raise ValueError(f"groups must be int32 [{n}] (one group id per gallery row, -1 = none), got {groups.dtype} "
+                             f"{tuple(groups.shape)}")
+        groups = groups.contiguous() if n else torch.full((1,), -1, dtype=torch.int32, device=self.device)   # (non-null)
+        _lib.check(self._lib.revo_search_set_groups(self._h, _lib.ptr(groups), n, 1, _lib.current_stream()),
+                   "revo_search_set_groups")
+        try:
+            yield
+        finally:
+            self._lib.revo_search_set_groups(self._h, None, 0, 0, None)
+
+    def search_groups(self, queries, groups, limit=5, group_size=1, score_threshold=None, index_offset=0, allow=None):
+        """The best ``limit`` groups of rows for each query (Qdrant's ``search_groups``; include/revo.h, GROUPED).
+        ``groups``: int32 ``[len]`` device tensor, the group of every row (-1 = none: never returned).  A group ranks by
+        its best row; each carries its best ``group_size`` rows (``limit * group_size <= 50``).  Exactly the grouping of an
+        exhaustive fp32 scoring of the rows ``allow`` selects (see :meth:`search`).  Returns (scores ``[Q, limit,
+        group_size]`` fp32, indices (same, int64), hit_counts ``[Q, limit]`` int32, group_ids ``[Q, limit]`` int32,
+        group_counts ``[Q]`` int32), padded with -inf / -1 / 0 / -1."""
+        _require_cuda(queries, "queries", self.device)
+        q = queries.detach().to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        Q, L, S = q.shape[0], int(limit), int(group_size)
+        scores = torch.empty((Q, L, S), dtype=torch.float32, device=q.device)
+        idx = torch.empty((Q, L, S), dtype=torch.int64, device=q.device)
+        hits = torch.empty((Q, L), dtype=torch.int32, device=q.device)
+        gids = torch.empty((Q, L), dtype=torch.int32, device=q.device)
+        ngroups = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        with self._lock, torch.cuda.device(self.device), self._filter(allow), self._groups(groups):
+            _lib.check(self._lib.revo_search_groups(
+                self._h, _lib.ptr(q), Q, L, S, int(score_threshold is not None),
+                float(score_threshold if score_threshold is not None else 0.0), int(index_offset), _lib.ptr(scores),
+                _lib.ptr(idx), _lib.ptr(hits), _lib.ptr(gids), _lib.ptr(ngroups), _lib.current_stream()),
+                "revo_search_groups")
+        return scores, idx, hits, gids, ngroups
 
     # -- the exactness certificate (include/revo.h, "EXACTNESS") ------------------------------------------
     MODES = {"certified": 0, "collect": 1, "bruteforce": 2, "uncertified": 3}
 
     def set_search_mode(self, mode="certified"):
         """``certified`` (default): every query's result is certified exact or re-done exactly; ``collect`` /
-        ``bruteforce``: every query takes that fallback (parity tests); ``uncertified``: certificate counted only."""
+        ``bruteforce``: every query takes that fallback (parity tests; ``bruteforce`` also sends every query of a grouped
+        search through the grouped fallback); ``uncertified``: certificate counted only."""
         if not self.experiments:
             raise _lib.RevoError("set_search_mode is a parity-test hook of librevo_exp.so: create the gallery with "
                                  "experiments=True (the product library's searches are always certified exact)")
@@ -310,7 +354,7 @@ class Gallery:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.revo_search_stats(self._h, out, _lib.current_stream()), "revo_search_stats")
         return {"uncertified": int(out[0]), "bruteforced": int(out[1]), "checked": int(out[2]), "collected_rows": int(out[3]),
-                "from_segments": int(out[4])}
+                "from_segments": int(out[4]), "grouped_fallback": int(out[5])}
 
     def set_total_rows(self, total_rows):
         """This handle holds ONE SHARD of a row-sharded gallery of ``total_rows`` rows (0: forget): its two-phase scans

@@ -165,8 +165,14 @@ class _KeyColumn:
         self.s = np.zeros(0, object)
         self.num = np.zeros(0, np.float64)
         self._dirty = False
+        self.has_list = False         # some point holds a list under this key (group_ids refuses it)
+        self.group_rows = []          # (point, value) of the points whose value is a str or an int (not a bool)
 
     def add(self, row, value):
+        if isinstance(value, (list, tuple)):
+            self.has_list = True
+        elif isinstance(value, str) or (isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))):
+            self.group_rows.append((row, value))
         for v in (value if isinstance(value, (list, tuple)) else (value,)):
             c = _cat(v)
             self._rows.append(row)
@@ -214,6 +220,28 @@ class PayloadIndex:
                     col.add(r, v)
         self.n = len(payloads)
         return self
+
+    def group_ids(self, key):
+        """Qdrant's ``group_by=key`` as dense ids: (int32 [n] group of every point, -1 = none; the list of values, id i
+        being values[i], in order of first appearance).  ``str`` and ``int`` values form groups (``"1"`` and ``1`` are
+        different groups); a missing key or any other scalar (bool, float, None, dict) gives -1.  A list value would put
+        a point into several groups, which the grouped search does not do: it raises ValueError."""
+        out = np.full(self.n, -1, np.int32)
+        values = []
+        col = self.cols.get(key)
+        if col is None:
+            return out, values
+        if col.has_list:
+            raise ValueError(f"group_by over a list-valued key is not supported ({key!r})")
+        ids = {}
+        for row, v in col.group_rows:
+            k = (type(v) is str, v if isinstance(v, str) else int(v))
+            g = ids.get(k)
+            if g is None:
+                g = ids[k] = len(values)
+                values.append(v if isinstance(v, str) else int(v))
+            out[row] = g
+        return out, values
 
     def _match(self, cond):
         out = np.zeros(self.n, bool)

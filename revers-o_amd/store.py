@@ -146,6 +146,19 @@ class ScoredPoint:
     payload: dict
 
 
+@dataclass
+class PointGroup:
+    """One group of a grouped search (Qdrant's ``PointGroup``): the payload value ``id`` and its best hits."""
+    id: object
+    hits: list
+
+
+@dataclass
+class GroupsResult:
+    """Qdrant's ``GroupsResult``: the groups best first."""
+    groups: list
+
+
 class GalleryStore:
     def __init__(self, dim, device=0, capacity=65536, collection="simple_reverso", path=None, _fresh=True, build_info=None):
         """``build_info``: what the vectors were made from and how (source folder, model, region mode, ...), written into
@@ -165,6 +178,7 @@ class GalleryStore:
         self.files_done = set()      # source files covered by the shards on disk
         self._pindex = _filters.PayloadIndex()   # columnar payload index of query_filter, caught up lazily
         self._filter_cache = None                # (filter key, len(store), device allow-bitmap) of the last filtered search
+        self._group_cache = None                 # ((group_by, len(store)), device group ids, values) of the last grouped search
         if path:
             os.makedirs(path, exist_ok=True)
             open(os.path.join(path, ".lock"), "a").close()
@@ -223,6 +237,30 @@ class GalleryStore:
         n = int(c[0])
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
+
+    def _group_ids(self, group_by):
+        key = (group_by, len(self))
+        if self._group_cache is None or self._group_cache[0] != key:
+            ids, values = self._pindex.sync(self.ids, self.payloads).group_ids(group_by)
+            self._group_cache = (key, torch.from_numpy(ids).to(self.gallery.device), values)
+        return self._group_cache[1], self._group_cache[2]
+
+    def search_groups(self, query_vector, group_by, limit, group_size=1, score_threshold=None, query_filter=None):
+        """One query, Qdrant's ``search_groups`` shape: the best ``limit`` values of payload key ``group_by``, each with its
+        best ``group_size`` hits (``limit * group_size <= 50``).  Points without a str / int value under the key are in no
+        group; a list value raises ValueError.  Exact, in the kernels (include/revo.h, GROUPED)."""
+        q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(1, -1)
+        dev = self.gallery.device
+        groups, values = self._group_ids(group_by)
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        s, i, hc, gid, gc = self.gallery.search_groups(q.to(dev), groups, limit=int(limit), group_size=int(group_size),
+                                                       score_threshold=score_threshold, allow=allow)
+        s, i, hc, gid = s[0].tolist(), i[0].tolist(), hc[0].tolist(), gid[0].tolist()
+        out = []
+        for r in range(int(gc[0])):
+            hits = [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[r][:hc[r]], i[r][:hc[r]])]
+            out.append(PointGroup(values[gid[r]], hits))
+        return GroupsResult(out)
 
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
