@@ -180,11 +180,19 @@ int launch_topk_reduce(uint64_t* part, int Q, int splits, int ksel, hipStream_t 
 constexpr int EXACT_COL_CAP = 2048;     // collected keys per uncertified query
 constexpr int EXACT_L3_SLICES = 32;     // gallery slices of the brute-force pass (their 64-key lists reuse the query's collect buffer)
 static_assert(EXACT_L3_SLICES * 64 == EXACT_COL_CAP, "the brute-force partial lists live in the collect buffer");
+// the slots of ExactWs::ctr
+enum ExactCtr : int {
+    CTR_UNCERTIFIED,     // uncertified queries of this search
+    CTR_BRUTEFORCE,      // of those: collect list overflowed -> brute force
+    CTR_CHECKED,         // queries the certificate was evaluated for
+    CTR_COLLECTED,       // rows collected (all lists)
+    CTR_MODE3_FAILED,    // mode 3: failed (counted only)
+    CTR_FROM_SEGS,       // uncertified queries resolved from the scan's segments (numbered from the back)
+    CTR_GROUPED,         // grouped searches: queries sent to the grouped fallback (GroupWs)
+    CTR_SLOTS
+};
 struct ExactWs {
-    int* ctr;            // [0] uncertified queries of this search, [1] of those: collect list overflowed -> brute force,
-                         // [2] queries the certificate was evaluated for, [3] rows collected (all lists), [4] mode 3: failed
-                         // (counted only), [5] uncertified queries resolved from the scan's segments (numbered from the back),
-                         // [6] grouped searches: queries sent to the grouped fallback (GroupWs)
+    int* ctr;            // [CTR_SLOTS] counters of the last search (ExactCtr)
     int* unc_q;          // [cap] query index of uncertified entry j (or the output row, see out_compact)
     float* unc_lb;       // [cap] bf16-score bound of entry j's collect pass
     bf16_t* qb_u;        // [cap][ldqb] its bf16 query row (compacted: the collect pass reads whole query tiles)
@@ -194,12 +202,12 @@ struct ExactWs {
     int* over_j;         // [cap] entries that overflowed
     int* orow;           // [cap] out_compact results: the output row of entry j (its place in the caller's list)
     int cap;             // entries the arrays hold.  Entries the finish step fills from the scan's own segments (no gallery
-                         // pass needed) are numbered from the BACK: cap - 1, cap - 2, ...; their count is ctr[5]
+                         // pass needed) are numbered from the BACK: cap - 1, cap - 2, ...; their count is ctr[CTR_FROM_SEGS]
 };
 // ---- grouped search (revo_search_groups; topk_exact.hip).  The exact top-GROUP_K1 rows of the ungrouped search decide a
 // query's groups when they certify it (topk_group_select_kernel); other queries are entries of the grouped fallback:
 // pass A (bruteforce_body, group mode) finds the best groups over the whole gallery in fp32, pass B (group_size > 1) the
-// best rows of the chosen groups.  Entry count: ExactWs::ctr[6]; slice lists: ExactWs::col, as for the brute force.
+// best rows of the chosen groups.  Entry count: ExactWs::ctr[CTR_GROUPED]; slice lists: ExactWs::col, as for the brute force.
 constexpr int GROUP_K1 = 50;
 struct GroupWs {
     const int* group_of_row;   // [N] group of each row, -1 = none
@@ -277,7 +285,7 @@ struct Collect256Args {
     const uint32_t* allow;        // optional allow-bitmap (revo_search_set_filter; padded to whole 256-row tiles): rows whose bit is clear are skipped
 };
 int launch_topk_collect256(const Collect256Args& a, int max_queries, hipStream_t st);
-// Fallback passes over the entries ws.ctr[0] (device count; launches are sized for max_entries).
+// Fallback passes over the entries ws.ctr[CTR_UNCERTIFIED] (device count; launches are sized for max_entries).
 // exact_finish: fp32 re-score of every collected row, exact top-k; entries whose list overflowed go to ws.over_j.
 // bruteforce: for those, the fp32 score of EVERY gallery row (same fma chain as the re-score), exact top-k.
 // out_compact = 0: results go to row unc_q[j] of the outputs; 1: to row j (unc_q then only names the query row in Qf).
@@ -290,12 +298,12 @@ int launch_topk_exact_bruteforce(const ExactWs& ws, int max_entries, const float
                                  const uint32_t* allow = nullptr);
 // (allow, optional: the allow-bitmap of a filtered search; the brute force skips rows whose bit is clear)
 // entries from an explicit list (the row-sharded search's second round): entry j = query q_idx[j], collect bound
-// need[j] - eps(query, this gallery); sets ws.ctr[0] = n
+// need[j] - eps(query, this gallery); sets ws.ctr[CTR_UNCERTIFIED] = n
 int launch_topk_exact_prepare(const ExactWs& ws, const int* q_idx, const float* need, int n, const CertArgs& cert, int D,
                               const uint64_t* cand, long cand_stride, int ksel, hipStream_t st);
 // (cand: the handle's candidate lists of the last scan, [Q][cand_stride], best first: with segments to draw from
 //  (cert.nsegs > 0) an entry whose bound they cover is filled from them and numbered from the back, ExactWs::cap;
-//  ws.ctr[0..7] must be zero when this runs)
+//  every ws.ctr slot must be zero when this runs)
 // bounds[q][0..top_m) = order-preserving u32 scores of the query's best top_m candidates (0 = none)
 int launch_topk_publish(const uint64_t* part, long part_stride, int Q, int top_m, uint32_t* bounds, hipStream_t st);
 // 256 x 256 tile scan (topk256.hip): survivors are appended to per-(query, slice) segments of 2 * ksel keys and

@@ -1,0 +1,717 @@
+// C ABI of the gallery handle and the search (include/revo.h): the handle's rows, filter, group ids and workspace, the
+// search pipeline with its exactness fallback, grouped search, the row-sharded protocol's entry points and the merges.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <memory>
+
+#include "../../include/revo.h"
+#include "api_internal.h"
+#include "kernels.h"
+
+// ------------------------------------------------------------ the gallery --
+namespace {
+// A device allocation owned by the handle, grown on demand and never shrunk.  Growing a buffer that holds an allocation
+// first waits for the stream (an earlier launch may still read it), then frees it.  After a failed allocation the
+// buffer is empty.
+template <class T = char> struct DeviceBuffer {
+    T* p = nullptr; size_t bytes = 0;
+    DeviceBuffer() = default; DeviceBuffer(const DeviceBuffer&) = delete; DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+    int grow(size_t need, hipStream_t st) {
+        if (bytes >= need) return 0;
+        if (p) REVO_HIP_CHECK(hipStreamSynchronize(st));
+        release();
+        REVO_HIP_CHECK(hipMalloc((void**)&p, need));
+        bytes = need;
+        return 0;
+    }
+  private:
+    void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
+};
+
+// Sub-arrays carved out of one buffer in order, each at the next multiple of 256 bytes (a null base: sizing only).
+struct Layout {
+    char* base = nullptr;
+    size_t size = 0;
+    template <class T> T* take(size_t count) {
+        size = (size + 255) / 256 * 256;
+        T* p = base ? (T*)(base + size) : nullptr;
+        size += count * sizeof(T);
+        return p;
+    }
+};
+// Runs carve(Layout&) once to size `buf`, grows it, and again to hand out the sub-arrays of the grown buffer.
+template <class F> int carve_buffer(DeviceBuffer<>& buf, hipStream_t st, F&& carve) {
+    Layout sizing; carve(sizing);
+    CHECK_RC(buf.grow(sizing.size, st));
+    Layout l{buf.p}; carve(l);
+    return 0;
+}
+}  // namespace
+
+struct revo_gallery {
+    int D = 0, device = 0, keep_f32 = 1;
+    int64_t capacity = 0, size = 0;
+    DeviceBuffer<bf16_t> gb;   // [capacity][D] normalised rows, scan copy
+    DeviceBuffer<float> gf;    // [capacity][D] normalised rows, fp32 master (re-score + persistence)
+    // per-call workspace, grown on demand: the per-query arrays (sized for q_cap queries; qstat, marg and dropflag
+    // below), the scan's workspace (part) and the staging rows of an append from the host
+    DeviceBuffer<float> qf; DeviceBuffer<bf16_t> qb; DeviceBuffer<uint32_t> tau0; int q_cap = 0;
+    DeviceBuffer<> part;
+    DeviceBuffer<float> stage;
+    // candidates of the last scan (inside `part`), consumed by the finish step
+    const uint64_t* cand = nullptr; long cand_stride = 0; int cand_Q = 0, cand_ksel = 0;
+    // the last scan ran with an admission margin: its segments can answer uncertified queries (CertArgs, kernels.h)
+    revo::SegSrc segs[2] = {}; int nsegs = 0; const uint64_t* prelist = nullptr;
+    DeviceBuffer<float> marg; DeviceBuffer<int> dropflag;
+    int64_t total_rows = 0;        // revo_search_set_total_rows: this handle is one shard of a gallery of that many rows (0: the whole)
+    bool cand_estimated = false;   // the last scan started from estimated admission scores (CertArgs::estimated)
+    // exactness certificate (kernels.h): per-query rounding norms of the last search's queries, running maxima over the
+    // gallery's rows, the fallback workspace (xbuf, sized with q_cap; its layout is xw) and the handle's mode
+    DeviceBuffer<float> qstat; DeviceBuffer<uint32_t> gstat;
+    DeviceBuffer<> xbuf; revo::ExactWs xw{};
+    int mode = 0;
+    const uint32_t* seed_bounds = nullptr;   // experiment build only (revo_debug_seed_bounds): admission bounds from outside
+    // revo_search_set_filter: the handle's own copy of the allow-bitmap, zero-padded to whole 256-row tiles; filter_rows =
+    // the gallery size it was set for, -1 = no filter
+    DeviceBuffer<uint32_t> filter; int64_t filter_rows = -1;
+    // revo_search_set_groups: the handle's copy of the rows' group ids, set for groups_rows rows, -1 = none; the grouped
+    // search's workspace: top-GROUP_K1 scores | indices | counts | fallback queries | chosen groups
+    DeviceBuffer<int32_t> groups; int64_t groups_rows = -1;
+    DeviceBuffer<> gbuf;
+    revo::CertArgs cert_args(float* cert_out) const {
+        revo::CertArgs c{};
+        c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
+        c.nsegs = nsegs; c.segs[0] = segs[0]; c.segs[1] = segs[1]; c.seg_ksel = cand_ksel; c.prelist = prelist;
+        c.tau_base = tau0.p; c.marg = marg.p; c.dropflag = dropflag.p; c.estimated = cand_estimated ? 1 : 0;
+        return c;
+    }
+};
+
+extern "C" int32_t revo_gallery_create(int32_t dim, int64_t capacity, int32_t device, int32_t keep_f32,
+                                       revo_gallery** out) {
+    API_BEGIN
+    REVO_REQUIRE(out, "gallery_create: null argument");
+    REVO_REQUIRE(dim >= 64 && dim % 64 == 0, "gallery_create: dim must be a positive multiple of 64");
+    REVO_REQUIRE(capacity >= 1 && capacity < (1ll << 32), "gallery_create: capacity must be in [1, 2^32)");
+    REVO_ON_DEVICE(device);
+    std::unique_ptr<revo_gallery> g(new revo_gallery());
+    g->D = dim; g->device = device; g->capacity = capacity; g->keep_f32 = keep_f32 != 0;
+    CHECK_RC(g->gb.grow((size_t)capacity * dim * 2, nullptr));
+    if (g->keep_f32) CHECK_RC(g->gf.grow((size_t)capacity * dim * 4, nullptr));
+    CHECK_RC(g->gstat.grow(8, nullptr));
+    REVO_HIP_CHECK(hipMemset(g->gstat.p, 0, 8));
+    *out = g.release();
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_destroy(revo_gallery* g) {
+    API_BEGIN
+    if (g) { DeviceGuard dg(g->device); delete g; }
+    return 0;
+    API_END
+}
+extern "C" int64_t revo_gallery_size(const revo_gallery* g) { return g ? g->size : -1; }
+extern "C" int32_t revo_search_set_total_rows(revo_gallery* g, int64_t total_rows) {
+    REVO_REQUIRE(g && total_rows >= 0, "search_set_total_rows: null handle or negative row count");
+    g->total_rows = total_rows;
+    return 0;
+}
+// the handle's copy of an allow-bitmap: dst[i] = src[i] for the `nsrc` words that hold rows, bits from row `rows` on cleared,
+// zero words up to `total` (whole 256-row tiles: the filtered scans read a wave's 64 bits of any tile they touch).  src may
+// be dst (a host bitmap is first copied into place).
+__global__ void filter_copy_kernel(uint32_t* dst, const uint32_t* src, long rows, long nsrc, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    uint32_t w = i < nsrc ? src[i] : 0u;
+    if (i == rows >> 5 && (rows & 31)) w &= (1u << (rows & 31)) - 1u;
+    dst[i] = w;
+}
+extern "C" int32_t revo_search_set_filter(revo_gallery* g, const uint32_t* allow_bits, int64_t rows, int32_t src_on_device,
+                                          void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_set_filter: null handle");
+    REVO_REQUIRE(rows >= 0, "search_set_filter: negative row count");
+    if (!allow_bits) { g->filter_rows = -1; return 0; }
+    REVO_REQUIRE(rows == g->size, "search_set_filter: rows must equal revo_gallery_size (the filter covers the whole gallery)");
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    const long nsrc = (long)((rows + 31) / 32);
+    const long total = (long)((rows + 255) / 256 * 8) > 8 ? (long)((rows + 255) / 256 * 8) : 8;
+    g->filter_rows = -1;                                  // (until the copy below has been enqueued)
+    CHECK_RC(g->filter.grow((size_t)total * 4, st));
+    const uint32_t* src = allow_bits;
+    if (!src_on_device) {
+        // the caller may free its host buffer on return: copy now
+        if (nsrc > 0) REVO_HIP_CHECK(hipMemcpyAsync(g->filter.p, allow_bits, (size_t)nsrc * 4, hipMemcpyHostToDevice, st));
+        src = g->filter.p;
+    }
+    hipLaunchKernelGGL(filter_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g->filter.p, src, (long)rows,
+                       nsrc, total);
+    REVO_HIP_CHECK(hipGetLastError());
+    if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));
+    g->filter_rows = rows;
+    return 0;
+    API_END
+}
+// the allow-bitmap the next search of this handle runs with (null: none) -- a filter set for another gallery size is an
+// error, never a silently unfiltered search
+static int search_filter(const revo_gallery* g, const uint32_t** out) {
+    *out = nullptr;
+    if (g->filter_rows < 0) return 0;
+    REVO_REQUIRE(g->filter_rows == g->size,
+                 "search: the filter was set for " + std::to_string(g->filter_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set it again after appending)");
+    *out = g->filter.p;
+    return 0;
+}
+
+extern "C" int32_t revo_search_set_groups(revo_gallery* g, const int32_t* group_of_row, int64_t rows, int32_t src_on_device,
+                                          void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_set_groups: null handle");
+    REVO_REQUIRE(rows >= 0, "search_set_groups: negative row count");
+    if (!group_of_row) { g->groups_rows = -1; return 0; }
+    REVO_REQUIRE(rows == g->size, "search_set_groups: rows must equal revo_gallery_size (one group id per gallery row)");
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    g->groups_rows = -1;                                  // (until the copy below has been enqueued)
+    CHECK_RC(g->groups.grow((size_t)(rows > 1 ? rows : 1) * 4, st));
+    if (rows > 0)
+        REVO_HIP_CHECK(hipMemcpyAsync(g->groups.p, group_of_row, (size_t)rows * 4,
+                                      src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));   // the caller may free its host buffer on return
+    g->groups_rows = rows;
+    return 0;
+    API_END
+}
+
+extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
+    REVO_REQUIRE(g, "null handle");
+    REVO_ON_DEVICE(g->device);
+    REVO_HIP_CHECK(hipMemset(g->gstat.p, 0, 8));      // the row maxima of the certificate start over with the rows
+    g->size = 0;
+    return 0;
+}
+
+extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize,
+                                       int32_t src_on_device, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && (vecs || n == 0), "gallery_append: null argument");
+    REVO_REQUIRE(n >= 0 && g->size + n <= g->capacity, "gallery_append: exceeds the capacity given at create");
+    if (n == 0) return 0;
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int D = g->D;
+    const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
+    for (int64_t done = 0; done < n; done += chunk_rows) {
+        const int64_t m = std::min(chunk_rows, n - done);
+        const float* src = vecs + done * D;
+        if (!src_on_device) {
+            const size_t need = (size_t)m * D * 4;
+            CHECK_RC(g->stage.grow(need, st));
+            REVO_HIP_CHECK(hipMemcpyAsync(g->stage.p, src, need, hipMemcpyHostToDevice, st));
+            src = g->stage.p;
+        }
+        const int64_t row0 = g->size + done;
+        bf16_t* db = g->gb.p + row0 * D;
+        float* df = g->keep_f32 ? g->gf.p + row0 * D : nullptr;
+        ProfScope ps("gallery_append", st);
+        // one kernel either way: fp32 master row, bf16 scan row, and the row's share of the certificate's maxima
+        // (max ||g||, max ||bf16(g) - g||; with normalize = 0 the rows are stored as given, whatever their length)
+        CHECK_RC(revo::launch_l2norm_rows(src, D, df, D, db, D, m, D, st, normalize ? 1 : 0, nullptr, g->gstat.p));
+        if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));   // staging buffer is reused
+    }
+    g->size += n;
+    return 0;
+    API_END
+}
+
+extern "C" int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst, int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g && dst, "gallery_read: null argument");
+    REVO_REQUIRE(g->keep_f32, "gallery_read: gallery was created without the fp32 master copy");
+    REVO_REQUIRE(start >= 0 && n >= 0 && start + n <= g->size, "gallery_read: range outside the gallery");
+    if (n == 0) return 0;
+    REVO_ON_DEVICE(g->device);
+    REVO_HIP_CHECK(hipMemcpy(dst, g->gf.p + start * g->D, (size_t)n * g->D * 4,
+                             dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return 0;
+    API_END
+}
+
+#ifdef REVO_EXPERIMENTS
+// experiment (bound exchange between shards): raise the scan's admission bounds to values handed in
+__global__ void seed_bounds_kernel(uint32_t* tau, const uint32_t* seed, int Q) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < Q && seed[i] > tau[i]) tau[i] = seed[i];
+}
+#endif
+// Rows of the pre-pass of the 256 x 256 scan: about one round of GEMM tiles, at most a quarter of the gallery
+static long search_prepass_rows(int Q, long N) {
+#ifdef REVO_EXPERIMENTS
+    // (sweep of the pre-pass size, scripts/: 2048 / 4096 / 8192 / 16384 rows at 10 000 queries -> 4.22 / 3.43 / 3.36 /
+    //  3.50 ms per search of a 125 k-row shard: 8192 it is)
+    if (const char* e = getenv("REVO_NPRE")) { const long v = atol(e) / 256 * 256; if (v >= 1024 && v <= N / 4) return v; }
+#endif
+    // (few queries, 1 M rows, whole search in ms at 1 / 64 queries: 8192 rows 0.557 / 0.600, 16 384 0.555 / 0.596, 32 768
+    //  0.529 / 0.566, 65 536 0.564 / 0.596: a weaker seed costs the HBM-rate scan more survivors than the rows save)
+    const long qtiles = (Q + 255) / 256;
+    long n_pre = (65536 / qtiles) / 256 * 256;
+    n_pre = n_pre > 32768 ? 32768 : (n_pre < 8192 ? 8192 : n_pre);
+    if (n_pre > N / 4) n_pre = (N / 4) / 256 * 256;
+    const long cap_pre = ((512l << 20) / (4l * Q)) / 256 * 256;
+    if (n_pre > cap_pre) n_pre = cap_pre;
+    if (n_pre < 1024) n_pre = 1024;
+    return n_pre;
+}
+constexpr long SEARCH_SMALL_ROWS = 16384;     // below this the 128 x 128 scan with LDS lists takes the gallery
+constexpr long SEARCH_WIDE_ROWS = 1l << 22;   // from here on the unsharded search keeps 64 candidates per query for every k
+
+// z with P(standard normal > z) = p (Acklam's rational approximation, |relative error| < 1.2e-9; 0 < p < 0.5 here)
+static double upper_normal_quantile(double p) {
+    static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02,
+                               -3.066479806614716e+01, 2.506628277459239e+00};
+    static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+                               -1.328068155288572e+01};
+    static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00,
+                               4.374664141464968e+00, 2.938163982698783e+00};
+    static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+    if (p < 0.02425) {
+        const double q = std::sqrt(-2.0 * std::log(p));
+        return -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+    }
+    const double q = (1.0 - p) - 0.5, r = q * q;
+    return (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+           (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
+}
+
+// Phase 1 of a search: normalise the queries, scan the gallery (bf16 MFMA scores) and leave each query's best
+// ksel candidates, sorted best first, in the handle (cand / cand_stride).  The gallery must not be empty.
+static int search_candidates(revo_gallery* g, const float* queries, int Q, int ksel, const uint32_t* allow, hipStream_t st,
+                             uint32_t* bounds = nullptr, int top_m = 0, bool margin = false) {
+    using namespace revo;
+    const int D = g->D;
+    const long N = g->size;
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    if (g->q_cap < Q) {
+        g->q_cap = 0; g->xw = ExactWs{};
+        CHECK_RC(g->qf.grow((size_t)Q * D * 4, st)); CHECK_RC(g->qb.grow((size_t)Q * D * 2, st));
+        CHECK_RC(g->tau0.grow((size_t)Q * 4 * 2, st)); CHECK_RC(g->qstat.grow((size_t)Q * 8, st));   // tau0: pre-pass | live bounds
+        CHECK_RC(g->marg.grow((size_t)Q * 4, st)); CHECK_RC(g->dropflag.grow((size_t)Q * 4, st));
+        if (g->keep_f32) {
+            // fallback workspace of the exactness certificate; the counters come first, zeroed here and by every search
+            ExactWs xw{};
+            CHECK_RC(carve_buffer(g->xbuf, st, [&](Layout& l) {
+                xw.ctr = l.take<int>(CTR_SLOTS);
+                xw.unc_q = l.take<int>(Q); xw.unc_lb = l.take<float>(Q); xw.col_cnt = l.take<int>(Q);
+                xw.over_j = l.take<int>(Q); xw.orow = l.take<int>(Q); xw.qb_u = l.take<bf16_t>((size_t)Q * D); xw.ldqb = D;
+                xw.col = l.take<uint64_t>((size_t)Q * EXACT_COL_CAP); xw.cap = Q;
+            }));
+            REVO_HIP_CHECK(hipMemsetAsync(xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+            g->xw = xw;
+        }
+        g->q_cap = Q;
+    }
+    // the admission margin only pays where the certificate is expected to fail (see revo_search_topk) and only the
+    // 256 x 256 scan has segments; it needs the fp32 rows (no certificate without them)
+    margin = margin && g->keep_f32 && N >= SEARCH_SMALL_ROWS;
+    // (a filtered scan of more than 128 queries has no margin form: launch_topk_scan256; its uncertified queries take the
+    //  collect pass instead -- exact either way)
+    if (allow && Q > 128) margin = false;
+    // query normalisation (+ rounding norms); the same kernel clears the certificate's counters and -- 256 x 256 scan -- the
+    // score histograms (two memset launches fewer per search: a quarter of a one-query search is launches)
+    auto prep = [&](uint32_t* hist, long hist_words) -> int {
+        ProfScope ps("search_prep", st);
+        CHECK_RC(launch_l2norm_rows(queries, D, g->qf.p, D, g->qb.p, D, Q, D, st, 1, g->qstat.p, nullptr,
+                                    (uint32_t*)g->xw.ctr, g->xw.ctr ? CTR_SLOTS : 0, hist, hist_words));
+        if (margin) CHECK_RC(launch_cert_margin(g->qstat.p, g->gstat.p, D, Q, g->marg.p, g->dropflag.p, st));
+        return 0;
+    };
+
+    if (N >= SEARCH_SMALL_ROWS) {
+        // ---- 256 x 256 scan.  Pre-pass: a plain GEMM of the queries against the first n_pre rows and a
+        // per-row selection seed the admission scores; the fused scan covers rows [n_pre, N).
+        // Pre-pass size: about one round of 256 x 256 GEMM tiles; with few queries (short gallery slices
+        // per CU) up to 32 k rows, which seed the 0.1 % quantile.
+        const long n_pre = search_prepass_rows(Q, N);
+        // the scan runs as one launch, or as a main launch of whole query tiles plus one for a ragged tail of queries
+        const int q_main = topk_scan256_main_queries(Q, N - n_pre);
+        struct Part { int q0, nq, splits; uint64_t* seg; int* cnt; } parts[2] = {{0, q_main, 0}, {q_main, Q - q_main, 0}};
+        const int nparts = q_main < Q ? 2 : 1;
+        for (int i = 0; i < nparts; ++i) parts[i].splits = topk_scan256_splits(parts[i].nq, N - n_pre);
+        const int NB = topk_scan256_hist_buckets();
+        // workspace: histograms (zeroed) | per part: segment counts, segments | pre-pass lists | final lists | pre-pass scores
+        uint32_t* hist; uint64_t *prelist, *final_lists; float* pre_scores;
+        CHECK_RC(carve_buffer(g->part, st, [&](Layout& l) {
+            hist = l.take<uint32_t>((size_t)Q * NB);
+            for (int i = 0; i < nparts; ++i) {
+                Part& pt = parts[i];
+                pt.cnt = l.take<int>((size_t)pt.nq * pt.splits);
+                pt.seg = l.take<uint64_t>((size_t)pt.nq * pt.splits * (2 * ksel));
+            }
+            prelist = l.take<uint64_t>((size_t)Q * ksel);
+            final_lists = l.take<uint64_t>((size_t)Q * ksel);
+            pre_scores = l.take<float>((size_t)Q * n_pre);
+        }));
+        uint32_t* tau_base = g->tau0.p, *tau_live = g->tau0.p + g->q_cap;
+        CHECK_RC(prep(hist, (long)Q * NB));
+        {
+            ProfScope ps("topk_prepass", st);
+            GemmArgs ga{};
+            ga.A = g->qb.p; ga.lda = D; ga.B = g->gb.p; ga.ldb = D; ga.M = Q; ga.N = (int)n_pre; ga.K = D;
+            ga.C = pre_scores; ga.ldc = n_pre; ga.prefer256 = 1;
+            // (few queries: the skinny form instead -- measured: pre-pass 48 -> 37 us at one query, 50 -> 57 at 64; nothing in the search)
+            // Up to 128 queries: 128 x 64 tiles on the six-deep ring (two rounds of workgroups with five K-steps of loads in
+            // flight; one 256 x 256 tile per CU is a chain of sixteen DMA latencies): pre-pass 48 -> 40 us at one query,
+            // 49 -> 42 at 64, 52 -> 46 at 128
+            bool ring = Q <= 128 && n_pre % 64 == 0;
+#ifdef REVO_EXPERIMENTS
+            if (getenv("REVO_PREPASS_256")) ring = false;
+#endif
+            if (ring) CHECK_RC(launch_gemm_f32_ring(ga, st));
+            else CHECK_RC(launch_gemm(EPI_F32, ga, st));
+            // One shard of a larger gallery, in the two-phase search: what its candidates have to reach is decided by ALL
+            // shards' rows (the finish step re-scores only candidates among the best min(64, 2 ksel) of the whole gallery),
+            // but its scan can only learn its own rows' scores -- at an eighth of the rows its admission bound sits at an
+            // 8 x higher quantile and a third of its tile fragments still hold a survivor.  So it
+            // starts from an ESTIMATE of the whole gallery's level, extrapolated from its own pre-pass scores
+            // (topk_select_rows_kernel); an estimate, not a bound: the protocol's certificate and second round cover it.
+            float est_z = 0.f;
+            // (not under a filter: the estimate extrapolates from ALL of the whole gallery's rows, a filtered search needs the
+            //  level of the allowed ones -- the bound exchange decides instead)
+            if (bounds && !margin && g->total_rows > N && !allow) {
+                int j = 2 * ksel < 64 ? 2 * ksel : 64;
+#ifdef REVO_EXPERIMENTS
+                if (const char* e = getenv("REVO_EST_J")) j = atoi(e) > 0 ? atoi(e) : j;      // sweep of the estimate's rank (scripts/)
+#endif
+                est_z = (float)upper_normal_quantile((double)j / (double)g->total_rows);
+                g->cand_estimated = true;
+            }
+            CHECK_RC(launch_topk_select_rows(pre_scores, n_pre, (int)n_pre, Q, prelist, ksel, 0, tau_base, ksel, hist, NB,
+                                             topk_scan256_hist_shift(), st, tau_live, est_z, allow));
+#ifdef REVO_EXPERIMENTS
+            if (g->seed_bounds) hipLaunchKernelGGL(seed_bounds_kernel, dim3((Q + 255) / 256), dim3(256), 0, st, tau_live, g->seed_bounds, Q);
+#endif
+        }
+        { ProfScope ps("topk_scan", st);
+          for (int i = 0; i < nparts; ++i) {
+              const Part& pt = parts[i];
+              CHECK_RC(launch_topk_scan256(g->qb.p + (size_t)pt.q0 * D, D, g->gb.p, D, pt.nq, N, D, n_pre, pt.splits,
+                                           pt.seg, pt.cnt, tau_live + pt.q0, tau_base + pt.q0, hist + (size_t)pt.q0 * NB, ksel, st,
+                                           margin ? g->marg.p + pt.q0 : nullptr, margin ? g->dropflag.p + pt.q0 : nullptr, allow));
+              if (margin) g->segs[i] = SegSrc{pt.seg, pt.cnt, pt.splits, pt.q0, pt.nq};
+          }
+          if (margin) { g->nsegs = nparts; g->prelist = prelist; } }
+        { ProfScope ps("topk_reduce", st);
+          for (int i = 0; i < nparts; ++i) {
+              const Part& pt = parts[i];
+              CHECK_RC(launch_topk_reduce_segs(pt.seg, pt.cnt, pt.splits, prelist + (size_t)pt.q0 * ksel,
+                                               final_lists + (size_t)pt.q0 * ksel, pt.nq, ksel, st,
+                                               bounds ? bounds + (size_t)pt.q0 * top_m : nullptr, top_m));
+          } }
+        g->cand = final_lists; g->cand_stride = ksel;
+    } else {
+        // ---- small galleries: 128 x 128 scan with per-wave LDS lists
+        const int splits = topk_scan_workspace_splits(Q, N);
+        CHECK_RC(g->part.grow((size_t)Q * splits * ksel * 8, st));
+        uint64_t* part = (uint64_t*)g->part.p;
+        CHECK_RC(prep(nullptr, 0));
+        ScanArgs a{};
+        a.Qb = g->qb.p; a.ldq = D; a.Gb = g->gb.p; a.ldg = D; a.Q = Q; a.N = N; a.D = D; a.ksel = ksel;
+        a.splits = splits; a.part = part; a.allow = allow;
+        { ProfScope ps("topk_scan", st); CHECK_RC(launch_topk_scan(a, st)); }
+        { ProfScope ps("topk_reduce", st); CHECK_RC(launch_topk_reduce(part, Q, splits, ksel, st)); }
+        g->cand = part; g->cand_stride = (long)splits * ksel;
+        if (bounds) { ProfScope ps("topk_bounds", st); CHECK_RC(launch_topk_publish(g->cand, g->cand_stride, Q, top_m, bounds, st)); }
+    }
+    g->cand_Q = Q; g->cand_ksel = ksel;
+    return 0;
+}
+
+// The fallback of the exactness certificate for the entries in the handle's workspace (count on the device): collect
+// pass, exact re-score of what it collected, brute force for the entries whose lists overflowed.  Idle passes cost a
+// few microseconds each.
+static int search_fallback(revo_gallery* g, int max_entries, int k, int has_thr, float thr, long index_offset, int out_compact,
+                           float* scores, long long* indices, int* counts, const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    ProfScope ps("topk_exact", st);
+    if (g->mode != 2) {
+        Collect256Args ca{};
+        ca.Qb = g->xw.qb_u; ca.ldq = g->xw.ldqb; ca.Gb = g->gb.p; ca.ldg = g->D; ca.N = g->size; ca.D = g->D;
+        ca.n_q = g->xw.ctr + CTR_UNCERTIFIED; ca.lb = g->xw.unc_lb; ca.cnt = g->xw.col_cnt; ca.col = g->xw.col;
+        ca.cap = EXACT_COL_CAP; ca.allow = allow;
+        CHECK_RC(launch_topk_collect256(ca, max_entries, st));
+    }
+    CHECK_RC(launch_topk_exact_finish(g->xw, max_entries, g->qf.p, g->D, g->gf.p, g->D, g->D, k, has_thr, thr, index_offset,
+                                      g->mode == 2, out_compact, scores, indices, counts, st));
+    return launch_topk_exact_bruteforce(g->xw, max_entries, g->qf.p, g->D, g->gf.p, g->D, g->size, g->D, k, has_thr, thr,
+                                        index_offset, out_compact, scores, indices, counts, st, allow);
+}
+
+// over-selection: the bf16 scan keeps ksel >= k + margin candidates, the fp32 re-score decides
+static int search_ksel(int k) { return (k <= 16) ? 32 : 64; }
+extern "C" int32_t revo_search_ksel(int32_t k) { return (k >= 1 && k <= 50) ? search_ksel(k) : -1; }
+// k > 25: the scan runs with the admission margin (revo_search_topk); a shard's two-phase scan estimates the whole gallery's
+// admission level only without it -- one rule, asked for by the host side that decides whether to exchange bounds
+static bool search_uses_margin(int k) { return k > 25; }
+extern "C" int32_t revo_search_estimates(int32_t k) { return (k >= 1 && k <= 50) ? (search_uses_margin(k) ? 0 : 1) : -1; }
+extern "C" int32_t revo_search_plan(const revo_gallery* g, int32_t Q, int32_t k, int64_t* out4) {
+    REVO_REQUIRE(g && out4 && Q >= 1 && k >= 1 && k <= 50, "search_plan: bad arguments");
+    const long N = g->size;
+    const bool big = N >= SEARCH_SMALL_ROWS;
+    const long n_pre = big ? search_prepass_rows(Q, N) : 0;
+    out4[0] = big ? 1 : 0;
+    out4[1] = n_pre;
+    out4[2] = big ? revo::topk_scan256_splits(revo::topk_scan256_main_queries(Q, N - n_pre), N - n_pre)
+                  : revo::topk_scan_workspace_splits(Q, N);
+    out4[3] = N >= SEARCH_WIDE_ROWS ? 64 : search_ksel(k);
+    return 0;
+}
+
+// revo_search_topk / revo_search_groups after their argument checks (Q >= 1, device current, `allow` = search_filter)
+static int search_topk(revo_gallery* g, const float* queries, int Q, int k, int has_thr, float thr, long index_offset,
+                       float* scores, long long* indices, int* counts, const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    if (g->size == 0) return launch_topk_fill_empty(scores, indices, counts, Q, k, st);
+    // candidates per query: 32 for k <= 16, 64 beyond -- and 64 on very large galleries whatever k is: there a query
+    // that fails its certificate costs a whole extra pass over the gallery (10 M x 1536: 5.9 ms next to a 7.7 ms scan),
+    // and the wider list all but rules that out (the k-th to 64th score gap is 1.6 x the k-th to 32nd) for 0.1 ms of re-scores
+    int ksel = g->size >= SEARCH_WIDE_ROWS ? 64 : search_ksel(k);
+#ifdef REVO_EXPERIMENTS
+    if (const char* e = getenv("REVO_KSEL")) ksel = atoi(e) == 64 ? 64 : ksel;         // candidate-list width study (scripts/)
+#endif
+    // k > 25: 64 candidates leave the certificate less room than its error bound on ordinary data (the 50th-to-64th score
+    // gap of a random 1 M gallery is half of eps), so nearly every query fails it.  The scan then runs with an admission
+    // margin of 2 eps: what an uncertified query needs is in its segments, and no second pass over the gallery is made
+    // (Not for smaller k, not even on very large galleries where a second pass costs most of a search: measured on 10 M x
+    //  1536 with 256 queries, the margin's extra survivors cost the scan 18 % on EVERY search -- 7.5 -> 8.9 ms -- to save a
+    //  pass that the 64-candidate lists kept there for every k already make a rarity.)
+    CHECK_RC(search_candidates(g, queries, Q, ksel, allow, st, nullptr, 0, search_uses_margin(k)));
+    const CertArgs ca = g->cert_args(nullptr);
+    { ProfScope ps("topk_finish", st);
+      CHECK_RC(launch_topk_finish(g->cand, g->cand_stride, ksel, g->qf.p, g->D, g->keep_f32 ? g->gf.p : nullptr, g->D, g->D, Q, k,
+                                  has_thr, thr, index_offset, nullptr, 0, 0, scores, indices, counts,
+                                  g->keep_f32 ? &ca : nullptr, st)); }
+    if (g->keep_f32 && g->mode != 3)
+        CHECK_RC(search_fallback(g, Q, k, has_thr, thr, index_offset, 0, scores, indices, counts, allow, st));
+    return 0;
+}
+
+extern "C" int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t Q, int32_t k, int32_t has_thr,
+                                    float thr, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
+                                    void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (queries || Q == 0), "search: null argument");
+    REVO_REQUIRE(Q >= 0, "search: negative query count");
+    REVO_REQUIRE(k >= 1 && k <= 50, "search: k must be in [1, 50]");
+    if (Q == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_topk(g, queries, Q, k, has_thr, thr, index_offset, scores, (long long*)indices, counts, allow,
+                       (hipStream_t)stream);
+    API_END
+}
+
+// ---- the same search in two phases, for a gallery that is row-sharded over several GPUs (include/revo.h)
+extern "C" int32_t revo_search_candidates(revo_gallery* g, const float* queries, int32_t Q, int32_t k, int32_t top_m,
+                                          uint32_t* bounds, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && bounds && (queries || Q == 0), "search_candidates: null argument");
+    REVO_REQUIRE(Q >= 0, "search_candidates: negative query count");
+    REVO_REQUIRE(k >= 1 && k <= 50, "search_candidates: k must be in [1, 50]");
+    const int ksel = search_ksel(k);
+    REVO_REQUIRE(top_m >= 1 && top_m <= ksel, "search_candidates: top_m must be in [1, revo_search_ksel(k)]");
+    if (Q == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    g->cand = nullptr; g->cand_Q = Q; g->cand_ksel = ksel;
+    if (g->size == 0) {                                   // an empty shard publishes nothing
+        REVO_HIP_CHECK(hipMemsetAsync(bounds, 0, (size_t)Q * top_m * 4, st));
+        return 0;
+    }
+    // (the published scores come out of the final selection kernel: no launch of their own; k > 25: with the admission
+    //  margin, so that the second round the merge's certificate then asks for needs no pass over the shard -- revo_search_topk)
+    return search_candidates(g, queries, Q, ksel, allow, st, bounds, top_m, search_uses_margin(k));
+    API_END
+}
+extern "C" int32_t revo_search_finish(revo_gallery* g, int32_t Q, int32_t k, int32_t has_thr, float thr,
+                                      int64_t index_offset, const uint32_t* all_bounds, int32_t parts, int32_t top_m,
+                                      float* scores, int64_t* indices, int32_t* counts, float* cert, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts, "search_finish: null argument");
+    REVO_REQUIRE(k >= 1 && k <= 50 && Q >= 0, "search_finish: bad k or query count");
+    REVO_REQUIRE(Q == g->cand_Q && search_ksel(k) == g->cand_ksel,
+                 "search_finish: no matching revo_search_candidates call on this handle");
+    REVO_REQUIRE(!all_bounds || (parts >= 1 && top_m >= 1 && top_m <= g->cand_ksel), "search_finish: bad bounds layout");
+    // A scan that started from an ESTIMATED admission level (revo_search_set_total_rows) has dropped rows on the strength of
+    // that estimate: only the certificate (cert -> revo_topk_merge_packed -> revo_search_exact) makes the result exhaustive
+    REVO_REQUIRE(cert || !g->cand_estimated,
+                 "search_finish: this shard scanned against an estimated admission level (revo_search_set_total_rows): cert must "
+                 "be given and checked by revo_topk_merge_packed, with revo_search_exact as the second round");
+    if (Q == 0) return 0;
+    { const uint32_t* allow; CHECK_RC(search_filter(g, &allow)); }
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    if (g->size == 0 || !g->cand) {
+        // an empty shard holds no row that could change a result: its certificate bound is -inf
+        if (cert) REVO_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)cert, (int)0xff800000u, (size_t)Q, st));
+        return launch_topk_fill_empty(scores, (long long*)indices, counts, Q, k, st);
+    }
+    ProfScope ps("topk_finish", st);
+    const CertArgs ca = g->cert_args(cert);
+    return launch_topk_finish(g->cand, g->cand_stride, g->cand_ksel, g->qf.p, g->D, g->keep_f32 ? g->gf.p : nullptr, g->D, g->D,
+                              Q, k, has_thr, thr, index_offset, all_bounds, parts, top_m, scores, (long long*)indices,
+                              counts, cert ? &ca : nullptr, st);
+    API_END
+}
+
+// Second round of a row-sharded search: exact local results for the queries the merge step could not certify.
+extern "C" int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, const float* need, int32_t k,
+                                     int32_t has_thr, float thr, int64_t index_offset, float* scores, int64_t* indices,
+                                     int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (n == 0 || (q_idx && need)), "search_exact: null argument");
+    REVO_REQUIRE(k >= 1 && k <= 50 && n >= 0, "search_exact: bad k or entry count");
+    REVO_REQUIRE(n <= g->cand_Q, "search_exact: more entries than queries in the last revo_search_candidates call");
+    if (n == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    if (g->size == 0) return launch_topk_fill_empty(scores, (long long*)indices, counts, n, k, st);
+    REVO_REQUIRE(g->keep_f32 && g->xw.ctr, "search_exact: the gallery was created without the fp32 master copy");
+    const CertArgs ca = g->cert_args(nullptr);
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    CHECK_RC(launch_topk_exact_prepare(g->xw, q_idx, need, n, ca, g->D, g->cand, g->cand_stride, g->cand_ksel, st));
+    return search_fallback(g, n, k, has_thr, thr, index_offset, 1, scores, (long long*)indices, counts, allow, st);
+    API_END
+}
+
+// Grouped search (include/revo.h): the certified search at k = GROUP_K1 into the handle's workspace, the groups of each
+// query's list (certified, or an entry of the grouped fallback), the fallback's fp32 passes over the gallery.  Every launch
+// is sized for Q entries and reads the entry count from the device.
+extern "C" int32_t revo_search_groups(revo_gallery* g, const float* queries, int32_t Q, int32_t limit, int32_t group_size,
+                                      int32_t has_thr, float thr, int64_t index_offset, float* scores, int64_t* indices,
+                                      int32_t* hit_counts, int32_t* group_ids, int32_t* group_counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(Q >= 0, "search_groups: negative query count");
+    REVO_REQUIRE(limit >= 1 && limit <= 50 && group_size >= 1 && group_size <= 50 && limit * group_size <= 50,
+                 "search_groups: needs 1 <= limit, 1 <= group_size and limit * group_size <= 50");
+    REVO_REQUIRE(g, "search_groups: null handle");
+    REVO_REQUIRE(scores && indices && hit_counts && group_ids && group_counts && (queries || Q == 0), "search_groups: null argument");
+    REVO_REQUIRE(g->keep_f32, "search_groups: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    REVO_REQUIRE(g->groups_rows >= 0, "search_groups: no group ids set (revo_search_set_groups)");
+    REVO_REQUIRE(g->groups_rows == g->size,
+                 "search_groups: the group ids were set for " + std::to_string(g->groups_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set them again after appending)");
+    if (Q == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    float* s1; long long* i1; int* c1;
+    GroupWs gw{};
+    CHECK_RC(carve_buffer(g->gbuf, st, [&](Layout& l) {
+        s1 = l.take<float>((size_t)Q * GROUP_K1); i1 = l.take<long long>((size_t)Q * GROUP_K1);
+        c1 = l.take<int>(Q); gw.gq = l.take<int>(Q);
+        gw.chosen = l.take<int>((size_t)Q * 64);
+    }));
+    CHECK_RC(search_topk(g, queries, Q, GROUP_K1, has_thr, thr, 0, s1, i1, c1, allow, st));
+    ProfScope ps("topk_groups", st);
+    gw.group_of_row = g->groups.p; gw.has_thr = has_thr ? 1 : 0; gw.thr = thr;
+    GroupOut o{};
+    o.scores = scores; o.idx = (long long*)indices; o.hit_counts = hit_counts; o.group_ids = group_ids;
+    o.group_counts = group_counts; o.limit = limit; o.group_size = group_size; o.idx_offset = (long)index_offset;
+    // (an empty gallery: the search wrote empty lists and left the counters alone -- every query is certified)
+    if (g->size == 0) return launch_topk_group_select(s1, i1, c1, Q, g->xw, gw, 0, o, st);
+    REVO_REQUIRE(g->xw.ctr, "search_groups: no certificate workspace");
+    CHECK_RC(launch_topk_group_select(s1, i1, c1, Q, g->xw, gw, g->mode == 2, o, st));
+    return launch_topk_group_fallback(g->xw, gw, Q, g->qf.p, g->D, g->gf.p, g->D, g->size, g->D, allow, o, st);
+    API_END
+}
+
+#ifdef REVO_EXPERIMENTS   // librevo.so cannot be put into a non-exact mode
+extern "C" int32_t revo_search_set_mode(revo_gallery* g, int32_t mode) {
+    REVO_REQUIRE(g && mode >= 0 && mode <= 3, "search_set_mode: mode must be 0..3");
+    g->mode = mode;
+    return 0;
+}
+#endif
+extern "C" int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && out8, "search_stats: null argument");
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    if (!g->xw.ctr) { out8[0] = -1; return 0; }     // no fp32 master rows (or no search yet): nothing was certified
+    REVO_ON_DEVICE(g->device);
+    using namespace revo;
+    int c[CTR_SLOTS];
+    REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    REVO_HIP_CHECK(hipMemcpy(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost));
+    out8[0] = c[CTR_UNCERTIFIED] + c[CTR_MODE3_FAILED] + c[CTR_FROM_SEGS]; out8[1] = c[CTR_BRUTEFORCE];
+    out8[2] = c[CTR_CHECKED]; out8[3] = c[CTR_COLLECTED]; out8[4] = c[CTR_FROM_SEGS]; out8[5] = c[CTR_GROUPED];
+    return 0;
+    API_END
+}
+
+extern "C" int32_t revo_topk_merge(const float* scores, const int64_t* indices, int32_t parts, int32_t Q, int32_t k,
+                                   int32_t has_thr, float thr, float* out_scores, int64_t* out_indices,
+                                   int32_t* out_counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(scores && indices && out_scores && out_indices && out_counts, "merge: null argument");
+    ProfScope ps("topk_merge", (hipStream_t)stream);
+    return revo::launch_topk_merge(scores, (const long long*)indices, parts, Q, k, has_thr, thr, out_scores,
+                                   (long long*)out_indices, out_counts, (hipStream_t)stream);
+    API_END
+}
+
+extern "C" int64_t revo_topk_packed_bytes(int32_t Q, int32_t k) {
+    return Q < 0 || k < 1 ? -1 : (((int64_t)Q * k * 12 + (int64_t)Q * 4 + 15) / 16) * 16;
+}
+extern "C" int32_t revo_topk_merge_packed(const void* packed, int32_t parts, int32_t Q, int32_t k, int32_t has_thr, float thr,
+                                          float* out_scores, int64_t* out_indices, int32_t* out_counts,
+                                          int32_t* unc_count, int32_t* unc_q, float* unc_need, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(packed && out_scores && out_indices && out_counts, "merge: null argument");
+    REVO_REQUIRE(Q >= 0 && k >= 1, "merge: bad sizes");
+    REVO_REQUIRE(!unc_count || (unc_q && unc_need), "merge: the certificate needs all three of unc_count, unc_q, unc_need");
+    const int64_t pb = revo_topk_packed_bytes(Q, k);
+    ProfScope ps("topk_merge", (hipStream_t)stream);
+    // part p: [Q][k] int64 indices, then [Q][k] fp32 scores, then [Q] fp32 certificate bounds
+    revo::MergeCert mc{};
+    if (unc_count) {
+        REVO_HIP_CHECK(hipMemsetAsync(unc_count, 0, 4, (hipStream_t)stream));
+        mc.cert = (const float*)((const char*)packed + (size_t)Q * k * 12); mc.cert_part_stride = pb / 4;
+        mc.unc_count = unc_count; mc.unc_q = unc_q; mc.unc_need = unc_need;
+    }
+    return revo::launch_topk_merge_strided((const float*)((const char*)packed + (size_t)Q * k * 8), pb / 4,
+                                           (const long long*)packed, pb / 8, parts, Q, k, has_thr, thr, out_scores,
+                                           (long long*)out_indices, out_counts, (hipStream_t)stream, unc_count ? &mc : nullptr);
+    API_END
+}
+
+#ifdef REVO_EXPERIMENTS
+// copy bytes [offset, offset + bytes) of the handle's search workspace to the host (debugging the scan's buffers)
+extern "C" int64_t revo_debug_read_workspace(revo_gallery* g, int64_t offset, int64_t bytes, void* host_dst) {
+    if (!g || !g->part.p) return -1;
+    if (!host_dst) return (int64_t)g->part.bytes;
+    if (offset < 0 || bytes < 0 || (size_t)(offset + bytes) > g->part.bytes) return -2;
+    if (hipDeviceSynchronize() != hipSuccess) return -3;
+    if (hipMemcpy(host_dst, g->part.p + offset, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) return -3;
+    return bytes;
+}
+extern "C" int32_t revo_debug_seed_bounds(revo_gallery* g, const uint32_t* bounds) {
+    if (!g) return -1;
+    g->seed_bounds = bounds;
+    return 0;
+}
+extern "C" int32_t revo_debug_scan_stats(int64_t* out4) {
+    REVO_HIP_CHECK(hipDeviceSynchronize());
+    REVO_HIP_CHECK(hipMemcpy(out4, revo::topk_scan256_stats(), 64, hipMemcpyDeviceToHost));
+    REVO_HIP_CHECK(hipMemset(revo::topk_scan256_stats(), 0, 64));
+    return 0;
+}
+#endif

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256) void topk_finish_kernel(const uint64_t* __rest
     const float sk = kth ? key_score(kth) : -INFINITY;
     const float need = has_thr ? fmaxf(sk, thr) : sk;
     const bool certified = (U == -INFINITY || need > U + eps) && cert.mode != 1 && cert.mode != 2;
-    if (lane == 0) atomicAdd(cert.ws.ctr + 2, 1);
+    if (lane == 0) atomicAdd(cert.ws.ctr + CTR_CHECKED, 1);
     if (certified) return;
     float lb = need - eps;                     // rows that can enter the result have a bf16 score of at least this
     lb -= fabsf(lb) * 2.4e-7f;                 // (the subtraction's own rounding)
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void topk_finish_kernel(const uint64_t* __rest
     // If `lb` reaches that level, the rows the collect pass would find are all there: no pass over the gallery.
     const bool from_seg = cert.mode == 0 && ne == ksel && cert_segments_cover(cert, q, lb, U);
     int j = 0;
-    if (lane == 0) j = atomicAdd(cert.ws.ctr + (cert.mode == 3 ? 4 : (from_seg ? 5 : 0)), 1);
+    if (lane == 0) j = atomicAdd(cert.ws.ctr + (cert.mode == 3 ? CTR_MODE3_FAILED : (from_seg ? CTR_FROM_SEGS : CTR_UNCERTIFIED)), 1);
     if (cert.mode == 3) return;                // counted only
     j = __builtin_amdgcn_readfirstlane(j);
     if (from_seg) j = cert.ws.cap - 1 - j;     // numbered from the back: the collect pass takes the front entries
@@ -603,7 +603,7 @@ __device__ __forceinline__ void topk_select_rows_body(const float* __restrict__ 
         const uint64_t last = readlane_u64(run, KSEL - 1);
         uint32_t base = f32_orderable(last ? key_score(last) : -INFINITY);      // order-preserving u32
         if (est_z != 0.f) {
-            // One shard of a row-sharded gallery (api.hip, revo_search_set_total_rows): start the scan not from this shard's
+            // One shard of a row-sharded gallery (search.hip, revo_search_set_total_rows): start the scan not from this shard's
             // own KSEL-th best of the pre-pass rows but from an ESTIMATE of the score that the candidates of the WHOLE
             // gallery will have to reach -- mean + z sigma of this query's pre-pass scores, z from the quantile
             // min(64, 2 KSEL) / total rows (a Gaussian tail: what unit vectors in many dimensions give; a heavier tail

@@ -620,7 +620,7 @@ int launch_topk_scan256(const bf16_t* Qb, long ldq, const bf16_t* Gb, long ldg, 
     a.dbg = g_scan_dbg; a.stats = (g_scan_dbg & 2) ? topk_scan256_stats() : nullptr;
     a.allow = allow;
     // (the filtered 256-row form is not built with the margin: it spilled 12 VGPRs, 4 inside the tile loop -- a filtered
-    //  search of more than 128 queries with k > 25 scans without the margin, api.hip)
+    //  search of more than 128 queries with k > 25 scans without the margin, search.hip)
     REVO_REQUIRE(!(allow && marg && Q > 128), "search: a filtered scan of more than 128 queries runs without the margin");
     const dim3 grid((unsigned)blocks), block(G256_THREADS);
 #define S256_LAUNCH_M(KS, RW, MG)                                                                              \
@@ -637,7 +637,7 @@ int launch_topk_scan256(const bf16_t* Qb, long ldq, const bf16_t* Gb, long ldg, 
             hipLaunchKernelGGL((topk_scan256_kernel<KS, RW, MG>), grid, block, S256_LDS, st, a);               \
         }                                                                                                      \
     } while (0)
-    // the margin form exists for 64-candidate scans only (searches with k > 25: api.hip)
+    // the margin form exists for 64-candidate scans only (searches with k > 25: search.hip)
     REVO_REQUIRE(!marg || (ksel == 64 && dropflag), "search: the admission margin goes with 64 candidates and drop flags");
 #define S256_LAUNCH(KS, RW)                                                                                    \
     do {                                                                                                       \

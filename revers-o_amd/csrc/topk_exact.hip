@@ -45,16 +45,17 @@ __global__ __launch_bounds__(XF_WAVES * 64) void topk_exact_finish_kernel(ExactW
                                                                           int* __restrict__ out_counts) {
     __shared__ uint64_t partial[XF_WAVES][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // entries 0 .. ctr[0] - 1 were filled by the collect pass, cap - 1 .. cap - ctr[5] by the finish step from the scan's segments
-    const int nfront = ws.ctr[0], entries = nfront + ws.ctr[5];
+    // entries 0 .. nfront - 1 were filled by the collect pass, cap - 1 .. cap - ctr[CTR_FROM_SEGS] by the finish step from the
+    // scan's segments
+    const int nfront = ws.ctr[CTR_UNCERTIFIED], entries = nfront + ws.ctr[CTR_FROM_SEGS];
     for (int jj = blockIdx.x; jj < entries; jj += gridDim.x) {
     const int j = jj < nfront ? jj : ws.cap - 1 - (jj - nfront);
     const int n = ws.col_cnt[j];
     if (n > EXACT_COL_CAP || force_bruteforce) {
-        if (threadIdx.x == 0) ws.over_j[atomicAdd(ws.ctr + 1, 1)] = j;
+        if (threadIdx.x == 0) ws.over_j[atomicAdd(ws.ctr + CTR_BRUTEFORCE, 1)] = j;
         continue;
     }
-    if (threadIdx.x == 0) atomicAdd(ws.ctr + 3, n);
+    if (threadIdx.x == 0) atomicAdd(ws.ctr + CTR_COLLECTED, n);
     const int q = ws.unc_q[j];
     const float* qr = Qf + (long)q * ldqf;
     const uint64_t* col = ws.col + (long)j * EXACT_COL_CAP;
@@ -137,7 +138,7 @@ __device__ __forceinline__ int group_of_key(const int* __restrict__ group_of_row
 }
 
 // FILTER: rows whose allow-bit is clear are skipped (the test is wave-uniform: one row per step of the insertion).
-// GROUP: the grouped fallback's entries (ws.ctr[6], gw.gq) instead of the overflowed ones.  Pass A (gw.hits == 0) keeps
+// GROUP: the grouped fallback's entries (ws.ctr[CTR_GROUPED], gw.gq) instead of the overflowed ones.  Pass A (gw.hits == 0) keeps
 // the best 64 GROUPS, each with its best key; pass B (gw.hits = group_size) only the rows of the entry's chosen groups, at
 // most gw.hits per group.  Rows of no group and rows below the threshold never enter.
 template <bool FILTER, bool GROUP>
@@ -146,7 +147,7 @@ __device__ __forceinline__ void bruteforce_body(const ExactWs& ws, const float* 
                                                 const uint32_t* __restrict__ allow, const GroupWs& gw) {
     __shared__ uint64_t partial[BF_WAVES][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int over = GROUP ? ws.ctr[6] : ws.ctr[1];
+    const int over = GROUP ? ws.ctr[CTR_GROUPED] : ws.ctr[CTR_BRUTEFORCE];
     for (int i = blockIdx.y; i < over; i += gridDim.y) {
     const int j = GROUP ? i : ws.over_j[i];
     const float* qr = Qf + (long)(GROUP ? gw.gq[i] : ws.unc_q[j]) * ldqf;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(256) void topk_exact_bruteforce_final_kernel(ExactW
                                                                           long long* __restrict__ out_idx,
                                                                           int* __restrict__ out_counts) {
     const int lane = threadIdx.x & 63;
-    const int over = ws.ctr[1];
+    const int over = ws.ctr[CTR_BRUTEFORCE];
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < over; i += gridDim.x * 4) {
     const int j = ws.over_j[i];
     const uint64_t* lists = ws.col + (long)j * EXACT_COL_CAP;
@@ -291,7 +292,7 @@ __device__ __forceinline__ void group_write(const GroupOut& o, long orow, uint64
 // Certified: the list is complete (fewer than GROUP_K1 entries: every allowed row at or above the threshold is in it), or it
 // holds >= limit groups and each of the first limit groups holds >= group_size of its entries (a row outside the list
 // scores at most the last entry's score and, on a tie, has a larger index: it can neither found a group that outranks a
-// listed group nor displace a listed hit).  Otherwise the query becomes an entry of the grouped fallback (ws.ctr[6]).
+// listed group nor displace a listed hit).  Otherwise the query becomes an entry of the grouped fallback (ws.ctr[CTR_GROUPED]).
 __global__ __launch_bounds__(256) void topk_group_select_kernel(const float* __restrict__ s1, const long long* __restrict__ i1,
                                                                 const int* __restrict__ c1, int Q, ExactWs ws, GroupWs gw,
                                                                 int force_fallback, GroupOut o) {
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(256) void topk_group_select_kernel(const float* __r
     const int L = o.limit, S = o.group_size;
     const bool full_groups = it >= L && __ballot(lane < L && hc_l < S) == 0ull;
     if (force_fallback || (cnt >= GROUP_K1 && !full_groups)) {
-        if (lane == 0) gw.gq[atomicAdd(ws.ctr + 6, 1)] = q;
+        if (lane == 0) gw.gq[atomicAdd(ws.ctr + CTR_GROUPED, 1)] = q;
         return;
     }
     if (lane >= L) { gid_l = -1; hc_l = 0; }
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(256) void topk_group_select_kernel(const float* __r
 // chosen groups (and write the result if group_size == 1), pass B, write the result.  One wave per entry.
 __global__ __launch_bounds__(256) void topk_group_final_kernel(ExactWs ws, GroupWs gw, GroupOut o) {
     const int lane = threadIdx.x & 63;
-    const int over = ws.ctr[6];
+    const int over = ws.ctr[CTR_GROUPED];
     const int cap = gw.hits ? gw.hits : 1;
     const int L = o.limit;
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < over; i += gridDim.x * 4) {
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(256) void topk_exact_prepare_kernel(ExactWs ws, con
         from_seg = last != 0ull && cert_segments_cover(cert, q, lb, key_score(last));
     }
     int j = 0;
-    if (lane == 0) j = atomicAdd(ws.ctr + (from_seg ? 5 : 0), 1);
+    if (lane == 0) j = atomicAdd(ws.ctr + (from_seg ? CTR_FROM_SEGS : CTR_UNCERTIFIED), 1);
     j = __builtin_amdgcn_readfirstlane(j);
     if (from_seg) j = ws.cap - 1 - j;
     if (lane == 0) {

@@ -39,7 +39,7 @@ for rep in range(3):
         msg.append((q, missing, extra))
     print("rep", rep, "bad queries", len(bad), msg, flush=True)
     if bad and os.environ.get("DUMP", "1") == "1":
-        # layout of api.hip's workspace for this search (hist | per part: counts, segments | prelist | final lists | scores)
+        # layout of search.hip's workspace for this search (hist | per part: counts, segments | prelist | final lists | scores)
         lib = _lib.load()
         total = lib.revo_debug_read_workspace(G._h, 0, 0, None)
         buf = np.zeros(total, np.uint8)

@@ -71,9 +71,9 @@ def test_product_has_no_oracle_import():
 
 
 def test_host_paths_under_address_and_ub_sanitizers():
-    """api.hip's host code (argument validation, the checkpoint name / size map, error strings, handle lifetime,
-    graceful failure without a device) compiled with -fsanitize=address,undefined and driven through every entry
-    point by tests/native/abi_host_check.cpp.  (GPU sanitizers are not available on this pool: CPU build only.)"""
+    """The host code of api.hip and search.hip (argument validation, the checkpoint name / size map, error strings,
+    handle lifetime, graceful failure without a device) compiled with -fsanitize=address,undefined and driven through
+    every entry point by tests/native/abi_host_check.cpp.  (GPU sanitizers are not available on this pool: CPU build only.)"""
     import subprocess
     csrc = os.path.join(ROOT, "revers-o_amd", "csrc")
     subprocess.run(["make", "-C", csrc, "-j", "4", "all", "asan"], check=True, capture_output=True, timeout=900)

@@ -639,7 +639,7 @@ def test_config4_gallery_10m_x_1536(dev):
     ms, mi, mc = engine.merge_topk(torch.stack(parts_s), torch.stack(parts_i), k)
     assert torch.equal(mi, i) and torch.equal(ms, s) and torch.equal(mc, c)
     plan = G.search_plan(Q, k)
-    assert plan["scan256"] and plan["ksel"] == 64          # 10 M rows: the wide candidate lists (api.hip SEARCH_WIDE_ROWS)
+    assert plan["scan256"] and plan["ksel"] == 64          # 10 M rows: the wide candidate lists (search.hip SEARCH_WIDE_ROWS)
     G.close()
 
 
