@@ -132,6 +132,20 @@ int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst,
 int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
                          float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
                          void* stream);
+/* LARGE K: the same search for 1 <= k <= 1024, same arguments, same result contract word for word (EXACTNESS, FILTERED,
+ * threshold, index_offset, padding, the filter's lifecycle).  Needs the fp32 master rows (keep_f32 = 0: status -2).  It
+ * takes its own path for every k (the k <= 50 path of revo_search_topk cannot be widened: 32 or 64 candidates per query):
+ * the k-th best bf16 score of a sample of the first rows bounds where the answer can start; one MFMA pass histograms every
+ * allowed row above that; the histogram gives a band {bf16 score >= b} that provably holds every row of the exact top-k,
+ * ties included (b = h - 2 eps, h = a score that k rows reach in bf16); a collecting pass gathers the band, which is
+ * re-scored in fp32 (the same chain as every other re-score: the same bits) and sorted.  A query whose band may exceed
+ * 8192 rows (thousands of rows within the error bound of its k-th score: near-duplicates) is answered by an exhaustive
+ * fp32 scoring of its allowed rows and an exact selection instead.  On `stream`, no host round trip.  revo_search_stats
+ * after it: slot 3 = band rows re-scored in fp32, slot 6 = queries that took the exhaustive fallback.  Not for the
+ * two-phase sharded protocol below (k <= 50 there). */
+int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
+                               float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
+                               void* stream);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:
@@ -212,7 +226,9 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * certificate failed for (-1: the gallery has no fp32 rows), of those: brute-forced, queries the certificate was
  * evaluated for, rows the exact passes re-scored, of the failed queries: resolved from what the scan had kept (no second
  * pass over the gallery: searches with k > 25 scan with an admission margin for that), grouped search
- * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), 0, 0 } */
+ * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), revo_search_topk_large: queries
+ * that took the exhaustive fallback (0 after every other search), 0 }.  After revo_search_topk_large slot 3 counts the rows
+ * of the bands it re-scored and slots 0, 1, 2, 4, 5 are 0. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */
@@ -284,7 +300,7 @@ int32_t revo_vit_read_residual(revo_vit* vit, int32_t batch, float* dst, void* s
 int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch, void* dst, void* stream);
 /* how the certificate treats the handle's searches: 0 = certificate + fallback (the product library's only behaviour),
  * 1 = every query takes the collecting pass, 2 = every query takes the brute-force pass -- and every query of a grouped
- * search the grouped fp32 passes (1 and 2: parity tests of the fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
+ * search the grouped fp32 passes, and every query of revo_search_topk_large its exhaustive fallback (1 and 2: parity tests of the fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
 int32_t revo_search_set_mode(revo_gallery* g, int32_t mode);
 /* phase groups of the persistent 256 x 256 GEMM (an experiment, measured in round 5 and not adopted): 0 / 1 = off (all
  * workgroups in step), 2..4 = that many groups, a workgroup of group g doing the first (g + 1) / groups of its first tile at the start and the

@@ -49,6 +49,7 @@ SIGNATURES = {
     "revo_gallery_clear": (_i32, [_p]),
     "revo_gallery_read": (_i32, [_p, _i64, _i64, _p, _i32]),
     "revo_search_topk": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
+    "revo_search_topk_large": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
     "revo_search_ksel": (_i32, [_i32]),
     "revo_search_set_total_rows": (_i32, [_p, _i64]),
     "revo_search_set_filter": (_i32, [_p, _p, _i64, _i32, _p]),

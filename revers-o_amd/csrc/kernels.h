@@ -189,6 +189,7 @@ enum ExactCtr : int {
     CTR_MODE3_FAILED,    // mode 3: failed (counted only)
     CTR_FROM_SEGS,       // uncertified queries resolved from the scan's segments (numbered from the back)
     CTR_GROUPED,         // grouped searches: queries sent to the grouped fallback (GroupWs)
+    CTR_LARGE_FALLBACK,  // large-k searches: queries sent to the exhaustive fallback (LargeWs)
     CTR_SLOTS
 };
 struct ExactWs {
@@ -339,6 +340,44 @@ int launch_topk_select_rows(const float* scores, long ld, int n, int Q, uint64_t
                             uint32_t* tau0, int ksel, uint32_t* hist, int hist_buckets, int hist_shift, hipStream_t st,
                             uint32_t* tau_copy = nullptr, float est_z = 0.f, const uint32_t* allow = nullptr);
 // (est_z != 0: tau0[q] = max(KSEL-th best score, mean + est_z * sigma of the row's scores): an estimated admission level)
+// ---- large-k search (revo_search_topk_large; topk_large.hip): sample bound, count pass, level, collect
+// of the band, fp32 finish; queries whose band may exceed LARGE_CAP rows take the exhaustive fallback
+constexpr int LARGE_K_MAX = 1024;
+constexpr int LARGE_NB = 4096;         // count-pass buckets per query (about eps / 4 each)
+constexpr int LARGE_CAP = 8192;        // band rows per query: what the finish sorts in LDS (64 KiB of keys)
+constexpr int LARGE_LVL = 8;           // floats per query in LargeWs::lvl: lo, bucket base, 1 / step, step, eps
+constexpr int LARGE_FB_SLICES = 256;   // gallery slices of the fallback's scoring pass
+struct LargeWs {
+    float* lvl;            // [Q][LARGE_LVL]
+    uint32_t* hist;        // [Q][LARGE_NB] (zeroed by the search's first kernel)
+    int* ctr;              // [0] band entries, [1] fallback entries (zeroed with hist)
+    int* band_q; float* band_lb; int* band_cnt;   // [Q]: band entry j's query, collect bound, rows collected
+    bf16_t* band_qb;       // [Q][D] band entry j's bf16 query row (the collect pass reads compacted query tiles)
+    uint64_t* band_col;    // [Q][LARGE_CAP] band entry j's keys: bf16 keys from the collect pass, fp32 keys after the re-score
+    int* fb_q;             // [Q] fallback entry i's query
+    float* fb_scores;      // [F][N] the fp32 scores of one round of fallback entries (NaN: row not allowed)
+    int F;
+    int* stats;            // ExactWs::ctr of the handle (CTR_COLLECTED, CTR_LARGE_FALLBACK)
+};
+struct LargeCountArgs {
+    const bf16_t* Qb; long ldq; const bf16_t* Gb; long ldg;
+    long N; int D, nq, splits;
+    const float* lvl; uint32_t* hist;
+    const uint32_t* allow;       // optional allow-bitmap, padded to whole 256-row tiles
+};
+// pre: [Q][ld] bf16-GEMM scores of the first n_s rows (n_s = 0: no sample, lo = -inf)
+int launch_topk_large_sample(const float* pre, long ld, int n_s, const uint32_t* allow, const float* qstat, const uint32_t* gstat,
+                             int D, int Q, int k, int has_thr, float thr, const LargeWs& ws, hipStream_t st);
+int launch_topk_large_count(const bf16_t* Qb, long ldq, const bf16_t* Gb, long ldg, long N, int D, int Q, const LargeWs& ws,
+                            const uint32_t* allow, hipStream_t st);
+int launch_topk_large_level(const LargeWs& ws, const bf16_t* Qb, long ldq, int D, int Q, int k, int force_fallback, hipStream_t st);
+// band entries: fp32 re-score, sort, results to row band_q[j] of the outputs (launches sized for max_entries)
+int launch_topk_large_finish(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, int D,
+                             int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
+                             int* out_counts, hipStream_t st);
+int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, long N,
+                               int D, int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
+                               int* out_counts, const uint32_t* allow, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

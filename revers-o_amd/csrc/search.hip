@@ -80,6 +80,8 @@ struct revo_gallery {
     // search's workspace: top-GROUP_K1 scores | indices | counts | fallback queries | chosen groups
     DeviceBuffer<int32_t> groups; int64_t groups_rows = -1;
     DeviceBuffer<> gbuf;
+    // revo_search_topk_large's workspace (revo::LargeWs, carved per search)
+    DeviceBuffer<> lbuf;
     revo::CertArgs cert_args(float* cert_out) const {
         revo::CertArgs c{};
         c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
@@ -287,14 +289,10 @@ static double upper_normal_quantile(double p) {
            (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
 }
 
-// Phase 1 of a search: normalise the queries, scan the gallery (bf16 MFMA scores) and leave each query's best
-// ksel candidates, sorted best first, in the handle (cand / cand_stride).  The gallery must not be empty.
-static int search_candidates(revo_gallery* g, const float* queries, int Q, int ksel, const uint32_t* allow, hipStream_t st,
-                             uint32_t* bounds = nullptr, int top_m = 0, bool margin = false) {
+// The handle's per-query arrays, grown to hold Q queries (every search that normalises queries into the handle)
+static int search_grow_queries(revo_gallery* g, int Q, hipStream_t st) {
     using namespace revo;
     const int D = g->D;
-    const long N = g->size;
-    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
     if (g->q_cap < Q) {
         g->q_cap = 0; g->xw = ExactWs{};
         CHECK_RC(g->qf.grow((size_t)Q * D * 4, st)); CHECK_RC(g->qb.grow((size_t)Q * D * 2, st));
@@ -314,6 +312,18 @@ static int search_candidates(revo_gallery* g, const float* queries, int Q, int k
         }
         g->q_cap = Q;
     }
+    return 0;
+}
+
+// Phase 1 of a search: normalise the queries, scan the gallery (bf16 MFMA scores) and leave each query's best
+// ksel candidates, sorted best first, in the handle (cand / cand_stride).  The gallery must not be empty.
+static int search_candidates(revo_gallery* g, const float* queries, int Q, int ksel, const uint32_t* allow, hipStream_t st,
+                             uint32_t* bounds = nullptr, int top_m = 0, bool margin = false) {
+    using namespace revo;
+    const int D = g->D;
+    const long N = g->size;
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, Q, st));
     // the admission margin only pays where the certificate is expected to fail (see revo_search_topk) and only the
     // 256 x 256 scan has segments; it needs the fp32 rows (no certificate without them)
     margin = margin && g->keep_f32 && N >= SEARCH_SMALL_ROWS;
@@ -514,6 +524,110 @@ extern "C" int32_t revo_search_topk(revo_gallery* g, const float* queries, int32
     API_END
 }
 
+// ---- large k (include/revo.h revo_search_topk_large; topk_large.hip)
+constexpr int LARGE_CHUNK = 1024;   // queries per pass of the pipeline (the workspace is sized for one chunk)
+// Rows of the large-k sample: what the pre-pass of the k <= 50 search would take, at least 64 k (the sample's k-th best is then
+// about the gallery's (N / n_s) k-th: fewer rows counted and a tighter start for the buckets), at most a quarter of the
+// gallery and 512 MB of scores.  None below the small-gallery size: lo = -inf there, the count pass histograms every row.
+static long large_sample_rows(int Q, long N, int k) {
+    if (N < SEARCH_SMALL_ROWS) return 0;
+    long n = search_prepass_rows(Q, N);
+    const long want = (64l * k + 255) / 256 * 256;
+    if (n < want) n = want;
+    if (n > N / 4) n = (N / 4) / 256 * 256;
+    const long cap = ((512l << 20) / (4l * Q)) / 256 * 256;
+    return n < cap ? n : cap;
+}
+// Fallback entries per round: F score rows of N floats, at most 256 MB (and at least one row, whatever N is)
+static int large_fallback_rows(int Qc, long N) {
+    long f = (256l << 20) / (4l * (N > 0 ? N : 1));
+    f = f < 1 ? 1 : f;
+    return (int)(f < Qc ? f : Qc);
+}
+static int search_topk_large(revo_gallery* g, const float* queries, int Q, int k, int has_thr, float thr, long index_offset,
+                             float* scores, long long* indices, int* counts, const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    const int QC = Q < LARGE_CHUNK ? Q : LARGE_CHUNK;
+    if (g->size == 0) {
+        for (int c0 = 0; c0 < Q; c0 += QC)
+            CHECK_RC(launch_topk_fill_empty(scores + (size_t)c0 * k, indices + (size_t)c0 * k, counts + c0,
+                                            Q - c0 < QC ? Q - c0 : QC, k, st));
+        return 0;
+    }
+    const int D = g->D;
+    const long N = g->size;
+    // (the two-phase protocol's state refers to the handle's query rows, which this search overwrites)
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, QC, st));
+    REVO_REQUIRE(g->xw.ctr, "search_topk_large: no certificate workspace");
+    const long n_s = large_sample_rows(QC, N, k);
+    LargeWs ws{};
+    ws.F = large_fallback_rows(QC, N);
+    ws.stats = g->xw.ctr;
+    float* pre = nullptr; uint32_t* zeroed = nullptr;
+    CHECK_RC(carve_buffer(g->lbuf, st, [&](Layout& l) {
+        zeroed = l.take<uint32_t>(64 + (size_t)QC * LARGE_NB);       // entry counters | histograms
+        ws.lvl = l.take<float>((size_t)QC * LARGE_LVL);
+        ws.band_q = l.take<int>(QC); ws.band_lb = l.take<float>(QC); ws.band_cnt = l.take<int>(QC);
+        ws.band_qb = l.take<bf16_t>((size_t)QC * D);
+        ws.band_col = l.take<uint64_t>((size_t)QC * LARGE_CAP);
+        ws.fb_q = l.take<int>(QC);
+        ws.fb_scores = l.take<float>((size_t)ws.F * N);
+        pre = l.take<float>((size_t)QC * n_s);
+    }));
+    ws.ctr = (int*)zeroed; ws.hist = zeroed + 64;
+    for (int c0 = 0; c0 < Q; c0 += QC) {
+        const int Qc = Q - c0 < QC ? Q - c0 : QC;
+        float* s_out = scores + (size_t)c0 * k; long long* i_out = indices + (size_t)c0 * k; int* c_out = counts + c0;
+        { ProfScope ps("search_prep", st);
+          // the first chunk also clears the handle's counters (revo_search_stats: the whole search's)
+          CHECK_RC(launch_l2norm_rows(queries + (size_t)c0 * D, D, g->qf.p, D, g->qb.p, D, Qc, D, st, 1, g->qstat.p, nullptr,
+                                      c0 == 0 ? (uint32_t*)g->xw.ctr : nullptr, c0 == 0 ? CTR_SLOTS : 0, zeroed,
+                                      64 + (long)Qc * LARGE_NB)); }
+        { ProfScope ps("large_sample", st);
+          if (n_s > 0) {
+              GemmArgs ga{};
+              ga.A = g->qb.p; ga.lda = D; ga.B = g->gb.p; ga.ldb = D; ga.M = Qc; ga.N = (int)n_s; ga.K = D;
+              ga.C = pre; ga.ldc = n_s; ga.prefer256 = 1;
+              if (Qc <= 128 && n_s % 64 == 0) CHECK_RC(launch_gemm_f32_ring(ga, st));
+              else CHECK_RC(launch_gemm(EPI_F32, ga, st));
+          }
+          CHECK_RC(launch_topk_large_sample(pre, n_s, (int)n_s, allow, g->qstat.p, g->gstat.p, D, Qc, k, has_thr, thr, ws, st)); }
+        { ProfScope ps("large_count", st);
+          CHECK_RC(launch_topk_large_count(g->qb.p, D, g->gb.p, D, N, D, Qc, ws, allow, st)); }
+        { ProfScope ps("large_level", st);
+          CHECK_RC(launch_topk_large_level(ws, g->qb.p, D, D, Qc, k, g->mode == 2, st)); }
+        { ProfScope ps("large_collect", st);
+          Collect256Args ca{};
+          ca.Qb = ws.band_qb; ca.ldq = D; ca.Gb = g->gb.p; ca.ldg = D; ca.N = N; ca.D = D;
+          ca.n_q = ws.ctr; ca.lb = ws.band_lb; ca.cnt = ws.band_cnt; ca.col = ws.band_col; ca.cap = LARGE_CAP; ca.allow = allow;
+          CHECK_RC(launch_topk_collect256(ca, Qc, st)); }
+        { ProfScope ps("large_finish", st);
+          CHECK_RC(launch_topk_large_finish(ws, Qc, g->qf.p, D, g->gf.p, D, D, k, has_thr, thr, index_offset, s_out, i_out, c_out,
+                                            st)); }
+        { ProfScope ps("large_fallback", st);
+          CHECK_RC(launch_topk_large_fallback(ws, Qc, g->qf.p, D, g->gf.p, D, N, D, k, has_thr, thr, index_offset, s_out, i_out,
+                                              c_out, allow, st)); }
+    }
+    return 0;
+}
+
+extern "C" int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t Q, int32_t k, int32_t has_thr,
+                                          float thr, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
+                                          void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (queries || Q == 0), "search_topk_large: null argument");
+    REVO_REQUIRE(Q >= 0, "search_topk_large: negative query count");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_topk_large: k must be in [1, 1024]");
+    REVO_REQUIRE(g->keep_f32, "search_topk_large: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    if (Q == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_topk_large(g, queries, Q, k, has_thr, thr, index_offset, scores, (long long*)indices, counts, allow,
+                             (hipStream_t)stream);
+    API_END
+}
+
 // ---- the same search in two phases, for a gallery that is row-sharded over several GPUs (include/revo.h)
 extern "C" int32_t revo_search_candidates(revo_gallery* g, const float* queries, int32_t Q, int32_t k, int32_t top_m,
                                           uint32_t* bounds, void* stream) {
@@ -653,6 +767,7 @@ extern "C" int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* strea
     REVO_HIP_CHECK(hipMemcpy(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost));
     out8[0] = c[CTR_UNCERTIFIED] + c[CTR_MODE3_FAILED] + c[CTR_FROM_SEGS]; out8[1] = c[CTR_BRUTEFORCE];
     out8[2] = c[CTR_CHECKED]; out8[3] = c[CTR_COLLECTED]; out8[4] = c[CTR_FROM_SEGS]; out8[5] = c[CTR_GROUPED];
+    out8[6] = c[CTR_LARGE_FALLBACK];
     return 0;
     API_END
 }

@@ -273,7 +273,8 @@ class Gallery:
         indices [Q,k] int64, counts [Q] int32), best first, padded with -inf/-1
         past ``counts`` (the reference's ``limit`` / ``score_threshold`` semantics,
         core_system.py:659-664).  ``allow`` (device tensor, bool [len] or a packed int32 bitmap): search only those
-        rows -- exactly the result an unfiltered search of a gallery holding just the allowed rows would give."""
+        rows -- exactly the result an unfiltered search of a gallery holding just the allowed rows would give.  k <= 1024
+        (51 and up: include/revo.h, LARGE K)."""
         _require_cuda(queries, "queries", self.device)
         q = queries.detach().to(torch.float32).contiguous()
         if q.dim() == 1:
@@ -284,11 +285,13 @@ class Gallery:
         scores = torch.empty((Q, k), dtype=torch.float32, device=q.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
         counts = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        # k <= 50: the certified scan; 51 <= k <= 1024: the large-k path (include/revo.h, LARGE K), same result contract
+        fn = "revo_search_topk" if k <= 50 else "revo_search_topk_large"
         with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_topk(
+            _lib.check(getattr(self._lib, fn)(
                 self._h, _lib.ptr(q), Q, int(k), int(score_threshold is not None),
                 float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_topk")
+                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), fn)
         return scores, idx, counts
 
     @contextlib.contextmanager
@@ -354,7 +357,7 @@ class Gallery:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.revo_search_stats(self._h, out, _lib.current_stream()), "revo_search_stats")
         return {"uncertified": int(out[0]), "bruteforced": int(out[1]), "checked": int(out[2]), "collected_rows": int(out[3]),
-                "from_segments": int(out[4]), "grouped_fallback": int(out[5])}
+                "from_segments": int(out[4]), "grouped_fallback": int(out[5]), "large_k_fallback": int(out[6])}
 
     def set_total_rows(self, total_rows):
         """This handle holds ONE SHARD of a row-sharded gallery of ``total_rows`` rows (0: forget): its two-phase scans
