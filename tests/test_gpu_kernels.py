@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import _kernel_bounds as kb
 import reverso_amd  # noqa: F401
 from reverso_amd import _lib
 
@@ -123,6 +124,7 @@ def test_layernorm(lib, dev, W, out_bf16):
     ref = torch.nn.functional.layer_norm(x, (W,), w, b, 1e-5)
     tol = 0.04 if out_bf16 else 2e-5
     assert (out.float() - ref).abs().max().item() <= tol
+    assert kb.ratio(out, kb.LayerNorm.reference(x, w, b, 1e-5), kb.LayerNorm.bound(x, w, b, 1e-5, out_bf16)) <= 1.0
 
 
 @pytest.mark.parametrize("B,S,W,H", [(64, 577, 1024, 8), (48, 197, 768, 8), (5, 577, 1024, 8), (32, 1025, 1536, 8), (200, 17, 192, 3)])
@@ -238,6 +240,10 @@ def test_rope(lib, dev):
     got = qkv.float().cpu().double().reshape(B, S, 3, H, hd)
     assert (got[:, :, 0] - q).abs().max().item() <= 0.03
     assert (got[:, :, 1] - k).abs().max().item() <= 0.03
+    cs_cpu = cs.cpu()
+    for i in (0, 1):                                                        # the per-element bound (tests/_kernel_bounds.py)
+        x = ref_in[:, :, i].transpose(1, 2)
+        assert kb.ratio(got[:, :, i].transpose(1, 2), kb.Rope.reference(x, cs_cpu), kb.Rope.bound(x, cs_cpu)) <= 1.0
     assert torch.equal(got[:, :, 2], ref_in[:, :, 2])                       # v untouched
     assert torch.equal(got[:, 0, :2], ref_in[:, 0, :2])                     # cls token: identity rotation
 
@@ -258,6 +264,8 @@ def test_attention(lib, dev, B, S, H, hd):
     ref = (att @ v).transpose(1, 2).reshape(B * S, W)
     err = (out.float() - ref).abs().max().item()
     assert err <= 0.03, err
+    q, k, v = kb.attention_split(qkv, B, S, H, hd)
+    assert kb.ratio(kb.attention_unsplit(out, B, S, H, hd), kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v)) <= 1.0
 
 
 def test_attention_peaked_softmax(lib, dev):
