@@ -146,6 +146,26 @@ int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t n_querie
 int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
                                float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
                                void* stream);
+/* ---- near-duplicate pairs of one gallery (no reference counterpart; same exactness contract as the searches)
+ * PAIRS.  The result is exactly the set of pairs (i, j), i < j, of rows that the handle's filter allows (both of them;
+ * revo_search_set_filter, with its lifecycle: a filter set for another gallery size gives status -2) whose fp32 score
+ * reaches `threshold`.  A score is the fma chain of every re-score in this library (EXACTNESS) over the two fp32 master
+ * rows: the same bits a search returns for the same two fp32 rows, and, the product inside fmaf being commutative,
+ * score(i, j) == score(j, i) bit for bit.  Pairs are ordered by (i asc, j asc); two calls give identical bytes.  (i, i) is
+ * never returned; identical rows at distinct indices are.  How: one MFMA pass over the upper triangle of 256 x 256 tiles of
+ * the gallery's bf16 rows keeps every pair whose bf16 score is within the certificate's rounding bound of the threshold
+ * (for a row against a row), and those candidates are re-scored in fp32 and sorted on the device.
+ * revo_gallery_pairs computes the result into the handle's workspace and writes the pair count to the host *n_pairs.  Unlike
+ * the searches it is SYNCHRONOUS on `stream`: it reads the candidate count between its passes.  Needs the fp32 master rows
+ * (keep_f32 = 0: status -2) and row indices below 2^31.  A threshold so low that more than 2^28 candidate pairs qualify
+ * gives status -2, the count in revo_last_error().  revo_search_stats after it: slot 3 = candidate pairs re-scored in fp32,
+ * slot 7 = join passes run (1, or 2 when the candidate workspace had to grow), every other slot 0.
+ * revo_gallery_pairs_read copies result entries [start, start + n) to pairs ([n][2] int64) and scores ([n] fp32), host or
+ * device memory (dst_on_device).  A result stays valid until the next revo_gallery_pairs call or a change of the gallery's
+ * rows: after an append or a clear, or with no result, it gives status -2, as does a range past the result. */
+int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream);
+int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,
+                                int32_t dst_on_device);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:
@@ -227,8 +247,9 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * evaluated for, rows the exact passes re-scored, of the failed queries: resolved from what the scan had kept (no second
  * pass over the gallery: searches with k > 25 scan with an admission margin for that), grouped search
  * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), revo_search_topk_large: queries
- * that took the exhaustive fallback (0 after every other search), 0 }.  After revo_search_topk_large slot 3 counts the rows
- * of the bands it re-scored and slots 0, 1, 2, 4, 5 are 0. */
+ * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes (0 after every search) }.
+ * After revo_search_topk_large slot 3 counts the rows of the bands it re-scored and slots 0, 1, 2, 4, 5 are 0; after
+ * revo_gallery_pairs see PAIRS. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */

@@ -902,6 +902,35 @@ class SimpleReverso:
             items.append({"image": img, "score": r.score, "filename": filename, "bbox": payload.get("bbox")})
         return text, items
 
+    def find_duplicates(self, similarity_threshold=0.95, query_filter=None):
+        """Groups of near-duplicate regions in the loaded database: every stored region whose vector scores at least
+        ``similarity_threshold`` against another one, joined transitively (re-posted, re-compressed or re-cropped copies of
+        one picture).  ``query_filter`` restricts it to the points a Qdrant-style payload filter selects.  Returns
+        ``(text, groups)``: ``groups`` is a list of groups, each a list of ``{"filename", "image_source", "bbox", "id"}`` in
+        storage order.  The default 0.95 is a guess: no trained checkpoint has been run here (parity
+        unpinned), so what score separates copies from look-alikes is not measured."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        with self._lock:
+            db = self.vector_db
+            out = []
+            for grp in db.duplicate_row_groups(float(similarity_threshold), query_filter=query_filter):
+                members = []
+                for r in grp:
+                    payload = db.payloads[r]
+                    members.append({"filename": payload.get("filename", "Unknown"), "image_source": payload.get("image_source", ""),
+                                    "bbox": payload.get("bbox"), "id": db.ids[r]})
+                out.append(members)
+        if not out:
+            return f"No near-duplicates found at similarity threshold {similarity_threshold}", []
+        text = f"🎯 Found {len(out)} groups of near-duplicates:\n\n"
+        for g, members in enumerate(out):
+            text += f"{g + 1}. {len(members)} regions\n"
+            for m in members:
+                text += f"   {m['filename']}  (Source: {m['image_source']})\n"
+            text += "\n"
+        return text, out
+
     def visualize_detections(self, image, selected_region_index=None):
         """core_system.py:719-757 draws mask contours with OpenCV (UI cosmetics, out of scope);
         boxes are outlined with PIL so the UI keeps working."""

@@ -190,6 +190,7 @@ enum ExactCtr : int {
     CTR_FROM_SEGS,       // uncertified queries resolved from the scan's segments (numbered from the back)
     CTR_GROUPED,         // grouped searches: queries sent to the grouped fallback (GroupWs)
     CTR_LARGE_FALLBACK,  // large-k searches: queries sent to the exhaustive fallback (LargeWs)
+    CTR_PAIR_PASSES,     // revo_gallery_pairs: join passes run (1, or 2 after a workspace regrow)
     CTR_SLOTS
 };
 struct ExactWs {
@@ -378,6 +379,31 @@ int launch_topk_large_finish(const LargeWs& ws, int max_entries, const float* Qf
 int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, long N,
                                int D, int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
                                int* out_counts, const uint32_t* allow, hipStream_t st);
+// ---- near-duplicate pairs of one gallery (revo_gallery_pairs; pairs.hip): triangular self-join on the
+// 256 x 256 main loop, fp32 re-score of the candidates, radix sort of the kept pairs
+constexpr long PAIRS_WS_KEYS = 1l << 20;     // candidate keys the workspace holds before its first regrow
+constexpr long PAIRS_MAX_CAND = 1l << 28;    // candidate pairs a call may have (2 GiB of keys); more: status -2
+constexpr int PAIRS_SORT_BLOCKS = 2048;      // at most this many blocks per radix pass (the offsets scan is one workgroup)
+struct PairsJoinArgs {
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    long N; int D;
+    long T, pairs;                // set by the launcher: row tiles, tile pairs of the upper triangle
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    float thr;
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    unsigned long long* cnt;      // candidates found (counts past cap)
+    uint64_t* keys; long cap;     // [cap] candidate keys (i << 32) | j
+};
+int launch_pairs_join(const PairsJoinArgs& a, hipStream_t st);
+// fp32 score of candidates [0, n); those >= thr appended to out_keys ((i << b) | j) / out_scores, count in *kept
+int launch_pairs_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, float thr, int b,
+                         unsigned long long* kept, uint64_t* out_keys, float* out_scores, hipStream_t st);
+long pairs_sort_tile(long n);                // keys per block of a radix pass (cnt: 256 words per block)
+// ascending sort of n (key, value) entries over the low key_bits bits; the result is in (*out_keys, *out_vals), one of the
+// two buffer pairs
+int launch_pairs_sort(uint64_t* keys, float* vals, uint64_t* keys_alt, float* vals_alt, long n, int key_bits, uint32_t* cnt,
+                      uint64_t** out_keys, float** out_vals, hipStream_t st);
+int launch_pairs_emit(const uint64_t* keys, const float* vals, long n, int b, long long* pairs, float* scores, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

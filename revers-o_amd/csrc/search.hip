@@ -82,6 +82,11 @@ struct revo_gallery {
     DeviceBuffer<> gbuf;
     // revo_search_topk_large's workspace (revo::LargeWs, carved per search)
     DeviceBuffer<> lbuf;
+    // revo_gallery_pairs: its workspace (counters | candidate keys | kept keys and scores | sort buffers), the candidate keys
+    // that workspace holds, and the last result ([pairs_n][2] row pairs, [pairs_n] scores), valid until the rows change
+    DeviceBuffer<> pbuf; long pairs_cap = 0;
+    DeviceBuffer<long long> pair_idx; DeviceBuffer<float> pair_score;
+    int64_t pairs_n = 0; bool pairs_valid = false;
     revo::CertArgs cert_args(float* cert_out) const {
         revo::CertArgs c{};
         c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
@@ -194,6 +199,7 @@ extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     REVO_ON_DEVICE(g->device);
     REVO_HIP_CHECK(hipMemset(g->gstat.p, 0, 8));      // the row maxima of the certificate start over with the rows
     g->size = 0;
+    g->pairs_valid = false;
     return 0;
 }
 
@@ -205,6 +211,7 @@ extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64
     if (n == 0) return 0;
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
+    g->pairs_valid = false;
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
     for (int64_t done = 0; done < n; done += chunk_rows) {
@@ -748,6 +755,97 @@ extern "C" int32_t revo_search_groups(revo_gallery* g, const float* queries, int
     API_END
 }
 
+// ---- near-duplicate pairs of one gallery (include/revo.h revo_gallery_pairs; pairs.hip)
+extern "C" int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_pairs, "gallery_pairs: null argument");
+    REVO_REQUIRE(!std::isnan(threshold), "gallery_pairs: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "gallery_pairs: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    REVO_REQUIRE(g->size < (1ll << 31), "gallery_pairs: row indices must fit in 31 bits");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    g->pairs_valid = false;
+    const long N = g->size;
+    const int D = g->D;
+    // the handle's counters (revo_search_stats): this call's alone
+    CHECK_RC(search_grow_queries(g, 1, st));
+    REVO_REQUIRE(g->xw.ctr, "gallery_pairs: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept
+    uint64_t *cand = nullptr, *kept_k = nullptr; float *kept_v = nullptr, *alt_v = nullptr; uint32_t* hist = nullptr;
+    auto carve = [&](long cap) -> int {
+        CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+            cnt = l.take<unsigned long long>(2);
+            cand = l.take<uint64_t>(cap); kept_k = l.take<uint64_t>(cap);
+            kept_v = l.take<float>(cap); alt_v = l.take<float>(cap);
+            hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
+        }));
+        g->pairs_cap = cap;
+        return 0;
+    };
+    CHECK_RC(carve(g->pairs_cap > PAIRS_WS_KEYS ? g->pairs_cap : PAIRS_WS_KEYS));
+    PairsJoinArgs ja{};
+    ja.Gb = g->gb.p; ja.ldg = D; ja.N = N; ja.D = D; ja.gstat = g->gstat.p; ja.thr = threshold; ja.allow = allow;
+    unsigned long long n_cand = 0;
+    int passes = 0;
+    for (;;) {
+        ja.cnt = cnt; ja.keys = cand; ja.cap = g->pairs_cap;
+        REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
+        { ProfScope ps("pairs_join", st);
+          CHECK_RC(launch_pairs_join(ja, st)); }
+        ++passes;
+        REVO_HIP_CHECK(hipMemcpyAsync(&n_cand, cnt, sizeof(n_cand), hipMemcpyDeviceToHost, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        REVO_REQUIRE(n_cand <= (unsigned long long)PAIRS_MAX_CAND,
+                     "gallery_pairs: " + std::to_string(n_cand) + " candidate pairs exceed the limit of " +
+                         std::to_string(PAIRS_MAX_CAND) + " (raise the threshold)");
+        if (n_cand <= (unsigned long long)g->pairs_cap) break;
+        REVO_REQUIRE(passes == 1, "gallery_pairs: the candidate count changed between two joins");
+        CHECK_RC(carve((long)n_cand));     // grown to the counted size, then joined once more
+    }
+    // fp32 re-score; the kept entries as (i << b) | j, b = the bits of the largest row index
+    int b = 1;
+    while (N > 1 && (1l << b) < N) ++b;
+    unsigned long long n_kept = 0;
+    { ProfScope ps("pairs_rescore", st);
+      CHECK_RC(launch_pairs_rescore(cand, (long)n_cand, g->gf.p, D, D, threshold, b, cnt + 1, kept_k, kept_v, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    uint64_t* sk; float* sv;
+    { ProfScope ps("pairs_sort", st);
+      CHECK_RC(launch_pairs_sort(kept_k, kept_v, cand, alt_v, (long)n_kept, 2 * b, hist, &sk, &sv, st)); }
+    CHECK_RC(g->pair_idx.grow((size_t)(n_kept > 0 ? n_kept : 1) * 16, st));
+    CHECK_RC(g->pair_score.grow((size_t)(n_kept > 0 ? n_kept : 1) * 4, st));
+    CHECK_RC(launch_pairs_emit(sk, sv, (long)n_kept, b, g->pair_idx.p, g->pair_score.p, st));
+    const int stats[2] = {(int)n_cand, passes};    // slot 3 = candidates re-scored, slot 7 = join passes
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    g->pairs_n = (int64_t)n_kept;
+    g->pairs_valid = true;
+    *n_pairs = (int64_t)n_kept;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,
+                                           int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_pairs_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "gallery_pairs_read: negative start or count");
+    REVO_REQUIRE((pairs && scores) || n == 0, "gallery_pairs_read: null argument");
+    REVO_REQUIRE(g->pairs_valid, "gallery_pairs_read: no result (call revo_gallery_pairs again after the rows change)");
+    REVO_REQUIRE(start + n <= g->pairs_n, "gallery_pairs_read: range past the result's " + std::to_string(g->pairs_n) + " pairs");
+    if (n == 0) return 0;
+    REVO_ON_DEVICE(g->device);
+    const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    REVO_HIP_CHECK(hipMemcpy(pairs, g->pair_idx.p + start * 2, (size_t)n * 16, kind));
+    REVO_HIP_CHECK(hipMemcpy(scores, g->pair_score.p + start, (size_t)n * 4, kind));
+    return 0;
+    API_END
+}
+
 #ifdef REVO_EXPERIMENTS   // librevo.so cannot be put into a non-exact mode
 extern "C" int32_t revo_search_set_mode(revo_gallery* g, int32_t mode) {
     REVO_REQUIRE(g && mode >= 0 && mode <= 3, "search_set_mode: mode must be 0..3");
@@ -767,7 +865,7 @@ extern "C" int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* strea
     REVO_HIP_CHECK(hipMemcpy(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost));
     out8[0] = c[CTR_UNCERTIFIED] + c[CTR_MODE3_FAILED] + c[CTR_FROM_SEGS]; out8[1] = c[CTR_BRUTEFORCE];
     out8[2] = c[CTR_CHECKED]; out8[3] = c[CTR_COLLECTED]; out8[4] = c[CTR_FROM_SEGS]; out8[5] = c[CTR_GROUPED];
-    out8[6] = c[CTR_LARGE_FALLBACK];
+    out8[6] = c[CTR_LARGE_FALLBACK]; out8[7] = c[CTR_PAIR_PASSES];
     return 0;
     API_END
 }

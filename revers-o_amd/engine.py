@@ -294,6 +294,22 @@ class Gallery:
                 _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), fn)
         return scores, idx, counts
 
+    def pairs(self, threshold, allow=None):
+        """Near-duplicate pairs of the gallery (include/revo.h, PAIRS): every pair of rows ``i < j`` whose fp32 score
+        reaches ``threshold``, both allowed by ``allow`` (as in :meth:`search`).  Returns ``(pairs [n, 2] int64, scores [n]
+        fp32)`` device tensors ordered by ``(i, j)``, exactly what an exhaustive fp32 scoring of every pair would give.
+        Synchronous (the kernels read the candidate count between their passes)."""
+        n = C.c_int64()
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_gallery_pairs(self._h, float(threshold), C.byref(n), _lib.current_stream()),
+                       "revo_gallery_pairs")
+            n = int(n.value)
+            pairs = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+            scores = torch.empty((n,), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.revo_gallery_pairs_read(self._h, 0, n, _lib.ptr(pairs), _lib.ptr(scores), 1),
+                       "revo_gallery_pairs_read")
+        return pairs, scores
+
     @contextlib.contextmanager
     def _groups(self, groups):
         """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.
@@ -357,7 +373,8 @@ class Gallery:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.revo_search_stats(self._h, out, _lib.current_stream()), "revo_search_stats")
         return {"uncertified": int(out[0]), "bruteforced": int(out[1]), "checked": int(out[2]), "collected_rows": int(out[3]),
-                "from_segments": int(out[4]), "grouped_fallback": int(out[5]), "large_k_fallback": int(out[6])}
+                "from_segments": int(out[4]), "grouped_fallback": int(out[5]), "large_k_fallback": int(out[6]),
+                "join_passes": int(out[7])}
 
     def set_total_rows(self, total_rows):
         """This handle holds ONE SHARD of a row-sharded gallery of ``total_rows`` rows (0: forget): its two-phase scans

@@ -159,6 +159,40 @@ class GroupsResult:
     groups: list
 
 
+@dataclass
+class DuplicatePair:
+    """Two points whose vectors score at least the threshold of :meth:`GalleryStore.duplicate_pairs`."""
+    id_a: str
+    id_b: str
+    score: float
+
+
+def connected_groups(pairs, n):
+    """The connected components with at least two members of the graph on rows ``0 .. n - 1`` whose edges are ``pairs``
+    (int array [m, 2]): lists of rows, each in ascending order, the lists ordered by their first row.  Union-find on numpy."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    parent = np.arange(n, dtype=np.int64)
+
+    def find(x):
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:
+            parent[x], x = root, parent[x]
+        return root
+
+    for a, b in pairs.tolist():
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)        # the smaller row is the root: a component's root is its first row
+    rows = np.unique(pairs)
+    roots = np.array([find(r) for r in rows.tolist()], dtype=np.int64)
+    groups = {}
+    for r, root in zip(rows.tolist(), roots.tolist()):
+        groups.setdefault(root, []).append(r)
+    return [groups[root] for root in sorted(groups) if len(groups[root]) >= 2]
+
+
 class GalleryStore:
     def __init__(self, dim, device=0, capacity=65536, collection="simple_reverso", path=None, _fresh=True, build_info=None):
         """``build_info``: what the vectors were made from and how (source folder, model, region mode, ...), written into
@@ -261,6 +295,28 @@ class GalleryStore:
             hits = [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[r][:hc[r]], i[r][:hc[r]])]
             out.append(PointGroup(values[gid[r]], hits))
         return GroupsResult(out)
+
+    def _pairs(self, score_threshold, query_filter):
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        pairs, scores = self.gallery.pairs(float(score_threshold), allow=allow)
+        return pairs.cpu().numpy(), scores.cpu().numpy()
+
+    def duplicate_pairs(self, score_threshold, query_filter=None):
+        """Every pair of points (both selected by ``query_filter``, if given) whose vectors score at least
+        ``score_threshold``: :class:`DuplicatePair` entries in row order (first point, then second).  Exact (include/revo.h,
+        PAIRS)."""
+        pairs, scores = self._pairs(score_threshold, query_filter)
+        return [DuplicatePair(self.ids[a], self.ids[b], float(s)) for (a, b), s in zip(pairs.tolist(), scores.tolist())]
+
+    def duplicate_groups(self, score_threshold, query_filter=None):
+        """The groups of near-duplicates: connected components (at least two points) of the graph whose edges are the
+        pairs of :meth:`duplicate_pairs`, as lists of point ids.  Members in row order; groups ordered by their first row."""
+        return [[self.ids[r] for r in grp] for grp in self.duplicate_row_groups(score_threshold, query_filter)]
+
+    def duplicate_row_groups(self, score_threshold, query_filter=None):
+        """:meth:`duplicate_groups` as lists of row indices (the places of the points in ``ids`` / ``payloads``)."""
+        pairs, _ = self._pairs(score_threshold, query_filter)
+        return connected_groups(pairs, len(self))
 
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
