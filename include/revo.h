@@ -166,6 +166,32 @@ int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t n_
 int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream);
 int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,
                                 int32_t dst_on_device);
+/* ---- range search: every row above a threshold, per query (the reference's score_threshold without its limit,
+ * core_system.py:659-664)
+ * RANGE.  For each query q the result is exactly the rows the handle's filter allows (revo_search_set_filter, with its
+ * lifecycle: a filter set for another gallery size gives status -2) whose fp32 score is >= threshold.  Scores and tie rule
+ * are the EXACTNESS contract of revo_search_topk: every score comes from the one fma chain, so it has the bits the other
+ * searches return.  Within a query, results are ordered by (score desc, row index asc).  Indices are row + index_offset.
+ * offsets[q] .. offsets[q + 1] is query q's slice (CSR), with offsets[0] = 0 and offsets[n_queries] = *n_results.  Two calls
+ * give identical bytes.  How: one MFMA pass over the gallery's bf16 rows per chunk of queries keeps every row whose bf16
+ * score is within the certificate's rounding bound of the threshold for that query, and those candidates are re-scored in
+ * fp32 and sorted on the device.
+ * revo_search_range computes the result into the handle and writes its entry count to the host *n_results.  Like
+ * revo_gallery_pairs it is SYNCHRONOUS on `stream`.  Needs the fp32 master rows (keep_f32 = 0: status -2); a NaN threshold, a
+ * negative n_queries or a null pointer (queries may be null when n_queries = 0) give status -2.  More than 2^28 candidates
+ * in one call give status -2, the count in revo_last_error().  n_queries = 0: *n_results = 0 and offsets = {0}; an empty
+ * gallery, or a filter that allows no row: all offsets 0.  revo_search_stats after it: slot 3 = candidates re-scored in
+ * fp32, slot 7 = candidate passes run (1, or 2 when the candidate workspace had to grow; 0 when no pass ran), every other
+ * slot 0.
+ * revo_search_range_read copies the offsets ([n_queries + 1] int64; offsets may be NULL) and result entries
+ * [start, start + n) to indices ([n] int64) and scores ([n] fp32), host or device memory (dst_on_device).  A result stays
+ * valid until the next revo_search_range call or a change of the gallery's rows: after an append or a clear, or with no
+ * result, it gives status -2, as does a range past the result.  revo_gallery_pairs and the top-k searches leave it valid
+ * (and a range search leaves a pairs result valid). */
+int32_t revo_search_range(revo_gallery* g, const float* queries, int32_t n_queries, float threshold, int64_t index_offset,
+                          int64_t* n_results, void* stream);
+int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start, int64_t n, int64_t* indices, float* scores,
+                               int32_t dst_on_device);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:
@@ -247,9 +273,9 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * evaluated for, rows the exact passes re-scored, of the failed queries: resolved from what the scan had kept (no second
  * pass over the gallery: searches with k > 25 scan with an admission margin for that), grouped search
  * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), revo_search_topk_large: queries
- * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes (0 after every search) }.
- * After revo_search_topk_large slot 3 counts the rows of the bands it re-scored and slots 0, 1, 2, 4, 5 are 0; after
- * revo_gallery_pairs see PAIRS. */
+ * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
+ * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
+ * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */

@@ -902,6 +902,27 @@ class SimpleReverso:
             items.append({"image": img, "score": r.score, "filename": filename, "bbox": payload.get("bbox")})
         return text, items
 
+    def search_all_similar(self, similarity_threshold=0.7, query_filter=None):
+        """:meth:`search_similar` without ``max_results``: EVERY stored region whose vector scores at least
+        ``similarity_threshold`` against the first region embedding (``query_filter``: only the points a Qdrant-style payload
+        filter selects).  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox", "id", "score"}`` best first.
+        No thumbnails: the list can hold thousands of hits."""
+        if not self.region_embeddings:
+            return "❌ No query embeddings available. Please detect/process an image first.", []
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        query = self.region_embeddings[0]
+        with self._lock:
+            hits = self.vector_db.search_range(query, float(similarity_threshold), query_filter=query_filter)
+        if not hits:
+            return f"❌ No similar regions found above threshold {similarity_threshold}", []
+        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
+                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+        text = f"🎯 Found {len(items)} similar regions:\n\n"
+        for n, it in enumerate(items):
+            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
+        return text, items
+
     def find_duplicates(self, similarity_threshold=0.95, query_filter=None):
         """Groups of near-duplicate regions in the loaded database: every stored region whose vector scores at least
         ``similarity_threshold`` against another one, joined transitively (re-posted, re-compressed or re-cropped copies of

@@ -404,6 +404,37 @@ long pairs_sort_tile(long n);                // keys per block of a radix pass (
 int launch_pairs_sort(uint64_t* keys, float* vals, uint64_t* keys_alt, float* vals_alt, long n, int key_bits, uint32_t* cnt,
                       uint64_t** out_keys, float** out_vals, hipStream_t st);
 int launch_pairs_emit(const uint64_t* keys, const float* vals, long n, int b, long long* pairs, float* scores, hipStream_t st);
+// ---- range search (revo_search_range; range.hip): the 256 x 256 scan's main loop and work plan with
+// an epilogue that appends every (query, row) whose bf16 score reaches the query's bound; fp32 re-score; the pairs' sort
+constexpr int RANGE_CHUNK = 1024;            // queries per candidate pass (fewer when the sort key would pass 64 bits)
+constexpr long RANGE_WS_PER_QUERY = 1024;    // candidate keys per query of a chunk the workspace holds before a regrow
+constexpr long RANGE_MAX_CAND = 1l << 28;    // candidates a call may have, over all its chunks (2 GiB of keys); more: status -2
+constexpr int RANGE_PHASES = 8;              // = S256_PHASES (scan_plan.h)
+struct RangeJoinArgs {
+    const bf16_t* Qb; long ldq;   // the chunk's bf16 query rows
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    int Q; long N; int D;
+    const float* qstat;           // [Q][2] the queries' rounding norms (launch_l2norm_rows row_stats)
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    float thr;
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    unsigned long long* cnt;      // candidates found (counts past cap)
+    uint64_t* keys; long cap;     // [cap] candidate keys (query << 32) | row
+    // set by the launcher: the scan's phases (launch_topk_scan256)
+    int nph;
+    int ph_first[RANGE_PHASES + 1], ph_q0[RANGE_PHASES], ph_qn[RANGE_PHASES], ph_ns[RANGE_PHASES];
+};
+int launch_range_join(const RangeJoinArgs& a, hipStream_t st);
+// fp32 score of candidates [0, n) (query rows Qf, gallery rows Gf); those >= thr appended to out_keys ((query << (32 + b)) |
+// (~order-preserving score bits << b) | row) / out_scores, count in *kept, per query in counts[query]
+int launch_range_rescore(const uint64_t* cand, long n, const float* Qf, long ldq, const float* Gf, long ldg, int D, float thr,
+                         int b, unsigned long long* kept, unsigned long long* counts, uint64_t* out_keys, float* out_scores,
+                         hipStream_t st);
+// sorted keys -> row + idx_offset / scores
+int launch_range_emit(const uint64_t* keys, const float* vals, long n, int b, long idx_offset, long long* idx, float* scores,
+                      hipStream_t st);
+// inclusive prefix sums of c[0 .. n) in place (one workgroup)
+int launch_range_offsets(unsigned long long* c, long n, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

@@ -26,6 +26,23 @@ template <class T = char> struct DeviceBuffer {
         bytes = need;
         return 0;
     }
+    // grown to at least `need` bytes (at least twice its size) with its first `keep` bytes carried over
+    int grow_keep(size_t need, size_t keep, hipStream_t st) {
+        if (bytes >= need) return 0;
+        const size_t nb = need > 2 * bytes ? need : 2 * bytes;
+        T* q = nullptr;
+        REVO_HIP_CHECK(hipMalloc((void**)&q, nb));
+        hipError_t e = keep > 0 ? hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st) : hipSuccess;
+        if (e == hipSuccess && keep > 0) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            revo_set_error(std::string("DeviceBuffer::grow_keep: ") + hipGetErrorString(e));
+            return -1;
+        }
+        release();
+        p = q; bytes = nb;
+        return 0;
+    }
   private:
     void release() { (void)hipFree(p); p = nullptr; bytes = 0; }
 };
@@ -87,6 +104,11 @@ struct revo_gallery {
     DeviceBuffer<> pbuf; long pairs_cap = 0;
     DeviceBuffer<long long> pair_idx; DeviceBuffer<float> pair_score;
     int64_t pairs_n = 0; bool pairs_valid = false;
+    // revo_search_range: the candidate keys its workspace (in pbuf) holds, and the last result ([range_n] indices and scores,
+    // [range_q + 1] offsets), valid until the rows change
+    long range_cap = 0;
+    DeviceBuffer<long long> range_idx; DeviceBuffer<float> range_score; DeviceBuffer<unsigned long long> range_off;
+    int64_t range_n = 0, range_q = 0; bool range_valid = false;
     revo::CertArgs cert_args(float* cert_out) const {
         revo::CertArgs c{};
         c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
@@ -200,6 +222,7 @@ extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     REVO_HIP_CHECK(hipMemset(g->gstat.p, 0, 8));      // the row maxima of the certificate start over with the rows
     g->size = 0;
     g->pairs_valid = false;
+    g->range_valid = false;
     return 0;
 }
 
@@ -212,6 +235,7 @@ extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     g->pairs_valid = false;
+    g->range_valid = false;
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
     for (int64_t done = 0; done < n; done += chunk_rows) {
@@ -842,6 +866,131 @@ extern "C" int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64
     const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     REVO_HIP_CHECK(hipMemcpy(pairs, g->pair_idx.p + start * 2, (size_t)n * 16, kind));
     REVO_HIP_CHECK(hipMemcpy(scores, g->pair_score.p + start, (size_t)n * 4, kind));
+    return 0;
+    API_END
+}
+
+// ---- range search (include/revo.h revo_search_range; range.hip)
+static int search_range(revo_gallery* g, const float* queries, int Q, float thr, long index_offset, const uint32_t* allow,
+                        hipStream_t st, int64_t* n_results) {
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    // sort keys (query << (32 + b)) | (score << b) | row in 64 bits: at most 2^(32 - b) queries per chunk
+    int b = 1;
+    while (N > 1 && (1l << b) < N) ++b;
+    int QC = Q < RANGE_CHUNK ? Q : RANGE_CHUNK;
+    if ((long)QC > (1l << (32 - b))) QC = (int)(1l << (32 - b));
+    int qbits = 0;
+    while ((1l << qbits) < QC) ++qbits;
+    // (the two-phase protocol's state refers to the handle's query rows, which this search overwrites)
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, QC > 0 ? QC : 1, st));
+    REVO_REQUIRE(g->xw.ctr, "search_range: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    // offsets: off[1 + q] collects query q's count, then the prefix sums make them the CSR offsets (off[0] = 0)
+    CHECK_RC(g->range_off.grow((size_t)(Q + 1) * 8, st));
+    REVO_HIP_CHECK(hipMemsetAsync(g->range_off.p, 0, (size_t)(Q + 1) * 8, st));
+    unsigned long long* off = g->range_off.p;
+    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept
+    uint64_t *cand = nullptr, *kept_k = nullptr; float *kept_v = nullptr, *alt_v = nullptr; uint32_t* hist = nullptr;
+    auto carve = [&](long cap) -> int {
+        CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+            cnt = l.take<unsigned long long>(2);
+            cand = l.take<uint64_t>(cap); kept_k = l.take<uint64_t>(cap);
+            kept_v = l.take<float>(cap); alt_v = l.take<float>(cap);
+            hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
+        }));
+        g->range_cap = cap;
+        return 0;
+    };
+    long total = 0;
+    unsigned long long cand_total = 0;
+    int max_passes = 0;
+    if (N > 0 && Q > 0) {
+        const long cap0 = (long)QC * RANGE_WS_PER_QUERY;
+        CHECK_RC(carve(g->range_cap > cap0 ? g->range_cap : cap0));
+        for (int c0 = 0; c0 < Q; c0 += QC) {
+            const int Qc = Q - c0 < QC ? Q - c0 : QC;
+            { ProfScope ps("search_prep", st);
+              CHECK_RC(launch_l2norm_rows(queries + (size_t)c0 * D, D, g->qf.p, D, g->qb.p, D, Qc, D, st, 1, g->qstat.p)); }
+            RangeJoinArgs ja{};
+            ja.Qb = g->qb.p; ja.ldq = D; ja.Gb = g->gb.p; ja.ldg = D; ja.Q = Qc; ja.N = N; ja.D = D;
+            ja.qstat = g->qstat.p; ja.gstat = g->gstat.p; ja.thr = thr; ja.allow = allow;
+            unsigned long long n_cand = 0;
+            int passes = 0;
+            for (;;) {
+                ja.cnt = cnt; ja.keys = cand; ja.cap = g->range_cap;
+                REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
+                { ProfScope ps("range_join", st);
+                  CHECK_RC(launch_range_join(ja, st)); }
+                ++passes;
+                REVO_HIP_CHECK(hipMemcpyAsync(&n_cand, cnt, sizeof(n_cand), hipMemcpyDeviceToHost, st));
+                REVO_HIP_CHECK(hipStreamSynchronize(st));
+                REVO_REQUIRE(cand_total + n_cand <= (unsigned long long)RANGE_MAX_CAND,
+                             "search_range: " + std::to_string(cand_total + n_cand) + " candidates exceed the limit of " +
+                                 std::to_string(RANGE_MAX_CAND) + " (raise the threshold or search fewer queries per call)");
+                if (n_cand <= (unsigned long long)g->range_cap) break;
+                REVO_REQUIRE(passes == 1, "search_range: the candidate count changed between two passes");
+                CHECK_RC(carve((long)n_cand));     // grown to the counted size, then run once more
+            }
+            cand_total += n_cand;
+            max_passes = passes > max_passes ? passes : max_passes;
+            unsigned long long n_kept = 0;
+            { ProfScope ps("range_rescore", st);
+              CHECK_RC(launch_range_rescore(cand, (long)n_cand, g->qf.p, D, g->gf.p, D, D, thr, b, cnt + 1, off + 1 + c0, kept_k,
+                                            kept_v, st)); }
+            REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
+            REVO_HIP_CHECK(hipStreamSynchronize(st));
+            uint64_t* sk; float* sv;
+            { ProfScope ps("range_sort", st);
+              CHECK_RC(launch_pairs_sort(kept_k, kept_v, cand, alt_v, (long)n_kept, qbits + 32 + b, hist, &sk, &sv, st)); }
+            const size_t need = (size_t)(total + (long)n_kept > 0 ? total + (long)n_kept : 1);
+            CHECK_RC(g->range_idx.grow_keep(need * 8, (size_t)total * 8, st));
+            CHECK_RC(g->range_score.grow_keep(need * 4, (size_t)total * 4, st));
+            CHECK_RC(launch_range_emit(sk, sv, (long)n_kept, b, index_offset, g->range_idx.p + total, g->range_score.p + total, st));
+            total += (long)n_kept;
+        }
+        CHECK_RC(launch_range_offsets(off + 1, Q, st));
+    }
+    const int stats[2] = {(int)cand_total, max_passes};    // slot 3 = candidates re-scored, slot 7 = candidate passes
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    g->range_n = total;
+    g->range_q = Q;
+    g->range_valid = true;
+    *n_results = total;
+    return 0;
+}
+extern "C" int32_t revo_search_range(revo_gallery* g, const float* queries, int32_t n_queries, float threshold,
+                                     int64_t index_offset, int64_t* n_results, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_results && (queries || n_queries == 0), "search_range: null argument");
+    REVO_REQUIRE(n_queries >= 0, "search_range: negative query count");
+    REVO_REQUIRE(!std::isnan(threshold), "search_range: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "search_range: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    g->range_valid = false;
+    return search_range(g, queries, n_queries, threshold, index_offset, allow, (hipStream_t)stream, n_results);
+    API_END
+}
+extern "C" int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start, int64_t n, int64_t* indices,
+                                          float* scores, int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_range_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "search_range_read: negative start or count");
+    REVO_REQUIRE((indices && scores) || n == 0, "search_range_read: null argument");
+    REVO_REQUIRE(g->range_valid, "search_range_read: no result (call revo_search_range again after the rows change)");
+    REVO_REQUIRE(start + n <= g->range_n,
+                 "search_range_read: range past the result's " + std::to_string(g->range_n) + " entries");
+    REVO_ON_DEVICE(g->device);
+    const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (offsets) REVO_HIP_CHECK(hipMemcpy(offsets, g->range_off.p, (size_t)(g->range_q + 1) * 8, kind));
+    if (n == 0) return 0;
+    REVO_HIP_CHECK(hipMemcpy(indices, g->range_idx.p + start, (size_t)n * 8, kind));
+    REVO_HIP_CHECK(hipMemcpy(scores, g->range_score.p + start, (size_t)n * 4, kind));
     return 0;
     API_END
 }

@@ -93,6 +93,28 @@ __device__ __forceinline__ void exact_dot4(const float* __restrict__ qr, const f
     for (int u = 0; u < 4; ++u) out[u] = wave_sum(acc[u]);
 }
 
+// The fp32 scores of four (query row, gallery row) pairs, one wave (pairs.hip, range.hip): exact_dot4's chain (per-lane
+// fma chain over the elements lane*4 + 256*i, +0..3 in that order, then wave_sum) with a row of its own for each pair.
+// fmaf's product is commutative, so score(i, j) and score(j, i) -- and the score a search of row i's fp32 copy gives row
+// j -- are the same bits.
+__device__ __forceinline__ void pairs_dot4(const float* const (&qr)[4], const float* const (&gr)[4], int D, int lane,
+                                           float (&out)[4]) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a[u] = *(const f32x4*)(qr[u] + c); b[u] = *(const f32x4*)(gr[u] + c); }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[u] = fmaf(a[u][0], b[u][0], acc[u]);
+            acc[u] = fmaf(a[u][1], b[u][1], acc[u]);
+            acc[u] = fmaf(a[u][2], b[u][2], acc[u]);
+            acc[u] = fmaf(a[u][3], b[u][3], acc[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) out[u] = wave_sum(acc[u]);
+}
 // ------------------------------------- uncertified queries answered by the scan's own segments (CertArgs, kernels.h) ----
 // Can the segments of query q hold every row whose scan score reaches lb?  The scan admitted every row scoring at least
 // max(base, fl(t - marg)) for bounds t <= U (U = the query's ksel-th best scan score; fl(t - marg) is monotone in t), so

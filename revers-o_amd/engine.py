@@ -310,6 +310,30 @@ class Gallery:
                        "revo_gallery_pairs_read")
         return pairs, scores
 
+    def search_range(self, queries, score_threshold, index_offset=0, allow=None):
+        """Range search (include/revo.h, RANGE): for each query every row (allowed by ``allow``, as in :meth:`search`) whose
+        fp32 score reaches ``score_threshold`` -- the reference's threshold without its ``limit``.  Returns ``(offsets [Q + 1]
+        int64, indices [n] int64, scores [n] fp32)`` device tensors: query q's results are ``offsets[q] .. offsets[q + 1]``,
+        best first (score desc, index asc), with the bits :meth:`search` returns.  Synchronous."""
+        _require_cuda(queries, "queries", self.device)
+        q = queries.detach().to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        Q = q.shape[0]
+        n = C.c_int64()
+        offsets = torch.empty((Q + 1,), dtype=torch.int64, device=self.device)
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_search_range(self._h, _lib.ptr(q), Q, float(score_threshold), int(index_offset),
+                                                   C.byref(n), _lib.current_stream()), "revo_search_range")
+            n = int(n.value)
+            idx = torch.empty((n,), dtype=torch.int64, device=self.device)
+            scores = torch.empty((n,), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.revo_search_range_read(self._h, _lib.ptr(offsets), 0, n, _lib.ptr(idx), _lib.ptr(scores), 1),
+                       "revo_search_range_read")
+        return offsets, idx, scores
+
     @contextlib.contextmanager
     def _groups(self, groups):
         """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.

@@ -272,6 +272,26 @@ class GalleryStore:
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
 
+    def search_range_batch(self, query_vectors, score_threshold, query_filter=None):
+        """Every point (selected by ``query_filter``, if given) whose vector scores at least ``score_threshold`` against each
+        query: one :class:`ScoredPoint` list per query, best first, with no cap on its length -- e.g. "which of these new
+        vectors are already in the database".  Exact (include/revo.h, RANGE)."""
+        q = torch.as_tensor(query_vectors, dtype=torch.float32)
+        q = q.reshape(-1, q.shape[-1]) if q.dim() != 2 else q
+        if q.shape[0] == 0:
+            return []
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        off, idx, sc = self.gallery.search_range(q.to(self.gallery.device), float(score_threshold), allow=allow)
+        off, idx, sc = off.tolist(), idx.tolist(), sc.tolist()
+        return [[ScoredPoint(self.ids[j], float(s), self.payloads[j]) for j, s in zip(idx[off[r]:off[r + 1]], sc[off[r]:off[r + 1]])]
+                for r in range(len(off) - 1)]
+
+    def search_range(self, query_vector, score_threshold, query_filter=None):
+        """One query: every point (selected by ``query_filter``, if given) scoring at least ``score_threshold``, best first --
+        :meth:`search` without ``limit``."""
+        q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(1, -1)
+        return self.search_range_batch(q, score_threshold, query_filter=query_filter)[0]
+
     def _group_ids(self, group_by):
         key = (group_by, len(self))
         if self._group_cache is None or self._group_cache[0] != key:
