@@ -321,6 +321,19 @@ int32_t revo_op_gemm_ln_in(int32_t epilogue, const void* a_bf16, int64_t lda, co
                            int32_t parts, float eps, void* tele, void* stream);
 /*    tele (optional; device, 3 x uint64, zeroed by the caller): the counters behind revo_vit_stats -- rows merged, rows with
  *    |mean| * rstd > 8, rows with |mean| * rstd > 32. */
+/* The two launches of the forward that the entries above cannot make:
+ *  - revo_op_gemm_ln_in_rope: the qkv projection of a batch-sized forward, revo_op_gemm_ln_in's folded consumer with
+ *    revo_op_gemm_rope's rotary epilogue (rope of rstd * (A . B^T - mean * csum) + bias);
+ *  - revo_op_gemm_resid_norm: revo_op_gemm's residual epilogue (C f32 += gamma * (A . B^T + bias), split-K scratch of its
+ *    own) with the LayerNorm that follows offered to the launcher as a one-image forward offers it: where the form is split-K
+ *    with the LayerNorm in the reduce, ln_out (bf16 [m][ln_ldo]) receives the normalised new rows (no affine) and
+ *    *fused = 1; else only C is written and *fused = 0. */
+int32_t revo_op_gemm_ln_in_rope(const void* a_bf16, int64_t lda, const void* b_bf16, int64_t ldb, int32_t m, int32_t n, int32_t k,
+                                void* c_bf16, int64_t ldc, const float* bias, const float* csum, const void* stats, int32_t parts,
+                                float eps, const float* cos_sin, int32_t seq, int32_t head_dim, int32_t rope_cols, void* stream);
+int32_t revo_op_gemm_resid_norm(const void* a_bf16, int64_t lda, const void* b_bf16, int64_t ldb, int32_t m, int32_t n, int32_t k,
+                                float* c, int64_t ldc, const float* bias, const float* gamma, void* ln_out_bf16, int64_t ln_ldo,
+                                float eps, int32_t* fused, void* stream);
 /* ---- calibration probes (bench.py's `calibration` object; not on the reference's path: nothing there to cite).  Two fixed
  * kernels that say how fast the BOX is, so that bench lines taken on different MI355X devices can be compared:
  *  - revo_probe_mfma: `blocks` workgroups of four waves, each wave `iters` trips of 32 register-resident
@@ -362,6 +375,9 @@ int32_t revo_debug_gemm_stamps(void* buf, int32_t items);
 /* diagnostic: device array [workgroups][2] of uint64 the body attention kernel fills with the shader-clock ticks and the 100 MHz
  * ticks of each workgroup's lifetime (their ratio x 100 MHz = the clock the chip holds under this kernel); NULL = off */
 int32_t revo_debug_attention_clock(void* buf);
+/* the GEMM launch forms issued since the last call with reset != 0, as a bitmask (gemm kernels and properties of the
+ * launch: the GemmForm bits of revers-o_amd/csrc/kernels.h); reset != 0 also clears the record.  Host-side only. */
+int32_t revo_debug_gemm_forms(int32_t reset);
 /* 0 = size heuristic (default), 128 or 256 = force that GEMM tile */
 int32_t revo_op_set_gemm_tile(int32_t tile);
 /* bits 4-7 = force the XCD arrangement (N-stripes 1, 2, 4 or 8; 0 = heuristic), bits 8-11 = force the attention

@@ -73,6 +73,10 @@ SIGNATURES = {
                                      _i32, _p]),
     "revo_op_gemm_ln_in": (_i32, [_i32, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p, _i32, _f32, _p, _p]),
     "revo_op_gemm_rope": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _i32, _i32, _i32, _p]),
+    "revo_op_gemm_ln_in_rope": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p, _i32, _f32, _p, _i32, _i32, _i32,
+                                       _p]),
+    "revo_op_gemm_resid_norm": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p, _i64, _f32, C.POINTER(C.c_int32),
+                                       _p]),
     "revo_op_layernorm": (_i32, [_p, _i64, _p, _p, _f32, _i32, _i32, _p, _i64, _i32, _p]),
     "revo_op_layernorm_logits": (_i32, [_p, _i64, _p, _p, _f32, _i32, _i32, _p, _i64, _p, _p, _i32, _i32, _p, _p]),
     "revo_op_linear_f32": (_i32, [_i32, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p]),
@@ -98,6 +102,7 @@ EXPERIMENT_SIGNATURES = {
     "revo_op_set_gemm_tile": (_i32, [_i32]),
     "revo_op_set_phase_groups": (_i32, [_i32]),
     "revo_op_set_qstores": (_i32, [_i32]),
+    "revo_debug_gemm_forms": (_i32, [_i32]),
     "revo_debug_gemm_stamps": (_i32, [_p, _i32]),
     "revo_debug_attention_clock": (_i32, [_p]),
     "revo_op_set_variant": (_i32, [_i32]),

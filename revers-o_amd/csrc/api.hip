@@ -735,6 +735,40 @@ extern "C" int32_t revo_op_gemm_rope(const void* a, int64_t lda, const void* b, 
     return revo::launch_gemm(revo::EPI_BF16_ROPE, g, (hipStream_t)stream);
     API_END
 }
+// The qkv launch of a batch-sized forward: the folded LayerNorm's consumer and the fused RoPE in one epilogue (vit_forward_range)
+extern "C" int32_t revo_op_gemm_ln_in_rope(const void* a, int64_t lda, const void* b, int64_t ldb, int32_t m, int32_t n, int32_t k,
+                                           void* c, int64_t ldc, const float* bias, const float* csum, const void* stats,
+                                           int32_t parts, float eps, const float* cos_sin, int32_t seq, int32_t head_dim,
+                                           int32_t rope_cols, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(a && b && c && csum && stats && cos_sin, "op_gemm_ln_in_rope: null argument");
+    revo::GemmArgs g{};
+    g.A = (const bf16_t*)a; g.lda = lda; g.B = (const bf16_t*)b; g.ldb = ldb; g.M = m; g.N = n; g.K = k; g.C = c; g.ldc = ldc;
+    g.bias = bias; g.rope_cs = (const float2*)cos_sin; g.rope_S = seq; g.rope_hd = head_dim; g.rope_cols = rope_cols;
+    g.lnc_stats = (const float2*)stats; g.lnc_parts = parts; g.lnc_c = csum; g.lnc_eps = eps;
+    return revo::launch_gemm(revo::EPI_BF16_ROPE, g, (hipStream_t)stream);
+    API_END
+}
+// A residual GEMM with the LayerNorm behind it offered to the launcher the way a one-image forward offers it (gemm() with an
+// LnAfter of `fused` only): the split-K form with the LayerNorm in its reduce normalises the new rows into ln_out (no affine)
+extern "C" int32_t revo_op_gemm_resid_norm(const void* a, int64_t lda, const void* b, int64_t ldb, int32_t m, int32_t n, int32_t k,
+                                           float* c, int64_t ldc, const float* bias, const float* gamma, void* ln_out,
+                                           int64_t ln_ldo, float eps, int32_t* fused, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(a && b && c && ln_out && fused, "op_gemm_resid_norm: null argument");
+    constexpr long OP_WS_ELEMS = 16l << 20;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = nullptr;
+    REVO_HIP_CHECK(hipMallocAsync((void**)&ws, OP_WS_ELEMS * 4, st));
+    int flag = 0;
+    const LnAfter ln{eps, (bf16_t*)ln_out, ln_ldo, &flag, nullptr, nullptr, nullptr, 0, 0};
+    const int rc = gemm("gemm_op", revo::EPI_RESID_F32, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, m, n, k, c, ldc, bias, gamma,
+                        st, ws, OP_WS_ELEMS, &ln);
+    REVO_HIP_CHECK(hipFreeAsync(ws, st));
+    *fused = flag;
+    return rc;
+    API_END
+}
 #ifdef REVO_EXPERIMENTS
 // result-preserving kernel-variant switches (librevo_exp.so only; see revo.h)
 extern "C" int32_t revo_op_set_variant(int32_t flags) {
@@ -778,6 +812,8 @@ extern "C" int32_t revo_debug_gemm_stamps(void* buf, int32_t items) {
     revo::gemm_set_stamps((unsigned long long*)buf, buf ? items : 0);
     return 0;
 }
+// the GEMM launch forms issued since the last reset (kernels.h GemmForm bits); reset != 0 clears the record
+extern "C" int32_t revo_debug_gemm_forms(int32_t reset) { return (int32_t)revo::gemm_debug_forms(reset); }
 extern "C" int32_t revo_op_set_gemm_tile(int32_t tile) {
     REVO_REQUIRE(tile == 0 || tile == 128 || tile == 256, "set_gemm_tile: 0, 128 or 256");
     revo::gemm_force_tile(tile);

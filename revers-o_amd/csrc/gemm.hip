@@ -1505,6 +1505,14 @@ static const char* check_args(const GemmArgs& a) {
 // the current kernels, alternated per layer shape (scripts/gemm_gy_sweep.py, profiles/r06_gemm_gy_sweep.json): up to 7 column
 // tiles every XCD sweeps all of N for its M stripe; from 8 on two N stripes (L14 qkv, 12 tiles: -2.9 % against the four
 // stripes round 4 chose; fc1, 16: -1.8 %; G14 qkv, 18: -3.4 %); four only from 24 on (G14 fc1, 35 tiles: -1.7 %).
+// Which launch forms ran (librevo_exp.so only, revo_debug_gemm_forms): one host-side bit per launch site, nothing on the device.
+#ifdef REVO_EXPERIMENTS
+static unsigned g_forms = 0;
+#define REVO_FORM(bit) (g_forms |= (bit))
+unsigned gemm_debug_forms(int reset) { const unsigned f = g_forms; if (reset) g_forms = 0; return f; }
+#else
+#define REVO_FORM(bit) ((void)0)
+#endif
 static int xcd_stripes(int tiles_n) { return tiles_n >= 24 ? 4 : (tiles_n >= 8 ? 2 : 1); }
 static int g_force_gy = 0;     // timing experiments only: force the XCD arrangement (1, 2, 4, 8)
 void gemm_force_gy(int gy) { g_force_gy = gy; }
@@ -1522,6 +1530,7 @@ static int launch_256d(const GemmArgs& a, hipStream_t st) {
     const int gx = 8 / gy;
     const int region = ((tiles_m + gx - 1) / gx) * ((tiles_n + gy - 1) / gy);
     hipLaunchKernelGGL((gemm256_kernel<EPI, DBG>), dim3(8 * region), dim3(G256_THREADS), G256_LDS_LN, st, b);
+    REVO_FORM(GF_256_TILE);
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1547,6 +1556,9 @@ static int launch_256p(const GemmArgs& a, hipStream_t st) {
     b.stamps = g_stamps; b.stamp_items = g_stamp_items;
 #endif
     const int tiles_m = BMR == 256 ? (a.M + 255) / 256 : a.t192_tiles, tiles_n = (a.N + 255) / 256;
+    REVO_FORM(BMR == 256 ? GF_256P : GF_256P_192);
+    if (EPI == EPI_RESID_F32 && b.xp_in) REVO_FORM(GF_PLANES_IN);
+    if (EPI == EPI_RESID_F32 && b.xp_out) REVO_FORM(GF_PLANES_OUT);
     int gy = xcd_stripes(tiles_n);
     if (g_force_gy) gy = g_force_gy;
     b.gy = gy;
@@ -1631,6 +1643,7 @@ static int launch_256q(const GemmArgs& a, hipStream_t st) {
         const int nslot = region < 32 ? region : 32;          // 32 CUs per XCD
         REVO_FUNC_LDS((gemm256q_kernel<EPI>), G256Q_LDS);
         hipLaunchKernelGGL((gemm256q_kernel<EPI>), dim3(8 * nslot), dim3(G256_THREADS), G256Q_LDS, st, b, nslot);
+        REVO_FORM(b.qtail_rows > 0 ? GF_256Q_QTAIL : GF_256Q);
         REVO_HIP_CHECK(hipGetLastError());
         return 0;
     } else {
@@ -1815,6 +1828,7 @@ static int try_splitk_tail(const GemmArgs& a, hipStream_t st) {
                 else if (groups <= 3) RLN_LAUNCH(3);
                 else RLN_LAUNCH(4);
 #undef RLN_LAUNCH
+                REVO_FORM(GF_SPLITK_RING_LN);
                 REVO_HIP_CHECK(hipGetLastError());
                 *a.ln_fused = 1;
                 return 1;
@@ -1822,6 +1836,7 @@ static int try_splitk_tail(const GemmArgs& a, hipStream_t st) {
             const long quads = plane / 4;
             hipLaunchKernelGGL(splitk_reduce_resid_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, a.ws, S, plane,
                                a.M, a.N, a.bias, a.gamma, (float*)a.C, a.ldc);
+            REVO_FORM(GF_SPLITK_RING);
             REVO_HIP_CHECK(hipGetLastError());
             return 1;
         }
@@ -1849,6 +1864,7 @@ static int try_splitk_tail(const GemmArgs& a, hipStream_t st) {
     const long quads = plane / 4;
     hipLaunchKernelGGL(splitk_reduce_resid_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, a.ws, S, plane,
                        a.M, a.N, a.bias, a.gamma, (float*)a.C, a.ldc);
+    REVO_FORM(GF_SPLITK_256);
     REVO_HIP_CHECK(hipGetLastError());
     return 1;
 }
@@ -1886,10 +1902,13 @@ static int launch_skinny(const GemmArgs& a, hipStream_t st) {
     // workgroup per 16 x 16 fragment, all loads of 256 k per wave in flight -- 64 x 1024 x 4096: 21 -> 9 us, x 1024: 8 -> 6
     // (same bits: per element the same K order and the same fixed-order sum of the waves' parts)
     // (not for fc1's 64 x 4096 x 1024 leftover rows: measured in the step, round 5: fc1 7.70 -> 7.79 ms with the fragment form)
-    if (a.K % 1024 == 0 && a.N <= 2048)
+    if (a.K % 1024 == 0 && a.N <= 2048) {
         hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 4, 4, 4>), dim3((a.N + 15) / 16, (a.M + 15) / 16), dim3(256), 0, st, a);
-    else
+        REVO_FORM(GF_SKINNY_444);
+    } else {
         hipLaunchKernelGGL((gemm_skinny_kernel<EPI, 4, 1, 1>), dim3((a.N + 15) / 16), dim3(256), 0, st, a);
+        REVO_FORM(GF_SKINNY_411);
+    }
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1958,7 +1977,7 @@ static int launch_t(const GemmArgs& a_in, hipStream_t st) {
                 } else {
                     rc = launch_256p<EPI>(a1, st);
                 }
-                if (rc == 0 && lnf_ok) *a.lnf_done = 1;
+                if (rc == 0 && lnf_ok) { *a.lnf_done = 1; REVO_FORM(GF_LN_FOLDED); }
                 return rc;
             }
         }
@@ -2045,12 +2064,15 @@ static int launch_128(const GemmArgs& a, hipStream_t st) {
             constexpr int LDS = G128R_NST * (128 + 64) * 128;
             REVO_FUNC_LDS((gemm128r_kernel<EPI>), LDS);
             hipLaunchKernelGGL((gemm128r_kernel<EPI>), dim3(tiles64), dim3(GEMM_THREADS), LDS, st, a);
+            REVO_FORM(GF_128R);
             REVO_HIP_CHECK(hipGetLastError());
             return 0;
         }
         hipLaunchKernelGGL((gemm128_kernel<EPI, 64>), dim3(tiles64), dim3(GEMM_THREADS), 2 * (128 + 64) * 128, st, a);
+        REVO_FORM(GF_128_64);
     } else {
         hipLaunchKernelGGL((gemm128_kernel<EPI, 128>), dim3(tiles), dim3(GEMM_THREADS), 2 * (128 + 128) * 128, st, a);
+        REVO_FORM(GF_128_128);
     }
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
@@ -2084,6 +2106,7 @@ int launch_gemm(int epi, const GemmArgs& a, hipStream_t st) {
         revo_set_error("gemm: a folded LayerNorm (lnc_*) needs a bf16 epilogue, the column sums and 1..6 statistics slots per row");
         return -2;
     }
+    if (a.lnc_stats) REVO_FORM(GF_LN_CONSUMED);
     switch (epi) {
         case EPI_BF16: return launch_t<EPI_BF16>(a, st);
         case EPI_BF16_GELU: return launch_t<EPI_BF16_GELU>(a, st);

@@ -73,6 +73,30 @@ constexpr float LNC_TELE_RATIO = 8.0f;
 // true when launch_gemm would run the 256 x 256 kernel with the row-coalesced epilogue for these sizes
 bool gemm_uses_wide_epilogue(int M, int N, long lda, long ldb, long ldc);
 int launch_gemm(int epi, const GemmArgs& a, hipStream_t st);
+// The launch forms launch_gemm can issue (bits of revo_debug_gemm_forms, librevo_exp.so; tests/test_gpu_gemm_bounds.py lists
+// them too): kernels, then properties of the launch
+enum GemmForm : unsigned {
+    GF_SKINNY_444 = 1u << 0,      // gemm_skinny_kernel<., 4, 4, 4>
+    GF_SKINNY_411 = 1u << 1,      // gemm_skinny_kernel<., 4, 1, 1>
+    GF_128_128 = 1u << 2,         // gemm128_kernel<., 128>
+    GF_128_64 = 1u << 3,          // gemm128_kernel<., 64>
+    GF_128R = 1u << 4,            // gemm128r_kernel (six-deep ring)
+    GF_256_TILE = 1u << 5,        // gemm256_kernel, one workgroup per tile
+    GF_256P = 1u << 6,            // gemm256p_kernel, 256-row tiles
+    GF_256P_192 = 1u << 7,        // gemm256p_kernel, 192-row tiles
+    GF_256Q = 1u << 8,            // gemm256q_kernel
+    GF_256Q_QTAIL = 1u << 9,      // gemm256q_kernel with qtail_rows
+    GF_SPLITK_RING = 1u << 10,    // split-K on the ring kernel + splitk_reduce_resid_kernel
+    GF_SPLITK_RING_LN = 1u << 11, // split-K on the ring kernel + splitk_reduce_resid_ln_kernel
+    GF_SPLITK_256 = 1u << 12,     // split-K on gemm256_kernel<EPI_F32, 4> + splitk_reduce_resid_kernel
+    GF_LN_FOLDED = 1u << 13,      // producer wrote bf16(x) and the row statistics (*lnf_done)
+    GF_LN_CONSUMED = 1u << 14,    // consumer applied row statistics (lnc_*)
+    GF_PLANES_IN = 1u << 15,      // old residual values from the two bf16 planes
+    GF_PLANES_OUT = 1u << 16,     // new residual values to the two bf16 planes
+};
+#ifdef REVO_EXPERIMENTS
+unsigned gemm_debug_forms(int reset);
+#endif
 // EPI_F32 on 128 x 64 ring tiles whatever the tile count (few rows x very many columns: the search pre-pass of few queries)
 int launch_gemm_f32_ring(const GemmArgs& a, hipStream_t st);
 // true when launch_gemm(EPI_RESID_F32) would take one of the two launch forms that can fold the LayerNorm behind it (and

@@ -30,7 +30,8 @@ def ulp(x, bits):
     2^(floor(log2 |x|) - bits + 1), the subnormal spacing below 2^-126."""
     a = x.double().abs().clamp_min(2.0 ** -126)
     _, e = torch.frexp(a)                      # a = m 2^e, m in [0.5, 1): floor(log2 a) = e - 1
-    return torch.ldexp(torch.ones_like(a), (e - bits).to(torch.int64))
+    # 2^(e - bits) built from its fp64 exponent field: exact (torch.ldexp rounds: it gave 0.0625 as 0.06249999999999999)
+    return ((e.to(torch.int64) - bits + 1023) << 52).view(torch.float64)
 
 
 def bf16_ulp(x):
@@ -395,6 +396,13 @@ NOT_CAUGHT = {
 }
 
 
+NOT_CAUGHT.update({
+    (op, "split-K planes summed in bf16"): (lambda c: c["K"] >= 3072,
+                                            "the fp32 bound of any summation order, K U_F32 (|A||B|^T), grows with K: from "
+                                            "K = 3072 it is as large as the bf16 rounding of a partial plane")
+    for op in ("gemm f32", "resid", "splitk ln x")})
+
+
 def not_caught(op, name, case):
     e = NOT_CAUGHT.get((op, name))
     return e is not None and e[0](case)
@@ -445,3 +453,685 @@ def gemm_case(M, N, K):
     b = (torch.randn(N, K, generator=g) * 0.1).bfloat16()
     bias = torch.randn(N, generator=g)
     return a, b, bias
+
+
+# ====================================================================== the GEMM family ====
+# The rest of the GEMM's epilogues, one class each, on a `GemmCase` (the exact bf16 / fp32 inputs the kernel receives).
+# Common to all of them: acc = A.B^T summed in fp32 in any order -- one K range, split-K partial planes added in a fixed
+# order, the eight-wave order of the queued kernel's leftover rows -- is within K U_F32 (|A||B|^T)_ij of the exact sum
+# (the bound of a sum tree of depth <= K), so one acc term covers every launch form.
+class GemmCase:
+    """a: bf16 [M, K], b: bf16 [N, K], bias fp32 [N]; optional: gamma fp32 [N] (residual), x fp32 [M, N] (the old residual
+    rows) or hi / lo bf16 [M, N] (the old stream in planes), stats fp32 [M, P, 2] + csum fp32 [N] + eps (folded-LayerNorm
+    consumer), cs fp32 [S, hd / 2, 2] + S + hd + rope_cols (RoPE), ksplit (the K parts of a split-K form; 1 = none)."""
+
+    def __init__(self, a, b, bias, **kw):
+        self.a, self.b, self.bias = a, b, bias
+        self.gamma = self.x = self.hi = self.lo = self.stats = self.csum = self.cs = None
+        self.eps, self.S, self.hd, self.rope_cols, self.ksplit, self.epi = 1e-5, 1, 64, 0, 1, "bf16"
+        self.row0 = 0                          # index of row 0 in the whole problem (RoPE tokens of a row chunk)
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def K(self):
+        return self.a.shape[1]
+
+    def acc(self, k_end=None, dtype=torch.float64):
+        k_end = self.K if k_end is None else k_end
+        return self.a[:, :k_end].to(dtype) @ self.b[:, :k_end].to(dtype).T
+
+    def acc_abs(self):
+        return self.a.double().abs() @ self.b.double().abs().T
+
+    def old(self):
+        """the old residual values, fp64: x, or hi + lo as given"""
+        if self.hi is not None:
+            return self.hi.double() + self.lo.double()
+        return self.x.double()
+
+    def rows(self, r0, r1):
+        """the sub-problem of rows [r0, r1) (the GPU test's fp64 reference goes in row chunks)"""
+        kw = {k: getattr(self, k)[r0:r1] for k in ("a", "x", "hi", "lo", "stats") if getattr(self, k) is not None}
+        return self.with_(row0=self.row0 + r0, **kw)
+
+    def with_(self, **kw):
+        c = GemmCase(self.a, self.b, self.bias)
+        c.__dict__.update(self.__dict__)
+        c.__dict__.update(kw)
+        return c
+
+
+def _acc_err(c):
+    return c.K * U_F32 * c.acc_abs()
+
+
+def _acc_drop_last_ktile(c):
+    return c.acc(c.K - 64)
+
+
+def _acc_drop_plane(c):
+    """split-K: the last of the c.ksplit K ranges never added (one K range: the last K-tile)"""
+    S = max(c.ksplit, 1)
+    nt = c.K // 64
+    return c.acc(c.K - (nt - (S - 1) * (nt // S)) * 64 if S > 1 else c.K - 64)
+
+
+def _acc_planes_bf16(c):
+    """split-K: each partial plane rounded to bf16 before the fixed-order sum (the reduce reading bf16 planes)"""
+    S = max(c.ksplit, 2)
+    nt = c.K // 64
+    edges = [(nt // S) * s * 64 for s in range(S)] + [c.K]
+    tot = 0
+    for k0, k1 in zip(edges[:-1], edges[1:]):
+        tot = tot + (c.a[:, k0:k1].double() @ c.b[:, k0:k1].double().T).float().bfloat16().double()
+    return tot
+
+
+# ------------------------------------------------------------------------ EPI_F32 ----
+# C = fp32(acc + bias): the acc error plus the bias add's one rounding (U_F32 of |acc| + |bias|) -- the add IS the output's
+# rounding, so there is no separate ulp term.
+class GemmF32:
+    @staticmethod
+    def reference(c, acc=None):
+        return (c.acc() if acc is None else acc) + c.bias.double()
+
+    @staticmethod
+    def bound(c):
+        acc = c.acc()
+        return _acc_err(c) + U_F32 * (acc.abs() + c.bias.double().abs())
+
+    @staticmethod
+    def emulate(c):
+        return (c.acc(dtype=torch.float32) + c.bias.float()).double()
+
+
+GemmF32.MUTATIONS = [
+    ("the last K-tile dropped", lambda c: GemmF32.reference(c, _acc_drop_last_ktile(c)), 3.0),
+    ("bias dropped", lambda c: c.acc(), 3.0),
+    ("bias added twice", lambda c: c.acc() + 2 * c.bias.double(), 3.0),
+    ("split-K planes summed in bf16", lambda c: GemmF32.reference(c, _acc_planes_bf16(c)), 3.0),
+]
+
+
+# ------------------------------------------------------------------ EPI_RESID_F32 ----
+# x_new = x_old + gamma (acc + bias): fp32 steps  t = acc + bias (U_F32 (|acc| + |bias|)), t gamma (U_F32 |gamma t|), then
+# the add, which is the output's rounding (ulp_f32(ref)).  The old value is x, or hi + lo (exact in fp32: lo is below
+# half an ulp of hi).  Planes out: hi = bf16(x_new), lo = bf16(x_new - hi) (the difference is exact), so hi + lo misses
+# x_new by half a bf16 ulp of |x_new - hi| <= ulp_bf16(x_new) / 2: at most 2^-9 ulp_bf16(ref) more (x2 for the binade).
+class GemmResid:
+    @staticmethod
+    def reference(c, acc=None, bias_gamma=True, old=None):
+        acc = c.acc() if acc is None else acc
+        g = c.gamma.double() if c.gamma is not None else 1.0
+        t = g * (acc + c.bias.double()) if bias_gamma else g * acc + c.bias.double()
+        return (c.old() if old is None else old) + t
+
+    @staticmethod
+    def bound(c, planes_out=False):
+        acc = c.acc()
+        g = c.gamma.double().abs() if c.gamma is not None else 1.0
+        t = acc + c.bias.double()
+        ref = GemmResid.reference(c)
+        d = g * (_acc_err(c) + U_F32 * (acc.abs() + c.bias.double().abs())) + U_F32 * (g * t.abs()) + f32_ulp(ref)
+        if planes_out:
+            d = d + 2.0 ** -8 * bf16_ulp(ref)
+        return d
+
+    @staticmethod
+    def emulate(c, planes_out=False):
+        t = c.acc(dtype=torch.float32) + c.bias.float()
+        if c.gamma is not None:
+            t = t * c.gamma.float()
+        old = (c.hi.float() + c.lo.float()) if c.hi is not None else c.x.float()
+        x = old + t
+        if planes_out:
+            hi = x.bfloat16()
+            return hi.double() + (x - hi.float()).bfloat16().double()
+        return x.double()
+
+
+GemmResid.MUTATIONS = [
+    ("the last K-tile dropped", lambda c: GemmResid.reference(c, _acc_drop_last_ktile(c)), 3.0),
+    ("one split-K plane dropped", lambda c: GemmResid.reference(c, _acc_drop_plane(c)), 3.0),
+    ("split-K planes summed in bf16", lambda c: GemmResid.reference(c, _acc_planes_bf16(c)), 3.0),
+    ("gamma not applied to the bias", lambda c: GemmResid.reference(c, bias_gamma=False) if c.gamma is not None else None, 3.0),
+    ("lo dropped from the old value", lambda c: GemmResid.reference(c, old=c.hi.double()) if c.hi is not None else None, 3.0),
+    ("old value read as bf16(x)", lambda c: GemmResid.reference(c, old=c.x.bfloat16().double()) if c.hi is None else None, 3.0),
+]
+
+
+def planes_ok(hi, lo):
+    """the planes' own invariant: |lo| <= ulp_bf16(hi) / 2 (lo is the rounded remainder of hi's rounding)"""
+    return bool((lo.double().abs() <= bf16_ulp(hi) / 2).all())
+
+
+# ------------------------------------------------------------------- fused RoPE ----
+# EPI_BF16_ROPE: v = fp32(acc + bias), then -- by design, the same bits on every path -- x0 = bf16(v0), x1 = bf16(v1) for
+# each interleaved pair of a rotated column, y = (x0 c - x1 s, x1 c + x0 s) in fp32 with the fp32 table of token row % S,
+# and one more bf16 rounding.  Two roundings: x_k is within ulp_bf16(r_k) + d_k of r_k = acc + bias (d_k the fp32 error),
+# which the rotation passes on weighted by |c| and |s|; the rotation's fp32 steps add 2 U_F32 (|x0 c| + |x1 s|); then
+# ulp_bf16(ref).  Columns at or past rope_cols: GemmBf16's bound (the rotation is the identity there).
+def _rope_apply(x, c, cs_rows, swap_sign=False):
+    """x fp64 [M, N]; rotate the pairs of the first c.rope_cols columns with table rows cs_rows ([M] token indices)"""
+    R, hd = c.rope_cols, c.hd
+    y = x.clone()
+    if R == 0:
+        return y
+    cs = c.cs.to(x.device).double()[cs_rows]                     # [M, hd / 2, 2]
+    reps = R // hd
+    co = cs[..., 0].repeat(1, reps)                               # [M, R / 2]
+    si = cs[..., 1].repeat(1, reps)
+    x0, x1 = x[:, 0:R:2], x[:, 1:R:2]
+    y[:, 0:R:2] = x0 * co - x1 * si
+    y[:, 1:R:2] = x1 * co + x0 * si
+    return y
+
+
+def _rope_tokens(c, M, device, shift=0, by_row=False):
+    """table row of each output row: row % S; the mutations: shifted by one token, or the row itself (rows past the table
+    read its last row)"""
+    r = torch.arange(M, device=device) + c.row0
+    if by_row:
+        return r.clamp_max(c.S - 1)
+    return (r % c.S + shift) % c.S
+
+
+class GemmRope:
+    @staticmethod
+    def reference(c, acc=None, tokens=None):
+        x = (c.acc() if acc is None else acc) + c.bias.double()
+        return _rope_apply(x, c, _rope_tokens(c, x.shape[0], x.device) if tokens is None else tokens)
+
+    @staticmethod
+    def rotated_bound(c, r, d):
+        """bound of the rotated output given the pre-rounding values r (fp64 [M, N]) and their fp32 error d"""
+        M, R, hd = r.shape[0], c.rope_cols, c.hd
+        ref = _rope_apply(r, c, _rope_tokens(c, M, r.device))
+        out = bf16_ulp(ref) + d
+        if R:
+            cs = c.cs.to(r.device).double()[_rope_tokens(c, M, r.device)]
+            co = cs[..., 0].abs().repeat(1, R // hd)
+            si = cs[..., 1].abs().repeat(1, R // hd)
+            e = bf16_ulp(r[:, :R]) + d[:, :R]                      # |x_k - r_k|
+            x0, x1 = r[:, 0:R:2].abs() + e[:, 0::2], r[:, 1:R:2].abs() + e[:, 1::2]
+            out[:, 0:R:2] = bf16_ulp(ref[:, 0:R:2]) + co * e[:, 0::2] + si * e[:, 1::2] + 2 * U_F32 * (x0 * co + x1 * si)
+            out[:, 1:R:2] = bf16_ulp(ref[:, 1:R:2]) + co * e[:, 1::2] + si * e[:, 0::2] + 2 * U_F32 * (x1 * co + x0 * si)
+        return out
+
+    @staticmethod
+    def bound(c):
+        acc = c.acc()
+        d = _acc_err(c) + U_F32 * (acc.abs() + c.bias.double().abs())
+        return GemmRope.rotated_bound(c, acc + c.bias.double(), d)
+
+    @staticmethod
+    def emulate_rotate(c, v):
+        """v fp32 [M, N] (the value before the RoPE's roundings) -> the kernel's bf16 output as fp64"""
+        R = c.rope_cols
+        y = v.bfloat16().float()
+        if R:
+            cs = c.cs.to(v.device)[_rope_tokens(c, v.shape[0], v.device)]
+            co, si = cs[..., 0].repeat(1, R // c.hd), cs[..., 1].repeat(1, R // c.hd)
+            x0, x1 = y[:, 0:R:2].clone(), y[:, 1:R:2].clone()
+            y[:, 0:R:2] = x0 * co - x1 * si
+            y[:, 1:R:2] = x1 * co + x0 * si
+        return y.bfloat16().double()
+
+    @staticmethod
+    def emulate(c):
+        return GemmRope.emulate_rotate(c, c.acc(dtype=torch.float32) + c.bias.float())
+
+
+def _rope_mutations(ref_fn):
+    """the RoPE mutations of an output function ref_fn(c, tokens=...)"""
+    def by_row(c):
+        M = c.a.shape[0]
+        if M <= c.S or not c.rope_cols:
+            return None                                           # (n/a: one image)
+        return ref_fn(c, tokens=_rope_tokens(c, M, c.a.device, by_row=True))
+
+    def shifted(c):
+        if not c.rope_cols:
+            return None
+        return ref_fn(c, tokens=_rope_tokens(c, c.a.shape[0], c.a.device, shift=1))
+    return [("RoPE indexed by row instead of row % S", by_row, 3.0),
+            ("RoPE table shifted by one token", shifted, 3.0)]
+
+
+GemmRope.MUTATIONS = [
+    ("the last K-tile dropped", lambda c: GemmRope.reference(c, _acc_drop_last_ktile(c)), 3.0),
+    ("bias dropped", lambda c: GemmRope.reference(c.with_(bias=torch.zeros_like(c.bias))), 3.0),
+] + _rope_mutations(lambda c, tokens: GemmRope.reference(c, tokens=tokens))
+
+
+# ------------------------------------------------- folded LayerNorm: the consumer ----
+# out = epi(rstd (acc - mean csum) + bias'), mean / rstd merged from the row's P fp32 slots (mean_i, M2_i) of 256-column
+# slices (gemm.hip lnf_merge, and merge_n<4> / merge_n<6> in the same order).  Reference: the fp64 merge of the same slots,
+#   mean = sum m_i / P,  var = (sum M2_i + 256 sum (m_i - mean)^2) / (256 P),  rstd = 1 / sqrt(var + eps).
+# The kernel's fp32 merge: sm over P slots and the division: dm <= (P + 1) U_F32 mean_i|m_i|; sq = sum M2_i: (P - 1) U_F32 sq;
+# d_i = m_i - mean is off by dm + U_F32 |d_i| (e_i), dd = sum d_i^2 by fma: P U_F32 dd + sum (2 |d_i| e_i + e_i^2); the fma
+# with 256 and the division: 2 U_F32 var; + eps: U_F32 (var + eps); rsqrtf (v_rsq_f32, 1 ulp): 2 U_F32.  So
+#   er = |d rstd| / rstd <= 1.01 (dvar / (2 (var + eps)) + 2 U_F32),   mr = -mean rstd: off by rstd dm + |mean| rstd (er + U_F32).
+# The epilogue's fp32 steps (acc rstd, csum mr, + bias', the sum; fma or not): 3 U_F32 (|acc rstd| + |csum mr| + |bias'|).
+# The acc error passes through rstd.  Then GELU or RoPE as for the plain epilogues, and one bf16 rounding.
+def fold_merge64(stats):
+    """fp64 (mean, var) of rows from their fp32 slots [M, P, 2]"""
+    s = stats.double()
+    P = s.shape[1]
+    m = s[..., 0].mean(1)
+    var = (s[..., 1].sum(1) + LNF_SLICE * ((s[..., 0] - m[:, None]) ** 2).sum(1)) / (LNF_SLICE * P)
+    return m, var
+
+
+LNF_SLICE = 256
+
+
+def fold_merge32(stats, eps):
+    """the kernel's fp32 merge, in lnf_merge's order: (rstd, mr = -mean rstd)"""
+    s = stats.float()
+    P = s.shape[1]
+    sm = torch.zeros(s.shape[0], dtype=torch.float32, device=s.device)
+    sq = torch.zeros_like(sm)
+    for i in range(P):
+        sm = sm + s[:, i, 0]
+        sq = sq + s[:, i, 1]
+    mean = sm / P
+    dd = torch.zeros_like(sm)
+    for i in range(P):
+        d = s[:, i, 0] - mean
+        dd = (d.double() * d.double() + dd.double()).float()      # fmaf
+    var = ((LNF_SLICE * dd.double() + sq.double()).float()) / float(LNF_SLICE * P)
+    rstd = torch.rsqrt(var + np.float32(eps))
+    return rstd, -mean * rstd
+
+
+def _fold_err(stats, eps):
+    """(mean, rstd, dm, er) per row: the fp64 merge and the fp32 merge's error bounds above"""
+    s = stats.double()
+    P = s.shape[1]
+    m, var = fold_merge64(stats)
+    mabs = s[..., 0].abs().mean(1)
+    dm = (P + 1) * U_F32 * mabs
+    di = (s[..., 0] - m[:, None]).abs()
+    e = dm[:, None] + U_F32 * di
+    sq = s[..., 1].sum(1)
+    dd = (di ** 2).sum(1)
+    dvar = ((P - 1) * U_F32 * sq + LNF_SLICE * (P * U_F32 * dd + (2 * di * e + e * e).sum(1))) / (LNF_SLICE * P) \
+        + 2 * U_F32 * var + U_F32 * (var + eps)
+    er = 1.01 * (dvar / (2 * (var + eps)) + 2 * U_F32)
+    return m, 1.0 / torch.sqrt(var + eps), dm, er
+
+
+class GemmLnIn:
+    """c.stats [M, P, 2] fp32, c.csum [N] fp32, c.eps; c.epi in ("bf16", "gelu", "rope")."""
+
+    @staticmethod
+    def pre(c, acc=None, stats=None, eps=None, mean_csum=True, between=True):
+        """the fp64 value before GELU / RoPE; the keyword arguments are the mutations' handles"""
+        acc = c.acc() if acc is None else acc
+        s = (c.stats if stats is None else stats).double()
+        P = s.shape[1]
+        m = s[..., 0].mean(1)
+        var = (s[..., 1].sum(1) + (LNF_SLICE * ((s[..., 0] - m[:, None]) ** 2).sum(1) if between else 0)) / (LNF_SLICE * P)
+        rstd = 1.0 / torch.sqrt(var + (c.eps if eps is None else eps))
+        cm = m[:, None] * c.csum.double()[None, :] if mean_csum else 0
+        return rstd[:, None] * (acc - cm) + c.bias.double()
+
+    @staticmethod
+    def finish(c, x, tokens=None):
+        if c.epi == "gelu":
+            return _gelu64(x)
+        if c.epi == "rope":
+            return _rope_apply(x, c, _rope_tokens(c, x.shape[0], x.device) if tokens is None else tokens)
+        return x
+
+    @staticmethod
+    def reference(c, tokens=None, **kw):
+        return GemmLnIn.finish(c, GemmLnIn.pre(c, **kw), tokens)
+
+    @staticmethod
+    def bound(c):
+        acc = c.acc()
+        m, rstd, dm, er = (t[:, None] for t in _fold_err(c.stats, c.eps))
+        cs = c.csum.double()[None, :].abs()
+        b = c.bias.double().abs()
+        d = (rstd * _acc_err(c) + (acc.abs() + cs * m.abs()) * rstd * er + cs * rstd * dm + cs * (m * rstd).abs() * U_F32
+             + 3 * U_F32 * (acc.abs() * rstd + cs * (m * rstd).abs() + b))
+        x = GemmLnIn.pre(c)
+        if c.epi == "gelu":
+            return bf16_ulp(_gelu64(x)) + GELU_SLOPE_MAX * d + x.abs() * (1e-6 + 2.0 ** -22)
+        if c.epi == "rope":
+            return GemmRope.rotated_bound(c, x, d)
+        return bf16_ulp(x) + d
+
+    @staticmethod
+    def emulate(c):
+        rstd, mr = fold_merge32(c.stats, c.eps)
+        v = c.acc(dtype=torch.float32) * rstd[:, None] + (c.csum.float()[None, :] * mr[:, None] + c.bias.float()[None, :])
+        if c.epi == "gelu":
+            return torch.nn.functional.gelu(v).bfloat16().double()
+        if c.epi == "rope":
+            return GemmRope.emulate_rotate(c, v)
+        return v.bfloat16().double()
+
+
+def _stats_neighbour_row(c):
+    return GemmLnIn.reference(c, stats=torch.roll(c.stats, 1, dims=0))
+
+
+def _stats_one_slot_twice(c):
+    """slot 1 read in place of slot 0 (an off-by-one slot index)"""
+    if c.stats.shape[1] < 2:
+        return None
+    s = c.stats.clone()
+    s[:, 0] = s[:, 1]
+    return GemmLnIn.reference(c, stats=s)
+
+
+GemmLnIn.MUTATIONS = [
+    ("the last K-tile dropped", lambda c: GemmLnIn.reference(c, acc=_acc_drop_last_ktile(c)), 3.0),
+    ("the mean csum term dropped", lambda c: GemmLnIn.reference(c, mean_csum=False), 3.0),
+    ("statistics of the neighbouring row", _stats_neighbour_row, 3.0),
+    ("statistics slot 1 read for slot 0", _stats_one_slot_twice, 3.0),
+    ("the between-slice term LNF_SLICE dd dropped", lambda c: GemmLnIn.reference(c, between=False), 3.0),
+    ("eps dropped", lambda c: GemmLnIn.reference(c, eps=0.0), 3.0),
+] + _rope_mutations(lambda c, tokens: GemmLnIn.reference(c, tokens=tokens) if c.epi == "rope" else None)
+
+
+# ------------------------------------------------- folded LayerNorm: the producer ----
+# Per row and 256-column slice (one column tile) the residual epilogue writes (mean, M2) of the new values: each of the 4
+# waves sums its 64 columns in a tree of depth 6 (dm_w <= 6 U_F32 sum|x| / 64, plus a margin of one level) and sums
+# (x - m_w)^2 by fma (depth <= 11 with the lanes' tree; the rounding of d: 2 U_F32); m_w off by dm_w adds exactly 64 dm_w^2
+# (sum (x - m_w) = 0).  lnf_store_tile_stats: mean = ((a + b) + (c + d)) / 4 (2 U_F32 of the mean of |m_w|, plus the mean of
+# dm_w); M2 = sum q_w + 64 sum (m_w - mean)^2: the q errors, 2 U_F32 sum q_w for the adds, 64 sum (2 |d_w| e_w + e_w^2)
+# with e_w = dm_w + dmean + U_F32 |d_w|, 3 U_F32 of the between term, U_F32 M2 for the last add.
+# The reference is fp64 statistics of the kernel's own output row (fp32 rows, or hi + lo: the kernel worked on the fp32
+# value, which hi + lo misses by <= 2^-8 ulp_bf16: its effect on mean and M2 is added).
+class LnStats:
+    @staticmethod
+    def reference(x):
+        """x fp64 [M, N] -> [M, N / 256, 2] (mean, M2)"""
+        M, N = x.shape
+        s = x.double().reshape(M, N // LNF_SLICE, LNF_SLICE)
+        m = s.mean(-1)
+        return torch.stack((m, ((s - m[..., None]) ** 2).sum(-1)), dim=-1)
+
+    @staticmethod
+    def bound(x, planes=False):
+        M, N = x.shape
+        s = x.double().reshape(M, N // LNF_SLICE, 4, 64)
+        a = s.abs()
+        mw = s.mean(-1)
+        dmw = 7 * U_F32 * a.mean(-1)
+        qw = ((s - mw[..., None]) ** 2).sum(-1)
+        dqw = (qw + 64 * dmw ** 2) * (13 * U_F32) + 64 * dmw ** 2
+        mean = mw.mean(-1)
+        dmean = dmw.mean(-1) + 2 * U_F32 * mw.abs().mean(-1)
+        dw = (mw - mean[..., None]).abs()
+        ew = dmw + dmean[..., None] + U_F32 * dw
+        between = 64 * (dw ** 2).sum(-1)
+        m2 = qw.sum(-1) + between
+        dm2 = dqw.sum(-1) + 2 * U_F32 * qw.sum(-1) + 64 * (2 * dw * ew + ew * ew).sum(-1) + 3 * U_F32 * between + U_F32 * m2
+        if planes:
+            delta = 2.0 ** -8 * bf16_ulp(s)
+            dmean = dmean + delta.mean((-1, -2))
+            dm2 = dm2 + (2 * (s - mean[..., None, None]).abs() * delta + delta ** 2).sum((-1, -2)) \
+                + 2 * 256 * delta.mean((-1, -2)) ** 2
+        return torch.stack((dmean + f32_ulp(mean), dm2 + f32_ulp(m2)), dim=-1)
+
+    @staticmethod
+    def emulate(x):
+        M, N = x.shape
+        s = x.float().reshape(M, N // LNF_SLICE, 4, 64)
+        mw = s.sum(-1) / 64
+        qw = ((s - mw[..., None]) ** 2).sum(-1)
+        mean = ((mw[..., 0] + mw[..., 1]) + (mw[..., 2] + mw[..., 3])) * 0.25
+        d = mw - mean[..., None]
+        m2 = ((qw[..., 0] + qw[..., 1]) + (qw[..., 2] + qw[..., 3])) + 64 * (d * d).sum(-1)
+        return torch.stack((mean, m2), dim=-1).double()
+
+
+def _stats_no_between(x):
+    M, N = x.shape
+    s = x.double().reshape(M, N // LNF_SLICE, 4, 64)
+    mw = s.mean(-1)
+    return torch.stack((mw.mean(-1), ((s - mw[..., None]) ** 2).sum((-1, -2))), dim=-1)
+
+
+def _stats_next_slot(x):
+    r = LnStats.reference(x)
+    if r.shape[1] < 2:
+        return None
+    return torch.roll(r, 1, dims=1)
+
+
+def _stats_one_pass(x):
+    s = x.float().reshape(x.shape[0], -1, LNF_SLICE)
+    m = s.mean(-1)
+    return torch.stack((m, (s * s).sum(-1) - LNF_SLICE * m * m), dim=-1).double()
+
+
+LnStats.MUTATIONS = [
+    ("the between-wave term 64 sum (m_w - mean)^2 dropped", _stats_no_between, 3.0),
+    ("statistics written to the neighbouring slot", _stats_next_slot, 3.0),
+    ("statistics of the neighbouring row", lambda x: torch.roll(LnStats.reference(x), 1, dims=0), 3.0),
+    ("one-pass M2 = sum x^2 - 256 mean^2 in fp32", _stats_one_pass, 3.0),
+]
+
+
+# ------------------------------------------- split-K reduce + LayerNorm (one image) ----
+# splitk_reduce_resid_ln_kernel: x_new = x + gamma (sum of the fp32 planes + bias), stored (GemmResid's bound), and the same
+# registers normalised (w = 1, b = 0, bf16): the LayerNorm bound of the kernel's own x_new -- it normalises exactly the
+# values it stores, so the reference for h is the fp64 LayerNorm of the stored x_new.
+class SplitkResidLn:
+    @staticmethod
+    def h_reference(x_new, eps, one_pass=False, eps_on=True):
+        xd = x_new.double()
+        mu = xd.mean(-1, keepdim=True)
+        if one_pass:
+            x32 = x_new.float()
+            m32 = x32.mean(-1, keepdim=True)
+            var = ((x32 * x32).mean(-1, keepdim=True) - m32 * m32).double()
+        else:
+            var = ((xd - mu) ** 2).mean(-1, keepdim=True)
+        return (xd - mu) / torch.sqrt(var + (eps if eps_on else 0.0))
+
+    @staticmethod
+    def h_bound(x_new, eps):
+        W = x_new.shape[1]
+        one = torch.ones(W, dtype=torch.float32, device=x_new.device)
+        return LayerNorm.bound(x_new, one, torch.zeros_like(one), eps, True)
+
+    @staticmethod
+    def h_emulate(x_new, eps):
+        W = x_new.shape[1]
+        one = torch.ones(W, dtype=torch.float32, device=x_new.device)
+        return LayerNorm.emulate(x_new, one, torch.zeros_like(one), eps, True)
+
+
+SplitkResidLn.MUTATIONS_H = [
+    ("eps dropped", lambda x, eps: SplitkResidLn.h_reference(x, eps, eps_on=False), 3.0),
+    ("one-pass variance E[x^2] - mean^2 in fp32", lambda x, eps: SplitkResidLn.h_reference(x, eps, one_pass=True), 3.0),
+]
+
+
+# -------------------------------------------------- rounding direction of bf16 stores ----
+# A per-element bound of ulp_bf16 cannot tell round-to-nearest from truncation (both are within one ulp).  Over many
+# outputs the mean of sign(ref) (got - ref) / ulp_bf16(ref) can: ~0 for round-to-nearest (the fp32 error is far below an
+# ulp and symmetric), about -0.5 for a store that truncates toward zero.
+ROUNDING_BIAS_MAX = 0.1
+ROUNDING_MIN_OUTPUTS = 10 ** 6
+
+
+def rounding_bias(got, ref):
+    """(mean signed error in ulps, outputs counted) over the outputs of at least 1/64 of the output's rms: below that (the
+    GELU's negative tail) the fp32 error before the rounding is not small against an ulp of the output"""
+    got, ref = got.double().flatten(), ref.double().flatten()
+    keep = (ref.abs() >= ref.pow(2).mean().sqrt() / 64) & torch.isfinite(got)
+    r = ref[keep]
+    return float((torch.sign(r) * (got[keep] - r) / bf16_ulp(r)).mean()), int(keep.sum())
+
+
+def bf16_truncate(x):
+    """fp32 -> bf16 by dropping the low 16 bits (the bug the statistic catches), as fp64"""
+    b = x.float().contiguous().view(torch.int32) & -65536
+    return b.view(torch.float32).double()
+
+
+
+
+# ------------------------------------------------------------------- test data ----
+def fold_rows(M, W, seed, device="cpu"):
+    """Residual rows the fold is weak on: per-row offsets 0 .. 33 sigma, 256-column slices with different means, outlier
+    channels, every 37th row near-constant (std 1e-3: var below eps = 1e-5, so eps matters).  fp32 [M, W]."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    sig = torch.rand(M, 1, generator=g, device=device) * 1.5 + 0.25
+    x = torch.randn(M, W, generator=g, device=device) * sig
+    P = -(-W // LNF_SLICE)
+    x += (torch.randn(M, P, generator=g, device=device) * sig).repeat_interleave(LNF_SLICE, dim=1)[:, :W]
+    off = torch.linspace(0, 33, M, device=device)[torch.randperm(M, generator=g, device=device)]
+    x += (off[:, None] * sig) * torch.sign(torch.randn(M, 1, generator=g, device=device))
+    ch = torch.randperm(W, generator=g, device=device)[:4]
+    x[:, ch] += 20 * sig
+    const = near_constant_rows(M, device)
+    x[const] = (torch.randn(len(const), 1, generator=g, device=device) * 3
+                + torch.randn(len(const), W, generator=g, device=device) * 1e-3)
+    return x
+
+
+def near_constant_rows(M, device="cpu"):
+    return torch.arange(3, max(M, 3), 37, device=device)
+
+
+def spread(n, seed, lo=-3, hi=1, device="cpu"):
+    """n fp32 values of either sign over binades 2^lo .. 2^hi (bias / gamma)"""
+    g = torch.Generator(device=device).manual_seed(seed)
+    e = torch.randint(lo, hi + 1, (n,), generator=g, device=device).float()
+    return torch.sign(torch.randn(n, generator=g, device=device)) * (1 + torch.rand(n, generator=g, device=device)) * torch.exp2(e)
+
+
+def weights(N, K, seed, device="cpu"):
+    g = torch.Generator(device=device).manual_seed(seed)
+    return (torch.randn(N, K, generator=g, device=device) * K ** -0.5).bfloat16()
+
+
+def resid_case(M, N, K, seed, device="cpu", planes_in=False, ksplit=1):
+    """a residual GEMM: A = bf16 of GELU-like activations, old rows from fold_rows"""
+    g = torch.Generator(device=device).manual_seed(seed + 1)
+    a = torch.nn.functional.gelu(torch.randn(M, K, generator=g, device=device) * 2).bfloat16()
+    x = fold_rows(M, N, seed, device)
+    bias, gamma = spread(N, seed + 3, device=device), spread(N, seed + 4, -6, 0, device)
+    # the near-constant rows stay near-constant in x_new: A's row is zero there and x_old holds the row minus gamma bias
+    const = near_constant_rows(M, device)
+    a[const] = 0
+    x[const] -= (gamma * bias).float()
+    c = GemmCase(a, weights(N, K, seed + 2, device), bias, gamma=gamma, x=x, ksplit=ksplit)
+    if planes_in:
+        c.hi = x.bfloat16()
+        c.lo = (x - c.hi.float()).bfloat16()
+    return c
+
+
+def ln_in_case(M, N, K, seed, epi, device="cpu", S=577, hd=64, rope_cols=0, cs=None):
+    """a folded-LayerNorm consumer: A = bf16(x) of fold_rows, its fp32 slot statistics, W' bf16, csum = fp32 sum of W'"""
+    x = fold_rows(M, K, seed, device)
+    b = weights(N, K, seed + 2, device)
+    st = LnStats.reference(x).float()
+    csum = b.double().sum(1).float()
+    return GemmCase(x.bfloat16(), b, spread(N, seed + 3, device=device), stats=st, csum=csum, eps=1e-5, epi=epi, S=S, hd=hd,
+                    rope_cols=rope_cols, cs=cs)
+
+
+def plain_case(M, N, K, seed, device="cpu"):
+    g = torch.Generator(device=device).manual_seed(seed)
+    a = (torch.randn(M, K, generator=g, device=device) * 2).bfloat16()
+    return GemmCase(a, weights(N, K, seed + 2, device), spread(N, seed + 3, device=device))
+
+
+# ------------------------------------------------------------------ the cases ----
+# Shared by the CPU teeth test (M cut to a few hundred rows) and the GPU module (the towers' M).  S / hd / rope table of
+# L14 (grid 24, class token: S 577, hd 64) and G14 (grid 32, no class token: S 1024, hd 96).
+TOWERS = {"L14": dict(W=1024, Md=4096, S=577, hd=64, grid=24, cls=True),
+          "G14": dict(W=1536, Md=8960, S=1024, hd=96, grid=32, cls=False),
+          "B16": dict(W=768, Md=3072, S=197, hd=64, grid=14, cls=True)}
+
+# (label, N, K, parts, epi) of the folded consumer; RoPE rows rotate the first 2W columns (q and k)
+LN_IN_CASES = [("L14 qkv rope", 3072, 1024, "rope", "L14"), ("L14 fc1 gelu", 4096, 1024, "gelu", "L14"),
+               ("K512 bf16 (lnf_merge, parts 2)", 1024, 512, "bf16", "L14"), ("K768 gelu (lnf_merge, parts 3)", 3072, 768, "gelu", "B16"),
+               ("G14 qkv rope (merge_n<6>)", 4608, 1536, "rope", "G14"), ("G14 fc1 gelu", 8960, 1536, "gelu", "G14")]
+
+# (label, N, K, ksplit, planes) of the residual epilogue; ksplit = the K parts of the split-K form the GPU case takes
+RESID_CASES = [("L14 out-proj fp32", 1024, 1024, 1, "none"), ("L14 out-proj planes out", 1024, 1024, 1, "out"),
+               ("L14 fc2 planes in/out", 1024, 4096, 1, "inout"), ("L14 fc2 planes in, fp32 out", 1024, 4096, 1, "in"),
+               ("L14 fc2 split-K 3", 1024, 4096, 3, "none"), ("fc2 split-K 2", 1024, 2048, 2, "none"),
+               ("G14 fc2 planes in/out", 1536, 8960, 1, "inout")]
+
+# (label, N, K, ksplit) of the split-K reduce with the LayerNorm (MAXG = ceil(N / 512))
+SPLITK_LN_CASES = [("L14 out-proj MAXG 2", 1024, 1024, 3), ("L14 fc2 MAXG 2", 1024, 4096, 3), ("N256 MAXG 1", 256, 1024, 3),
+                   ("N1536 MAXG 3", 1536, 1024, 3), ("N2048 MAXG 4", 2048, 1024, 3), ("B16 fc2 MAXG 2", 768, 3072, 3)]
+
+
+def tower_rope(tower):
+    t = TOWERS[tower]
+    return rope_table(t["grid"], t["hd"], t["cls"])
+
+
+# ------------------------------------------------------------ launch forms ----
+# The bits of revo_debug_gemm_forms (revers-o_amd/csrc/kernels.h GemmForm), in bit order.
+GEMM_FORMS = ["SKINNY_444", "SKINNY_411", "128_128", "128_64", "128R", "256_TILE", "256P", "256P_192", "256Q", "256Q_QTAIL",
+              "SPLITK_RING", "SPLITK_RING_LN", "SPLITK_256", "LN_FOLDED", "LN_CONSUMED", "PLANES_IN", "PLANES_OUT"]
+
+
+def form_bits(names):
+    return sum(1 << GEMM_FORMS.index(n) for n in names)
+
+
+def form_names(bits):
+    return sorted(n for i, n in enumerate(GEMM_FORMS) if bits >> i & 1)
+
+
+# The GPU cases of tests/test_gpu_gemm_bounds.py: (label, kind, M, N, K, options, expected forms on librevo_exp.so).
+# kind: "f32" / "bf16" / "gelu" / "resid" (revo_op_gemm), "rope" (revo_op_gemm_rope), "ln_in:bf16" / "ln_in:gelu"
+# (revo_op_gemm_ln_in), "ln_in_rope", "resid_ln:<planes>" (revo_op_gemm_resid_ln: none = fp32 rows + bf16 copy, out, inout,
+# in), "resid_norm" (revo_op_gemm_resid_norm).  options: tower (RoPE table / S / hd), variant / qstores (forced forms: then
+# the experiment library only), pad (NaN margins past N and M), ksplit (the split-K parts the form takes, for the record).
+_L, _G = 36928, 32768
+GEMM_FORM_CASES = [
+    # PE-L14 at batch 64: the forward's own launches
+    ("L14 b64 qkv rope + fold", "ln_in_rope", _L, 3072, 1024, dict(tower="L14"), ["256P", "LN_CONSUMED"]),
+    ("L14 b64 out-proj fold, planes out", "resid_ln:out", _L, 1024, 1024, {}, ["256P_192", "LN_FOLDED", "PLANES_OUT"]),
+    ("L14 b64 fc1 gelu + fold", "ln_in:gelu", _L, 4096, 1024, dict(pad=True), ["256Q_QTAIL", "LN_CONSUMED"]),
+    ("L14 b64 fc2 planes in/out", "resid_ln:inout", _L, 1024, 4096, {}, ["256P_192", "LN_FOLDED", "PLANES_IN", "PLANES_OUT"]),
+    ("L14 b64 last fc2 planes in, fp32 out", "resid_ln:in", _L, 1024, 4096, {}, ["256P_192", "PLANES_IN"]),
+    ("L14 b64 out-proj fold, fp32 rows + bf16 copy", "resid_ln:none", _L, 1024, 1024, {}, ["256P_192", "LN_FOLDED"]),
+    # PE-L14 at batch 8
+    ("L14 b8 qkv rope", "rope", 4616, 3072, 1024, dict(tower="L14"), ["256_TILE"]),
+    ("L14 b8 fc2", "resid", 4616, 1024, 4096, {}, ["SPLITK_256"]),
+    # PE-L14 at batch 1
+    ("L14 b1 out-proj + LayerNorm", "resid_norm", 577, 1024, 1024, dict(ksplit=3), ["SPLITK_RING_LN"]),
+    ("L14 b1 fc2 + LayerNorm", "resid_norm", 577, 1024, 4096, dict(ksplit=3), ["SPLITK_RING_LN"]),
+    ("L14 b1 fc1 gelu", "gelu", 577, 4096, 1024, {}, ["128_64"]),
+    ("L14 b1 qkv rope", "rope", 577, 3072, 1024, dict(tower="L14"), ["128R"]),
+    # the consumer's merge at the other slot counts; G14
+    ("K512 consumer (parts 2)", "ln_in:bf16", _L, 1024, 512, {}, ["256Q", "128_64", "LN_CONSUMED"]),
+    ("K768 consumer gelu (parts 3)", "ln_in:gelu", _L, 3072, 768, dict(tower="B16"), ["256Q", "LN_CONSUMED"]),
+    ("G14 qkv rope + fold (parts 6)", "ln_in_rope", _G, 4608, 1536, dict(tower="G14"), ["256P", "LN_CONSUMED"]),
+    ("G14 fc1 gelu + fold (parts 6)", "ln_in:gelu", _G, 8960, 1536, {}, ["256Q", "128_128", "LN_CONSUMED"]),
+    ("G14 fc2 planes in/out", "resid_ln:inout", _G, 1536, 8960, {}, ["256P", "LN_FOLDED", "PLANES_IN", "PLANES_OUT"]),
+    # the split-K reduce with the LayerNorm at the widths the towers do not reach
+    ("reduce N256 MAXG 1", "resid_norm", 577, 256, 1024, dict(ksplit=4), ["SPLITK_RING_LN"]),
+    ("reduce N1536 MAXG 3", "resid_norm", 577, 1536, 1024, dict(ksplit=2), ["SPLITK_RING_LN"]),
+    ("reduce N2048 MAXG 4", "resid_norm", 300, 2048, 1024, dict(ksplit=2), ["SPLITK_RING_LN"]),
+    ("reduce B16 fc2 MAXG 2 (partial group)", "resid_norm", 197, 768, 3072, dict(ksplit=8), ["SPLITK_RING_LN"]),
+    # the tail split: whole rounds of 256-row tiles + the leftover rows' own launch
+    ("tail split resid + ring split-K", "resid", 33000, 1024, 2048, dict(ksplit=4), ["256P", "SPLITK_RING"]),
+    ("tail split resid + 256 split-K", "resid", 17000, 2048, 2048, dict(ksplit=4), ["256P", "SPLITK_256"]),
+    ("tail split gelu, drained kernel", "gelu", _L, 4096, 1024, dict(qstores=0), ["256P", "SKINNY_411"]),
+    # forced forms
+    ("forced one workgroup per tile", "gelu", _L, 4096, 1024, dict(variant=1 << 16), ["256_TILE", "SKINNY_411"]),
+    ("forced no split-K leftover", "resid", 33000, 1024, 2048, dict(variant=1 << 17), ["256P", "128R"]),
+    ("forced no ring", "rope", 577, 3072, 1024, dict(tower="L14", variant=1 << 19), ["128_64"]),
+    ("forced no 192-row tiles", "resid", _L, 1024, 1024, dict(variant=1 << 3), ["256P", "128_64"]),
+] + [(f"{m}x{n}x{k} {e}", e, m, n, k, {}, [f]) for e in ("f32", "resid") for (m, n, k), f in zip(
+    GEMM_CASES, ["128_128", "SKINNY_444", "SKINNY_411", "SKINNY_444", "SKINNY_411", "SKINNY_411", "SKINNY_411", "SKINNY_411"])]

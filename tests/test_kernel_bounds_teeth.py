@@ -3,7 +3,10 @@
 For each op and each shape the GPU tier (test_gpu_kernel_bounds.py) runs: every listed mutation exceeds the bound by its
 required ratio somewhere (3x; 1.5x for the softmax scale off by 1 %), and the emulation of the kernel's rounding stays at
 <= 0.75x of the bound everywhere.  Mutations listed in NOT_CAUGHT must really stay under their ratio at those cases.  The
-bound is per element, so the large attention shapes are checked on a sample of (image, head) pairs."""
+bound is per element, so the large attention shapes are checked on a sample of (image, head) pairs.  The GEMM family
+(GemmF32, GemmResid, GemmRope, GemmLnIn, LnStats, SplitkResidLn) runs at the GPU cases' N, K, slot counts, S and head_dim
+with M cut to a few hundred rows; the rounding-direction statistic and the coverage of the launch-form record are checked
+here too."""
 import pytest
 import torch
 
@@ -91,3 +94,119 @@ def test_f32_to_bf16_specials_are_what_the_gpu_test_expects():
             assert out == want[bits], (hex(bits), hex(out))
     nan = torch.isnan(x)
     assert int(nan.sum()) == 5 and torch.isnan(x.bfloat16()[nan]).all()
+
+
+# ---------------------------------------------------------------- the GEMM family ----
+TEETH_ROWS = 160
+
+
+def _mut(c, muts):
+    return [(name, f(c), need) for name, f, need in muts]
+
+
+@pytest.mark.parametrize("MNK", kb.GEMM_CASES, ids=[f"{m}x{n}x{k}" for m, n, k in kb.GEMM_CASES])
+def test_gemm_f32_bound_has_teeth(MNK):
+    c = kb.plain_case(*MNK, seed=sum(MNK))
+    G = kb.GemmF32
+    _check("gemm f32", "x".join(map(str, MNK)), {"K": MNK[2]}, G.reference(c), G.bound(c), G.emulate(c), _mut(c, G.MUTATIONS))
+
+
+@pytest.mark.parametrize("case", kb.RESID_CASES, ids=[x[0] for x in kb.RESID_CASES])
+def test_gemm_resid_bound_has_teeth(case):
+    label, N, K, ksplit, planes = case
+    c = kb.resid_case(TEETH_ROWS, N, K, seed=N + K, planes_in=planes in ("in", "inout"), ksplit=ksplit)
+    G, pout = kb.GemmResid, planes in ("out", "inout")
+    _check("resid", label, {"K": K}, G.reference(c), G.bound(c, pout), G.emulate(c, pout), _mut(c, G.MUTATIONS))
+    if pout:                                                      # the planes the emulation writes keep their invariant
+        x = G.emulate(c).float()
+        hi = x.bfloat16()
+        assert kb.planes_ok(hi, (x - hi.float()).bfloat16())
+
+
+@pytest.mark.parametrize("MNK", kb.GEMM_CASES, ids=[f"{m}x{n}x{k}" for m, n, k in kb.GEMM_CASES])
+def test_gemm_resid_small_shapes_have_teeth(MNK):
+    c = kb.resid_case(*MNK, seed=sum(MNK))
+    G = kb.GemmResid
+    _check("resid", "x".join(map(str, MNK)), {"K": MNK[2]}, G.reference(c), G.bound(c), G.emulate(c), _mut(c, G.MUTATIONS))
+
+
+@pytest.mark.parametrize("tower", ["L14", "G14"])
+def test_gemm_rope_bound_has_teeth(tower):
+    t = kb.TOWERS[tower]
+    W = t["W"]
+    c = kb.plain_case(t["S"] + 23, 3 * W, W, seed=W)
+    c = c.with_(cs=kb.tower_rope(tower), S=t["S"], hd=t["hd"], rope_cols=2 * W)
+    G = kb.GemmRope
+    _check("gemm rope", tower, {}, G.reference(c), G.bound(c), G.emulate(c), _mut(c, G.MUTATIONS))
+
+
+@pytest.mark.parametrize("case", kb.LN_IN_CASES, ids=[x[0] for x in kb.LN_IN_CASES])
+def test_gemm_ln_in_bound_has_teeth(case):
+    label, N, K, epi, tower = case
+    t = kb.TOWERS[tower]
+    rope = epi == "rope"
+    M = t["S"] + 23 if rope else TEETH_ROWS
+    c = kb.ln_in_case(M, N, K, seed=N + K, epi=epi, S=t["S"], hd=t["hd"], rope_cols=2 * t["W"] if rope else 0,
+                      cs=kb.tower_rope(tower) if rope else None)
+    G = kb.GemmLnIn
+    _check("gemm ln_in", label, {}, G.reference(c), G.bound(c), G.emulate(c), _mut(c, G.MUTATIONS))
+
+
+@pytest.mark.parametrize("planes", [False, True])
+@pytest.mark.parametrize("N", [512, 768, 1024, 1536])
+def test_ln_stats_bound_has_teeth(N, planes):
+    c = kb.resid_case(TEETH_ROWS, N, 1024, seed=N)
+    x = kb.GemmResid.emulate(c, planes_out=planes)                # the kernel's row (fp32, or hi + lo)
+    L = kb.LnStats
+    # the emulation runs on the fp32 row the kernel holds; with planes the reference sees hi + lo of it
+    x32 = kb.GemmResid.emulate(c).float()
+    emu = L.emulate(x32)
+    _check("ln stats", f"N{N}{' planes' if planes else ''}", {}, L.reference(x), L.bound(x, planes), emu,
+           [(name, f(x), need) for name, f, need in L.MUTATIONS])
+
+
+@pytest.mark.parametrize("case", kb.SPLITK_LN_CASES, ids=[x[0] for x in kb.SPLITK_LN_CASES])
+def test_splitk_resid_ln_bound_has_teeth(case):
+    label, N, K, ksplit = case
+    c = kb.resid_case(TEETH_ROWS, N, K, seed=N * 3 + K, ksplit=ksplit)
+    G, H, eps = kb.GemmResid, kb.SplitkResidLn, 1e-5
+    _check("splitk ln x", label, {"K": K}, G.reference(c), G.bound(c), G.emulate(c), _mut(c, G.MUTATIONS))
+    x_new = G.emulate(c).float()                                  # the values the kernel stores and normalises
+    muts = [(name, f(x_new, eps), need) for name, f, need in H.MUTATIONS_H]
+    muts.append(("normalised the old row instead of the new one", H.h_reference(c.x, eps), 3.0))
+    muts.append(("a plane dropped before the normalisation",
+                 H.h_reference(G.reference(c, kb._acc_drop_plane(c)).float(), eps), 3.0))
+    _check("splitk ln h", label, {}, H.h_reference(x_new, eps), H.h_bound(x_new, eps), H.h_emulate(x_new, eps), muts)
+
+
+def test_bf16_rounding_direction_statistic_has_teeth():
+    """Round-to-nearest stores average to ~0 ulp of signed error; truncating stores to ~-0.5 (per-element bounds of one
+    ulp cannot tell them apart)."""
+    c = kb.ln_in_case(400, 4096, 1024, seed=7, epi="gelu")
+    ref, bound = kb.GemmLnIn.reference(c), kb.GemmLnIn.bound(c)
+    rstd, mr = kb.fold_merge32(c.stats, c.eps)
+    v = c.acc(dtype=torch.float32) * rstd[:, None] + (c.csum.float()[None, :] * mr[:, None] + c.bias.float()[None, :])
+    v = torch.nn.functional.gelu(v)
+    near, n = kb.rounding_bias(v.bfloat16(), ref)
+    trunc, _ = kb.rounding_bias(kb.bf16_truncate(v), ref)
+    assert n >= kb.ROUNDING_MIN_OUTPUTS, n
+    print(f"[rounding direction] {n} outputs: round-to-nearest {near:+.4f}, truncation {trunc:+.4f} (limit {kb.ROUNDING_BIAS_MAX})")
+    assert abs(near) <= kb.ROUNDING_BIAS_MAX
+    assert abs(trunc) > 3 * kb.ROUNDING_BIAS_MAX
+    # and the truncated outputs stay within the per-element bound: only the statistic sees them
+    assert kb.ratio(kb.bf16_truncate(v), ref, bound) <= 1.0
+
+
+def test_every_gemm_launch_form_has_a_gpu_case():
+    """The GPU cases (kb.GEMM_FORM_CASES, each asserting the exact set of forms it runs) cover every bit of the launcher's
+    form record, and that record is kernels.h's GemmForm enum, in order: a new launch form without a case fails here."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "revers-o_amd", "csrc",
+                            "kernels.h")).read()
+    enum = re.findall(r"GF_(\w+) = 1u << (\d+)", src)
+    assert [n for n, _ in enum] == kb.GEMM_FORMS and [int(b) for _, b in enum] == list(range(len(enum)))
+    reached = set()
+    for case in kb.GEMM_FORM_CASES:
+        reached |= set(case[-1])
+    assert reached == set(kb.GEMM_FORMS), sorted(set(kb.GEMM_FORMS) - reached)
