@@ -192,6 +192,34 @@ int32_t revo_search_range(revo_gallery* g, const float* queries, int32_t n_queri
                           int64_t* n_results, void* stream);
 int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start, int64_t n, int64_t* indices, float* scores,
                                int32_t dst_on_device);
+/* ---- search by examples: "more like these, and not like those" (relevance feedback; the best_score strategy of the
+ * vector database the reference sits on)
+ * RECOMMEND.  examples: [n_positive + n_negative, dim] fp32 on the device, the positives first; n_positive >= 1,
+ * n_negative >= 0, n_positive + n_negative <= 128.  They are normalised like every query.  For a gallery row r, with
+ * s(e, r) the fp32 score of example e against row r (the one fma chain of EXACTNESS: the bits every search returns),
+ *   sp = max of s over the positives,  sn = max of s over the negatives  (no negatives: score = sp)
+ *   score(r) = sp           if sp > sn
+ *            = -(sn * sn)   otherwise   (one fp32 multiply, rounded to nearest, fused with nothing)
+ * The result is the best k (1 <= k <= 1024) rows the handle's filter allows (revo_search_set_filter, with its lifecycle),
+ * ordered by (score desc, row index asc); has_threshold keeps score >= threshold.  Outputs as revo_search_topk_large for ONE
+ * query: scores [k], indices [k] (row + index_offset), counts [1], device memory, padding -inf / -1.  EXACT: the rows, order
+ * and score bits that computing score(r) as written for every allowed row and sorting gives.  So one positive and no
+ * negative returns what revo_search_topk_large returns for that vector, no negatives return the merge (max per row) of the
+ * positives' single searches, and two calls give identical bytes.  How: with e the largest rounding bound of the
+ * certificate over the examples, a row's bf16 scan scores bound score(r) from both sides (per branch of the formula, which
+ * jumps at sp = sn); the k-th largest lower bound over a sample of the first rows is a level tau that k rows reach; one
+ * MFMA pass over the gallery's bf16 rows, which reduces each tile's scores over the example rows in registers, keeps every
+ * allowed row whose upper bound reaches tau; those rows are re-scored in fp32 against every example and sorted on the
+ * device.  No certificate can fail: tau is a proven lower bound of the k-th score whatever the data; bad data costs
+ * candidates, never exactness.
+ * Like revo_search_range it is SYNCHRONOUS on `stream`.  Needs the fp32 master rows (keep_f32 = 0: status -2).  A null
+ * handle or pointer, n_positive < 1, n_negative < 0, more than 128 examples, k outside 1..1024 or a NaN threshold give
+ * status -2 before the device is touched.  An empty gallery, or a filter that allows no row: counts = 0, all padding.
+ * revo_search_stats after it: slot 3 = candidate rows re-scored in fp32, slot 7 = 1 when the candidate pass met an allowed
+ * row (0: empty gallery, or no row allowed), every other slot 0.  A pairs or a range result held by the handle stays valid. */
+int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_positive, int32_t n_negative, int32_t k,
+                              int32_t has_threshold, float threshold, int64_t index_offset, float* scores, int64_t* indices,
+                              int32_t* counts, void* stream);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:
@@ -275,7 +303,8 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), revo_search_topk_large: queries
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
- * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE. */
+ * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE,
+ * after revo_search_recommend see RECOMMEND. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */

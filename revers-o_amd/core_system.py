@@ -923,6 +923,53 @@ class SimpleReverso:
             text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
         return text, items
 
+    def search_by_examples(self, positive, negative=(), similarity_threshold=None, max_results=5, query_filter=None):
+        """Relevance feedback: "more like these, and not like those".  Each example is the ``id`` of a stored region (as
+        earlier results return it), an embedding (tensor / array of the model's width) or an image (PIL image, array or
+        path: embedded whole through the loaded model).  A region's score is its best score against a positive example
+        when that beats its best score against a negative one, else minus the square of the latter; examples given by id
+        are not returned.  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox", "id", "score"}`` best first."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+
+        def resolve(examples):
+            if isinstance(examples, (str, bytes)) or torch.is_tensor(examples) or isinstance(examples, (np.ndarray, Image.Image)):
+                examples = [examples]
+            out, images, slots = [], [], []
+            for e in examples or ():
+                is_id = isinstance(e, str) and not os.path.exists(e)
+                is_vec = (torch.is_tensor(e) or isinstance(e, np.ndarray)) and np.ndim(e) == 1
+                if is_id or is_vec:
+                    out.append(e)
+                else:
+                    slots.append(len(out))
+                    out.append(None)
+                    images.append(pp.to_pil(Image.open(e).convert("RGB") if isinstance(e, str) else e))
+            if images:
+                for slot, v in zip(slots, self._embed_pils(images)):
+                    out[slot] = v
+            return out
+
+        pos, neg = resolve(positive), resolve(negative)
+        if not pos:
+            return "❌ No positive examples given. Please pick at least one result or image.", []
+        try:
+            with self._lock:
+                hits = self.vector_db.recommend(pos, neg, limit=int(max_results),
+                                                score_threshold=None if similarity_threshold is None else float(similarity_threshold),
+                                                query_filter=query_filter)
+        except KeyError as e:
+            return f"❌ {e.args[0]}", []
+        if not hits:
+            return ("❌ No regions found for these examples" +
+                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
+        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
+                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+        text = f"🎯 Found {len(items)} regions like the {len(pos)} positive and unlike the {len(neg)} negative examples:\n\n"
+        for n, it in enumerate(items):
+            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
+        return text, items
+
     def find_duplicates(self, similarity_threshold=0.95, query_filter=None):
         """Groups of near-duplicate regions in the loaded database: every stored region whose vector scores at least
         ``similarity_threshold`` against another one, joined transitively (re-posted, re-compressed or re-cropped copies of

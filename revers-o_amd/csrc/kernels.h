@@ -459,6 +459,33 @@ int launch_range_emit(const uint64_t* keys, const float* vals, long n, int b, lo
                       hipStream_t st);
 // inclusive prefix sums of c[0 .. n) in place (one workgroup)
 int launch_range_offsets(unsigned long long* c, long n, hipStream_t st);
+// ---- search by examples (revo_search_recommend; recommend.hip): sample pass -> level tau, candidate
+// pass (the range join's skeleton with an epilogue that reduces over the example rows), fp32 re-score, the pairs' sort
+constexpr int RECOMMEND_MAX_EXAMPLES = 128;  // the example rows of a tile column live in one wave up to here
+struct RecommendPassArgs {
+    const bf16_t* Qb; long ldq;   // the bf16 example rows, positives first
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    int P, Nn;                    // positive / negative examples
+    long N; int D;                // rows the pass covers (from row 0)
+    const float* qstat;           // [P + Nn][2] the examples' rounding norms (launch_l2norm_rows row_stats)
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    const float* tau;             // candidate pass: [1] the level (device)
+    unsigned long long* cnt;      // candidate pass: [0] candidates found (counts past cap), [2] allowed rows met
+    uint32_t* rows; long cap;     // candidate pass: [cap] candidate rows
+    float* lb_out;                // sample pass: [N] lower bound of every row's score (-inf: not allowed)
+};
+int launch_recommend_pass(const RecommendPassArgs& a, int sample, hipStream_t st);
+// tau[0] = the k-th largest of lb[0 .. n) (-inf when n < k), raised to thr when has_thr
+int launch_recommend_level(const float* lb, int n, int k, int has_thr, float thr, float* tau, hipStream_t st);
+// score(r) of candidate rows [0, n) against the P + Nn fp32 example rows Qf; those passing the threshold appended to out_keys
+// ((~order-preserving score bits << b) | row) / out_scores, count in *kept
+int launch_recommend_rescore(const uint32_t* cand, long n, const float* Qf, long ldq, int P, int Nn, const float* Gf, long ldg,
+                             int D, int has_thr, float thr, int b, unsigned long long* kept, uint64_t* out_keys, float* out_scores,
+                             hipStream_t st);
+// the first min(n, k) sorted entries -> scores / row + idx_offset, padding behind them, counts[0]
+int launch_recommend_emit(const uint64_t* keys, const float* vals, long n, int k, int b, long idx_offset, float* scores,
+                          long long* idx, int* counts, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

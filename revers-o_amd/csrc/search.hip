@@ -995,6 +995,92 @@ extern "C" int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int
     API_END
 }
 
+// ---- search by examples (include/revo.h revo_search_recommend; recommend.hip)
+static int search_recommend(revo_gallery* g, const float* examples, int P, int Nn, int k, int has_thr, float thr, long index_offset,
+                            float* scores, long long* indices, int* counts, const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    const int E = P + Nn;
+    // (the two-phase protocol's state refers to the handle's query rows, which this search overwrites)
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, E, st));
+    REVO_REQUIRE(g->xw.ctr, "search_recommend: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    if (N == 0) {
+        CHECK_RC(launch_topk_fill_empty(scores, indices, counts, 1, k, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    // the sample: the rows revo_search_topk_large's sample pass covers (none in a small gallery: tau = -inf or the threshold)
+    const long n_s = large_sample_rows(E, N, k);
+    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept, [2] allowed rows the candidate pass met
+    float *tau = nullptr, *lb = nullptr, *kept_v = nullptr, *alt_v = nullptr;
+    uint32_t *cand = nullptr, *hist = nullptr; uint64_t *kept_k = nullptr, *alt_k = nullptr;
+    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+        cnt = l.take<unsigned long long>(4); tau = l.take<float>(1);
+        lb = l.take<float>(n_s > 0 ? n_s : 1);
+        cand = l.take<uint32_t>(N); kept_k = l.take<uint64_t>(N); alt_k = l.take<uint64_t>(N);
+        kept_v = l.take<float>(N); alt_v = l.take<float>(N);
+        hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
+    }));
+    // (the pairs' and the range search's layouts of this buffer are carved again by their next call)
+    { ProfScope ps("search_prep", st);
+      CHECK_RC(launch_l2norm_rows(examples, D, g->qf.p, D, g->qb.p, D, E, D, st, 1, g->qstat.p)); }
+    REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
+    RecommendPassArgs pa{};
+    pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.P = P; pa.Nn = Nn; pa.D = D;
+    pa.qstat = g->qstat.p; pa.gstat = g->gstat.p; pa.allow = allow;
+    { ProfScope ps("recommend_sample", st);
+      if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(launch_recommend_pass(pa, 1, st)); }
+      CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
+    { ProfScope ps("recommend_pass", st);
+      pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = cnt; pa.rows = cand; pa.cap = N;
+      CHECK_RC(launch_recommend_pass(pa, 0, st)); }
+    unsigned long long h[3] = {0, 0, 0};
+    REVO_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    const unsigned long long n_cand = h[0], n_allowed = h[2];
+    REVO_REQUIRE(n_cand <= (unsigned long long)N, "search_recommend: more candidates than rows");
+    int b = 1;
+    while (N > 1 && (1l << b) < N) ++b;
+    unsigned long long n_kept = 0;
+    { ProfScope ps("recommend_rescore", st);
+      CHECK_RC(launch_recommend_rescore(cand, (long)n_cand, g->qf.p, D, P, Nn, g->gf.p, D, D, has_thr, thr, b, cnt + 1, kept_k,
+                                        kept_v, st)); }
+    if (n_cand > 0) {
+        REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    uint64_t* sk; float* sv;
+    { ProfScope ps("recommend_sort", st);
+      CHECK_RC(launch_pairs_sort(kept_k, kept_v, alt_k, alt_v, (long)n_kept, 32 + b, hist, &sk, &sv, st)); }
+    CHECK_RC(launch_recommend_emit(sk, sv, (long)n_kept, k, b, index_offset, scores, indices, counts, st));
+    const int stats[2] = {(int)n_cand, n_allowed > 0 ? 1 : 0};    // slot 3 = candidate rows re-scored, slot 7 = candidate passes
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_positive, int32_t n_negative, int32_t k,
+                                         int32_t has_threshold, float threshold, int64_t index_offset, float* scores,
+                                         int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && examples && scores && indices && counts, "search_recommend: null argument");
+    REVO_REQUIRE(n_positive >= 1, "search_recommend: needs at least one positive example");
+    REVO_REQUIRE(n_negative >= 0, "search_recommend: negative count of negative examples");
+    REVO_REQUIRE((int64_t)n_positive + n_negative <= revo::RECOMMEND_MAX_EXAMPLES,
+                 "search_recommend: at most 128 examples (n_positive + n_negative)");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_recommend: k must be in [1, 1024]");
+    REVO_REQUIRE(!has_threshold || !std::isnan(threshold), "search_recommend: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "search_recommend: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_recommend(g, examples, n_positive, n_negative, k, has_threshold, threshold, index_offset, scores,
+                            (long long*)indices, counts, allow, (hipStream_t)stream);
+    API_END
+}
+
 #ifdef REVO_EXPERIMENTS   // librevo.so cannot be put into a non-exact mode
 extern "C" int32_t revo_search_set_mode(revo_gallery* g, int32_t mode) {
     REVO_REQUIRE(g && mode >= 0 && mode <= 3, "search_set_mode: mode must be 0..3");

@@ -334,6 +334,35 @@ class Gallery:
                        "revo_search_range_read")
         return offsets, idx, scores
 
+    def recommend(self, positive, negative=None, k=5, score_threshold=None, index_offset=0, allow=None):
+        """Search by examples (include/revo.h, RECOMMEND): ``positive`` fp32 ``[P, dim]`` and ``negative`` fp32 ``[N, dim]``
+        (or None) device tensors, ``P >= 1``, ``P + N <= 128``.  A row's score is its best score ``sp`` against a positive if
+        that exceeds its best score ``sn`` against a negative, else ``-(sn * sn)``; returns the best ``k <= 1024`` rows
+        (allowed by ``allow``, as in :meth:`search`) as ``(scores [k] fp32, indices [k] int64, count)`` device tensors
+        (``count`` a 0-d int32), best first, padded with -inf / -1 -- exactly what scoring every row that way in fp32 and
+        sorting gives.  Synchronous."""
+        def rows(t, name):
+            _require_cuda(t, name, self.device)
+            t = t.detach().to(torch.float32).contiguous()
+            if t.dim() == 1:
+                t = t[None]
+            if t.dim() != 2 or t.shape[1] != self.dim:
+                raise ValueError(f"{name} must be [n, {self.dim}], got {tuple(t.shape)}")
+            return t
+        pos = rows(positive, "positive")
+        neg = rows(negative, "negative") if negative is not None and negative.numel() > 0 else None
+        ex = pos if neg is None else torch.cat([pos, neg]).contiguous()
+        k = int(k)
+        scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
+        idx = torch.empty((max(k, 1),), dtype=torch.int64, device=self.device)
+        counts = torch.empty((1,), dtype=torch.int32, device=self.device)
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_search_recommend(
+                self._h, _lib.ptr(ex), pos.shape[0], 0 if neg is None else neg.shape[0], k, int(score_threshold is not None),
+                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
+                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_recommend")
+        return scores, idx, counts[0]
+
     @contextlib.contextmanager
     def _groups(self, groups):
         """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.

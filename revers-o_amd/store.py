@@ -193,6 +193,19 @@ def connected_groups(pairs, n):
     return [groups[root] for root in sorted(groups) if len(groups[root]) >= 2]
 
 
+def average_vector_query(positive, negative=None):
+    """The query vector of Qdrant's ``average_vector`` recommendation strategy (host, numpy): with the examples normalised,
+    ``mean(positive) + (mean(positive) - mean(negative))``, or ``mean(positive)`` alone without negatives.  fp32 ``[dim]``."""
+    def unit_rows(a):
+        a = np.asarray(a, dtype=np.float32)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        return a / np.linalg.norm(a, axis=1, keepdims=True)
+    pos = unit_rows(positive).mean(axis=0)
+    if negative is None or np.asarray(negative).size == 0:
+        return pos.astype(np.float32)
+    return (pos + (pos - unit_rows(negative).mean(axis=0))).astype(np.float32)
+
+
 class GalleryStore:
     def __init__(self, dim, device=0, capacity=65536, collection="simple_reverso", path=None, _fresh=True, build_info=None):
         """``build_info``: what the vectors were made from and how (source folder, model, region mode, ...), written into
@@ -213,6 +226,7 @@ class GalleryStore:
         self._pindex = _filters.PayloadIndex()   # columnar payload index of query_filter, caught up lazily
         self._filter_cache = None                # (filter key, len(store), device allow-bitmap) of the last filtered search
         self._group_cache = None                 # ((group_by, len(store)), device group ids, values) of the last grouped search
+        self._id_rows = None                     # (len(store), {point id: row}) of the last recommend by id
         if path:
             os.makedirs(path, exist_ok=True)
             open(os.path.join(path, ".lock"), "a").close()
@@ -291,6 +305,62 @@ class GalleryStore:
         :meth:`search` without ``limit``."""
         q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(1, -1)
         return self.search_range_batch(q, score_threshold, query_filter=query_filter)[0]
+
+    def _row_of_id(self, point_id):
+        if self._id_rows is None or self._id_rows[0] != len(self):
+            self._id_rows = (len(self), {pid: r for r, pid in enumerate(self.ids)})
+        try:
+            return self._id_rows[1][point_id]
+        except (KeyError, TypeError):
+            raise KeyError(f"recommend: no point with id {point_id!r} in the store") from None
+
+    def _example_vectors(self, examples):
+        """(fp32 [n, dim] device tensor, rows of the examples given by id) of a list of point ids and / or vectors"""
+        if examples is None:
+            examples = []
+        elif isinstance(examples, (str, bytes, int)) or (torch.is_tensor(examples) and examples.dim() == 1) or \
+                (isinstance(examples, np.ndarray) and examples.ndim == 1):
+            examples = [examples]
+        dev = self.gallery.device
+        vecs, rows = [], []
+        for e in examples:
+            if isinstance(e, (str, bytes, int)):
+                r = self._row_of_id(e)
+                rows.append(r)
+                vecs.append(self.gallery.read(r, 1)[0])
+            else:
+                vecs.append(torch.as_tensor(e, dtype=torch.float32).reshape(-1).to(dev))
+        out = torch.stack(vecs) if vecs else torch.empty((0, self.dim), dtype=torch.float32, device=dev)
+        if out.shape[1] != self.dim:
+            raise ValueError(f"recommend: example vectors must have {self.dim} elements")
+        return out, rows
+
+    def recommend(self, positive, negative=None, limit=5, score_threshold=None, query_filter=None, strategy="best_score"):
+        """Search by examples in Qdrant's shape: each example is a point id of the store or a vector.  Points given by id
+        are never part of the result.  ``strategy="best_score"``: a point's score is its best score against a positive if
+        that beats its best score against a negative, else minus the square of the latter -- exact (include/revo.h,
+        RECOMMEND), up to 128 examples, ``limit <= 1024``.  ``strategy="average_vector"``: :meth:`search` of
+        :func:`average_vector_query`.  An unknown id raises ``KeyError``."""
+        if strategy not in ("best_score", "average_vector"):
+            raise ValueError(f"recommend: unknown strategy {strategy!r} (best_score, average_vector)")
+        pos, prow = self._example_vectors(positive)
+        neg, nrow = self._example_vectors(negative)
+        if pos.shape[0] < 1:
+            raise ValueError("recommend: needs at least one positive example")
+        allow = None
+        if prow or nrow or query_filter is not None:
+            mask = self.filter_mask(query_filter).copy() if query_filter is not None else np.ones(len(self), dtype=bool)
+            mask[prow + nrow] = False
+            allow = torch.from_numpy(_filters.pack_bits(mask)).to(self.gallery.device)
+        if strategy == "average_vector":
+            q = torch.from_numpy(average_vector_query(pos.cpu().numpy(), neg.cpu().numpy())).to(self.gallery.device)
+            s, i, c = self.gallery.search(q[None], k=int(limit), score_threshold=score_threshold, allow=allow)
+            s, i, n = s[0], i[0], int(c[0])
+        else:
+            s, i, c = self.gallery.recommend(pos, neg if neg.shape[0] else None, k=int(limit), score_threshold=score_threshold,
+                                             allow=allow)
+            n = int(c)
+        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
 
     def _group_ids(self, group_by):
         key = (group_by, len(self))
