@@ -220,6 +220,38 @@ int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start,
 int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_positive, int32_t n_negative, int32_t k,
                               int32_t has_threshold, float threshold, int64_t index_offset, float* scores, int64_t* indices,
                               int32_t* counts, void* stream);
+/* ---- diverse search: top-k by maximal marginal relevance (the Mmr(diversity, candidates_limit) re-ranking of a nearest-
+ * neighbour query in the vector database the reference sits on: a gallery of video frames and region crops is full of
+ * near-identical rows, and the plain top-10 of one is ten copies of the same frame)
+ * MMR.  1 <= k <= candidates <= 1024, 0 <= diversity <= 1.  queries as every search: [n_queries, dim] fp32 on the device,
+ * normalised internally.
+ * Candidates of a query: exactly the result of revo_search_topk_large(g, q, k = candidates, has_threshold, threshold) --
+ * the same rows, order (score desc, row asc), score bits, filter semantics (revo_search_set_filter, with its lifecycle) and
+ * threshold cut.  Call them c_0 .. c_{n-1} (n <= candidates) and rel(i) their scores.
+ * Similarity sim(i, j): the fp32 score of the two candidates' fp32 master rows under the one fma chain of EXACTNESS -- the
+ * bits revo_gallery_pairs reports for that pair (PAIRS).  Symmetric bit for bit; sim(i, i) is never used.
+ * Selection: lam = 1.0f - diversity (one fp32 subtraction).  S = the candidates picked so far, empty at the start.  Each of
+ * the min(k, n) steps picks, among the candidates not in S, the one with the largest
+ *   v(i) = fl( fl(lam * rel(i)) - fl(diversity * m(i)) ),   m(i) = max over j in S of sim(i, j)
+ * (S empty: v(i) = fl(lam * rel(i))): three separately rounded fp32 operations, nothing fused.  Values compare as fp32
+ * numbers with -0 = +0; among equal values the lower candidate position i wins.
+ * Outputs (device memory; [n_queries, k] each, counts [n_queries]) in PICK order: indices = row + index_offset, scores =
+ * rel (the bits the plain search returns), mmr_values = the v the row was picked with (mmr_values may be NULL).  Padding
+ * -inf / -inf / -1.  Two calls give identical bytes.  So diversity = 0 returns exactly revo_search_topk_large(k)'s rows,
+ * order and score bits; k = candidates returns a permutation of the candidates; the first pick is c_0 whenever lam > 0.
+ * How: the inner large-k search writes the candidate lists into the handle's workspace; one kernel computes each query's
+ * n x n similarity matrix from the gathered fp32 master rows (vector fma chains in the fixed order, no MFMA); one workgroup
+ * per query runs the greedy selection with the matrix row of each pick.
+ * Asynchronous on `stream` like revo_search_topk_large (no host round trip).  Needs the fp32 master rows (keep_f32 = 0:
+ * status -2).  A null handle or pointer (queries may be null when n_queries = 0), a negative n_queries, candidates outside
+ * 1..1024, k outside 1..candidates, a diversity that is NaN or outside [0, 1], or a NaN threshold give status -2 before
+ * the device is touched, the outputs untouched.  An empty gallery, or a filter that allows no row: counts = 0, all padding.
+ * revo_search_stats after it: what the inner large-k search leaves (slot 3 = band rows re-scored in fp32, slot 6 = queries
+ * that took the exhaustive fallback, every other slot 0).  A pairs or a range result held by the handle stays valid; the
+ * two-phase state below is dropped as revo_search_topk_large drops it. */
+int32_t revo_search_mmr(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t candidates,
+                        float diversity, int32_t has_threshold, float threshold, int64_t index_offset, float* scores,
+                        float* mmr_values, int64_t* indices, int32_t* counts, void* stream);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:
@@ -304,7 +336,7 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
  * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE,
- * after revo_search_recommend see RECOMMEND. */
+ * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */

@@ -970,6 +970,32 @@ class SimpleReverso:
             text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
         return text, items
 
+    def search_similar_diverse(self, similarity_threshold=0.7, max_results=5, diversity=0.5, candidates_limit=None,
+                               query_filter=None):
+        """:meth:`search_similar` without the near-copies: of the stored regions scoring at least ``similarity_threshold``
+        against the first region embedding (the best ``candidates_limit`` of them, default ``max(max_results, 100)``),
+        ``max_results`` are picked by maximal marginal relevance -- each pick trades its score against its similarity to
+        the regions already picked (``diversity`` 0: the plain search, 1: as different as possible).  A database built from
+        video frames or region crops otherwise answers with copies of one frame.  Returns ``(text, items)``, items
+        ``{"filename", "image_source", "bbox", "id", "score"}`` in pick order.  No thumbnails."""
+        if not self.region_embeddings:
+            return "❌ No query embeddings available. Please detect/process an image first.", []
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        query = self.region_embeddings[0]
+        with self._lock:
+            hits = self.vector_db.search_mmr(query, limit=int(max_results), diversity=float(diversity),
+                                             candidates_limit=candidates_limit, score_threshold=float(similarity_threshold),
+                                             query_filter=query_filter)
+        if not hits:
+            return f"❌ No similar regions found above threshold {similarity_threshold}", []
+        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
+                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+        text = f"🎯 Found {len(items)} similar regions (diversity {float(diversity):g}):\n\n"
+        for n, it in enumerate(items):
+            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
+        return text, items
+
     def find_duplicates(self, similarity_threshold=0.95, query_filter=None):
         """Groups of near-duplicate regions in the loaded database: every stored region whose vector scores at least
         ``similarity_threshold`` against another one, joined transitively (re-posted, re-compressed or re-cropped copies of

@@ -486,6 +486,31 @@ int launch_recommend_rescore(const uint32_t* cand, long n, const float* Qf, long
 // the first min(n, k) sorted entries -> scores / row + idx_offset, padding behind them, counts[0]
 int launch_recommend_emit(const uint64_t* keys, const float* vals, long n, int k, int b, long idx_offset, float* scores,
                           long long* idx, int* counts, hipStream_t st);
+// ---- diverse search (revo_search_mmr; mmr.hip): the candidates' similarity matrices, greedy selection
+struct MmrGramArgs {
+    const float* Gf; long ldg;    // the gallery's fp32 master rows
+    long N; int D;
+    const long long* cand;        // [Q][C] candidate rows of each query, best first (index offset 0)
+    const int* counts;            // [Q] candidates of each query (device)
+    float* gram;                  // [Q][C][C] out: sim(i, j) for i, j < counts[q], i != j (the diagonal is written too)
+    int Q, C;
+    int tile;                     // candidate pairs per wave: 8 (8 x 8) or 4 (4 x 4)
+    int W;                        // set by the launcher: workgroups per query
+};
+int launch_mmr_gram(const MmrGramArgs& a, hipStream_t st);
+struct MmrSelectArgs {
+    const float* rel;             // [Q][C] the candidates' scores
+    const long long* cand;        // [Q][C]
+    const int* counts;            // [Q]
+    const float* gram;            // [Q][C][C]
+    int C, k;
+    float lam, diversity;         // lam = fl(1 - diversity)
+    long idx_offset;
+    float* scores; float* mmr;    // [Q][k] out, pick order: relevance, the value of the pick (mmr may be null)
+    long long* idx;               // [Q][k] out: row + idx_offset
+    int* out_counts;              // [Q] out: min(k, counts[q])
+};
+int launch_mmr_select(const MmrSelectArgs& a, int Q, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

@@ -1081,6 +1081,62 @@ extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples,
     API_END
 }
 
+// ---- diverse search (include/revo.h revo_search_mmr; mmr.hip)
+constexpr size_t MMR_GRAM_BYTES = 256ul << 20;   // the similarity matrices of one chunk of queries
+static int search_mmr(revo_gallery* g, const float* queries, int Q, int k, int C, float diversity, int has_thr, float thr,
+                      long index_offset, float* scores, float* mmr_values, long long* indices, int* counts, const uint32_t* allow,
+                      hipStream_t st) {
+    using namespace revo;
+    const size_t per_query = (size_t)C * C * sizeof(float);
+    const int QC = (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, MMR_GRAM_BYTES / per_query));
+    float *rel = nullptr, *gram = nullptr; long long* cand = nullptr; int* n_cand = nullptr;
+    // (the pairs', the range search's and the recommend search's layouts of this buffer are carved again by their next call)
+    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+        rel = l.take<float>((size_t)Q * C); cand = l.take<long long>((size_t)Q * C); n_cand = l.take<int>(Q);
+        gram = l.take<float>((size_t)QC * C * C);
+    }));
+    // the candidates: the large-k search's own lists (it clears and fills the handle's counters, and drops the two-phase state)
+    CHECK_RC(search_topk_large(g, queries, Q, C, has_thr, thr, 0, rel, cand, n_cand, allow, st));
+    int tile = 8;
+#ifdef REVO_EXPERIMENTS
+    if (const char* e = getenv("REVO_MMR_TILE")) tile = atoi(e) == 4 ? 4 : 8;                // tile shape study (scripts/)
+#endif
+    for (int c0 = 0; c0 < Q; c0 += QC) {
+        const int Qc = Q - c0 < QC ? Q - c0 : QC;
+        MmrGramArgs ga{};
+        ga.Gf = g->gf.p; ga.ldg = g->D; ga.N = g->size; ga.D = g->D; ga.cand = cand + (size_t)c0 * C; ga.counts = n_cand + c0;
+        ga.gram = gram; ga.Q = Qc; ga.C = C; ga.tile = tile;
+        { ProfScope ps("mmr_gram", st);
+          CHECK_RC(launch_mmr_gram(ga, st)); }
+        MmrSelectArgs sa{};
+        sa.rel = rel + (size_t)c0 * C; sa.cand = ga.cand; sa.counts = ga.counts; sa.gram = gram; sa.C = C; sa.k = k;
+        sa.lam = 1.0f - diversity; sa.diversity = diversity; sa.idx_offset = index_offset;
+        sa.scores = scores + (size_t)c0 * k; sa.mmr = mmr_values ? mmr_values + (size_t)c0 * k : nullptr;
+        sa.idx = indices + (size_t)c0 * k; sa.out_counts = counts + c0;
+        { ProfScope ps("mmr_select", st);
+          CHECK_RC(launch_mmr_select(sa, Qc, st)); }
+    }
+    return 0;
+}
+extern "C" int32_t revo_search_mmr(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t candidates,
+                                   float diversity, int32_t has_threshold, float threshold, int64_t index_offset, float* scores,
+                                   float* mmr_values, int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (queries || n_queries == 0), "search_mmr: null argument");
+    REVO_REQUIRE(n_queries >= 0, "search_mmr: negative query count");
+    REVO_REQUIRE(candidates >= 1 && candidates <= revo::LARGE_K_MAX, "search_mmr: candidates must be in [1, 1024]");
+    REVO_REQUIRE(k >= 1 && k <= candidates, "search_mmr: k must be in [1, candidates]");
+    REVO_REQUIRE(diversity >= 0.f && diversity <= 1.f, "search_mmr: diversity must be in [0, 1] (and not NaN)");
+    REVO_REQUIRE(!has_threshold || !std::isnan(threshold), "search_mmr: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "search_mmr: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    if (n_queries == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_mmr(g, queries, n_queries, k, candidates, diversity, has_threshold, threshold, index_offset, scores, mmr_values,
+                      (long long*)indices, counts, allow, (hipStream_t)stream);
+    API_END
+}
+
 #ifdef REVO_EXPERIMENTS   // librevo.so cannot be put into a non-exact mode
 extern "C" int32_t revo_search_set_mode(revo_gallery* g, int32_t mode) {
     REVO_REQUIRE(g && mode >= 0 && mode <= 3, "search_set_mode: mode must be 0..3");

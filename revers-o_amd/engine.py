@@ -363,6 +363,35 @@ class Gallery:
                 _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_recommend")
         return scores, idx, counts[0]
 
+    def search_mmr(self, queries, k=5, candidates=None, diversity=0.5, score_threshold=None, index_offset=0, allow=None):
+        """Diverse search (include/revo.h, MMR): for each query the best ``candidates`` rows of :meth:`search` (default
+        ``min(1024, max(k, 100))``; same filter and threshold semantics), of which ``k`` are picked greedily by maximal
+        marginal relevance: each pick maximises ``(1 - diversity) * score - diversity * (largest score against a row already
+        picked)``.  ``diversity = 0`` is the plain top-k, ``1`` ignores relevance after the first pick.  Returns ``(scores
+        [Q, k] fp32, mmr_values [Q, k] fp32, indices [Q, k] int64, counts [Q] int32)`` device tensors in pick order
+        (``scores``: the rows' plain search scores; ``mmr_values``: the value each row was picked with), padded with
+        -inf / -inf / -1.  Exact: the candidates are those of the exhaustive fp32 search, every similarity has the bits
+        :meth:`pairs` reports, the selection is the fp32 arithmetic the header states.  Asynchronous like :meth:`search`."""
+        _require_cuda(queries, "queries", self.device)
+        q = queries.detach().to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        k = int(k)
+        candidates = min(1024, max(k, 100)) if candidates is None else int(candidates)
+        Q = q.shape[0]
+        scores = torch.empty((Q, max(k, 1)), dtype=torch.float32, device=q.device)
+        values = torch.empty((Q, max(k, 1)), dtype=torch.float32, device=q.device)
+        idx = torch.empty((Q, max(k, 1)), dtype=torch.int64, device=q.device)
+        counts = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_search_mmr(
+                self._h, _lib.ptr(q), Q, k, candidates, float(diversity), int(score_threshold is not None),
+                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
+                _lib.ptr(scores), _lib.ptr(values), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_mmr")
+        return scores, values, idx, counts
+
     @contextlib.contextmanager
     def _groups(self, groups):
         """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.

@@ -286,6 +286,20 @@ class GalleryStore:
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
 
+    def search_mmr(self, query_vector, limit, diversity=0.5, candidates_limit=None, score_threshold=None, query_filter=None):
+        """One query, diverse results (Qdrant's ``Mmr(diversity, candidates_limit)`` re-ranking of a nearest-neighbour query):
+        of the best ``candidates_limit`` points (default ``min(1024, max(limit, 100))``; selected by ``query_filter``, cut at
+        ``score_threshold``) ``limit`` are picked greedily, each pick trading its score against its similarity to the points
+        already picked.  Returns the :class:`ScoredPoint` list in pick order, ``score`` = the point's plain search score.
+        Exact (include/revo.h, MMR); ``diversity=0`` is :meth:`search`."""
+        q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(1, -1)
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        s, _, i, c = self.gallery.search_mmr(q.to(self.gallery.device), k=int(limit), candidates=candidates_limit,
+                                             diversity=float(diversity), score_threshold=score_threshold, allow=allow)
+        n = int(c[0])
+        s, i = s[0, :n].tolist(), i[0, :n].tolist()
+        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
+
     def search_range_batch(self, query_vectors, score_threshold, query_filter=None):
         """Every point (selected by ``query_filter``, if given) whose vector scores at least ``score_threshold`` against each
         query: one :class:`ScoredPoint` list per query, best first, with no cap on its length -- e.g. "which of these new
