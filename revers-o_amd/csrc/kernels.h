@@ -403,11 +403,20 @@ int launch_topk_large_finish(const LargeWs& ws, int max_entries, const float* Qf
 int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, long N,
                                int D, int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
                                int* out_counts, const uint32_t* allow, hipStream_t st);
-// ---- near-duplicate pairs of one gallery (revo_gallery_pairs; pairs.hip): triangular self-join on the
-// 256 x 256 main loop, fp32 re-score of the candidates, radix sort of the kept pairs
+// ------------------------------------------------- candidate pipeline ----
+// Pairs, range and recommend searches: join on the 256 x 256 main loop -> counted candidate buffer,
+// fp32 re-score -> 64-bit sort keys, sort, emit.  Shared device code: candidates.h; host side: search.hip's CandidateWs.
+// ---- the sort and the prefix sum (radix_sort.hip)
+constexpr int SORT_MAX_BLOCKS = 2048;        // at most this many blocks per radix pass (the offsets scan is one workgroup)
+// ascending sort of n (key, value) entries over the low key_bits bits; cnt: 256 * SORT_MAX_BLOCKS words; the result is in
+// (*out_keys, *out_vals), one of the two buffer pairs
+int launch_sort_keys_u64(uint64_t* keys, float* vals, uint64_t* keys_alt, float* vals_alt, long n, int key_bits, uint32_t* cnt,
+                         uint64_t** out_keys, float** out_vals, hipStream_t st);
+// inclusive prefix sums of c[0 .. n) in place (one workgroup)
+int launch_inclusive_sums_u64(unsigned long long* c, long n, hipStream_t st);
+// ---- near-duplicate pairs of one gallery (revo_gallery_pairs; pairs.hip): the join walks the upper triangle of row-tile pairs
 constexpr long PAIRS_WS_KEYS = 1l << 20;     // candidate keys the workspace holds before its first regrow
 constexpr long PAIRS_MAX_CAND = 1l << 28;    // candidate pairs a call may have (2 GiB of keys); more: status -2
-constexpr int PAIRS_SORT_BLOCKS = 2048;      // at most this many blocks per radix pass (the offsets scan is one workgroup)
 struct PairsJoinArgs {
     const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
     long N; int D;
@@ -422,14 +431,9 @@ int launch_pairs_join(const PairsJoinArgs& a, hipStream_t st);
 // fp32 score of candidates [0, n); those >= thr appended to out_keys ((i << b) | j) / out_scores, count in *kept
 int launch_pairs_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, float thr, int b,
                          unsigned long long* kept, uint64_t* out_keys, float* out_scores, hipStream_t st);
-long pairs_sort_tile(long n);                // keys per block of a radix pass (cnt: 256 words per block)
-// ascending sort of n (key, value) entries over the low key_bits bits; the result is in (*out_keys, *out_vals), one of the
-// two buffer pairs
-int launch_pairs_sort(uint64_t* keys, float* vals, uint64_t* keys_alt, float* vals_alt, long n, int key_bits, uint32_t* cnt,
-                      uint64_t** out_keys, float** out_vals, hipStream_t st);
 int launch_pairs_emit(const uint64_t* keys, const float* vals, long n, int b, long long* pairs, float* scores, hipStream_t st);
-// ---- range search (revo_search_range; range.hip): the 256 x 256 scan's main loop and work plan with
-// an epilogue that appends every (query, row) whose bf16 score reaches the query's bound; fp32 re-score; the pairs' sort
+// ---- range search (revo_search_range; range.hip): the join runs the 256 x 256 scan's work plan, with a
+// bound per query
 constexpr int RANGE_CHUNK = 1024;            // queries per candidate pass (fewer when the sort key would pass 64 bits)
 constexpr long RANGE_WS_PER_QUERY = 1024;    // candidate keys per query of a chunk the workspace holds before a regrow
 constexpr long RANGE_MAX_CAND = 1l << 28;    // candidates a call may have, over all its chunks (2 GiB of keys); more: status -2
@@ -457,10 +461,8 @@ int launch_range_rescore(const uint64_t* cand, long n, const float* Qf, long ldq
 // sorted keys -> row + idx_offset / scores
 int launch_range_emit(const uint64_t* keys, const float* vals, long n, int b, long idx_offset, long long* idx, float* scores,
                       hipStream_t st);
-// inclusive prefix sums of c[0 .. n) in place (one workgroup)
-int launch_range_offsets(unsigned long long* c, long n, hipStream_t st);
-// ---- search by examples (revo_search_recommend; recommend.hip): sample pass -> level tau, candidate
-// pass (the range join's skeleton with an epilogue that reduces over the example rows), fp32 re-score, the pairs' sort
+// ---- search by examples (revo_search_recommend; recommend.hip): sample pass -> level tau; the join is a
+// pass over gallery slices whose epilogue reduces over the example rows; candidates are rows
 constexpr int RECOMMEND_MAX_EXAMPLES = 128;  // the example rows of a tile column live in one wave up to here
 struct RecommendPassArgs {
     const bf16_t* Qb; long ldq;   // the bf16 example rows, positives first

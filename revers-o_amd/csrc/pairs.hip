@@ -4,22 +4,18 @@
 //
 //   join     the 256 x 256 main loop over the upper triangle of row-tile pairs (ti <= tj), both operands the gallery's
 //            bf16 rows; every score v >= lb = fl(thr - eps) lowered by its rounding is a candidate; keys (i << 32) | j are
-//            appended with one atomic per wave instruction.  The 64-bit counter counts past the workspace's end
+//            appended (candidates.h wave_append)
 //   rescore  the fp32 score of every candidate (the exact_dot4 chain); those >= thr are kept, as (i << b) | j, b = the bits
 //            of the largest row index
-//   sort     LSD radix sort of the kept keys (8-bit digits over their 2 b bits), stable scatter, scores carried along
+//   sort     radix_sort.hip over the 2 b bits of the kept keys
 //   emit     keys -> [n][2] int64 row pairs
-// The host reads the candidate count between join and re-score (and grows the workspace once if it overflowed) and the
-// kept count before the sort: the call is synchronous.
+// The host side of the pipeline (counts read back, the workspace's one regrow) is search.hip's CandidateWs.
+#include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
 #include "topk_util.h"
 
 namespace revo {
-
-// x lowered by more than the rounding of the one or two fp32 operations that produced it from values of magnitude <= |ref| + 1
-// (lk_down of topk_large.hip)
-__device__ __forceinline__ float pairs_down(float x, float ref) { return x - 4e-7f * (1.f + fabsf(ref)); }
 
 // The bf16-score bound of the join.  A row's bf16 copy gb_i has ||gb_i|| <= ||g_i|| + ||gb_i - g_i|| <= G + Eg, so a row used
 // as the query of cert_eps has e_q <= Eg and n_qb <= G + Eg; cert_eps increases in both, so this eps bounds the error of
@@ -27,7 +23,7 @@ __device__ __forceinline__ float pairs_down(float x, float ref) { return x - 4e-
 __device__ __forceinline__ float pairs_lb(const uint32_t* gstat, float thr, int D) {
     const float G = __uint_as_float(gstat[0]), Eg = __uint_as_float(gstat[1]);
     const float eps = cert_eps(Eg, G + Eg, G, Eg, D);
-    return pairs_down(thr - eps, thr);
+    return score_down(thr - eps, thr);
 }
 
 // first tile pair of row tile ti in the row-major linearisation of the upper triangle (ti <= tj < T)
@@ -77,16 +73,11 @@ __global__ __launch_bounds__(G256_THREADS, 2) void pairs_join_kernel(PairsJoinAr
         const int rbase = (wave >> 2) * 128 + lr;
         const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
         const long n0 = (long)cj * 256;
-        const long left = p.N - n0 - cw;                    // rows of the gallery from the wave's first column on
-        uint64_t fm = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
-        if (p.allow) {
-            const long w0 = (n0 + cw) >> 5;                 // (the bitmap is zero-padded to whole 256-row tiles)
-            fm &= (uint64_t)p.allow[w0] | ((uint64_t)p.allow[w0 + 1] << 32);
-        }
+        const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
         if (fm == 0ull) continue;                           // wave-uniform: no allowed column
         const uint64_t bits = fm >> (lq * 4);
         const bool diag = ci == cj;
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = lanes_below(lane);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int row = rbase + m * 16;
@@ -106,10 +97,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void pairs_join_kernel(PairsJoinAr
                     const bool take = rok && acc[m][n][j] >= lb && ((bits >> (n * 16 + j)) & 1ull) && (!diag || col > row);
                     const unsigned long long mk = __ballot(take);
                     if (mk == 0ull) continue;               // wave-uniform
-                    unsigned long long base = 0ull;
-                    if (lane == 0) base = atomicAdd(p.cnt, (unsigned long long)__popcll(mk));
-                    base = readlane_u64(base, 0);
-                    const unsigned long long pos = base + (unsigned long long)__popcll(mk & below);
+                    const unsigned long long pos = wave_append(mk, p.cnt, lane, below);
                     if (take && pos < (unsigned long long)p.cap) p.keys[pos] = ((uint64_t)gi << 32) | (uint64_t)(n0 + col);
                 }
         }
@@ -123,109 +111,26 @@ __global__ __launch_bounds__(256) void pairs_rescore_kernel(const uint64_t* __re
                                                             uint64_t* __restrict__ out_keys, float* __restrict__ out_scores) {
     const int lane = threadIdx.x & 63;
     const long waves = (long)gridDim.x * 4;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long below = lanes_below(lane);
     for (long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6); g * 4 < n; g += waves) {
-        const long c0 = g * 4;
-        const int m = n - c0 < 4 ? (int)(n - c0) : 4;
-        const float* qr[4];
-        const float* gr[4];
-        uint64_t key[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            key[u] = cand[c0 + (u < m ? u : m - 1)];
-            qr[u] = Gf + (long)(key[u] >> 32) * ldg;
-            gr[u] = Gf + (long)(uint32_t)key[u] * ldg;
-        }
-        float t[4];
-        pairs_dot4(qr, gr, D, lane, t);
-        const float v = lane == 0 ? t[0] : (lane == 1 ? t[1] : (lane == 2 ? t[2] : t[3]));
-        const uint64_t k = lane == 0 ? key[0] : (lane == 1 ? key[1] : (lane == 2 ? key[2] : key[3]));
+        float v;
+        uint64_t k;
+        const int m = rescore_group4(cand, n, g * 4, D, lane, [&](uint64_t key, const float*& q, const float*& r) {
+            q = Gf + (long)(key >> 32) * ldg;
+            r = Gf + (long)(uint32_t)key * ldg;
+        }, v, k);
         const bool take = lane < m && v >= thr;
         const unsigned long long mk = __ballot(take);
         if (mk == 0ull) continue;
-        unsigned long long base = 0ull;
-        if (lane == 0) base = atomicAdd(kept, (unsigned long long)__popcll(mk));
-        base = readlane_u64(base, 0);
+        const unsigned long long pos = wave_append(mk, kept, lane, below);
         if (take) {
-            const unsigned long long pos = base + (unsigned long long)__popcll(mk & below);
             out_keys[pos] = ((k >> 32) << b) | (k & 0xffffffffull);
             out_scores[pos] = v;
         }
     }
 }
 
-// -------------------------------------------------------------------------- sort ----
-// One LSD pass over digit (key >> shift) & 255: block j of `tile` keys counts its digits (hist), one workgroup turns the
-// counts [digit][block] into exclusive offsets (scan), block j scatters its keys in index order (stable).
-__global__ __launch_bounds__(256) void pairs_radix_hist_kernel(const uint64_t* __restrict__ keys, long n, long tile, int shift,
-                                                               uint32_t* __restrict__ cnt, int nblk) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-    const long e0 = (long)blockIdx.x * tile, e1 = e0 + tile < n ? e0 + tile : n;
-    for (long e = e0 + threadIdx.x; e < e1; e += 256) atomicAdd(&h[(keys[e] >> shift) & 255u], 1u);
-    __syncthreads();
-    cnt[(long)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
-}
-// exclusive prefix sums of cnt[0 .. M) in place, one workgroup: thread t takes the contiguous chunk t * per ..
-__global__ __launch_bounds__(1024) void pairs_radix_scan_kernel(uint32_t* __restrict__ cnt, long M) {
-    __shared__ uint32_t s[1024];
-    const int t = threadIdx.x;
-    const long per = (M + 1023) / 1024, a = (long)t * per, e = a + per < M ? a + per : M;
-    uint32_t sum = 0u;
-    for (long i = a; i < e; ++i) sum += cnt[i];
-    s[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {              // inclusive scan of the chunk sums
-        const uint32_t v = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - sum;
-    for (long i = a; i < e; ++i) { const uint32_t c = cnt[i]; cnt[i] = run; run += c; }
-}
-// Rounds of 256 keys in index order: a key's place = its digit's running offset + the keys of its digit in earlier waves of
-// the round + those in earlier lanes of its wave (8 ballots find the lanes with the same digit)
-__global__ __launch_bounds__(256) void pairs_radix_scatter_kernel(const uint64_t* __restrict__ kin, const float* __restrict__ vin,
-                                                                  uint64_t* __restrict__ kout, float* __restrict__ vout, long n,
-                                                                  long tile, int shift, const uint32_t* __restrict__ cnt, int nblk) {
-    __shared__ uint32_t run[256], wc[4][256];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    run[t] = cnt[(long)t * nblk + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wc[w][t] = 0u;
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const long e0 = (long)blockIdx.x * tile, e1 = e0 + tile < n ? e0 + tile : n;
-    for (long r0 = e0; r0 < e1; r0 += 256) {
-        const long e = r0 + t;
-        const bool valid = e < e1;
-        const uint64_t k = valid ? kin[e] : 0ull;
-        const float v = valid ? vin[e] : 0.f;
-        const uint32_t d = (uint32_t)(k >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const unsigned long long bb = __ballot((d >> bit) & 1u);
-            peers &= ((d >> bit) & 1u) ? bb : ~bb;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & below);
-        if (valid && rank == 0u) wc[wave][d] = (uint32_t)__popcll(peers);
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = run[d] + rank;
-            for (int w = 0; w < wave; ++w) pos += wc[w][d];
-            kout[pos] = k;
-            vout[pos] = v;
-        }
-        __syncthreads();
-        run[t] += wc[0][t] + wc[1][t] + wc[2][t] + wc[3][t];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) wc[w][t] = 0u;
-        __syncthreads();
-    }
-}
+// -------------------------------------------------------------------------- emit ----
 __global__ __launch_bounds__(256) void pairs_emit_kernel(const uint64_t* __restrict__ keys, const float* __restrict__ vals, long n,
                                                          int b, long long* __restrict__ pairs, float* __restrict__ scores) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -264,29 +169,6 @@ int launch_pairs_rescore(const uint64_t* cand, long n, const float* Gf, long ldg
     hipLaunchKernelGGL(pairs_rescore_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, cand, n, Gf, ldg,
                        D, thr, b, kept, out_keys, out_scores);
     REVO_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-long pairs_sort_tile(long n) {
-    long tile = (n + PAIRS_SORT_BLOCKS - 1) / PAIRS_SORT_BLOCKS;
-    tile = (tile + 255) / 256 * 256;
-    return tile < 4096 ? 4096 : tile;
-}
-int launch_pairs_sort(uint64_t* keys, float* vals, uint64_t* keys_alt, float* vals_alt, long n, int key_bits, uint32_t* cnt,
-                      uint64_t** out_keys, float** out_vals, hipStream_t st) {
-    *out_keys = keys; *out_vals = vals;
-    if (n <= 1) return 0;
-    const long tile = pairs_sort_tile(n);
-    const int nblk = (int)((n + tile - 1) / tile);
-    for (int shift = 0; shift < key_bits; shift += 8) {
-        hipLaunchKernelGGL(pairs_radix_hist_kernel, dim3((unsigned)nblk), dim3(256), 0, st, keys, n, tile, shift, cnt, nblk);
-        hipLaunchKernelGGL(pairs_radix_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, 256l * nblk);
-        hipLaunchKernelGGL(pairs_radix_scatter_kernel, dim3((unsigned)nblk), dim3(256), 0, st, keys, vals, keys_alt, vals_alt, n,
-                           tile, shift, cnt, nblk);
-        uint64_t* tk = keys; keys = keys_alt; keys_alt = tk;
-        float* tv = vals; vals = vals_alt; vals_alt = tv;
-    }
-    REVO_HIP_CHECK(hipGetLastError());
-    *out_keys = keys; *out_vals = vals;
     return 0;
 }
 int launch_pairs_emit(const uint64_t* keys, const float* vals, long n, int b, long long* pairs, float* scores, hipStream_t st) {

@@ -5,14 +5,14 @@
 //   join     the scan's 256 x 256 main loop and work plan (scan_plan.h: XCD-aware phases of query tiles x gallery slices,
 //            the 64 / 128 / 192-row forms for a chunk of one query tile, non-temporal gallery DMA when there is one query
 //            tile); every score v >= lb(q) = fl(thr - eps(q)) lowered by its rounding is a candidate; keys (q << 32) | row
-//            are appended with one atomic per wave instruction.  The 64-bit counter counts past the workspace's end
+//            are appended (candidates.h wave_append)
 //   rescore  the fp32 score of every candidate (the chain of every re-score, pairs_dot4); those >= thr are kept as
 //            (q << (32 + b)) | (~order-preserving score << b) | row, b = the bits of the largest row index, and counted per
 //            query (agent-scope atomics)
-//   sort     the pairs' LSD radix sort (pairs.hip) over those keys: (query, score desc, row asc)
-//   emit     keys -> row + index_offset, scores;  offsets: prefix sums of the per-query counts
-// The host reads the candidate count between join and re-score (and grows the workspace once if it overflowed) and the
-// kept count before the sort: the call is synchronous.
+//   sort     radix_sort.hip over those keys: (query, score desc, row asc)
+//   emit     keys -> row + index_offset, scores;  offsets: inclusive prefix sums of the per-query counts (radix_sort.hip)
+// The host side of the pipeline (counts read back, the workspace's one regrow) is search.hip's CandidateWs.
+#include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
 #include "scan_plan.h"
@@ -22,10 +22,6 @@ namespace revo {
 
 static_assert(RANGE_PHASES == S256_PHASES, "the range join runs the scan's phases");
 constexpr int RANGE_LDS = G256_LDS + 256 * 4;     // main loop | the tile's 256 query bounds
-
-// x lowered by more than the rounding of the one or two fp32 operations that produced it from values of magnitude <= |ref| + 1
-// (lk_down of topk_large.hip, pairs_down of pairs.hip)
-__device__ __forceinline__ float range_down(float x, float ref) { return x - 4e-7f * (1.f + fabsf(ref)); }
 
 // -------------------------------------------------------------------------- join ----
 // Block b of phase i -> query tile ph_q0[i] + j % ph_qn[i], slice j / ph_qn[i] of ph_ns[i] (j = b - ph_first[i]), as in the
@@ -61,7 +57,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
             const long q = q0 + tid;
             const float eps = cert_eps(p.qstat[q * 2], p.qstat[q * 2 + 1], __uint_as_float(p.gstat[0]),
                                        __uint_as_float(p.gstat[1]), p.D);
-            lb = range_down(p.thr - eps, p.thr);
+            lb = score_down(p.thr - eps, p.thr);
         }
         lbs[tid] = lb;
     }
@@ -88,15 +84,10 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
         const int lr = lane & 15, lq = lane >> 4;
         const int wrow = (wave >> 2) * 128;                 // the wave's first query row of the tile
         const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
-        const long left = p.N - n0 - cw;                    // rows of the gallery from the wave's first column on
-        uint64_t fm = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
-        if (p.allow) {
-            const long w0 = (n0 + cw) >> 5;                 // (the bitmap is zero-padded to whole 256-row tiles)
-            fm &= (uint64_t)p.allow[w0] | ((uint64_t)p.allow[w0 + 1] << 32);
-        }
+        const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
         if (fm == 0ull) continue;                           // wave-uniform: no allowed column
         const uint64_t bits = fm >> (lq * 4);
-        const unsigned long long below = (1ull << lane) - 1ull;
+        const unsigned long long below = lanes_below(lane);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             if (ROWS != 0 && wrow + m * 16 >= ROWS) continue;   // rows the row form never computed (no query there)
@@ -117,10 +108,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
                     const bool take = acc[m][n][j] >= lb && ((bits >> (n * 16 + j)) & 1ull);
                     const unsigned long long mk = __ballot(take);
                     if (mk == 0ull) continue;               // wave-uniform
-                    unsigned long long base = 0ull;
-                    if (lane == 0) base = atomicAdd(p.cnt, (unsigned long long)__popcll(mk));
-                    base = readlane_u64(base, 0);
-                    const unsigned long long pos = base + (unsigned long long)__popcll(mk & below);
+                    const unsigned long long pos = wave_append(mk, p.cnt, lane, below);
                     if (take && pos < (unsigned long long)p.cap) p.keys[pos] = qk | (uint64_t)(n0 + col);
                 }
         }
@@ -137,30 +125,19 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(const uint64_t* __re
                                                             uint64_t* __restrict__ out_keys, float* __restrict__ out_scores) {
     const int lane = threadIdx.x & 63;
     const long waves = (long)gridDim.x * 4;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned long long below = lanes_below(lane);
     const int qshift = 32 + b;                              // <= 64; 64 only for a one-query chunk (query 0)
     for (long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6); g * 4 < n; g += waves) {
-        const long c0 = g * 4;
-        const int m = n - c0 < 4 ? (int)(n - c0) : 4;
-        const float* qr[4];
-        const float* gr[4];
-        uint64_t key[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            key[u] = cand[c0 + (u < m ? u : m - 1)];
-            qr[u] = Qf + (long)(key[u] >> 32) * ldq;
-            gr[u] = Gf + (long)(uint32_t)key[u] * ldg;
-        }
-        float t[4];
-        pairs_dot4(qr, gr, D, lane, t);
-        const float v = lane == 0 ? t[0] : (lane == 1 ? t[1] : (lane == 2 ? t[2] : t[3]));
-        const uint64_t k = lane == 0 ? key[0] : (lane == 1 ? key[1] : (lane == 2 ? key[2] : key[3]));
+        float v;
+        uint64_t k;
+        const int m = rescore_group4(cand, n, g * 4, D, lane, [&](uint64_t key, const float*& q, const float*& r) {
+            q = Qf + (long)(key >> 32) * ldq;
+            r = Gf + (long)(uint32_t)key * ldg;
+        }, v, k);
         const bool take = lane < m && v >= thr;
         const unsigned long long mk = __ballot(take);
         if (mk == 0ull) continue;
-        unsigned long long base = 0ull;
-        if (lane == 0) base = atomicAdd(kept, (unsigned long long)__popcll(mk));
-        base = readlane_u64(base, 0);
+        const unsigned long long pos = wave_append(mk, kept, lane, below);
         const uint32_t q = (uint32_t)(k >> 32);
         // the kept entries of this query among lanes 0..3; the first of them adds the count
         unsigned long long same = 0ull;
@@ -171,7 +148,6 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(const uint64_t* __re
             if (((mk >> u) & 1ull) && qu == q) { ++same; if (u < lane) first = false; }
         }
         if (take) {
-            const unsigned long long pos = base + (unsigned long long)__popcll(mk & below);
             const uint64_t qkey = qshift < 64 ? (uint64_t)q << qshift : 0ull;
             out_keys[pos] = qkey | ((uint64_t)(~f32_orderable(v)) << b) | (k & 0xffffffffull);
             out_scores[pos] = v;
@@ -180,7 +156,7 @@ __global__ __launch_bounds__(256) void range_rescore_kernel(const uint64_t* __re
     }
 }
 
-// -------------------------------------------------------------------- emit, offsets ----
+// -------------------------------------------------------------------------- emit ----
 __global__ __launch_bounds__(256) void range_emit_kernel(const uint64_t* __restrict__ keys, const float* __restrict__ vals, long n,
                                                          int b, long idx_offset, long long* __restrict__ idx,
                                                          float* __restrict__ scores) {
@@ -188,24 +164,6 @@ __global__ __launch_bounds__(256) void range_emit_kernel(const uint64_t* __restr
     if (e >= n) return;
     idx[e] = (long long)(keys[e] & ((1ull << b) - 1ull)) + idx_offset;
     scores[e] = vals[e];
-}
-// inclusive prefix sums of c[0 .. M) in place, one workgroup: thread t takes the contiguous chunk t * per ..
-__global__ __launch_bounds__(1024) void range_offsets_kernel(unsigned long long* __restrict__ c, long M) {
-    __shared__ unsigned long long s[1024];
-    const int t = threadIdx.x;
-    const long per = (M + 1023) / 1024, a = (long)t * per, e = a + per < M ? a + per : M;
-    unsigned long long sum = 0ull;
-    for (long i = a; i < e; ++i) sum += c[i];
-    s[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {              // inclusive scan of the chunk sums
-        const unsigned long long v = t >= off ? s[t - off] : 0ull;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    unsigned long long run = s[t] - sum;
-    for (long i = a; i < e; ++i) { run += c[i]; c[i] = run; }
 }
 
 // ------------------------------------------------------------------------ launchers ----
@@ -260,12 +218,6 @@ int launch_range_emit(const uint64_t* keys, const float* vals, long n, int b, lo
     if (n <= 0) return 0;
     hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, vals, n, b, idx_offset, idx,
                        scores);
-    REVO_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-int launch_range_offsets(unsigned long long* c, long n, hipStream_t st) {
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(range_offsets_kernel, dim3(1), dim3(1024), 0, st, c, n);
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }

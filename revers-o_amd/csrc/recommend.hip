@@ -7,16 +7,17 @@
 //   sample   the pass below over the first n_s rows, writing lb(r) <= score(r) of every allowed row (-inf otherwise)
 //   level    tau = the k-th largest lb of the sample (-inf with fewer than k), raised to the threshold if there is one:
 //            k rows score at least tau, so every row of the answer has ub(r) >= score(r) >= tau
-//   pass     the range join's skeleton (64- / 128-row form of the 256 x 256 main loop, deep DMA schedule, non-temporal
-//            gallery requests, the next tile's prologue issued before the epilogue) with A = the example rows; its epilogue
+//   pass     the 64- / 128-row form of the 256 x 256 main loop (deep DMA schedule, non-temporal gallery requests, the next
+//            tile's prologue issued before the epilogue) with A = the example rows; its epilogue
 //            reduces each score column over the example rows (all of them live in ONE wave: registers, then DPP row
-//            rotations), computes ub(r) and appends the rows with ub(r) >= tau, one atomic per wave and tile
+//            rotations), computes ub(r) and appends the rows with ub(r) >= tau (candidates.h wave_append, once per tile)
 //   rescore  one wave per candidate row: the P + Nn fp32 scores (the chain of every re-score, pairs_dot4), score(r), the
 //            threshold cut; kept as (~order-preserving score << b) | row, b = the bits of the largest row index
-//   sort     the pairs' LSD radix sort (pairs.hip) over those keys: (score desc, row asc)
+//   sort     radix_sort.hip over those keys: (score desc, row asc)
 //   emit     the first k -> row + index_offset, scores; the rest padded
 // Candidates are rows: at most N of them, the workspace is sized once.  The host reads the candidate count before the
 // re-score and the kept count before the sort: the call is synchronous.
+#include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
 #include "topk_util.h"
@@ -25,23 +26,21 @@ namespace revo {
 
 constexpr int REC_LDS = G256_LDS + 256;           // main loop | e, tau
 
-// x moved outward by more than the rounding of the one or two fp32 operations that produced it (range_down and its mirror)
-__device__ __forceinline__ float rec_down(float x) { return x - 4e-7f * (1.f + fabsf(x)); }
-__device__ __forceinline__ float rec_up(float x) { return x + 4e-7f * (1.f + fabsf(x)); }
-
 // Bounds of score(r) from the bf16 maxima a (positives) and b (negatives; unused when there is no negative).
 // Branch A (sp > sn) is possible iff a + e > b - e and gives [a - e, a + e]; branch B iff a - e <= b + e and gives
-// [-M^2, -m^2], m / M the smallest / largest |x| on [b - e, b + e].  The interval ends are moved outward first, which only
-// makes a branch possible more often and its interval wider; one of the two is always possible.
+// [-M^2, -m^2], m / M the smallest / largest |x| on [b - e, b + e].  The interval ends are moved outward first (score_down /
+// score_up, each end its own reference), which only makes a branch possible more often and its interval wider; one of the
+// two is always possible.
 __device__ __forceinline__ void rec_bounds(float a, float b, float e, bool has_neg, float& lb, float& ub) {
-    const float a_lo = rec_down(a - e), a_hi = rec_up(a + e);
+    const float a_lo = score_down(a - e, a - e), a_hi = score_up(a + e, a + e);
     if (!has_neg) { lb = a_lo; ub = a_hi; return; }
-    const float b_lo = rec_down(b - e), b_hi = rec_up(b + e);
+    const float b_lo = score_down(b - e, b - e), b_hi = score_up(b + e, b + e);
     const bool br_a = a_hi >= b_lo, br_b = a_lo <= b_hi;
     const float x0 = fabsf(b_lo), x1 = fabsf(b_hi);
     const float M = fmaxf(x0, x1);
     const float m = (b_lo <= 0.f && b_hi >= 0.f) ? 0.f : fminf(x0, x1);
-    const float nb_lo = rec_down(-(M * M)), nb_hi = rec_up(-(m * m));
+    const float nM2 = -(M * M), nm2 = -(m * m);
+    const float nb_lo = score_down(nM2, nM2), nb_hi = score_up(nm2, nm2);
     lb = br_a ? (br_b ? fminf(a_lo, nb_lo) : a_lo) : nb_lo;
     ub = br_a ? (br_b ? fmaxf(a_hi, nb_hi) : a_hi) : nb_hi;
 }
@@ -106,17 +105,12 @@ __global__ __launch_bounds__(G256_THREADS, 2) void recommend_pass_kernel(Recomme
         asm volatile("" : "+v"(lane) :: "memory");
         const int lr = lane & 15, lq = lane >> 4;
         const int cw = wave * 64;                           // the wave's 64 columns: bits of one 64-bit word of the bitmap
-        const long left = p.N - n0 - cw;                    // rows of the gallery from the wave's first column on
-        uint64_t fm = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
-        if (p.allow) {
-            const long w0 = (n0 + cw) >> 5;                 // (the bitmap is zero-padded to whole 256-row tiles)
-            fm &= (uint64_t)p.allow[w0] | ((uint64_t)p.allow[w0 + 1] << 32);
-        }
+        const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
         // this lane's column after the reduction: fragment n = lr >> 2, element j = lr & 3 of its 16-lane row
         const int cbit = (lr >> 2) * 16 + lq * 4 + (lr & 3);
         const bool allowed = (fm >> cbit) & 1ull;
         if (SAMPLE) {
-            if (left <= 0) continue;                        // wave-uniform: past the gallery's end
+            if (p.N - n0 - cw <= 0) continue;               // wave-uniform: past the gallery's end
         } else {
             if (fm == 0ull) continue;                       // wave-uniform: no allowed column
             n_allowed += (unsigned long long)__popcll(fm);
@@ -182,10 +176,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void recommend_pass_kernel(Recomme
             const bool take = allowed && !(ub < par[1]);    // (a NaN bound keeps the row)
             const unsigned long long mk = __ballot(take);
             if (mk == 0ull) continue;                       // wave-uniform
-            unsigned long long base = 0ull;
-            if (lane == 0) base = atomicAdd(p.cnt, (unsigned long long)__popcll(mk));
-            base = readlane_u64(base, 0);
-            const unsigned long long pos = base + (unsigned long long)__popcll(mk & ((1ull << lane) - 1ull));
+            const unsigned long long pos = wave_append(mk, p.cnt, lane, lanes_below(lane));
             if (take && pos < (unsigned long long)p.cap) p.rows[pos] = (uint32_t)grow;
         }
     }

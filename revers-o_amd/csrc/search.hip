@@ -65,6 +65,73 @@ template <class F> int carve_buffer(DeviceBuffer<>& buf, hipStream_t st, F&& car
     Layout l{buf.p}; carve(l);
     return 0;
 }
+
+// The host side of the candidate pipeline (pairs, range and recommend searches): its workspace in one
+// buffer of the handle and the steps between its kernels (synchronous: the host reads the candidate and the kept count).
+struct CandidateWs {
+    DeviceBuffer<>& buf;
+    long& cap;                           // candidate keys the workspace holds (a handle remembers it: once grown, it stays grown)
+    unsigned long long* cnt = nullptr;   // [4] device counters: [0] candidates (counts past cap), [1] kept, [2], [3] the search's own
+    uint64_t *cand = nullptr, *kept_k = nullptr;   // [cap] candidate keys (then the sort's second key buffer), kept sort keys
+    float *kept_v = nullptr, *alt_v = nullptr;     // [cap] kept scores, the sort's second score buffer
+    uint32_t* hist = nullptr;            // the sort's digit counts
+    unsigned long long h[4] = {0, 0, 0, 0}, n_cand = 0, n_kept = 0;   // cnt as read behind the join; candidates, kept entries
+    int passes = 0;                      // joins run: 1, or 2 after a regrow
+    uint64_t* sk = nullptr; float* sv = nullptr;   // the sorted kept entries
+    // the layout for n candidate keys; extra(Layout&) takes the arrays a search adds behind it
+    template <class Extra> int carve(long n, hipStream_t st, Extra&& extra) {
+        CHECK_RC(carve_buffer(buf, st, [&](Layout& l) {
+            cnt = l.take<unsigned long long>(4);
+            cand = l.take<uint64_t>(n); kept_k = l.take<uint64_t>(n);
+            kept_v = l.take<float>(n); alt_v = l.take<float>(n);
+            hist = l.take<uint32_t>(256l * revo::SORT_MAX_BLOCKS);
+            extra(l);
+        }));
+        cap = n;
+        return 0;
+    }
+    int carve(long n, hipStream_t st) { return carve(n, st, [](Layout&) {}); }
+    // Clears the counters, runs join() and reads them; limit(candidates) is the caller's check.  A count past the workspace's
+    // end: carved again for the counted size, joined once more (`changed`: the error text if that does not fit either).
+    template <class Join, class Limit> int join_until_it_fits(hipStream_t st, Join&& join, Limit&& limit, const char* changed) {
+        for (passes = 0;;) {
+            REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(h), st));
+            CHECK_RC(join());
+            ++passes;
+            REVO_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+            REVO_HIP_CHECK(hipStreamSynchronize(st));
+            n_cand = h[0];
+            CHECK_RC(limit(n_cand));
+            if (n_cand <= (unsigned long long)cap) return 0;
+            REVO_REQUIRE(passes == 1, changed);
+            CHECK_RC(carve((long)n_cand, st));
+        }
+    }
+    // behind the re-score (it counted into cnt[1]): the kept count, the kept entries sorted over key_bits bits -> n_kept, sk, sv
+    int sort_kept(const char* prof, int key_bits, hipStream_t st) {
+        n_kept = 0;
+        if (n_cand > 0) {
+            REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
+            REVO_HIP_CHECK(hipStreamSynchronize(st));
+        }
+        ProfScope ps(prof, st);
+        return revo::launch_sort_keys_u64(kept_k, kept_v, cand, alt_v, (long)n_kept, key_bits, hist, &sk, &sv, st);
+    }
+};
+// revo_search_stats slot 3 = candidates re-scored, slot 7 = candidate passes; the call ends synchronised
+int publish_candidate_stats(int* ctr, unsigned long long candidates, int passes, hipStream_t st) {
+    const int stats[2] = {(int)candidates, passes};
+    REVO_HIP_CHECK(hipMemcpyAsync(ctr + revo::CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(ctr + revo::CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+// the bits of the largest row index of N rows (at least 1): the row field of a sort key
+int row_index_bits(long N) {
+    int b = 1;
+    while (N > 1 && (1l << b) < N) ++b;
+    return b;
+}
 }  // namespace
 
 struct revo_gallery {
@@ -797,56 +864,30 @@ extern "C" int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t*
     CHECK_RC(search_grow_queries(g, 1, st));
     REVO_REQUIRE(g->xw.ctr, "gallery_pairs: no counter workspace");
     REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
-    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept
-    uint64_t *cand = nullptr, *kept_k = nullptr; float *kept_v = nullptr, *alt_v = nullptr; uint32_t* hist = nullptr;
-    auto carve = [&](long cap) -> int {
-        CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
-            cnt = l.take<unsigned long long>(2);
-            cand = l.take<uint64_t>(cap); kept_k = l.take<uint64_t>(cap);
-            kept_v = l.take<float>(cap); alt_v = l.take<float>(cap);
-            hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
-        }));
-        g->pairs_cap = cap;
-        return 0;
-    };
-    CHECK_RC(carve(g->pairs_cap > PAIRS_WS_KEYS ? g->pairs_cap : PAIRS_WS_KEYS));
+    CandidateWs ws{g->pbuf, g->pairs_cap};
+    CHECK_RC(ws.carve(g->pairs_cap > PAIRS_WS_KEYS ? g->pairs_cap : PAIRS_WS_KEYS, st));
     PairsJoinArgs ja{};
     ja.Gb = g->gb.p; ja.ldg = D; ja.N = N; ja.D = D; ja.gstat = g->gstat.p; ja.thr = threshold; ja.allow = allow;
-    unsigned long long n_cand = 0;
-    int passes = 0;
-    for (;;) {
-        ja.cnt = cnt; ja.keys = cand; ja.cap = g->pairs_cap;
-        REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
-        { ProfScope ps("pairs_join", st);
-          CHECK_RC(launch_pairs_join(ja, st)); }
-        ++passes;
-        REVO_HIP_CHECK(hipMemcpyAsync(&n_cand, cnt, sizeof(n_cand), hipMemcpyDeviceToHost, st));
-        REVO_HIP_CHECK(hipStreamSynchronize(st));
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        ja.cnt = ws.cnt; ja.keys = ws.cand; ja.cap = ws.cap;
+        ProfScope ps("pairs_join", st);
+        return launch_pairs_join(ja, st);
+    }, [&](unsigned long long n_cand) -> int {
         REVO_REQUIRE(n_cand <= (unsigned long long)PAIRS_MAX_CAND,
                      "gallery_pairs: " + std::to_string(n_cand) + " candidate pairs exceed the limit of " +
                          std::to_string(PAIRS_MAX_CAND) + " (raise the threshold)");
-        if (n_cand <= (unsigned long long)g->pairs_cap) break;
-        REVO_REQUIRE(passes == 1, "gallery_pairs: the candidate count changed between two joins");
-        CHECK_RC(carve((long)n_cand));     // grown to the counted size, then joined once more
-    }
-    // fp32 re-score; the kept entries as (i << b) | j, b = the bits of the largest row index
-    int b = 1;
-    while (N > 1 && (1l << b) < N) ++b;
-    unsigned long long n_kept = 0;
+        return 0;
+    }, "gallery_pairs: the candidate count changed between two joins"));
+    // fp32 re-score; the kept entries as (i << b) | j
+    const int b = row_index_bits(N);
     { ProfScope ps("pairs_rescore", st);
-      CHECK_RC(launch_pairs_rescore(cand, (long)n_cand, g->gf.p, D, D, threshold, b, cnt + 1, kept_k, kept_v, st)); }
-    REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
-    uint64_t* sk; float* sv;
-    { ProfScope ps("pairs_sort", st);
-      CHECK_RC(launch_pairs_sort(kept_k, kept_v, cand, alt_v, (long)n_kept, 2 * b, hist, &sk, &sv, st)); }
+      CHECK_RC(launch_pairs_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, threshold, b, ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    CHECK_RC(ws.sort_kept("pairs_sort", 2 * b, st));
+    const unsigned long long n_kept = ws.n_kept;
     CHECK_RC(g->pair_idx.grow((size_t)(n_kept > 0 ? n_kept : 1) * 16, st));
     CHECK_RC(g->pair_score.grow((size_t)(n_kept > 0 ? n_kept : 1) * 4, st));
-    CHECK_RC(launch_pairs_emit(sk, sv, (long)n_kept, b, g->pair_idx.p, g->pair_score.p, st));
-    const int stats[2] = {(int)n_cand, passes};    // slot 3 = candidates re-scored, slot 7 = join passes
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    CHECK_RC(launch_pairs_emit(ws.sk, ws.sv, (long)n_kept, b, g->pair_idx.p, g->pair_score.p, st));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.passes, st));
     g->pairs_n = (int64_t)n_kept;
     g->pairs_valid = true;
     *n_pairs = (int64_t)n_kept;
@@ -877,8 +918,7 @@ static int search_range(revo_gallery* g, const float* queries, int Q, float thr,
     const long N = g->size;
     const int D = g->D;
     // sort keys (query << (32 + b)) | (score << b) | row in 64 bits: at most 2^(32 - b) queries per chunk
-    int b = 1;
-    while (N > 1 && (1l << b) < N) ++b;
+    const int b = row_index_bits(N);
     int QC = Q < RANGE_CHUNK ? Q : RANGE_CHUNK;
     if ((long)QC > (1l << (32 - b))) QC = (int)(1l << (32 - b));
     int qbits = 0;
@@ -892,24 +932,13 @@ static int search_range(revo_gallery* g, const float* queries, int Q, float thr,
     CHECK_RC(g->range_off.grow((size_t)(Q + 1) * 8, st));
     REVO_HIP_CHECK(hipMemsetAsync(g->range_off.p, 0, (size_t)(Q + 1) * 8, st));
     unsigned long long* off = g->range_off.p;
-    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept
-    uint64_t *cand = nullptr, *kept_k = nullptr; float *kept_v = nullptr, *alt_v = nullptr; uint32_t* hist = nullptr;
-    auto carve = [&](long cap) -> int {
-        CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
-            cnt = l.take<unsigned long long>(2);
-            cand = l.take<uint64_t>(cap); kept_k = l.take<uint64_t>(cap);
-            kept_v = l.take<float>(cap); alt_v = l.take<float>(cap);
-            hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
-        }));
-        g->range_cap = cap;
-        return 0;
-    };
+    CandidateWs ws{g->pbuf, g->range_cap};
     long total = 0;
     unsigned long long cand_total = 0;
     int max_passes = 0;
     if (N > 0 && Q > 0) {
         const long cap0 = (long)QC * RANGE_WS_PER_QUERY;
-        CHECK_RC(carve(g->range_cap > cap0 ? g->range_cap : cap0));
+        CHECK_RC(ws.carve(g->range_cap > cap0 ? g->range_cap : cap0, st));
         for (int c0 = 0; c0 < Q; c0 += QC) {
             const int Qc = Q - c0 < QC ? Q - c0 : QC;
             { ProfScope ps("search_prep", st);
@@ -917,46 +946,32 @@ static int search_range(revo_gallery* g, const float* queries, int Q, float thr,
             RangeJoinArgs ja{};
             ja.Qb = g->qb.p; ja.ldq = D; ja.Gb = g->gb.p; ja.ldg = D; ja.Q = Qc; ja.N = N; ja.D = D;
             ja.qstat = g->qstat.p; ja.gstat = g->gstat.p; ja.thr = thr; ja.allow = allow;
-            unsigned long long n_cand = 0;
-            int passes = 0;
-            for (;;) {
-                ja.cnt = cnt; ja.keys = cand; ja.cap = g->range_cap;
-                REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), st));
-                { ProfScope ps("range_join", st);
-                  CHECK_RC(launch_range_join(ja, st)); }
-                ++passes;
-                REVO_HIP_CHECK(hipMemcpyAsync(&n_cand, cnt, sizeof(n_cand), hipMemcpyDeviceToHost, st));
-                REVO_HIP_CHECK(hipStreamSynchronize(st));
+            CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+                ja.cnt = ws.cnt; ja.keys = ws.cand; ja.cap = ws.cap;
+                ProfScope ps("range_join", st);
+                return launch_range_join(ja, st);
+            }, [&](unsigned long long n_cand) -> int {
                 REVO_REQUIRE(cand_total + n_cand <= (unsigned long long)RANGE_MAX_CAND,
                              "search_range: " + std::to_string(cand_total + n_cand) + " candidates exceed the limit of " +
                                  std::to_string(RANGE_MAX_CAND) + " (raise the threshold or search fewer queries per call)");
-                if (n_cand <= (unsigned long long)g->range_cap) break;
-                REVO_REQUIRE(passes == 1, "search_range: the candidate count changed between two passes");
-                CHECK_RC(carve((long)n_cand));     // grown to the counted size, then run once more
-            }
-            cand_total += n_cand;
-            max_passes = passes > max_passes ? passes : max_passes;
-            unsigned long long n_kept = 0;
+                return 0;
+            }, "search_range: the candidate count changed between two passes"));
+            cand_total += ws.n_cand;
+            max_passes = ws.passes > max_passes ? ws.passes : max_passes;
             { ProfScope ps("range_rescore", st);
-              CHECK_RC(launch_range_rescore(cand, (long)n_cand, g->qf.p, D, g->gf.p, D, D, thr, b, cnt + 1, off + 1 + c0, kept_k,
-                                            kept_v, st)); }
-            REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
-            REVO_HIP_CHECK(hipStreamSynchronize(st));
-            uint64_t* sk; float* sv;
-            { ProfScope ps("range_sort", st);
-              CHECK_RC(launch_pairs_sort(kept_k, kept_v, cand, alt_v, (long)n_kept, qbits + 32 + b, hist, &sk, &sv, st)); }
-            const size_t need = (size_t)(total + (long)n_kept > 0 ? total + (long)n_kept : 1);
+              CHECK_RC(launch_range_rescore(ws.cand, (long)ws.n_cand, g->qf.p, D, g->gf.p, D, D, thr, b, ws.cnt + 1, off + 1 + c0,
+                                            ws.kept_k, ws.kept_v, st)); }
+            CHECK_RC(ws.sort_kept("range_sort", qbits + 32 + b, st));
+            const long n_kept = (long)ws.n_kept;
+            const size_t need = (size_t)(total + n_kept > 0 ? total + n_kept : 1);
             CHECK_RC(g->range_idx.grow_keep(need * 8, (size_t)total * 8, st));
             CHECK_RC(g->range_score.grow_keep(need * 4, (size_t)total * 4, st));
-            CHECK_RC(launch_range_emit(sk, sv, (long)n_kept, b, index_offset, g->range_idx.p + total, g->range_score.p + total, st));
-            total += (long)n_kept;
+            CHECK_RC(launch_range_emit(ws.sk, ws.sv, n_kept, b, index_offset, g->range_idx.p + total, g->range_score.p + total, st));
+            total += n_kept;
         }
-        CHECK_RC(launch_range_offsets(off + 1, Q, st));
+        CHECK_RC(launch_inclusive_sums_u64(off + 1, Q, st));
     }
-    const int stats[2] = {(int)cand_total, max_passes};    // slot 3 = candidates re-scored, slot 7 = candidate passes
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, cand_total, max_passes, st));
     g->range_n = total;
     g->range_q = Q;
     g->range_valid = true;
@@ -1014,53 +1029,36 @@ static int search_recommend(revo_gallery* g, const float* examples, int P, int N
     }
     // the sample: the rows revo_search_topk_large's sample pass covers (none in a small gallery: tau = -inf or the threshold)
     const long n_s = large_sample_rows(E, N, k);
-    unsigned long long* cnt = nullptr;     // [0] candidates, [1] kept, [2] allowed rows the candidate pass met
-    float *tau = nullptr, *lb = nullptr, *kept_v = nullptr, *alt_v = nullptr;
-    uint32_t *cand = nullptr, *hist = nullptr; uint64_t *kept_k = nullptr, *alt_k = nullptr;
-    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
-        cnt = l.take<unsigned long long>(4); tau = l.take<float>(1);
-        lb = l.take<float>(n_s > 0 ? n_s : 1);
-        cand = l.take<uint32_t>(N); kept_k = l.take<uint64_t>(N); alt_k = l.take<uint64_t>(N);
-        kept_v = l.take<float>(N); alt_v = l.take<float>(N);
-        hist = l.take<uint32_t>(256l * PAIRS_SORT_BLOCKS);
-    }));
+    // candidates are rows (32-bit indices in the key array), at most N: sized once; counter [2] = allowed rows the pass met
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *tau = nullptr, *lb = nullptr;
+    CHECK_RC(ws.carve(N, st, [&](Layout& l) { tau = l.take<float>(1); lb = l.take<float>(n_s > 0 ? n_s : 1); }));
+    uint32_t* cand = (uint32_t*)ws.cand;
     // (the pairs' and the range search's layouts of this buffer are carved again by their next call)
     { ProfScope ps("search_prep", st);
       CHECK_RC(launch_l2norm_rows(examples, D, g->qf.p, D, g->qb.p, D, E, D, st, 1, g->qstat.p)); }
-    REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st));
     RecommendPassArgs pa{};
     pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.P = P; pa.Nn = Nn; pa.D = D;
     pa.qstat = g->qstat.p; pa.gstat = g->gstat.p; pa.allow = allow;
-    { ProfScope ps("recommend_sample", st);
-      if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(launch_recommend_pass(pa, 1, st)); }
-      CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
-    { ProfScope ps("recommend_pass", st);
-      pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = cnt; pa.rows = cand; pa.cap = N;
-      CHECK_RC(launch_recommend_pass(pa, 0, st)); }
-    unsigned long long h[3] = {0, 0, 0};
-    REVO_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
-    const unsigned long long n_cand = h[0], n_allowed = h[2];
-    REVO_REQUIRE(n_cand <= (unsigned long long)N, "search_recommend: more candidates than rows");
-    int b = 1;
-    while (N > 1 && (1l << b) < N) ++b;
-    unsigned long long n_kept = 0;
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        { ProfScope ps("recommend_sample", st);
+          if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(launch_recommend_pass(pa, 1, st)); }
+          CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
+        ProfScope ps("recommend_pass", st);
+        pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = ws.cnt; pa.rows = cand; pa.cap = N;
+        return launch_recommend_pass(pa, 0, st);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)N, "search_recommend: more candidates than rows");
+        return 0;
+    }, "search_recommend: the candidate count changed between two passes"));
+    const int b = row_index_bits(N);
     { ProfScope ps("recommend_rescore", st);
-      CHECK_RC(launch_recommend_rescore(cand, (long)n_cand, g->qf.p, D, P, Nn, g->gf.p, D, D, has_thr, thr, b, cnt + 1, kept_k,
-                                        kept_v, st)); }
-    if (n_cand > 0) {
-        REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
-        REVO_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    uint64_t* sk; float* sv;
-    { ProfScope ps("recommend_sort", st);
-      CHECK_RC(launch_pairs_sort(kept_k, kept_v, alt_k, alt_v, (long)n_kept, 32 + b, hist, &sk, &sv, st)); }
-    CHECK_RC(launch_recommend_emit(sk, sv, (long)n_kept, k, b, index_offset, scores, indices, counts, st));
-    const int stats[2] = {(int)n_cand, n_allowed > 0 ? 1 : 0};    // slot 3 = candidate rows re-scored, slot 7 = candidate passes
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
-    return 0;
+      CHECK_RC(launch_recommend_rescore(cand, (long)ws.n_cand, g->qf.p, D, P, Nn, g->gf.p, D, D, has_thr, thr, b, ws.cnt + 1,
+                                        ws.kept_k, ws.kept_v, st)); }
+    CHECK_RC(ws.sort_kept("recommend_sort", 32 + b, st));
+    CHECK_RC(launch_recommend_emit(ws.sk, ws.sv, (long)ws.n_kept, k, b, index_offset, scores, indices, counts, st));
+    return publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.h[2] > 0 ? 1 : 0, st);   // (no allowed row: no candidate pass counted)
 }
 extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_positive, int32_t n_negative, int32_t k,
                                          int32_t has_threshold, float threshold, int64_t index_offset, float* scores,

@@ -16,6 +16,7 @@
 //   fallback every allowed row scored in fp32 into a per-entry buffer, radix select of the k-th best 64-bit key, the k
 //            keys at or above it sorted in LDS.  Entries run in rounds of LargeWs::F (bounded scratch)
 // Every launch past the sample reads its entry count from the device: no host round trip.
+#include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
 #include "topk_util.h"
@@ -28,8 +29,6 @@ __device__ __forceinline__ int lk_bucket(float v, float base, float inv) {
     t = fminf(fmaxf(t, 0.f), (float)(LARGE_NB - 1));
     return (int)t;
 }
-// x lowered by more than the rounding of the one or two fp32 operations that produced it from values of magnitude <= |ref| + 1
-__device__ __forceinline__ float lk_down(float x, float ref) { return x - 4e-7f * (1.f + fabsf(ref)); }
 __device__ __forceinline__ float lk_lds_f32(uint32_t off) { return *(__attribute__((address_space(3))) const float*)(uintptr_t)off; }
 
 // ---------------------------------------------------------------- block-wide selection ----
@@ -126,8 +125,8 @@ __global__ __launch_bounds__(256) void topk_large_sample_kernel(const float* __r
     const uint64_t kth = n_s > 0 ? lk_kth_largest(key_of, n_s, k, 4, hist, sh) : 0ull;
     if (threadIdx.x != 0) return;
     float lo = -INFINITY;
-    if (kth != 0ull) { const float sb = key_score(kth); lo = lk_down(sb - 2.f * eps, sb); }
-    if (has_thr) lo = fmaxf(lo, lk_down(thr - eps, thr));
+    if (kth != 0ull) { const float sb = key_score(kth); lo = score_down(sb - 2.f * eps, sb); }
+    if (has_thr) lo = fmaxf(lo, score_down(thr - eps, thr));
     // the buckets cover [base, 1 + 2 eps] (every bf16 score of unit rows lies below it; anything above lands in the last)
     const float base = lo > -INFINITY ? lo : -1.f - 2.f * eps;
     const float span = (1.f + 2.f * eps) - base;
@@ -186,13 +185,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void topk_large_count_kernel(Large
             const int lr = lane & 15, lq = lane >> 4;
             const int rbase = (wave >> 2) * 128 + lr;
             const int cw = (wave & 3) * 64;                 // the wave's 64 columns: bits of one 64-bit word of the bitmap
-            const long left = p.N - n0 - cw;                // rows of the gallery from the wave's first column on
-            uint64_t fm = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
-            if (p.allow) {
-                const long w0 = (n0 + cw) >> 5;             // (the bitmap is zero-padded to whole 256-row tiles)
-                fm &= (uint64_t)p.allow[w0] | ((uint64_t)p.allow[w0 + 1] << 32);
-            }
-            const uint64_t bits = fm >> (lq * 4);
+            const uint64_t bits = tile_column_mask(p.N, n0, cw, p.allow) >> (lq * 4);
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const int row = rbase + m * 16;
@@ -252,7 +245,7 @@ __global__ __launch_bounds__(256) void topk_large_level_kernel(LargeWs ws, const
     const int b = top_b;
     // rows of bucket >= b >= 1 score >= base + (b - 1) step (a whole bucket below the edge: covers the rounding of lk_bucket)
     float hh = b < 0 ? -INFINITY : (b == 0 ? lo : base + (float)(b - 1) * step);
-    const float lb = fmaxf(hh > -INFINITY ? lk_down(hh - 2.f * eps, hh) : -INFINITY, lo);
+    const float lb = fmaxf(hh > -INFINITY ? score_down(hh - 2.f * eps, hh) : -INFINITY, lo);
     const int bb = lk_bucket(lb, base, inv);                 // every row >= lb was counted in a bucket >= bb
     uint32_t mine = 0;
 #pragma unroll

@@ -2,18 +2,12 @@
 pairs into near-duplicate groups (store.connected_groups), and the register allocation of its kernels (pairs.hip, from
 hipcc's own resource report: hipcc cross-compiles for gfx950 without a GPU)."""
 import ctypes as C
-import os
-import re
-import subprocess
-
 import numpy as np
 
 import reverso_amd  # noqa: F401
 from reverso_amd import _lib, store
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from _hipcc_report import assert_no_spill
 
 
 def _fake_handle():
@@ -96,22 +90,10 @@ def test_connected_groups_on_synthetic_pair_lists():
 def test_pair_kernels_do_not_spill():
     """Every kernel of pairs.hip: no VGPR spills and no scratch (the join runs the 256 x 256 main loop at up to 256 VGPRs;
     a spill inside its tile loop would wait for the next tile's operand DMA)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-c",
-                          "pairs.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
-                         capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs Spill", r"VGPRs Spill: (\d+)"), ("ScratchSize", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    names = [k for k in d if "pairs_" in k]
-    assert len(names) == 6, names            # join, rescore, radix hist / scan / scatter, emit
-    for k in names:
-        assert d[k]["VGPRs Spill"] == 0 and d[k]["ScratchSize"] == 0, (k, d[k])
+    assert_no_spill("pairs.hip", "pairs_", 3)            # join, rescore, emit
+
+
+def test_sort_kernels_do_not_spill():
+    """Every kernel of radix_sort.hip (the sort step of the pairs, range and recommend searches, and the range offsets): no
+    VGPR spills and no scratch."""
+    assert_no_spill("radix_sort.hip", "_kernel", 4)       # radix hist / scatter, prefix sum (u32 exclusive, u64 inclusive)

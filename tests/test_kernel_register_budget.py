@@ -13,30 +13,11 @@ import subprocess
 
 import pytest
 
+from _hipcc_report import usage as _usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _usage(src):
-    """{mangled kernel name: {"VGPRs": n, "VGPRs Spill": n, "SGPRs Spill": n, "ScratchSize": n}} for one source file."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-c", src,
-                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True,
-                         text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs", r" VGPRs: (\d+)"), ("VGPRs Spill", r"VGPRs Spill: (\d+)"),
-                         ("SGPRs Spill", r"SGPRs Spill: (\d+)"), ("ScratchSize", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    return d
 
 
 def _find(d, *parts):

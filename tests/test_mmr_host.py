@@ -4,7 +4,6 @@ cross-compiles for gfx950 without a GPU), and the numpy statement of the greedy 
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,11 +12,10 @@ import reverso_amd  # noqa: F401
 from reverso_amd import _lib
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _hipcc_report import assert_no_spill  # noqa: E402
 from _mmr_checks import greedy  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _fake_handle():
@@ -76,26 +74,7 @@ def test_binding_and_export():
 def test_mmr_kernels_do_not_spill():
     """Every kernel of mmr.hip: no VGPR spills and no scratch (the 8 x 8 form of the similarity kernel holds 64 running
     sums and up to 16 row slices of four floats per lane; a spill would sit inside its fma loop)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-c",
-                          "mmr.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
-                         capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs Spill", r"VGPRs Spill: (\d+)"), ("SGPRs Spill", r"SGPRs Spill: (\d+)"),
-                         ("ScratchSize", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    names = [k for k in d if "mmr_" in k]
-    assert len(names) == 3, names            # similarity matrix (4 x 4 and 8 x 8 pairs per wave), selection
-    for k in names:
-        assert d[k]["VGPRs Spill"] == 0 and d[k]["ScratchSize"] == 0, (k, d[k])
+    assert_no_spill("mmr.hip", "mmr_", 3)            # similarity matrix (4 x 4 and 8 x 8 pairs per wave), selection
 
 
 def _bits(a):

@@ -2,16 +2,10 @@
 libraries, and the register allocation of its kernels (range.hip, from hipcc's own resource report: hipcc cross-compiles for
 gfx950 without a GPU)."""
 import ctypes as C
-import os
-import re
-import subprocess
-
 import reverso_amd  # noqa: F401
 from reverso_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from _hipcc_report import assert_no_spill
 
 
 def _fake_handle():
@@ -59,22 +53,4 @@ def test_binding_and_export():
 def test_range_kernels_do_not_spill():
     """Every kernel of range.hip: no VGPR spills and no scratch (the candidate pass runs the 256 x 256 main loop at up to 256
     VGPRs in five forms; a spill inside its tile loop would wait for the next tile's operand DMA)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-c",
-                          "range.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
-                         capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs Spill", r"VGPRs Spill: (\d+)"), ("ScratchSize", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    names = [k for k in d if "range_" in k]
-    assert len(names) == 8, names            # join (64, 128, 192, 256 rows; 256 with default-policy DMA), rescore, emit, offsets
-    for k in names:
-        assert d[k]["VGPRs Spill"] == 0 and d[k]["ScratchSize"] == 0, (k, d[k])
+    assert_no_spill("range.hip", "range_", 7)            # join (64, 128, 192, 256 rows; 256 with default-policy DMA), rescore, emit

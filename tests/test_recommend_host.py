@@ -4,7 +4,6 @@ for gfx950 without a GPU), and the pure host parts: the numpy statement of score
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,11 +12,10 @@ import reverso_amd  # noqa: F401
 from reverso_amd import _lib, store
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _hipcc_report import assert_no_spill  # noqa: E402
 from _recommend_checks import best_score, exhaustive  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _fake_handle():
@@ -65,25 +63,7 @@ def test_binding_and_export():
 def test_recommend_kernels_do_not_spill():
     """Every kernel of recommend.hip: no VGPR spills and no scratch (the pass runs the 256 x 256 main loop and then holds
     32 more maxima per lane; a spill inside its tile loop would wait for the next tile's operand DMA)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-c",
-                          "recommend.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
-                         capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs Spill", r"VGPRs Spill: (\d+)"), ("ScratchSize", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    names = [k for k in d if "recommend_" in k]
-    assert len(names) == 7, names            # pass (64 / 128 rows x sample / candidates), level, rescore, emit
-    for k in names:
-        assert d[k]["VGPRs Spill"] == 0 and d[k]["ScratchSize"] == 0, (k, d[k])
+    assert_no_spill("recommend.hip", "recommend_", 7)            # pass (64 / 128 rows x sample / candidates), level, rescore, emit
 
 
 def test_the_formula_on_hand_computed_cases():
