@@ -220,6 +220,39 @@ int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start,
 int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_positive, int32_t n_negative, int32_t k,
                               int32_t has_threshold, float threshold, int64_t index_offset, float* scores, int64_t* indices,
                               int32_t* counts, void* stream);
+/* ---- discovery and context search over (positive, negative) pairs: "the kind of thing I mean is on THIS side of each of
+ * these judgements" -- each pair stays a constraint of its own instead of being folded into one score as RECOMMEND does
+ * DISCOVER.  target: [dim] fp32 on the device, or NULL; positives / negatives: [n_pairs, dim] fp32 on the device each, pair
+ * i = (positives[i], negatives[i]).  All are normalised like every query.  For a gallery row r, with s(v, r) the fp32 score
+ * of vector v against row r (the one fma chain of EXACTNESS: the bits every search returns), sp_i = s(positives[i], r),
+ * sn_i = s(negatives[i], r), fs(x) = x / (1 + |x|):
+ *   discovery (target != NULL, 0 <= n_pairs <= 63):
+ *     rank_i = +1 if sp_i > sn_i else -1;  R = sum of rank_i (an integer, exact);
+ *     sig = 0.5 * (fs(s(target, r)) + 1);  score(r) = (float)R + sig
+ *   context (target == NULL, 1 <= n_pairs <= 64):
+ *     loss_i = fs(min((sp_i - sn_i) - FLT_EPSILON, 0));  score(r) = loss_0 + loss_1 + ... added in pair order, starting
+ *     from loss_0.  The score is <= 0; it is +0 for a row on the positive side of every pair.
+ * Every operation above is ONE fp32 operation rounded to nearest, in the order written, nothing fused: numpy in float32
+ * reproduces the bits.  These formulas are the contract.  So a row is ranked first by how many pairs it sits on the right
+ * side of and only then by its similarity to the target (0 < sig < 1); zero pairs with a target rank by sig alone.
+ * The result is the best k (1 <= k <= 1024) rows the handle's filter allows (revo_search_set_filter, with its lifecycle),
+ * ordered by (score desc, row index asc); has_threshold keeps score >= threshold.  Outputs as revo_search_recommend: scores
+ * [k], indices [k] (row + index_offset), counts [1], device memory, padding -inf / -1.  EXACT: the rows, order and score
+ * bits that computing score(r) as written for every allowed row and sorting gives; two calls give identical bytes.  How:
+ * RECOMMEND's plan.  With e the largest rounding bound of the certificate over the examples, the bf16 scan scores decide a
+ * pair's side unless their difference is within 2 e of zero (such a pair counts +1 in the upper bound of R and -1 in the
+ * lower), and bound sig and every loss_i from both sides; the k-th largest lower bound over a sample of the first rows is a
+ * level k rows reach; one MFMA pass keeps the allowed rows whose upper bound reaches it (a pair's two example rows are
+ * laid out so that their scores meet in one lane's registers); those rows are re-scored in fp32 and sorted on the device.
+ * No certificate can fail.
+ * SYNCHRONOUS on `stream`.  Needs the fp32 master rows (keep_f32 = 0: status -2).  A null handle or output pointer, null
+ * positives or negatives with n_pairs > 0, n_pairs outside the mode's range, k outside 1..1024 or a NaN threshold give
+ * status -2 before the device is touched, the outputs untouched.  An empty gallery, or a filter that allows no row: counts =
+ * 0, all padding.  revo_search_stats after it: slot 3 = candidate rows re-scored in fp32, slot 7 = 1 when the candidate pass
+ * met an allowed row, every other slot 0.  A pairs or a range result held by the handle stays valid. */
+int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
+                             int32_t n_pairs, int32_t k, int32_t has_threshold, float threshold, int64_t index_offset,
+                             float* scores, int64_t* indices, int32_t* counts, void* stream);
 /* ---- diverse search: top-k by maximal marginal relevance (the Mmr(diversity, candidates_limit) re-ranking of a nearest-
  * neighbour query in the vector database the reference sits on: a gallery of video frames and region crops is full of
  * near-identical rows, and the plain top-10 of one is ten copies of the same frame)

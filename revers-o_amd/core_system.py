@@ -970,6 +970,57 @@ class SimpleReverso:
             text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
         return text, items
 
+    def search_by_context(self, target, pairs, similarity_threshold=None, max_results=5, query_filter=None):
+        """Discovery: matches for ``target`` under judgements of the form "this is the kind of thing I mean, that is not".
+        ``pairs`` is a list of ``(positive, negative)``; ``target`` and every member of a pair is the ``id`` of a stored
+        region, an embedding or an image, as in :meth:`search_by_examples`.  A region is ranked first by the number of
+        pairs it lies on the positive side of, then by its similarity to the target; ``target=None`` returns the regions
+        that satisfy the pairs (score 0: all of them).  Regions given by id are not returned.  Returns ``(text, items)``,
+        items ``{"filename", "image_source", "bbox", "id", "score"}`` best first."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        pairs = list(pairs or ())
+        if any(not isinstance(p, (tuple, list)) or len(p) != 2 for p in pairs):
+            return "❌ Every context entry must be a (positive, negative) pair.", []
+        if target is None and not pairs:
+            return "❌ No target and no context pairs given. Please pick a target or at least one pair.", []
+
+        def resolve(examples):
+            out, images, slots = [], [], []
+            for e in examples:
+                is_id = isinstance(e, str) and not os.path.exists(e)
+                is_vec = (torch.is_tensor(e) or isinstance(e, np.ndarray)) and np.ndim(e) == 1
+                if is_id or is_vec:
+                    out.append(e)
+                else:
+                    slots.append(len(out))
+                    out.append(None)
+                    images.append(pp.to_pil(Image.open(e).convert("RGB") if isinstance(e, str) else e))
+            if images:
+                for slot, v in zip(slots, self._embed_pils(images)):
+                    out[slot] = v
+            return out
+
+        flat = resolve([e for pair in pairs for e in pair] + ([] if target is None else [target]))
+        context = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(pairs))]
+        try:
+            with self._lock:
+                hits = self.vector_db.discover(None if target is None else flat[-1], context, limit=int(max_results),
+                                               score_threshold=None if similarity_threshold is None else float(similarity_threshold),
+                                               query_filter=query_filter)
+        except KeyError as e:
+            return f"❌ {e.args[0]}", []
+        if not hits:
+            return ("❌ No regions found for this context" +
+                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
+        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
+                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+        text = (f"🎯 Found {len(items)} regions for the {'target' if target is not None else 'context'} under "
+                f"{len(pairs)} context pairs:\n\n")
+        for n, it in enumerate(items):
+            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
+        return text, items
+
     def search_similar_diverse(self, similarity_threshold=0.7, max_results=5, diversity=0.5, candidates_limit=None,
                                query_filter=None):
         """:meth:`search_similar` without the near-copies: of the stored regions scoring at least ``similarity_threshold``

@@ -488,6 +488,30 @@ int launch_recommend_rescore(const uint32_t* cand, long n, const float* Qf, long
 // the first min(n, k) sorted entries -> scores / row + idx_offset, padding behind them, counts[0]
 int launch_recommend_emit(const uint64_t* keys, const float* vals, long n, int k, int b, long idx_offset, float* scores,
                           long long* idx, int* counts, hipStream_t st);
+// ---- discovery and context search (revo_search_discover; discover.hip): the recommend search's plan
+// (its level and emit kernels as they are) over context pairs; a pair's two example rows sit half a tile apart
+constexpr int DISCOVER_MAX_PAIRS = 64;       // pairs, the target counting as one: what the 128-row form of the tile holds
+struct DiscoverPassArgs {
+    const bf16_t* Qb; long ldq;   // the bf16 example tile, discover_tile_rows rows: positive i in row i, negative i in row
+                                  // rows / 2 + i, the target in row rows / 2 - 1, zero rows elsewhere
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    int n_pairs, has_target;
+    long N; int D;                // rows the pass covers (from row 0)
+    const float* qstat;           // [rows][2] the examples' rounding norms, by tile row (launch_l2norm_rows row_stats)
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    const float* tau;             // candidate pass: [1] the level (device)
+    unsigned long long* cnt;      // candidate pass: [0] candidates found (counts past cap), [2] allowed rows met
+    uint32_t* rows; long cap;     // candidate pass: [cap] candidate rows
+    float* lb_out;                // sample pass: [N] lower bound of every row's score (-inf: not allowed)
+};
+int discover_tile_rows(int n_pairs, int has_target);   // 64 or 128
+int launch_discover_pass(const DiscoverPassArgs& a, int sample, hipStream_t st);
+// score(r) of candidate rows [0, n) against the fp32 example tile Qf (the pass's layout, half = rows / 2); those passing the
+// threshold appended to out_keys ((~order-preserving score bits << b) | row) / out_scores, count in *kept
+int launch_discover_rescore(const uint32_t* cand, long n, const float* Qf, long ldq, int half, int n_pairs, int has_target,
+                            const float* Gf, long ldg, int D, int has_thr, float thr, int b, unsigned long long* kept,
+                            uint64_t* out_keys, float* out_scores, hipStream_t st);
 // ---- diverse search (revo_search_mmr; mmr.hip): the candidates' similarity matrices, greedy selection
 struct MmrGramArgs {
     const float* Gf; long ldg;    // the gallery's fp32 master rows

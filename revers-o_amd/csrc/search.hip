@@ -1079,6 +1079,84 @@ extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples,
     API_END
 }
 
+// ---- discovery and context search (include/revo.h revo_search_discover; discover.hip)
+static int search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives, int n_pairs, int k,
+                           int has_thr, float thr, long index_offset, float* scores, long long* indices, int* counts,
+                           const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    const int has_target = target ? 1 : 0;
+    const int rows = discover_tile_rows(n_pairs, has_target), half = rows / 2;
+    // (the two-phase protocol's state refers to the handle's query rows, which this search overwrites)
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, rows, st));
+    REVO_REQUIRE(g->xw.ctr, "search_discover: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    if (N == 0) {
+        CHECK_RC(launch_topk_fill_empty(scores, indices, counts, 1, k, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    const long n_s = large_sample_rows(2 * n_pairs + has_target, N, k);
+    // candidates are rows (32-bit indices in the key array), at most N: sized once; counter [2] = allowed rows the pass met
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *tau = nullptr, *lb = nullptr;
+    CHECK_RC(ws.carve(N, st, [&](Layout& l) { tau = l.take<float>(1); lb = l.take<float>(n_s > 0 ? n_s : 1); }));
+    uint32_t* cand = (uint32_t*)ws.cand;
+    // (the pairs' and the range search's layouts of this buffer are carved again by their next call)
+    { ProfScope ps("search_prep", st);
+      // the example tile: zero rows, then positive i -> row i, negative i -> row half + i, the target -> row half - 1
+      REVO_HIP_CHECK(hipMemsetAsync(g->qb.p, 0, (size_t)rows * D * sizeof(bf16_t), st));
+      CHECK_RC(launch_l2norm_rows(positives, D, g->qf.p, D, g->qb.p, D, n_pairs, D, st, 1, g->qstat.p));
+      CHECK_RC(launch_l2norm_rows(negatives, D, g->qf.p + (size_t)half * D, D, g->qb.p + (size_t)half * D, D, n_pairs, D, st, 1,
+                                  g->qstat.p + 2 * half));
+      if (has_target)
+          CHECK_RC(launch_l2norm_rows(target, D, g->qf.p + (size_t)(half - 1) * D, D, g->qb.p + (size_t)(half - 1) * D, D, 1, D, st,
+                                      1, g->qstat.p + 2 * (half - 1))); }
+    DiscoverPassArgs pa{};
+    pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.n_pairs = n_pairs; pa.has_target = has_target; pa.D = D;
+    pa.qstat = g->qstat.p; pa.gstat = g->gstat.p; pa.allow = allow;
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        { ProfScope ps("discover_sample", st);
+          if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(launch_discover_pass(pa, 1, st)); }
+          CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
+        ProfScope ps("discover_pass", st);
+        pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = ws.cnt; pa.rows = cand; pa.cap = N;
+        return launch_discover_pass(pa, 0, st);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)N, "search_discover: more candidates than rows");
+        return 0;
+    }, "search_discover: the candidate count changed between two passes"));
+    const int b = row_index_bits(N);
+    { ProfScope ps("discover_rescore", st);
+      CHECK_RC(launch_discover_rescore(cand, (long)ws.n_cand, g->qf.p, D, half, n_pairs, has_target, g->gf.p, D, D, has_thr, thr, b,
+                                       ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    CHECK_RC(ws.sort_kept("discover_sort", 32 + b, st));
+    CHECK_RC(launch_recommend_emit(ws.sk, ws.sv, (long)ws.n_kept, k, b, index_offset, scores, indices, counts, st));
+    return publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.h[2] > 0 ? 1 : 0, st);   // (no allowed row: no candidate pass counted)
+}
+extern "C" int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
+                                        int32_t n_pairs, int32_t k, int32_t has_threshold, float threshold, int64_t index_offset,
+                                        float* scores, int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts, "search_discover: null argument");
+    if (target) REVO_REQUIRE(n_pairs >= 0 && n_pairs <= revo::DISCOVER_MAX_PAIRS - 1,
+                             "search_discover: n_pairs must be in [0, 63] with a target");
+    else REVO_REQUIRE(n_pairs >= 1 && n_pairs <= revo::DISCOVER_MAX_PAIRS,
+                      "search_discover: n_pairs must be in [1, 64] without a target (context search)");
+    REVO_REQUIRE(n_pairs == 0 || (positives && negatives), "search_discover: null positives or negatives");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_discover: k must be in [1, 1024]");
+    REVO_REQUIRE(!has_threshold || !std::isnan(threshold), "search_discover: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "search_discover: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_discover(g, target, positives, negatives, n_pairs, k, has_threshold, threshold, index_offset, scores,
+                           (long long*)indices, counts, allow, (hipStream_t)stream);
+    API_END
+}
+
 // ---- diverse search (include/revo.h revo_search_mmr; mmr.hip)
 constexpr size_t MMR_GRAM_BYTES = 256ul << 20;   // the similarity matrices of one chunk of queries
 static int search_mmr(revo_gallery* g, const float* queries, int Q, int k, int C, float diversity, int has_thr, float thr,

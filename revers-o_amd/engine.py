@@ -363,6 +363,46 @@ class Gallery:
                 _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_recommend")
         return scores, idx, counts[0]
 
+    def discover(self, target, positives, negatives, k=5, score_threshold=None, index_offset=0, allow=None):
+        """Discovery / context search (include/revo.h, DISCOVER): ``positives`` and ``negatives`` fp32 ``[n, dim]`` device
+        tensors, pair ``i`` being ``(positives[i], negatives[i])`` (both None or empty: no pairs), and ``target`` an fp32
+        ``[dim]`` device tensor or None.  With a target (``n <= 63``) a row's score is ``R + sig``: ``R`` counts +1 for every
+        pair whose positive it scores higher against than its negative and -1 otherwise, ``0 < sig < 1`` grows with its
+        score against the target.  Without one (context search, ``1 <= n <= 64``) the score is the sum over the pairs of
+        ``fs(min(sp - sn - FLT_EPSILON, 0))``, ``fs(x) = x / (1 + |x|)``: 0 for a row on the positive side of every pair.
+        Returns the best ``k <= 1024`` rows (allowed by ``allow``, as in :meth:`search`) as ``(scores [k] fp32, indices [k]
+        int64, count)`` device tensors, best first, padded with -inf / -1 -- exactly what scoring every row that way in
+        fp32 and sorting gives.  Synchronous."""
+        def rows(t, name):
+            _require_cuda(t, name, self.device)
+            t = t.detach().to(torch.float32).contiguous()
+            if t.dim() == 1:
+                t = t[None]
+            if t.dim() != 2 or t.shape[1] != self.dim:
+                raise ValueError(f"{name} must be [n, {self.dim}], got {tuple(t.shape)}")
+            return t
+        pos = rows(positives, "positives") if positives is not None and positives.numel() > 0 else None
+        neg = rows(negatives, "negatives") if negatives is not None and negatives.numel() > 0 else None
+        n = 0 if pos is None else pos.shape[0]
+        if n != (0 if neg is None else neg.shape[0]):
+            raise ValueError("discover: positives and negatives must hold the same number of rows (one of each per pair)")
+        tgt = None
+        if target is not None:
+            tgt = rows(target, "target")
+            if tgt.shape[0] != 1:
+                raise ValueError(f"target must be one vector of {self.dim} elements, got {tuple(target.shape)}")
+        k = int(k)
+        scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
+        idx = torch.empty((max(k, 1),), dtype=torch.int64, device=self.device)
+        counts = torch.empty((1,), dtype=torch.int32, device=self.device)
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_search_discover(
+                self._h, None if tgt is None else _lib.ptr(tgt), None if pos is None else _lib.ptr(pos),
+                None if neg is None else _lib.ptr(neg), n, k, int(score_threshold is not None),
+                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
+                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_discover")
+        return scores, idx, counts[0]
+
     def search_mmr(self, queries, k=5, candidates=None, diversity=0.5, score_threshold=None, index_offset=0, allow=None):
         """Diverse search (include/revo.h, MMR): for each query the best ``candidates`` rows of :meth:`search` (default
         ``min(1024, max(k, 100))``; same filter and threshold semantics), of which ``k`` are picked greedily by maximal

@@ -376,6 +376,31 @@ class GalleryStore:
             n = int(c)
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
 
+    def discover(self, target=None, context=(), limit=5, score_threshold=None, query_filter=None):
+        """Discovery search in Qdrant's shape: ``context`` is a list of ``(positive, negative)`` pairs and ``target`` the
+        vector to find matches for; ``target`` and every member of a pair is a point id of the store or a vector.  A point
+        is ranked first by the number of pairs it lies on the positive side of, then by its similarity to the target.
+        ``target=None`` is the context search: the points that satisfy the pairs, scored 0 when they satisfy all of them
+        and below 0 otherwise (1 to 64 pairs; with a target 0 to 63).  Points given by id are never part of the result; an
+        unknown id raises ``KeyError``.  Exact (include/revo.h, DISCOVER), ``limit <= 1024``."""
+        context = list(context or ())
+        if any(not isinstance(pair, (tuple, list)) or len(pair) != 2 for pair in context):
+            raise ValueError("discover: every context entry must be a (positive, negative) pair")
+        if target is None and not context:
+            raise ValueError("discover: needs a target or at least one context pair")
+        pos, prow = self._example_vectors([p for p, _ in context])
+        neg, nrow = self._example_vectors([n for _, n in context])
+        tgt, trow = (None, []) if target is None else self._example_vectors([target])
+        allow = None
+        if prow or nrow or trow or query_filter is not None:
+            mask = self.filter_mask(query_filter).copy() if query_filter is not None else np.ones(len(self), dtype=bool)
+            mask[prow + nrow + trow] = False
+            allow = torch.from_numpy(_filters.pack_bits(mask)).to(self.gallery.device)
+        s, i, c = self.gallery.discover(None if tgt is None else tgt[0], pos, neg, k=int(limit), score_threshold=score_threshold,
+                                        allow=allow)
+        n = int(c)
+        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
+
     def _group_ids(self, group_by):
         key = (group_by, len(self))
         if self._group_cache is None or self._group_cache[0] != key:
