@@ -253,6 +253,46 @@ int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_
 int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
                              int32_t n_pairs, int32_t k, int32_t has_threshold, float threshold, int64_t index_offset,
                              float* scores, int64_t* indices, int32_t* counts, void* stream);
+/* ---- multi-vector search: "which images contain ALL of what this image shows?" -- a point is a set of vectors (the rows of
+ * one group), a query is a set of vectors, the score is late-interaction MaxSim (the multi-vector comparator of the vector
+ * database the reference sits on)
+ * MAXSIM.  queries: [n_vectors, dim] fp32 on the device, 1 <= n_vectors <= 64, normalised like every query.  Groups are the
+ * handle's revo_search_set_groups ids: arbitrary int32 >= 0, sparse or non-contiguous, -1 = no group; the filter is the
+ * handle's revo_search_set_filter.  Both keep their lifecycle (set for another gallery size: status -2).  With s(i, r) the
+ * fp32 score of query vector i against row r (the one fma chain of EXACTNESS: the bits every search returns) and, for a
+ * group G, A(G) the set of its rows the filter allows (a group with empty A(G) is not a result):
+ *   M_i(G)   = max of s(i, r) over r in A(G)   (compared in fp32, -0 equal to +0)
+ *   score(G) = (((M_0 + M_1) + M_2) + ...) + M_{n-1}
+ * each addition ONE fp32 addition rounded to nearest, in query order, starting from M_0: numpy in float32 reproduces the
+ * bits.  These formulas are the contract.  The result is the best k (1 <= k <= 1024) groups ordered by (score desc, group
+ * id asc), -0 ordered as +0; has_threshold keeps score >= threshold (the raw sum, in [-n, n]).
+ * Outputs (device memory): scores [k], group_ids [k], counts [1]; optional, NULL independently: part_scores [k][n_vectors]
+ * = M_i and part_rows [k][n_vectors] = index_offset + the LOWEST allowed row of the group that attains M_i (part_scores
+ * holds that row's own score bits).  Padding -inf, -1, -inf, -1.  An empty gallery, no allowed row with a group, or every
+ * group cut by the threshold: counts = 0, all padding.
+ * EXACT: the groups, order and bits that evaluating the formulas for every group and sorting gives; two calls give
+ * identical bytes.  So n_vectors = 1 with every row its own group returns the rows, order and score bits of
+ * revo_search_topk_large; n_vectors = 1 with arbitrary groups returns the group keys of revo_search_groups(limit = k,
+ * group_size = 1) wherever that call is defined; the same vector given twice returns the one-vector order with scores
+ * fl(M + M).  How: a CSR of group -> rows is built on the device at the first call after revo_search_set_groups (sorted
+ * (group, row) keys) and cached in the handle until the ids or the rows change; one MFMA pass over the gallery's bf16 rows
+ * with the query vectors as the other operand stores every (allowed row, vector) scan score into a workspace of rows x
+ * n_pad x 4 bytes (n_pad = n_vectors rounded up to 4); per group the maxima m_i of those give a = sum m_i, and with e_i the
+ * certificate's rounding bound of vector i, score(G) lies within sum e_i plus the rounding of the two fp32 sums of a; tau =
+ * the k-th largest lower bound over ALL groups (raised to the threshold) is a level k groups reach; the allowed rows of the
+ * groups whose upper bound reaches tau are re-scored in fp32, work split by (row, four vectors), never one wave per group;
+ * an exact group reduction, the device radix sort and the emit follow.  No certificate can fail: bad data costs
+ * candidates, never exactness.
+ * SYNCHRONOUS on `stream`, like revo_search_recommend.  Needs the fp32 master rows (keep_f32 = 0: status -2).  A null
+ * handle, null queries, scores, group_ids or counts, n_vectors outside 1..64, k outside 1..1024 or a NaN threshold give
+ * status -2 before the device is touched, the outputs untouched, the message naming the argument.  No group ids set, or
+ * group ids or a filter set for another size: status -2.  The score workspace cannot be allocated: status -3, its size in
+ * the message.  revo_search_stats after it: slot 3 = rows re-scored in fp32 (the allowed rows of the candidate groups),
+ * slot 7 = 1 when the pass met an allowed row with a group, every other slot 0.  A pairs or a range result held by the
+ * handle stays valid. */
+int32_t revo_search_maxsim(revo_gallery* g, const float* queries, int32_t n_vectors, int32_t k, int32_t has_threshold,
+                           float threshold, int64_t index_offset, float* scores, int32_t* group_ids, int32_t* counts,
+                           float* part_scores, int64_t* part_rows, void* stream);
 /* ---- diverse search: top-k by maximal marginal relevance (the Mmr(diversity, candidates_limit) re-ranking of a nearest-
  * neighbour query in the vector database the reference sits on: a gallery of video frames and region crops is full of
  * near-identical rows, and the plain top-10 of one is ten copies of the same frame)
@@ -369,7 +409,7 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
  * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE,
- * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR. */
+ * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */

@@ -902,6 +902,36 @@ class SimpleReverso:
             items.append({"image": img, "score": r.score, "filename": filename, "bbox": payload.get("bbox")})
         return text, items
 
+    def search_similar_all_regions(self, similarity_threshold=None, max_results=5, query_filter=None, group_by="image_source"):
+        """"Which images contain ALL of what this image shows?": EVERY region embedding of the query image is a query
+        vector, the stored regions are grouped by payload key ``group_by``, and a group's score is the sum over the query
+        regions of its best score among the group's regions (late-interaction MaxSim; up to 64 query regions).
+        ``similarity_threshold`` cuts that SUM (it lies in [-n, n] for n query regions).  Returns ``(text, items)``: items
+        ``{"image": the group's value, "score", "regions": [{"bbox", "score", "id", "filename"} per query region]}`` best first."""
+        if not self.region_embeddings:
+            return "❌ No query embeddings available. Please detect/process an image first.", []
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        queries = torch.stack([torch.as_tensor(e, dtype=torch.float32).reshape(-1) for e in self.region_embeddings])
+        if queries.shape[0] > 64:
+            return f"❌ {queries.shape[0]} query regions: a multi-region search takes at most 64.", []
+        with self._lock:
+            res = self.vector_db.search_multivector(queries, group_by, limit=int(max_results),
+                                                    score_threshold=None if similarity_threshold is None else float(similarity_threshold),
+                                                    query_filter=query_filter)
+        if not res:
+            return ("❌ No images found for these regions" +
+                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
+        items = [{"image": r.value, "score": r.score,
+                  "regions": [{"bbox": h.payload.get("bbox"), "score": h.score, "id": h.id,
+                               "filename": h.payload.get("filename", "Unknown")} for h in r.hits]} for r in res]
+        text = f"🎯 Found {len(items)} images matching all {queries.shape[0]} query regions:\n\n"
+        for n, it in enumerate(items):
+            text += f"{n + 1}. {it['image']}  score {it['score']:.3f}\n"
+            for q, reg in enumerate(it["regions"]):
+                text += f"   region {q + 1}: 📍 {reg['bbox']}  score {reg['score']:.3f}\n"
+        return text, items
+
     def search_all_similar(self, similarity_threshold=0.7, query_filter=None):
         """:meth:`search_similar` without ``max_results``: EVERY stored region whose vector scores at least
         ``similarity_threshold`` against the first region embedding (``query_filter``: only the points a Qdrant-style payload

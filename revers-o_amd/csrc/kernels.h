@@ -512,6 +512,51 @@ int launch_discover_pass(const DiscoverPassArgs& a, int sample, hipStream_t st);
 int launch_discover_rescore(const uint32_t* cand, long n, const float* Qf, long ldq, int half, int n_pairs, int has_target,
                             const float* Gf, long ldg, int D, int has_thr, float thr, int b, unsigned long long* kept,
                             uint64_t* out_keys, float* out_scores, hipStream_t st);
+// ---- multi-vector search (revo_search_maxsim; maxsim.hip): late-interaction MaxSim of up to 64 query
+// vectors over the groups of the gallery's rows; the recommend search's pass form with a storing epilogue, bounds per group
+constexpr int MAXSIM_MAX_VECTORS = 64;       // the query vectors of a tile column live in one wave (the 64-row form of the tile)
+// the CSR of the handle's group ids: sorted keys (group << 32) | row -> gid [G] the distinct ids ascending, off [G + 1] their
+// row ranges in rows [grouped rows] (rows ascending inside a group), pos_group [grouped rows] the dense group of a position;
+// meta (device, 2 words) = { G, grouped rows }.  keys / keys_alt [N], vals / vals_alt [N], hist, flags [N]: scratch
+int launch_maxsim_index(const int32_t* groups, long N, uint64_t* keys, uint64_t* keys_alt, float* vals, float* vals_alt,
+                        uint32_t* hist, unsigned long long* flags, unsigned long long* meta, int32_t* gid, uint32_t* off,
+                        uint32_t* rows, uint32_t* pos_group, hipStream_t st);
+struct MaxsimPassArgs {
+    const bf16_t* Qb; long ldq;   // the bf16 query vectors
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    int n, n_pad;                 // query vectors; n rounded up to 4
+    long N; int D;
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    float* S;                     // [N][n_pad] out: the bf16 scan score of every (allowed row, vector)
+};
+int launch_maxsim_pass(const MaxsimPassArgs& a, hipStream_t st);
+// what the per-group kernels share
+struct MaxsimGroupArgs {
+    const float* S; int n, n_pad, lanes;   // lanes = maxsim_group_lanes(n_pad)
+    const int32_t* gid; const uint32_t* off; const uint32_t* rows; long G;   // the CSR
+    const uint32_t* allow;        // optional allow-bitmap
+    const float* qstat;           // [n][2] the query vectors' rounding norms (launch_l2norm_rows row_stats)
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    int D;
+};
+int maxsim_group_lanes(int n_pad);   // n_pad rounded up to a power of two: lanes of a wave that share one row
+// lb / ub [G]: bounds of score(G) from the bf16 scan scores (-inf: no allowed row), acnt [G] allowed rows; cnt[2] += groups
+// with an allowed row
+int launch_maxsim_bounds(const MaxsimGroupArgs& a, float* lb, float* ub, uint32_t* acnt, unsigned long long* cnt, hipStream_t st);
+// the groups with an allowed row and ub >= tau[0] -> cgroups (count cnt[3]), their allowed rows -> crows (count cnt[0])
+int launch_maxsim_select(const MaxsimGroupArgs& a, long n_grouped, const uint32_t* pos_group, const float* ub, const uint32_t* acnt,
+                         const float* tau, unsigned long long* cnt, uint32_t* crows, uint32_t* cgroups, hipStream_t st);
+// S[row][0 .. n_pad) := the fp32 chain scores of every candidate row
+int launch_maxsim_rescore(const uint32_t* crows, long n_rows, const float* Qf, long ldq, int n, int n_pad, const float* Gf, long ldg,
+                          int D, float* S, hipStream_t st);
+// score(G) of the candidate groups; those passing the threshold appended to out_keys ((~order-preserving score bits << 32) |
+// dense group position) / out_scores, count in *kept
+int launch_maxsim_reduce(const MaxsimGroupArgs& a, const uint32_t* cgroups, long n_groups, int has_thr, float thr,
+                         unsigned long long* kept, uint64_t* out_keys, float* out_scores, hipStream_t st);
+// the first min(n_kept, k) sorted entries -> scores / group ids / per-vector maxima and rows (optional), padding behind them
+int launch_maxsim_emit(const MaxsimGroupArgs& a, const uint64_t* keys, const float* vals, long n_kept, int k, int n_vec,
+                       long idx_offset, float* scores, int32_t* group_ids, int32_t* counts, float* part_scores, long long* part_rows,
+                       hipStream_t st);
 // ---- diverse search (revo_search_mmr; mmr.hip): the candidates' similarity matrices, greedy selection
 struct MmrGramArgs {
     const float* Gf; long ldg;    // the gallery's fp32 master rows

@@ -176,6 +176,12 @@ struct revo_gallery {
     long range_cap = 0;
     DeviceBuffer<long long> range_idx; DeviceBuffer<float> range_score; DeviceBuffer<unsigned long long> range_off;
     int64_t range_n = 0, range_q = 0; bool range_valid = false;
+    // revo_search_maxsim: the CSR of the group ids (gid | off | rows | pos_group in csr; revo::launch_maxsim_index), built at
+    // the first call for csr_rows rows (-1: none; dropped by revo_search_set_groups, an append and a clear), and the score
+    // workspace S [N][n_pad]
+    DeviceBuffer<> csr; int64_t csr_rows = -1; long csr_groups = 0, csr_grouped = 0;
+    int32_t* csr_gid = nullptr; uint32_t *csr_off = nullptr, *csr_row = nullptr, *csr_pos = nullptr;
+    DeviceBuffer<float> maxsim_s;
     revo::CertArgs cert_args(float* cert_out) const {
         revo::CertArgs c{};
         c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
@@ -268,6 +274,7 @@ extern "C" int32_t revo_search_set_groups(revo_gallery* g, const int32_t* group_
     API_BEGIN
     REVO_REQUIRE(g, "search_set_groups: null handle");
     REVO_REQUIRE(rows >= 0, "search_set_groups: negative row count");
+    g->csr_rows = -1;
     if (!group_of_row) { g->groups_rows = -1; return 0; }
     REVO_REQUIRE(rows == g->size, "search_set_groups: rows must equal revo_gallery_size (one group id per gallery row)");
     REVO_ON_DEVICE(g->device);
@@ -290,6 +297,7 @@ extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     g->size = 0;
     g->pairs_valid = false;
     g->range_valid = false;
+    g->csr_rows = -1;
     return 0;
 }
 
@@ -303,6 +311,7 @@ extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64
     hipStream_t st = (hipStream_t)stream;
     g->pairs_valid = false;
     g->range_valid = false;
+    g->csr_rows = -1;
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
     for (int64_t done = 0; done < n; done += chunk_rows) {
@@ -1154,6 +1163,125 @@ extern "C" int32_t revo_search_discover(revo_gallery* g, const float* target, co
     REVO_ON_DEVICE(g->device);
     return search_discover(g, target, positives, negatives, n_pairs, k, has_threshold, threshold, index_offset, scores,
                            (long long*)indices, counts, allow, (hipStream_t)stream);
+    API_END
+}
+
+// ---- multi-vector search (include/revo.h revo_search_maxsim; maxsim.hip)
+// the CSR of the handle's group ids, built for the gallery's current rows (N >= 1)
+static int maxsim_build_index(revo_gallery* g, hipStream_t st) {
+    using namespace revo;
+    const long N = g->size;
+    g->csr_rows = -1;
+    CHECK_RC(carve_buffer(g->csr, st, [&](Layout& l) {
+        g->csr_gid = l.take<int32_t>(N); g->csr_off = l.take<uint32_t>(N + 1); g->csr_row = l.take<uint32_t>(N);
+        g->csr_pos = l.take<uint32_t>(N);
+    }));
+    // (scratch of the build: the candidate pipeline's buffer, carved again by the next search that uses it)
+    uint64_t *keys = nullptr, *keys_alt = nullptr; float *vals = nullptr, *vals_alt = nullptr; uint32_t* hist = nullptr;
+    unsigned long long *flags = nullptr, *meta = nullptr;
+    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+        keys = l.take<uint64_t>(N); keys_alt = l.take<uint64_t>(N); vals = l.take<float>(N); vals_alt = l.take<float>(N);
+        hist = l.take<uint32_t>(256l * SORT_MAX_BLOCKS); flags = l.take<unsigned long long>(N); meta = l.take<unsigned long long>(2);
+    }));
+    ProfScope ps("maxsim_index", st);
+    CHECK_RC(launch_maxsim_index(g->groups.p, N, keys, keys_alt, vals, vals_alt, hist, flags, meta, g->csr_gid, g->csr_off,
+                                 g->csr_row, g->csr_pos, st));
+    unsigned long long h[2] = {0, 0};
+    REVO_HIP_CHECK(hipMemcpyAsync(h, meta, sizeof(h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    REVO_REQUIRE(h[0] <= h[1] && h[1] <= (unsigned long long)N, "search_maxsim: inconsistent group index");
+    g->csr_groups = (long)h[0]; g->csr_grouped = (long)h[1]; g->csr_rows = N;
+    return 0;
+}
+static int search_maxsim(revo_gallery* g, const float* queries, int n, int k, int has_thr, float thr, long index_offset,
+                         float* scores, int32_t* group_ids, int32_t* counts, float* part_scores, long long* part_rows,
+                         const uint32_t* allow, hipStream_t st) {
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    const int n_pad = (n + 3) / 4 * 4;
+    // (the two-phase protocol's state refers to the handle's query rows, which this search overwrites)
+    g->cand = nullptr; g->cand_Q = 0; g->nsegs = 0; g->prelist = nullptr; g->cand_estimated = false;
+    CHECK_RC(search_grow_queries(g, n, st));
+    REVO_REQUIRE(g->xw.ctr, "search_maxsim: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    MaxsimGroupArgs ga{};
+    ga.n = n; ga.n_pad = n_pad; ga.lanes = maxsim_group_lanes(n_pad); ga.allow = allow; ga.D = D;
+    if (N > 0 && g->csr_rows != N) CHECK_RC(maxsim_build_index(g, st));
+    const long G = N > 0 ? g->csr_groups : 0, n_grouped = N > 0 ? g->csr_grouped : 0;
+    if (G == 0) {
+        // an empty gallery, or no row with a group: all padding
+        CHECK_RC(launch_maxsim_emit(ga, nullptr, nullptr, 0, k, n, index_offset, scores, group_ids, counts, part_scores, part_rows, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    REVO_REQUIRE(G < (1l << 31), "search_maxsim: too many groups");
+    const size_t s_bytes = (size_t)N * n_pad * sizeof(float);
+    if (g->maxsim_s.bytes < s_bytes && g->maxsim_s.grow(s_bytes, st) != 0) {
+        (void)hipGetLastError();
+        revo_set_error("search_maxsim: could not allocate the score workspace of " + std::to_string(s_bytes) + " bytes (rows x " +
+                       std::to_string(n_pad) + " x 4)");
+        return -3;
+    }
+    // the candidate pipeline's workspace over GROUPS (kept keys, sort buffers), and behind it the bounds and the candidate lists
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *tau = nullptr, *lb = nullptr, *ub = nullptr; uint32_t *acnt = nullptr, *cgroups = nullptr, *crows = nullptr;
+    CHECK_RC(ws.carve(G, st, [&](Layout& l) {
+        tau = l.take<float>(1); lb = l.take<float>(G); ub = l.take<float>(G); acnt = l.take<uint32_t>(G);
+        cgroups = l.take<uint32_t>(G); crows = l.take<uint32_t>(n_grouped);
+    }));
+    { ProfScope ps("search_prep", st);
+      CHECK_RC(launch_l2norm_rows(queries, D, g->qf.p, D, g->qb.p, D, n, D, st, 1, g->qstat.p));
+      REVO_HIP_CHECK(hipMemsetAsync(ws.cnt, 0, sizeof(ws.h), st)); }
+    ga.S = g->maxsim_s.p; ga.gid = g->csr_gid; ga.off = g->csr_off; ga.rows = g->csr_row; ga.G = G;
+    ga.qstat = g->qstat.p; ga.gstat = g->gstat.p;
+    { ProfScope ps("maxsim_pass", st);
+      MaxsimPassArgs pa{};
+      pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.n = n; pa.n_pad = n_pad; pa.N = N; pa.D = D; pa.allow = allow;
+      pa.S = g->maxsim_s.p;
+      CHECK_RC(launch_maxsim_pass(pa, st)); }
+    { ProfScope ps("maxsim_bounds", st);
+      CHECK_RC(launch_maxsim_bounds(ga, lb, ub, acnt, ws.cnt, st)); }
+    { ProfScope ps("maxsim_level", st);
+      CHECK_RC(launch_recommend_level(lb, (int)G, k, has_thr, thr, tau, st));
+      CHECK_RC(launch_maxsim_select(ga, n_grouped, g->csr_pos, ub, acnt, tau, ws.cnt, crows, cgroups, st)); }
+    // counters: [0] candidate rows, [1] kept groups, [2] groups with an allowed row, [3] candidate groups
+    REVO_HIP_CHECK(hipMemcpyAsync(ws.h, ws.cnt, sizeof(ws.h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    REVO_REQUIRE(ws.h[0] <= (unsigned long long)n_grouped && ws.h[3] <= (unsigned long long)G, "search_maxsim: more candidates than rows");
+    { ProfScope ps("maxsim_rescore", st);
+      CHECK_RC(launch_maxsim_rescore(crows, (long)ws.h[0], g->qf.p, D, n, n_pad, g->gf.p, D, D, g->maxsim_s.p, st)); }
+    { ProfScope ps("maxsim_reduce", st);
+      CHECK_RC(launch_maxsim_reduce(ga, cgroups, (long)ws.h[3], has_thr, thr, ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    ws.n_cand = ws.h[3];
+    CHECK_RC(ws.sort_kept("maxsim_sort", 64, st));   // (the score sits above all 32 bits of the group position)
+    { ProfScope ps("maxsim_emit", st);
+      CHECK_RC(launch_maxsim_emit(ga, ws.sk, ws.sv, (long)ws.n_kept, k, n, index_offset, scores, group_ids, counts, part_scores,
+                                  part_rows, st)); }
+    return publish_candidate_stats(g->xw.ctr, ws.h[0], ws.h[2] > 0 ? 1 : 0, st);
+}
+extern "C" int32_t revo_search_maxsim(revo_gallery* g, const float* queries, int32_t n_vectors, int32_t k, int32_t has_threshold,
+                                      float threshold, int64_t index_offset, float* scores, int32_t* group_ids, int32_t* counts,
+                                      float* part_scores, int64_t* part_rows, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_maxsim: null handle");
+    REVO_REQUIRE(queries, "search_maxsim: null queries");
+    REVO_REQUIRE(scores, "search_maxsim: null scores");
+    REVO_REQUIRE(group_ids, "search_maxsim: null group_ids");
+    REVO_REQUIRE(counts, "search_maxsim: null counts");
+    REVO_REQUIRE(n_vectors >= 1 && n_vectors <= revo::MAXSIM_MAX_VECTORS, "search_maxsim: n_vectors must be in [1, 64]");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_maxsim: k must be in [1, 1024]");
+    REVO_REQUIRE(!has_threshold || !std::isnan(threshold), "search_maxsim: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "search_maxsim: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    REVO_REQUIRE(g->groups_rows >= 0, "search_maxsim: no group ids (revo_search_set_groups)");
+    REVO_REQUIRE(g->groups_rows == g->size,
+                 "search_maxsim: the group ids were set for " + std::to_string(g->groups_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set them again after appending)");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    return search_maxsim(g, queries, n_vectors, k, has_threshold, threshold, index_offset, scores, group_ids, counts, part_scores,
+                         (long long*)part_rows, allow, (hipStream_t)stream);
     API_END
 }
 

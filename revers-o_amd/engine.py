@@ -403,6 +403,35 @@ class Gallery:
                 _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_discover")
         return scores, idx, counts[0]
 
+    def search_maxsim(self, queries, groups, k=5, score_threshold=None, index_offset=0, allow=None, with_parts=False):
+        """Multi-vector search (include/revo.h, MAXSIM): ``queries`` fp32 ``[n, dim]`` device tensor, ``1 <= n <= 64``;
+        ``groups`` int32 ``[len]`` device tensor, the group of every row (-1 = none), as in :meth:`search_groups`.  A
+        group's score is the sum over the query vectors (in order, fp32) of its best score against the group's rows that
+        ``allow`` selects.  Returns the best ``k <= 1024`` groups as ``(scores [k] fp32, group_ids [k] int32, count)``
+        device tensors (``count`` a 0-d int32), best first (score desc, group id asc), padded with -inf / -1 -- exactly
+        what scoring every group that way in fp32 and sorting gives.  ``with_parts``: also ``part_scores [k, n]`` fp32 (the
+        best score per query vector) and ``part_rows [k, n]`` int64 (``index_offset`` + the lowest row attaining it),
+        padded with -inf / -1.  Synchronous."""
+        _require_cuda(queries, "queries", self.device)
+        q = queries.detach().to(torch.float32).contiguous()
+        if q.dim() == 1:
+            q = q[None]
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [n, {self.dim}], got {tuple(q.shape)}")
+        n, k = q.shape[0], int(k)
+        scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
+        gids = torch.empty((max(k, 1),), dtype=torch.int32, device=self.device)
+        counts = torch.empty((1,), dtype=torch.int32, device=self.device)
+        ps = torch.empty((max(k, 1), max(n, 1)), dtype=torch.float32, device=self.device) if with_parts else None
+        pr = torch.empty((max(k, 1), max(n, 1)), dtype=torch.int64, device=self.device) if with_parts else None
+        with self._lock, torch.cuda.device(self.device), self._filter(allow), self._groups(groups):
+            _lib.check(self._lib.revo_search_maxsim(
+                self._h, _lib.ptr(q), n, k, int(score_threshold is not None),
+                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
+                _lib.ptr(scores), _lib.ptr(gids), _lib.ptr(counts), _lib.ptr(ps), _lib.ptr(pr), _lib.current_stream()),
+                "revo_search_maxsim")
+        return (scores, gids, counts[0], ps, pr) if with_parts else (scores, gids, counts[0])
+
     def search_mmr(self, queries, k=5, candidates=None, diversity=0.5, score_threshold=None, index_offset=0, allow=None):
         """Diverse search (include/revo.h, MMR): for each query the best ``candidates`` rows of :meth:`search` (default
         ``min(1024, max(k, 100))``; same filter and threshold semantics), of which ``k`` are picked greedily by maximal

@@ -154,6 +154,15 @@ class PointGroup:
 
 
 @dataclass
+class MultiVectorResult:
+    """One group of a multi-vector search: the payload value ``value``, its MaxSim ``score`` and, per query vector, the
+    point of the group that matched it best (``hits[i].score`` is query vector i's share of ``score``)."""
+    value: object
+    score: float
+    hits: list
+
+
+@dataclass
 class GroupsResult:
     """Qdrant's ``GroupsResult``: the groups best first."""
     groups: list
@@ -424,6 +433,26 @@ class GalleryStore:
             hits = [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[r][:hc[r]], i[r][:hc[r]])]
             out.append(PointGroup(values[gid[r]], hits))
         return GroupsResult(out)
+
+    def search_multivector(self, query_vectors, group_by, limit=5, score_threshold=None, query_filter=None):
+        """A set of query vectors against the points grouped by payload key ``group_by`` (multi-vector points with the
+        MaxSim comparator): a group's score is the sum over the query vectors of its best score among the group's points
+        that ``query_filter`` selects.  Returns the best ``limit <= 1024`` groups as :class:`MultiVectorResult` entries
+        (``value``: the group's payload value, ``score``, ``hits``: one :class:`ScoredPoint` per query vector, the point
+        that matched it best with that score).  Up to 64 query vectors.  Exact (include/revo.h, MAXSIM)."""
+        q = torch.as_tensor(query_vectors, dtype=torch.float32)
+        q = q.reshape(-1, q.shape[-1]) if q.dim() != 2 else q
+        if q.shape[0] < 1:
+            raise ValueError("search_multivector: needs at least one query vector")
+        groups, values = self._group_ids(group_by)
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        s, gid, c, ps, pr = self.gallery.search_maxsim(q.to(self.gallery.device), groups, k=int(limit),
+                                                       score_threshold=score_threshold, allow=allow, with_parts=True)
+        n = int(c)
+        s, gid, ps, pr = s[:n].tolist(), gid[:n].tolist(), ps[:n].tolist(), pr[:n].tolist()
+        return [MultiVectorResult(values[gid[r]], float(s[r]),
+                                  [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(ps[r], pr[r])])
+                for r in range(n)]
 
     def _pairs(self, score_threshold, query_filter):
         allow = self._allow_bits(query_filter) if query_filter is not None else None
