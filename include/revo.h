@@ -91,6 +91,38 @@ int32_t revo_gallery_clear(revo_gallery* g);
 /* copy rows [start, start+n) of the fp32 master copy to dst (host or device); needs keep_f32 */
 int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst, int32_t dst_on_device);
 
+/* ---- EDIT: rows leave and change in place (the points-delete and the replacing upsert of the database behind the
+ * reference)
+ * revo_gallery_remove takes out every row whose bit is set in remove_bits -- the layout of revo_search_set_filter: bit
+ * (r & 31) of word r >> 5, ceil(rows / 32) words, host (src_on_device = 0) or device memory, bits at or past `rows`
+ * ignored.  `rows` must equal revo_gallery_size(g) (status -2 otherwise).  The survivors keep their relative order: survivor
+ * number j becomes row j, in the bf16 scan copy and in the fp32 master (where the gallery has one).  revo_gallery_size drops
+ * by *n_removed (host); the capacity is unchanged, so a later append uses the freed rows.  SYNCHRONOUS on `stream`, like
+ * revo_gallery_pairs: the host needs the new size.
+ * Contract: after the call every entry point of this library returns, byte for byte -- scores, indices, counts, offsets and
+ * padding -- what it returns on a fresh gallery to which the surviving fp32 master rows were appended in order with
+ * normalize = 0; for a keep_f32 = 0 gallery, what a keep_f32 = 0 gallery built from the same original vectors minus the
+ * removed ones returns.  The certificate's running row maxima are NOT recomputed: the maxima over the old rows are upper
+ * bounds of the maxima over the survivors, so every certificate stays valid and every result exact (a removed row of huge
+ * norm merely leaves the bound looser than a fresh gallery's); they start over, as in revo_gallery_clear, when the gallery
+ * becomes empty.
+ * The rows move in place in chunks on `stream`: no second copy of the gallery (device memory beyond it: one staging chunk of
+ * at most 64 MB, 8 bytes per chunk, and the bitmap's copy when it comes from the host), no traffic for the rows in front of
+ * the first removed row.
+ * revo_gallery_update overwrites row row_idx[i] (HOST array of n entries) with vecs[i] ([n, dim] fp32, host or device)
+ * exactly as an append would have written it: the same normalisation arithmetic, fp32 master, bf16 row, and the row's share
+ * merged into the certificate's maxima (which therefore also stay upper bounds).  An index outside [0, size) or a repeated
+ * index gives status -2 before the device is touched; n = 0 does nothing.  Enqueued on `stream` like an append.
+ * Both invalidate a held pairs and range result (their _read gives -2, as after an append) and the two-phase candidate
+ * state.  A remove that removes at least one row also drops the multi-vector search's index, and a filter or group ids set
+ * for the old size fail the next search with the message an append gives (set them again); an update leaves filter, group
+ * ids and index valid (none depends on a row's values).  A null handle or pointer or a negative count: status -2, nothing
+ * written.  A sharded search (ShardedSearch) over the handle is to be refreshed after a remove. */
+int32_t revo_gallery_remove(revo_gallery* g, const uint32_t* remove_bits, int64_t rows, int32_t src_on_device,
+                            int64_t* n_removed, void* stream);
+int32_t revo_gallery_update(revo_gallery* g, const int64_t* row_idx, const float* vecs, int64_t n, int32_t normalize,
+                            int32_t src_on_device, void* stream);
+
 /* ---- search: replaces vector_db.search(query_vector, limit, score_threshold) (core_system.py:659-664)
  * queries: [n_queries, dim] fp32 on the device (normalised internally, cosine semantics).
  * Results, best first under (score desc, index asc): scores [n_queries, k] fp32, indices
@@ -496,6 +528,9 @@ int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch, void* dst
  * 1 = every query takes the collecting pass, 2 = every query takes the brute-force pass -- and every query of a grouped
  * search the grouped fp32 passes, and every query of revo_search_topk_large its exhaustive fallback (1 and 2: parity tests of the fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
 int32_t revo_search_set_mode(revo_gallery* g, int32_t mode);
+/* rows per chunk of revo_gallery_remove (rounded up to a multiple of 32, at most 65536; 0 = the default, 64 MB of fp32 rows):
+ * tests cross many chunk boundaries with a small gallery.  Same result for every value. */
+int32_t revo_debug_set_remove_chunk(int64_t rows);
 /* phase groups of the persistent 256 x 256 GEMM (an experiment, measured in round 5 and not adopted): 0 / 1 = off (all
  * workgroups in step), 2..4 = that many groups, a workgroup of group g doing the first (g + 1) / groups of its first tile at the start and the
  * rest of that tile last.  Result-preserving (bit-identical). */

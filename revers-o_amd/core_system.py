@@ -31,6 +31,7 @@ import numpy as np
 import torch
 from PIL import Image, ImageDraw, ImageFont
 
+from . import filters
 from . import preprocess as pp
 from . import store as st
 from .config import DEFAULT_VARIANT, available_configs, get_config
@@ -1105,6 +1106,36 @@ class SimpleReverso:
                 text += f"   {m['filename']}  (Source: {m['image_source']})\n"
             text += "\n"
         return text, out
+
+    def delete_images(self, image_sources=None, query_filter=None):
+        """Remove stored regions from the loaded database, in place: every region of the source images ``image_sources``
+        (one path or a list; payload key ``image_source``) or every region a Qdrant-style ``query_filter`` selects (both
+        given: regions that meet both).  The database behind the reference does this with ``delete(points_selector=...)``;
+        here the rows move on the device and the database directory gets one ``delete`` line (``GalleryStore.delete``).
+        Returns a status string with the number of regions removed."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first."
+        if isinstance(image_sources, str):
+            image_sources = [image_sources]
+        image_sources = list(image_sources or [])
+        if not image_sources and query_filter is None:
+            return "❌ Please provide image sources or a filter"
+        try:
+            must = []
+            if image_sources:
+                must.append(filters.FieldCondition("image_source", match=filters.MatchAny(image_sources)))
+            if query_filter is not None:
+                must.append(filters.as_filter(query_filter))
+            with self._lock:
+                n = self.vector_db.delete(filters.Filter(must=must))
+                if n and self.vector_db.path:
+                    self.vector_db.save()                # the manifest is a finished database again
+                left = len(self.vector_db)
+        except Exception as e:
+            return f"❌ Error deleting regions: {str(e)}"
+        if n == 0:
+            return "⚠️ No stored regions matched: nothing deleted"
+        return f"✅ Deleted {n} regions ({left} left in database: {self.current_database})"
 
     def visualize_detections(self, image, selected_region_index=None):
         """core_system.py:719-757 draws mask contours with OpenCV (UI cosmetics, out of scope);

@@ -615,7 +615,8 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
                                                           bf16_t* __restrict__ dst_bf16, long ld_bf16, long rows,
                                                           int D, int normalize, float* __restrict__ row_stats,
                                                           uint32_t* __restrict__ max_stats, uint32_t* __restrict__ zero_a,
-                                                          long zero_a_words, uint32_t* __restrict__ zero_b, long zero_b_words) {
+                                                          long zero_a_words, uint32_t* __restrict__ zero_b, long zero_b_words,
+                                                          const long long* __restrict__ dst_rows) {
     // (a search's first kernel also clears the counters and histograms its later kernels add to: two launches fewer)
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_a_words; i += (long)gridDim.x * 256) zero_a[i] = 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_b_words; i += (long)gridDim.x * 256) zero_b[i] = 0;
@@ -623,6 +624,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* s = src + row * ld_src;
+    const long orow = dst_rows ? (long)dst_rows[row] : row;   // where the row is written (revo_gallery_update: a row of the gallery)
     float inv = 1.0f;
     float ny = 0.f, nb = 0.f, ne = 0.f;
     constexpr int NV = 32;                    // rows of up to 64 NV = 2048 elements are held in registers
@@ -647,8 +649,8 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
             if (c < D) {
                 const float y = v[i] * inv;
                 const bf16_t yb = f32_to_bf16(y);
-                if (dst_f32) dst_f32[row * ld_f32 + c] = y;
-                if (dst_bf16) dst_bf16[row * ld_bf16 + c] = yb;
+                if (dst_f32) dst_f32[orow * ld_f32 + c] = y;
+                if (dst_bf16) dst_bf16[orow * ld_bf16 + c] = yb;
                 const float fb = bf16_to_f32(yb), d = fb - y;     // the difference of two neighbouring floats is exact
                 ny = fmaf(y, y, ny); nb = fmaf(fb, fb, nb); ne = fmaf(d, d, ne);
             }
@@ -663,8 +665,8 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
         for (int c = lane; c < D; c += 64) {
             const float y = s[c] * inv;
             const bf16_t yb = f32_to_bf16(y);
-            if (dst_f32) dst_f32[row * ld_f32 + c] = y;
-            if (dst_bf16) dst_bf16[row * ld_bf16 + c] = yb;
+            if (dst_f32) dst_f32[orow * ld_f32 + c] = y;
+            if (dst_bf16) dst_bf16[orow * ld_bf16 + c] = yb;
             const float fb = bf16_to_f32(yb), d = fb - y;
             ny = fmaf(y, y, ny); nb = fmaf(fb, fb, nb); ne = fmaf(d, d, ne);
         }
@@ -682,11 +684,11 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
 }
 int launch_l2norm_rows(const float* src, long ld_src, float* dst_f32, long ld_f32, bf16_t* dst_bf16, long ld_bf16,
                        long rows, int D, hipStream_t st, int normalize, float* row_stats, uint32_t* max_stats,
-                       uint32_t* zero_a, long zero_a_words, uint32_t* zero_b, long zero_b_words) {
+                       uint32_t* zero_a, long zero_a_words, uint32_t* zero_b, long zero_b_words, const long long* dst_rows) {
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, src, ld_src, dst_f32,
                        ld_f32, dst_bf16, ld_bf16, rows, D, normalize, row_stats, max_stats, zero_a, zero_a_words, zero_b,
-                       zero_b_words);
+                       zero_b_words, dst_rows);
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -156,7 +156,20 @@ int launch_f32_to_bf16(const float* src, long ld_src, bf16_t* dst, long ld_dst, 
 int launch_l2norm_rows(const float* src, long ld_src, float* dst_f32, long ld_f32, bf16_t* dst_bf16, long ld_bf16,
                        long rows, int D, hipStream_t st, int normalize = 1, float* row_stats = nullptr,
                        uint32_t* max_stats = nullptr, uint32_t* zero_a = nullptr, long zero_a_words = 0,
-                       uint32_t* zero_b = nullptr, long zero_b_words = 0);
+                       uint32_t* zero_b = nullptr, long zero_b_words = 0, const long long* dst_rows = nullptr);
+// (dst_rows, optional, device [rows]: output row i goes to row dst_rows[i] of dst_f32 / dst_bf16 instead of row i -- the
+//  overwrite of gallery rows, revo_gallery_update; row_stats stays indexed by i)
+
+// ------------------------------------------------- gallery edit (gallery_edit.hip) ----
+constexpr long REMOVE_MAX_CHUNK = 65536;   // rows per chunk of a removal at most (a workgroup sums the chunk's words in front of its own)
+// per chunk c of `chunk` rows (a multiple of 32) of a remove-bitmap over N rows: cnt[c] = rows of the chunk whose bit is clear,
+// first[c] = offset in the chunk of its first row whose bit is set (the chunk's row count if none)
+int launch_remove_count(const uint32_t* bits, long N, long chunk, uint32_t* cnt, uint32_t* first, hipStream_t st);
+// the rows [row0, row0 + len) of src (rows of u4_per_row 16-byte units) whose bit is clear, gathered in order: the row with
+// j kept rows of the chunk in front of it goes to row j of dst, for j >= j0.  row0 % 32 == 0, len <= REMOVE_MAX_CHUNK; dst must
+// not overlap the source rows
+int launch_remove_gather(const uint32_t* bits, long N, long row0, long len, long j0, const uint4* src, uint4* dst,
+                         int u4_per_row, hipStream_t st);
 
 // ----------------------------------------------------------- attention -----
 // qkv [B*S][ld] bf16 (q | k | v thirds, heads contiguous inside a third) -> out [B*S][ldo] bf16

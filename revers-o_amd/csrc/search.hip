@@ -4,6 +4,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <memory>
+#include <string>
+#include <vector>
 
 #include "../../include/revo.h"
 #include "api_internal.h"
@@ -182,6 +184,13 @@ struct revo_gallery {
     DeviceBuffer<> csr; int64_t csr_rows = -1; long csr_groups = 0, csr_grouped = 0;
     int32_t* csr_gid = nullptr; uint32_t *csr_off = nullptr, *csr_row = nullptr, *csr_pos = nullptr;
     DeviceBuffer<float> maxsim_s;
+    // revo_gallery_remove: per-chunk counts | first removed rows | the copy of a host bitmap; revo_gallery_update: the row map
+    DeviceBuffer<> edit;
+    // the rows change: results held in the handle and the two-phase candidate state go
+    void rows_changed() {
+        pairs_valid = false; range_valid = false;
+        cand = nullptr; cand_Q = 0; cand_ksel = 0; nsegs = 0; prelist = nullptr; cand_estimated = false;
+    }
     revo::CertArgs cert_args(float* cert_out) const {
         revo::CertArgs c{};
         c.qstat = qstat.p; c.gstat = gstat.p; c.mode = mode; c.ws = xw; c.Qb = qb.p; c.ldq = D; c.cert_out = cert_out;
@@ -346,6 +355,135 @@ extern "C" int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, 
     REVO_ON_DEVICE(g->device);
     REVO_HIP_CHECK(hipMemcpy(dst, g->gf.p + start * g->D, (size_t)n * g->D * 4,
                              dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return 0;
+    API_END
+}
+
+// ---- rows leave and change in place (include/revo.h EDIT; gallery_edit.hip)
+#ifdef REVO_EXPERIMENTS
+static long g_remove_chunk = 0;
+extern "C" int32_t revo_debug_set_remove_chunk(int64_t rows) {
+    REVO_REQUIRE(rows >= 0, "debug_set_remove_chunk: negative row count");
+    g_remove_chunk = rows == 0 ? 0 : std::min<long>(revo::REMOVE_MAX_CHUNK, (long)((rows + 31) / 32 * 32));
+    return 0;
+}
+#endif
+extern "C" int32_t revo_gallery_remove(revo_gallery* g, const uint32_t* remove_bits, int64_t rows, int32_t src_on_device,
+                                       int64_t* n_removed, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_remove: null handle");
+    REVO_REQUIRE(n_removed, "gallery_remove: null n_removed");
+    REVO_REQUIRE(rows >= 0, "gallery_remove: negative row count");
+    REVO_REQUIRE(remove_bits || rows == 0, "gallery_remove: null remove_bits");
+    REVO_REQUIRE(rows == g->size, "gallery_remove: rows must equal revo_gallery_size (the bitmap covers the whole gallery)");
+    g->rows_changed();
+    if (rows == 0) { *n_removed = 0; return 0; }
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int D = g->D;
+    const long N = (long)rows;
+    // a chunk: the append's 64 MB of fp32 rows, in whole bitmap words
+    long chunk = std::min<long>(revo::REMOVE_MAX_CHUNK, std::max<long>(32, (64l << 20) / (D * 4) / 32 * 32));
+#ifdef REVO_EXPERIMENTS
+    if (g_remove_chunk > 0) chunk = g_remove_chunk;
+#endif
+    const long nchunks = (N + chunk - 1) / chunk, nwords = (N + 31) / 32;
+    uint32_t *cnt = nullptr, *first = nullptr, *own_bits = nullptr;
+    CHECK_RC(carve_buffer(g->edit, st, [&](Layout& l) {
+        cnt = l.take<uint32_t>(nchunks); first = l.take<uint32_t>(nchunks);
+        if (!src_on_device) own_bits = l.take<uint32_t>(nwords);
+    }));
+    const uint32_t* bits = remove_bits;
+    if (!src_on_device) {
+        REVO_HIP_CHECK(hipMemcpyAsync(own_bits, remove_bits, (size_t)nwords * 4, hipMemcpyHostToDevice, st));
+        bits = own_bits;
+    }
+    std::vector<uint32_t> h_cnt(nchunks), h_first(nchunks);
+    { ProfScope ps("gallery_remove", st);
+      CHECK_RC(revo::launch_remove_count(bits, N, chunk, cnt, first, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), cnt, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(h_first.data(), first, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    // Chunk after chunk, front to back, everything ordered on the stream.  The kept rows of chunk c go to rows
+    // [base, base + cnt) with base <= row0 and base + cnt <= row0 + len: below every later chunk's rows.  Where that range
+    // ends at or before row0 the gather writes it directly (source and destination rows are disjoint); otherwise it gathers
+    // into staging memory, and a copy ordered behind it brings the run down.  No launch writes a row it also reads.
+    long base = 0;
+    {
+        ProfScope ps("gallery_remove", st);
+        for (long c = 0; c < nchunks; ++c) {
+            const long row0 = c * chunk, len = std::min(chunk, N - row0), kept = (long)h_cnt[c];
+            REVO_REQUIRE(kept <= len && base <= row0, "gallery_remove: internal: inconsistent chunk counts");
+            // rows in front of the first removed row of the whole gallery stay where they are
+            const long j0 = base == row0 ? std::min<long>((long)h_first[c], kept) : 0;
+            if (kept > j0) {
+                const bool direct = base + kept <= row0;
+                if (!direct) CHECK_RC(g->stage.grow((size_t)chunk * D * 4, st));
+                for (int which = g->keep_f32 ? 0 : 1; which < 2; ++which) {
+                    const int u4 = which == 0 ? D / 4 : D / 8;       // 16-byte units of a row (D % 64 == 0)
+                    uint4* arr = which == 0 ? (uint4*)g->gf.p : (uint4*)g->gb.p;
+                    uint4* dst = direct ? arr + base * u4 : (uint4*)g->stage.p;
+                    CHECK_RC(revo::launch_remove_gather(bits, N, row0, len, j0, arr, dst, u4, st));
+                    if (!direct)
+                        REVO_HIP_CHECK(hipMemcpyAsync(arr + (base + j0) * u4, dst + j0 * u4, (size_t)(kept - j0) * u4 * 16,
+                                                      hipMemcpyDeviceToDevice, st));
+                }
+            }
+            base += kept;
+        }
+        // an emptied gallery starts its certificate maxima over, as revo_gallery_clear does; otherwise they stay: maxima over
+        // more rows are upper bounds still
+        if (base == 0) REVO_HIP_CHECK(hipMemsetAsync(g->gstat.p, 0, 8, st));
+    }
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    if (base < N) g->csr_rows = -1;
+    g->size = base;
+    *n_removed = N - base;
+    return 0;
+    API_END
+}
+
+extern "C" int32_t revo_gallery_update(revo_gallery* g, const int64_t* row_idx, const float* vecs, int64_t n, int32_t normalize,
+                                       int32_t src_on_device, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_update: null handle");
+    REVO_REQUIRE(n >= 0, "gallery_update: negative count");
+    if (n == 0) return 0;
+    REVO_REQUIRE(row_idx, "gallery_update: null row_idx");
+    REVO_REQUIRE(vecs, "gallery_update: null vecs");
+    {
+        std::vector<int64_t> sorted(row_idx, row_idx + n);
+        for (int64_t r : sorted)
+            REVO_REQUIRE(r >= 0 && r < g->size, "gallery_update: row_idx " + std::to_string(r) + " outside the gallery of " +
+                                                    std::to_string(g->size) + " rows");
+        std::sort(sorted.begin(), sorted.end());
+        for (int64_t i = 1; i < n; ++i)
+            REVO_REQUIRE(sorted[i] != sorted[i - 1], "gallery_update: row_idx " + std::to_string(sorted[i]) + " is given twice");
+    }
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    g->rows_changed();
+    const int D = g->D;
+    CHECK_RC(g->edit.grow((size_t)n * 8, st));
+    long long* map = (long long*)g->edit.p;
+    REVO_HIP_CHECK(hipMemcpyAsync(map, row_idx, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));             // the caller may free its host array on return
+    const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
+    for (int64_t done = 0; done < n; done += chunk_rows) {
+        const int64_t m = std::min(chunk_rows, n - done);
+        const float* src = vecs + done * D;
+        if (!src_on_device) {
+            const size_t need = (size_t)m * D * 4;
+            CHECK_RC(g->stage.grow(need, st));
+            REVO_HIP_CHECK(hipMemcpyAsync(g->stage.p, src, need, hipMemcpyHostToDevice, st));
+            src = g->stage.p;
+        }
+        ProfScope ps("gallery_update", st);
+        // the append's kernel with a destination-row map: the same bits an append of the vector would have written
+        CHECK_RC(revo::launch_l2norm_rows(src, D, g->keep_f32 ? g->gf.p : nullptr, D, g->gb.p, D, m, D, st, normalize ? 1 : 0,
+                                          nullptr, g->gstat.p, nullptr, 0, nullptr, 0, map + done));
+        if (!src_on_device) REVO_HIP_CHECK(hipStreamSynchronize(st));   // staging buffer is reused
+    }
     return 0;
     API_END
 }

@@ -227,6 +227,55 @@ class Gallery:
                                                      int(v.is_cuda), _lib.current_stream()), "revo_gallery_append")
         return start
 
+    def remove(self, rows):
+        """Take rows out in place (include/revo.h, EDIT): ``rows`` is a ``bool [len]`` mask, a packed int32 bitmap
+        ``[ceil(len / 32)]`` (bit ``r & 31`` of word ``r >> 5``) or an int64 index tensor, on the device or the host.  The
+        remaining rows keep their order and close up: every search afterwards returns exactly what it returns on a gallery
+        built from the remaining rows alone.  Returns the number of rows removed.  Synchronous."""
+        n = len(self)
+        rows = torch.as_tensor(rows)
+        if rows.is_cuda:
+            _require_cuda(rows, "rows", self.device)
+        if rows.dtype == torch.int64:
+            idx = rows.reshape(-1)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+                raise IndexError(f"remove: row index outside the gallery of {n} rows")
+            rows = torch.zeros(n, dtype=torch.bool, device=idx.device)
+            rows[idx] = True
+        words = (n + 31) // 32
+        if rows.dtype == torch.bool:
+            if rows.dim() != 1 or rows.shape[0] != n:
+                raise ValueError(f"rows must be bool [{n}] (one entry per gallery row), got {tuple(rows.shape)}")
+            if rows.is_cuda:
+                bits = self.allow_bits(rows)
+            else:
+                from .filters import pack_bits
+                bits = torch.from_numpy(pack_bits(rows.numpy()))
+        elif rows.dtype == torch.int32 and rows.dim() == 1 and rows.shape[0] == words:
+            bits = rows.contiguous()
+        else:
+            raise ValueError(f"rows must be bool [{n}], a packed int32 bitmap [{words}] or int64 indices, got {rows.dtype} "
+                             f"{tuple(rows.shape)}")
+        removed = C.c_int64()
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self._lib.revo_gallery_remove(self._h, _lib.ptr(bits), n, int(bits.is_cuda), C.byref(removed),
+                                                     _lib.current_stream()), "revo_gallery_remove")
+        return int(removed.value)
+
+    def update(self, rows, vectors, normalize=True):
+        """Overwrite row ``rows[i]`` with ``vectors[i]`` (fp32 ``[n, dim]``, device or host) exactly as :meth:`add` would
+        have written it (include/revo.h, EDIT).  ``rows``: int64 indices (tensor or list), each inside the gallery and given
+        once.  A filter or group ids stay valid: no row moves."""
+        idx = torch.as_tensor(rows, dtype=torch.int64).reshape(-1).cpu().contiguous()
+        v = vectors.detach().to(torch.float32).contiguous()
+        if v.dim() != 2 or v.shape[1] != self.dim or v.shape[0] != idx.shape[0]:
+            raise ValueError(f"vectors must be [{idx.shape[0]}, {self.dim}] (one per row index), got {tuple(v.shape)}")
+        if v.is_cuda:
+            _require_cuda(v, "vectors", self.device)
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self._lib.revo_gallery_update(self._h, _lib.ptr(idx), _lib.ptr(v), idx.shape[0], int(bool(normalize)),
+                                                     int(v.is_cuda), _lib.current_stream()), "revo_gallery_update")
+
     def read(self, start=0, n=None):
         n = len(self) - start if n is None else n
         out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)

@@ -7,6 +7,9 @@ SURVEY.md §8(f) row 2).  A database directory here is append-only:
 
     manifest.jsonl          line 1: {"format": 2, "collection", "dim"}; then one line per DELTA SHARD, in order:
                             {"shard": i, "file", "rows", "ids": [...], "payloads": [...], "files_done": [...]};
+                            one line per later change of flushed points:
+                            {"op": "delete", "ids": [...]}
+                            {"op": "update", "file": <new vectors or null>, "rows": n, "ids": [...], "payloads": [...]};
                             a last line {"complete": true, "rows": N} once a build has finished
     vectors.00000.f32.npy   the shard's normalised fp32 rows (the gallery's master copy)
     .lock                   present while a process has the database open
@@ -112,8 +115,10 @@ def recover(db_path, building_suffix=".building"):
 
 
 def read_manifest(man):
-    """Parse a manifest.  Returns (header, shard records in order, complete, bytes of the file that are whole lines).
-    A torn last line -- the process died while appending -- ends the parse: everything before it stands."""
+    """Parse a manifest.  Returns (header, records in order, complete, bytes of the file that are whole lines).  The
+    records are the shard lines and, between them, the ``"op"`` lines of deletes and updates (:func:`replay_manifest` turns
+    them into the points they leave).  A torn last line -- the process died while appending -- ends the parse: everything
+    before it stands."""
     header, shards, complete, good = None, [], False, 0
     with open(man, "rb") as f:
         for raw in f:
@@ -136,6 +141,41 @@ def read_manifest(man):
     if header is None:
         raise ValueError(f"{man}: empty manifest")
     return header, shards, complete, good
+
+
+def replay_manifest(records):
+    """The points a manifest's records (the second value of :func:`read_manifest`) leave, in the order of the store's rows:
+    a list of ``(id, payload, (vectors file, row in that file))``.  Pure host code: no device, no arrays.
+
+    A shard line appends its points.  ``{"op": "delete", "ids"}`` takes out every point with one of the ids (unknown ids
+    are ignored); the rest keep their order.  ``{"op": "update", "file", "rows", "ids", "payloads"}`` gives the point of
+    ``ids[i]`` (the last one, should the id occur twice) the payload ``payloads[i]`` and, unless ``file`` is null, the
+    vector in row i of ``file``; the point keeps its place.  An id deleted and upserted again is a new point at the end."""
+    points = []
+    last = None                      # id -> its last place in points, built when an update needs it, dropped when places move
+    for rec in records:
+        op = rec.get("op")
+        if op is None:
+            if rec["rows"] != len(rec["ids"]) or rec["rows"] != len(rec["payloads"]):
+                raise ValueError(f"manifest: shard line {rec.get('shard')} names {rec['rows']} rows but lists "
+                                 f"{len(rec['ids'])} ids and {len(rec['payloads'])} payloads")
+            for i, (pid, pl) in enumerate(zip(rec["ids"], rec["payloads"])):
+                if last is not None:
+                    last[pid] = len(points)
+                points.append((pid, pl, (rec["file"], i)))
+        elif op == "delete":
+            gone = set(rec["ids"])
+            points = [p for p in points if p[0] not in gone]
+            last = None
+        elif op == "update":
+            if last is None:
+                last = {p[0]: r for r, p in enumerate(points)}
+            for i, (pid, pl) in enumerate(zip(rec["ids"], rec["payloads"])):
+                r = last[pid]        # KeyError: the manifest updates a point it never held
+                points[r] = (pid, pl, (rec["file"], i) if rec["file"] is not None else points[r][2])
+        else:
+            raise ValueError(f"manifest: unknown op {op!r} (written by a newer version?)")
+    return points
 
 
 @dataclass
@@ -259,11 +299,22 @@ class GalleryStore:
         old.close()
         self.gallery = new
 
-    def upsert(self, vectors, ids, payloads, files=None):
+    def upsert(self, vectors, ids, payloads, files=None, replace_existing=False):
         """vectors: [n, dim] fp32 tensor, host or DEVICE (an ingest appends its embeddings where they are: they never
-        visit the host); rows are normalised at insert.  ``files``: source files these rows complete (resume bookkeeping)."""
+        visit the host); rows are normalised at insert.  ``files``: source files these rows complete (resume bookkeeping).
+        ``replace_existing=True`` is the database's own upsert: a point whose id is already in the store gets the new vector
+        and payload in place, the others are appended (of an id given twice in one call the last entry counts).  The
+        default appends every row, whatever its id."""
         vectors = torch.as_tensor(vectors, dtype=torch.float32)
         assert vectors.shape[0] == len(ids) == len(payloads)
+        if replace_existing and vectors.shape[0]:
+            last = {pid: i for i, pid in enumerate(ids)}
+            have = self._id_row_map()
+            old = [i for i in sorted(last.values()) if ids[i] in have]
+            new = [i for i in sorted(last.values()) if ids[i] not in have]
+            if old:
+                self._update([ids[i] for i in old], vectors[old], [payloads[i] for i in old])
+            vectors, ids, payloads = vectors[new], [ids[i] for i in new], [payloads[i] for i in new]
         if vectors.shape[0]:
             self._grow(len(self) + vectors.shape[0])
             self.gallery.add(vectors, normalize=True)
@@ -272,6 +323,106 @@ class GalleryStore:
         if files:
             self._files_pending.extend(files)
         self.complete = False
+
+    # -- changes of stored points (include/revo.h, EDIT): on the device in place, on disk one manifest line each ------
+    def _id_row_map(self):
+        if self._id_rows is None or self._id_rows[0] != len(self):
+            self._id_rows = (len(self), {pid: r for r, pid in enumerate(self.ids)})
+        return self._id_rows[1]
+
+    def _points_changed(self):
+        """ids / payloads changed under the caches built from them"""
+        self._pindex = _filters.PayloadIndex()
+        self._filter_cache = self._group_cache = self._id_rows = None
+        self.complete = False
+
+    def _log_op(self, line):
+        """one fsynced manifest line: a crash before it leaves the database as it was"""
+        with open(os.path.join(self.path, MANIFEST), "a") as f:
+            f.write(json.dumps(line) + "\n")
+            f.flush()
+            os.fsync(f.fileno())
+        self._shards += 1
+        self._flushed = len(self)
+
+    def delete(self, points):
+        """Remove points: ``points`` is a list of ids (unknown ones are ignored) or a filter (``filters.Filter`` or its dict
+        form).  Every row that carries the id of a selected point goes (a store filled without ``replace_existing`` may
+        hold an id twice).  The rows move on the device (``Gallery.remove``); ``ids`` and ``payloads`` close up the same
+        way.  Returns the number of points removed.  A store with a directory first flushes, then appends a ``delete``
+        line to the manifest: the shards are not rewritten -- ``save(path=<other directory>)`` writes a compact copy.
+        A ``ShardedSearch`` over the gallery is to be refreshed afterwards."""
+        if isinstance(points, (_filters.Filter, dict)):
+            gone = {self.ids[r] for r in np.flatnonzero(self.filter_mask(points)).tolist()}
+        else:
+            gone = set(points)
+        mask = np.fromiter((pid in gone for pid in self.ids), dtype=bool, count=len(self.ids))
+        n = int(mask.sum())
+        if n == 0:
+            return 0
+        if self.path:
+            self.flush()
+        removed = self.gallery.remove(torch.from_numpy(mask))
+        assert removed == n, (removed, n)
+        dead = list(dict.fromkeys(self.ids[r] for r in np.flatnonzero(mask).tolist()))
+        self.ids = [pid for pid, m in zip(self.ids, mask.tolist()) if not m]
+        self.payloads = [pl for pl, m in zip(self.payloads, mask.tolist()) if not m]
+        self._points_changed()
+        if self.path:
+            self._log_op({"op": "delete", "ids": dead})
+        return n
+
+    def _update(self, ids, vectors, payloads):
+        """the points ``ids`` (each once, all present) get ``vectors`` (None: kept) and ``payloads`` (None: kept)"""
+        have = self._id_row_map()
+        missing = [pid for pid in ids if pid not in have]
+        if missing:
+            raise KeyError(f"no point with id {missing[0]!r} in the store")
+        if len(set(ids)) != len(ids):
+            raise ValueError("an id is given twice")
+        if not ids:
+            return
+        rows = [have[pid] for pid in ids]
+        if self.path:
+            self.flush()
+        if vectors is not None:
+            vectors = torch.as_tensor(vectors, dtype=torch.float32)
+            self.gallery.update(rows, vectors, normalize=True)
+        if payloads is not None:
+            for r, pl in zip(rows, payloads):
+                self.payloads[r] = pl
+        id_rows = self._id_rows
+        self._points_changed()
+        self._id_rows = id_rows                              # no row moved
+        if self.path:
+            name = None
+            if vectors is not None:
+                name = f"vectors.{self._shards:05d}.f32.npy"
+                vec = torch.cat([self.gallery.read(r, 1) for r in rows]).cpu().numpy()      # the rows as stored: normalised
+                tmp = os.path.join(self.path, name + ".tmp.npy")
+                with open(tmp, "wb") as f:
+                    np.save(f, vec)
+                    f.flush()
+                    os.fsync(f.fileno())
+                os.replace(tmp, os.path.join(self.path, name))
+                _fsync_dir(self.path)
+            self._log_op({"op": "update", "file": name, "rows": len(rows), "ids": list(ids),
+                          "payloads": [self.payloads[r] for r in rows]})
+
+    def update_vectors(self, ids, vectors):
+        """New vectors (normalised at insert, like an upsert's) for the points ``ids``; payloads and places stay.  An
+        unknown id raises ``KeyError``.  With a directory: flush, then one ``update`` manifest line naming a new vectors file."""
+        vectors = torch.as_tensor(vectors, dtype=torch.float32)
+        assert vectors.shape[0] == len(ids)
+        self._update(list(ids), vectors, None)
+
+    def set_payload(self, ids, payload):
+        """Replace the payload of the points ``ids`` by ``payload`` (one dict for all of them, or a list with one per id).
+        Host only: no vector is touched.  An unknown id raises ``KeyError``."""
+        ids = list(ids)
+        payloads = [payload] * len(ids) if isinstance(payload, dict) else list(payload)
+        assert len(payloads) == len(ids)
+        self._update(ids, None, payloads)
 
     def filter_mask(self, query_filter):
         """bool numpy [len(self)]: the points a Qdrant-style filter (filters.Filter or its dict form) selects."""
@@ -510,7 +661,9 @@ class GalleryStore:
         return new
 
     def save(self, path=None):
-        """Flush what is new and mark the collection complete."""
+        """Flush what is new and mark the collection complete.  Deletes and updates only add manifest lines: the vectors of
+        removed and replaced points stay in the old shard files.  ``save(path=<other directory>)`` writes everything anew,
+        the current points only -- that is the way to compact a database."""
         path = path or self.path
         if not path:
             raise ValueError("this store has no directory (created without one, or loaded from the one-file format of "
@@ -551,17 +704,34 @@ class GalleryStore:
             # a torn last line (the process died while appending): cut it off before anything is appended behind it
             with open(man, "r+b") as f:
                 f.truncate(good_bytes)
-        rows = sum(s["rows"] for s in shards)
+        points = replay_manifest(shards)                   # what the shard, delete and update lines leave, in row order
+        rows = len(points)
         st = cls(header["dim"], device=device, capacity=max(rows, capacity, 1), collection=header["collection"], path=path,
                  _fresh=False, build_info=header.get("build"))
+        file_rows = {s["file"]: s["rows"] for s in shards if s.get("file") is not None}
+        opened = {}
+
+        def vectors_of(name):
+            if name not in opened:
+                vec = np.load(os.path.join(path, name), mmap_mode="r")
+                if vec.shape != (file_rows[name], st.dim):
+                    raise ValueError(f"{path}/{name}: {vec.shape} does not match its manifest line")
+                opened[name] = vec
+            return opened[name]
+
+        step = max(1, (128 << 20) // (st.dim * 4))          # the surviving rows in order, 128 MB at a time
+        for s0 in range(0, rows, step):
+            src = [p[2] for p in points[s0:s0 + step]]
+            vec = np.empty((len(src), st.dim), np.float32)
+            names = np.array([f for f, _ in src], dtype=object)
+            at = np.array([r for _, r in src], dtype=np.int64)
+            for name in dict.fromkeys(f for f, _ in src):
+                sel = np.flatnonzero(names == name)
+                vec[sel] = vectors_of(name)[at[sel]]
+            st.gallery.add(torch.from_numpy(vec), normalize=False)          # stored rows are already normalised
+        st.ids = [p[0] for p in points]
+        st.payloads = [p[1] for p in points]
         for s in shards:
-            if s["rows"]:
-                vec = np.load(os.path.join(path, s["file"]))
-                if vec.shape != (s["rows"], st.dim):
-                    raise ValueError(f"{path}/{s['file']}: {vec.shape} does not match its manifest line")
-                st.gallery.add(torch.from_numpy(vec), normalize=False)      # stored rows are already normalised
-                st.ids.extend(s["ids"])
-                st.payloads.extend(s["payloads"])
             st.files_done.update(s.get("files_done", []))
         st._flushed, st._shards, st.complete = rows, len(shards), complete
         return st
