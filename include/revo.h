@@ -160,7 +160,15 @@ int32_t revo_gallery_update(revo_gallery* g, const int64_t* row_idx, const float
  * from the one fma chain), ties and threshold cut as revo_search_topk.  A query's groups come from the certified top-50
  * of revo_search_topk when that list decides them (it holds every allowed row at or above the threshold, or >= limit
  * groups of which each of the first `limit` holds >= group_size of its rows: any row outside it ranks below all of
- * them); otherwise from two fp32 passes over the gallery (best groups, then the chosen groups' best rows). */
+ * them); otherwise from two fp32 passes over the gallery (best groups, then the chosen groups' best rows).
+ * LIMIT (galleries of more than 2^24 rows): the scan packs a row as a 24-bit index relative to its slice of the gallery, so
+ * a slice holds at most 2^24 rows.  A query tile (256 queries) gets 32, 16, 8, 4, 2 or 1 slices as the call brings 8, 16,
+ * 32, 64, 128 or 256 query tiles and more; a call is therefore refused (status -2, "a gallery slice holds at most 2^24 rows",
+ * nothing written) from 65 281 queries on when the scan covers more than 2^24 rows (the gallery less a pre-pass of at most
+ * 32 768 rows), from 32 513 when more than 2^25 and from 16 129 when more than 2^26 (tests/test_scan_plan.py walks the plan
+ * at 2^24 - 1 .. 2^27 rows); larger galleries are refused at fewer queries still.  Whatever the message says about splits,
+ * the caller's remedy is to search fewer queries per call: up to 16 128 at a time are served on every gallery of up to 2^27
+ * rows. */
 int32_t revo_search_topk(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t has_threshold,
                          float threshold, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
                          void* stream);

@@ -40,3 +40,27 @@ def _assert_indices_equal_up_to_fp32_ties(i, ri, rs, gal, qr, tie=3e-7):
             true = float(row @ qv / np.linalg.norm(row))
             assert abs(true - float(rs[q, j])) <= tie, (q, j, true, rs[q, j])
     return sum(sorted(i[q].tolist()) != sorted(ri[q].tolist()) for q in bad)      # queries whose index SETS differ
+
+
+OFFSETS_PAST_2_31 = (2 ** 31 + 5, 2 ** 40 + 3)
+
+
+def _assert_offset_moves_the_indices_only(call, index_positions, offsets=OFFSETS_PAST_2_31):
+    """call(index_offset) -> the result tensors of one search.  The int64 contract of index_offset at and above 2^31: the
+    tensors at index_positions are the offset-0 row indices plus the offset (padding stays -1), in int64; every other
+    tensor (scores, counts, offsets, group ids) is byte-identical to the offset-0 result."""
+    import torch
+    base = call(0)
+    assert any(bool((base[p] >= 0).any()) for p in index_positions)
+    for off in offsets:
+        got = call(off)
+        assert len(got) == len(base)
+        for p, (a, b) in enumerate(zip(base, got)):
+            a, b = torch.as_tensor(a), torch.as_tensor(b)
+            assert a.dtype == b.dtype and a.shape == b.shape, (off, p)
+            if p in index_positions:
+                assert b.dtype == torch.int64 and torch.equal(b, torch.where(a >= 0, a + off, a)), (off, p)
+            elif a.dtype == torch.float32:
+                assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (off, p)
+            else:
+                assert torch.equal(a, b), (off, p)

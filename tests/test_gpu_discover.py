@@ -433,3 +433,15 @@ def test_search_by_context_on_a_database(tmp_path):
     assert items == [] and "No regions found" in text and "5.0" in text
     text, items = r.search_by_context("no-such-id", [("p8", "p9")])
     assert text.startswith("❌") and "no-such-id" in text and items == []
+
+
+@pytest.mark.parametrize("has_target", [True, False])
+def test_index_offset_at_and_above_2_31(has_target):
+    from _search_checks import _assert_offset_moves_the_indices_only
+    x = _planted(20_037, 1024, seed=61)
+    G = _gallery(x)
+    t, pos, neg = _split(_examples(x, 1 + 2 * 4, seed=62), 4, True)
+    for k in (10, 51):
+        _assert_offset_moves_the_indices_only(
+            lambda off: G.discover(t if has_target else None, pos, neg, k=k, index_offset=off), {1})
+    G.close()

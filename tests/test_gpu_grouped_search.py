@@ -348,3 +348,15 @@ def test_search_similar_group_by_image_source(tmp_path, dev):
     # the default call is unchanged
     _, again = r.search_similar(-1.0, 5)
     assert [it["filename"] for it in again] == names
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    N = 20_037
+    G = _random_gallery(N, seed=5)
+    g = torch.Generator(device=DEV).manual_seed(6)
+    q = torch.randn(9, G.dim, device=DEV, generator=g)
+    groups = torch.randint(0, N // 3, (N,), device=DEV, generator=g).to(torch.int32)
+    _assert_offset_moves_the_indices_only(
+        lambda off: G.search_groups(q, groups, limit=10, group_size=3, index_offset=off), {1})
+    G.close()

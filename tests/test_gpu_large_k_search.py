@@ -327,3 +327,13 @@ def test_search_similar_100_results(tmp_path):
     for j in np.flatnonzero(np.array(got) != np.array(names)):             # only neighbours within fp32 resolution swap
         jj = names.index(got[j])
         assert abs(jj - j) == 1 and abs(rs[0][jj] - rs[0][j]) <= NEAR_TIE
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    gal = _rows(20_037, 1024, seed=81)
+    G = _gallery(gal)
+    q = torch.from_numpy(_queries(gal, 5, seed=82)).to(DEV)
+    for k in (51, 1024):
+        _assert_offset_moves_the_indices_only(lambda off: G.search(q, k, index_offset=off), {1})
+    G.close()

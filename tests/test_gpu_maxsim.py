@@ -491,3 +491,16 @@ def test_search_similar_all_regions_on_a_region_database(tmp_path, dev):
     assert [(it["image"], it["score"]) for it in items] == [(w.value, w.score) for w in want]
     text, items = r.search_similar_all_regions(similarity_threshold=3.5)
     assert items == [] and "No images found" in text and "3.5" in text
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    R = 20_037
+    x = _planted(R, 1024, seed=61)
+    G = _gallery(x)
+    q = _examples(x, 4, seed=62)
+    gt = _t(_layouts(R, seed=63, names=["random"])["random"])
+    for k in (10, 51):
+        _assert_offset_moves_the_indices_only(
+            lambda off: G.search_maxsim(q, gt, k=k, index_offset=off, with_parts=True), {4})
+    G.close()

@@ -429,3 +429,14 @@ def test_search_similar_diverse_on_a_database(tmp_path):
     assert all(int(it["id"][1:]) % 2 == 1 for it in fitems)
     text, items = r.search_similar_diverse(similarity_threshold=1.5)
     assert items == [] and "No similar regions found above threshold 1.5" in text
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    x = _planted(20_037, 1024, seed=15)
+    G = _gallery(x)
+    q = _queries(x, 5, seed=16)
+    for k, C in ((10, 100), (50, 1024)):
+        _assert_offset_moves_the_indices_only(
+            lambda off: G.search_mmr(q, k=k, candidates=C, diversity=0.3, index_offset=off), {2})
+    G.close()

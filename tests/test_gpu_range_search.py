@@ -439,3 +439,13 @@ def test_rows_as_queries_recover_the_pairs():
         found = set(idx[off[i]:off[i + 1]].tolist()) - {i}
         assert {j for j in partners[i] if far(j)} == {j for j in found if far(j)}, i
     G.close()
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    N, D = 20_037, 64
+    x = _planted(N, D, seed=24, n_clusters=2000)
+    G = _gallery(x)
+    q = _queries(x, 200, seed=25)
+    _assert_offset_moves_the_indices_only(lambda off: G.search_range(q, 0.6, index_offset=off), {1})
+    G.close()

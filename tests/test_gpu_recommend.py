@@ -464,3 +464,13 @@ def test_search_by_examples_on_a_database(tmp_path):
     assert items == [] and "No regions found" in text and "1.5" in text
     text, items = r.search_by_examples(["no-such-id"])
     assert text.startswith("❌") and "no-such-id" in text and items == []
+
+
+def test_index_offset_at_and_above_2_31():
+    from _search_checks import _assert_offset_moves_the_indices_only
+    x = _planted(20_037, 1024, seed=71)
+    G = _gallery(x)
+    ex = _examples(x, 6, seed=72)
+    for k in (10, 51):
+        _assert_offset_moves_the_indices_only(lambda off: G.recommend(ex[:4], ex[4:], k=k, index_offset=off), {1})
+    G.close()

@@ -981,3 +981,74 @@ def test_shard_admission_estimate_on_clustered_and_on_light_tailed_galleries(dev
         for Gp in shards:
             Gp.close()
         G.close()
+
+
+def test_index_offset_at_and_above_2_31(dev):
+    from _search_checks import _assert_offset_moves_the_indices_only
+    N, D, Q = 20_037, 1024, 70
+    g = torch.Generator(device=dev).manual_seed(231)
+    G = engine.Gallery(D, N, device=0)
+    G.add(torch.randn(N, D, generator=g, device=dev))
+    q = torch.randn(Q, D, generator=g, device=dev)
+    for k in (10, 50):
+        _assert_offset_moves_the_indices_only(lambda off: G.search(q, k, index_offset=off), {1})
+        _assert_offset_moves_the_indices_only(lambda off: G.search(q, k, 0.05, index_offset=off), {1})    # with padding
+    G.close()
+
+
+def test_index_offset_at_and_above_2_31_two_phase(dev):
+    """The two-phase calls of a row-sharded search take the shard's base row as index_offset (sharded.py finish / exact):
+    revo_search_finish into plain arrays and into the packed block that revo_topk_merge_packed reads, and the compact
+    rows of revo_search_exact, plain and packed.  Indices move by the offset in int64; scores, counts, certificate
+    bounds and the merge's uncertified list are byte-identical."""
+    from _search_checks import _assert_offset_moves_the_indices_only
+    N, D, Q, top_m = 20_037, 1024, 70, 8
+    g = torch.Generator(device=dev).manual_seed(232)
+    G = engine.Gallery(D, N, device=0)
+    G.add(torch.randn(N, D, generator=g, device=dev))
+    q = torch.randn(Q, D, generator=g, device=dev)
+    q[:8] = G.read(1000, 8) + 0.05 * torch.randn(8, D, generator=g, device=dev)
+    q_idx = torch.tensor([0, 3, 17, Q - 1], dtype=torch.int32, device=dev)
+    for k in (10, 50):
+        need = G.search(q, k)[0][q_idx.long(), k - 1].contiguous()        # what a row must reach to change the result
+
+        def finish_plain(off, bounds=True):
+            allb = G.search_candidates(q, k, top_m)[None]                 # [1, Q, top_m]: one shard
+            return G.search_finish(Q, k, allb if bounds else None, None, off)
+
+        def finish_packed(off):
+            allb = G.search_candidates(q, k, top_m)[None]
+            packed = torch.zeros((engine.packed_bytes(Q, k),), dtype=torch.uint8, device=dev)
+            s, i, c = G.search_finish(Q, k, allb, None, off, out_packed=packed)
+            cert = packed[Q * k * 12: Q * k * 12 + Q * 4].view(torch.float32)
+            ms, mi, mc, unc = engine.merge_topk_packed(packed, 1, Q, k, certify=True)
+            n = int(unc[0])
+            order = torch.argsort(unc[1][:n])
+            return s.clone(), i.clone(), c, cert.clone(), ms, mi, mc, unc[0], unc[1][:n][order], unc[2][:n][order]
+
+        def exact_plain(off):
+            G.search_candidates(q, k, top_m)
+            return G.search_exact(q_idx, need, k, off)
+
+        def exact_packed(off):
+            G.search_candidates(q, k, top_m)
+            n = q_idx.shape[0]
+            packed = torch.zeros((engine.packed_bytes(n, k),), dtype=torch.uint8, device=dev)
+            s, i, c = G.search_exact(q_idx, need, k, off, out_packed=packed)
+            ms, mi, mc = engine.merge_topk_packed(packed, 1, n, k)
+            return s.clone(), i.clone(), c, packed[n * k * 12: n * k * 12 + n * 4].view(torch.float32).clone(), ms, mi, mc
+
+        _assert_offset_moves_the_indices_only(finish_plain, {1})
+        _assert_offset_moves_the_indices_only(lambda off: finish_plain(off, bounds=False), {1})
+        _assert_offset_moves_the_indices_only(finish_packed, {1, 5})
+        _assert_offset_moves_the_indices_only(exact_plain, {1})
+        _assert_offset_moves_the_indices_only(exact_packed, {1, 5})
+        # and the offset-0 results are the search's own
+        ref = G.search(q, k)
+        out = finish_packed(0)
+        sure = torch.ones(Q, dtype=torch.bool, device=dev)
+        sure[out[8].long()] = False                                       # (what the merge could not certify goes to the second round)
+        assert torch.equal(out[5][sure], ref[1][sure]) and torch.equal(out[4][sure], ref[0][sure]) and torch.equal(out[6], ref[2])
+        ex = exact_plain(0)
+        assert torch.equal(ex[1], ref[1][q_idx.long()]) and torch.equal(ex[0], ref[0][q_idx.long()])
+    G.close()

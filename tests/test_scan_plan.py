@@ -63,3 +63,45 @@ def test_the_cases_the_design_quotes():
     assert phases == [(0, 0, 8, 32)]
     blocks, splits, phases = _plan(64, tiles_rows)              # one query tile: a small launch, one round of workgroups
     assert len(phases) == 1 and phases[0][2] == 1 and 128 <= phases[0][3] <= 256
+
+
+# ---- galleries past 2^24 rows: the scan's 24-bit relative row index (topk256.hip key packing; launch_topk_scan256 refuses a
+# slice of more than 2^24 rows) --------------------------------------------------------------------------------------------
+_SLICE_LIMIT = 1 << 24
+# The first query count at which a phase's slice passes 2^24 rows (None: never, the whole gallery fits one slice).  Pinned
+# phases give each query tile 32 / a slices, a = 1, 2 .. 32 query tiles per XCD: one slice from 256 query tiles on (65 281
+# queries), two from 128 (32 513), four from 64 (16 129) -- so a gallery of more than 2^26 rows is refused from 16 129
+# queries on, one of more than 2^25 from 32 513, any of more than 2^24 from 65 281.
+_FIRST_REFUSED = {2 ** 24 - 1: None, 2 ** 24: None, 2 ** 24 + 300: 65_281, 2 ** 25 + 1: 32_513, 10 ** 8: 16_129, 2 ** 27: 16_129}
+
+
+def _largest_slice(Q, rows):
+    """Rows of the longest slice of any phase.  revo_debug_scan_plan reports only the slice COUNT of a phase; the split into
+    slices is made in launch_topk_scan256 (per = ceil(tiles / ns), slice i = tiles [i per, (i + 1) per) clipped to the
+    gallery), and the lines below MIRROR that formula: they say what the launch does with the count (contiguous slices, the
+    last ends at the last tile, trailing slices may be empty) and check the count's sanity, not the launch's own arithmetic."""
+    _, _, phases = _plan(Q, rows)
+    tiles = (rows + 255) // 256
+    worst = 0
+    for _, _, _, ns in phases:
+        per = (tiles + ns - 1) // ns                                  # launch_topk_scan256: slice i = tiles [i per, (i + 1) per)
+        ends = [min((i + 1) * per, tiles) for i in range(ns)]
+        starts = [min(i * per, tiles) for i in range(ns)]
+        assert 1 <= ns <= tiles and starts[0] == 0 and ends[-1] == tiles and starts[1:] == ends[:-1], (Q, rows, ns)
+        worst = max(worst, per * 256)
+    return worst
+
+
+@pytest.mark.parametrize("rows", sorted(_FIRST_REFUSED))
+def test_slices_of_galleries_past_2_24_rows(rows):
+    first = _FIRST_REFUSED[rows]
+    # every query-tile count up to 520 (133 120 queries), at both ends of the tile
+    counts = sorted({1, 2, 255} | {256 * t + d for t in range(1, 521) for d in (0, 1)})
+    over = [Q for Q in counts if _largest_slice(Q, rows) > _SLICE_LIMIT]
+    assert (over[0] if over else None) == first, (rows, over[:3])
+    for Q in counts:
+        if Q <= 16_384 and (first is None or Q < first):
+            assert _largest_slice(Q, rows) <= _SLICE_LIMIT, (Q, rows)
+    if first is not None:
+        assert _largest_slice(first - 1, rows) <= _SLICE_LIMIT
+        assert all(Q in over for Q in counts if first <= Q <= 65_536), "refused from there on, up to 65 536 queries"
