@@ -113,7 +113,7 @@ int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst,
  * exactly as an append would have written it: the same normalisation arithmetic, fp32 master, bf16 row, and the row's share
  * merged into the certificate's maxima (which therefore also stay upper bounds).  An index outside [0, size) or a repeated
  * index gives status -2 before the device is touched; n = 0 does nothing.  Enqueued on `stream` like an append.
- * Both invalidate a held pairs and range result (their _read gives -2, as after an append) and the two-phase candidate
+ * Both invalidate a held pairs, clusters and range result (their _read gives -2, as after an append) and the two-phase candidate
  * state.  A remove that removes at least one row also drops the multi-vector search's index, and a filter or group ids set
  * for the old size fail the next search with the message an append gives (set them again); an update leaves filter, group
  * ids and index valid (none depends on a row's values).  A null handle or pointer or a negative count: status -2, nothing
@@ -206,6 +206,34 @@ int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t n_
 int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream);
 int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,
                                 int32_t dst_on_device);
+/* ---- duplicate clusters: the groups of near-duplicates, not the pairs (no reference counterpart)
+ * CLUSTERS.  The graph: its vertices are the rows that the handle's filter allows (revo_search_set_filter, with its
+ * lifecycle: a filter set for another gallery size gives status -2); {i, j}, i != j, is an edge exactly when the PAIRS score
+ * of the two fp32 master rows -- the one fma chain, symmetric bit for bit -- is >= `threshold`.  Wherever revo_gallery_pairs
+ * is defined the edge set is its result set.  labels ([size] int64): labels[r] = the lowest row index of r's connected
+ * component; an allowed row with no edge is its own label; a row the filter excludes has -1.  A cluster is a component of
+ * at least two rows; clusters are ordered by their lowest row, ascending, and members ascend within a cluster: offsets
+ * ([n_clusters + 1] int64, CSR, offsets[0] = 0, offsets[n_clusters] = n_members), members ([n_members] int64).  Two calls
+ * give identical bytes: neither the number of join passes nor the order in which the device merges affects the result.
+ * How: the PAIRS join with a lock-free union-find in its epilogue.  A pair whose bf16 score is above the threshold by more
+ * than the certificate's rounding bound is certainly an edge and is merged in place, never stored; only the pairs inside
+ * the bound of the threshold are stored and re-scored in fp32.  So a cluster's size sets no limit (24 000 identical rows
+ * are one cluster, where revo_gallery_pairs refuses their 2.9e8 pairs); more than 2^28 pairs INSIDE the bound give status
+ * -2, the count in revo_last_error().  Labels, sizes, the sort of the members and the offsets are computed on the device.
+ * revo_gallery_clusters computes the result into the handle and writes the two counts to the host *n_clusters and
+ * *n_members.  SYNCHRONOUS on `stream`, like revo_gallery_pairs.  Needs the fp32 master rows (keep_f32 = 0: status -2) and
+ * row indices below 2^31; a NaN threshold, a null handle or a null count pointer give status -2 before the device is
+ * touched.  An empty gallery, or a filter that allows no row: zero clusters, labels none or all -1.  Every loop of the
+ * union-find has a trip limit; one that is hit gives status -4 ("clusters: union-find did not converge").
+ * revo_search_stats after it: slot 3 = pairs re-scored in fp32 (the ambiguous ones only), slot 7 = join passes run (1, or 2
+ * when the candidate workspace had to grow), every other slot 0.
+ * revo_gallery_clusters_read copies labels, offsets and members, host or device memory (dst_on_device); each of the three
+ * pointers may be NULL independently.  The result stays valid until the next revo_gallery_clusters call or a change of the
+ * gallery's rows (append, clear, remove, update): after one, or with no result, it gives status -2.  A pairs result and a
+ * range result stay valid across revo_gallery_clusters, and its result across revo_gallery_pairs and revo_search_range. */
+int32_t revo_gallery_clusters(revo_gallery* g, float threshold, int64_t* n_clusters, int64_t* n_members, void* stream);
+int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, int64_t* offsets, int64_t* members,
+                                   int32_t dst_on_device);
 /* ---- range search: every row above a threshold, per query (the reference's score_threshold without its limit,
  * core_system.py:659-664)
  * RANGE.  For each query q the result is exactly the rows the handle's filter allows (revo_search_set_filter, with its
@@ -448,7 +476,7 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * (revo_search_groups): queries its top-50 did not decide (answered by the fp32 passes), revo_search_topk_large: queries
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
- * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_search_range see RANGE,
+ * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_gallery_clusters see CLUSTERS, after revo_search_range see RANGE,
  * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard

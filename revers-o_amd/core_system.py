@@ -1089,14 +1089,20 @@ class SimpleReverso:
             return "❌ No database loaded. Please create or load a database first.", []
         with self._lock:
             db = self.vector_db
-            out = []
-            for grp in db.duplicate_row_groups(float(similarity_threshold), query_filter=query_filter):
-                members = []
-                for r in grp:
-                    payload = db.payloads[r]
-                    members.append({"filename": payload.get("filename", "Unknown"), "image_source": payload.get("image_source", ""),
-                                    "bbox": payload.get("bbox"), "id": db.ids[r]})
-                out.append(members)
+            rows = db.duplicate_row_groups(float(similarity_threshold), query_filter=query_filter)
+            return self._duplicates_report(db, rows, similarity_threshold)
+
+    @staticmethod
+    def _duplicates_report(db, row_groups, similarity_threshold):
+        """``(text, groups)`` of :meth:`find_duplicates` for groups given as lists of rows (the caller holds the lock)."""
+        out = []
+        for grp in row_groups:
+            members = []
+            for r in grp:
+                payload = db.payloads[r]
+                members.append({"filename": payload.get("filename", "Unknown"), "image_source": payload.get("image_source", ""),
+                                "bbox": payload.get("bbox"), "id": db.ids[r]})
+            out.append(members)
         if not out:
             return f"No near-duplicates found at similarity threshold {similarity_threshold}", []
         text = f"🎯 Found {len(out)} groups of near-duplicates:\n\n"
@@ -1106,6 +1112,20 @@ class SimpleReverso:
                 text += f"   {m['filename']}  (Source: {m['image_source']})\n"
             text += "\n"
         return text, out
+
+    def find_duplicate_clusters(self, similarity_threshold=0.95, query_filter=None, largest_first=True):
+        """:meth:`find_duplicates` by the device route (``GalleryStore.duplicate_row_clusters``): the same groups in the same
+        ``(text, groups)`` format, found without listing the pairs, so a group of tens of thousands of regions (the frames
+        of a static shot) is returned where :meth:`find_duplicates` is refused.  ``largest_first`` orders the groups by
+        (size descending, first region ascending) instead of by their first region."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        with self._lock:
+            db = self.vector_db
+            rows = db.duplicate_row_clusters(float(similarity_threshold), query_filter=query_filter)
+            if largest_first:
+                rows = st.largest_first(rows)
+            return self._duplicates_report(db, rows, similarity_threshold)
 
     def delete_images(self, image_sources=None, query_filter=None):
         """Remove stored regions from the loaded database, in place: every region of the source images ``image_sources``

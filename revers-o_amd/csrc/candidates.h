@@ -22,6 +22,25 @@ __device__ __forceinline__ uint64_t tile_column_mask(long N, long n0, int cw, co
     return fm;
 }
 
+// The bf16-score bound of the pairs join (pairs.hip, clusters.hip).  A row's bf16 copy gb_i has ||gb_i|| <= ||g_i|| + ||gb_i - g_i|| <= G + Eg, so a row used
+// as the query of cert_eps has e_q <= Eg and n_qb <= G + Eg; cert_eps increases in both, so this eps bounds the error of
+// every row-against-row score.  fl(thr - eps) lowered by its rounding: every pair with fp32 score >= thr has bf16 score >= lb.
+__device__ __forceinline__ float pairs_lb(const uint32_t* gstat, float thr, int D) {
+    const float G = __uint_as_float(gstat[0]), Eg = __uint_as_float(gstat[1]);
+    const float eps = cert_eps(Eg, G + Eg, G, Eg, D);
+    return score_down(thr - eps, thr);
+}
+// The other side of that bound (clusters.hip): fl(thr + eps) raised by its rounding: every pair with bf16 score >= ub has fp32
+// score >= ub - eps >= thr.
+__device__ __forceinline__ float pairs_ub(const uint32_t* gstat, float thr, int D) {
+    const float G = __uint_as_float(gstat[0]), Eg = __uint_as_float(gstat[1]);
+    const float eps = cert_eps(Eg, G + Eg, G, Eg, D);
+    return score_up(thr + eps, thr);
+}
+
+// first tile pair of row tile ti in the row-major linearisation of the upper triangle (ti <= tj < T)
+__device__ __forceinline__ long pairs_row_start(long ti, long T) { return ti * T - ti * (ti - 1) / 2; }
+
 // Wave-aggregated append: mk = __ballot(take), not zero (the caller leaves, wave-uniformly, when no lane takes).  The lanes
 // of mk get consecutive slots of the buffer *counter counts, one atomic per wave instruction.  The counter counts past the
 // buffer's end: the caller bounds its store (take && pos < cap).  below = lanes_below(lane), computed outside unrolled loops.

@@ -441,10 +441,31 @@ struct PairsJoinArgs {
     uint64_t* keys; long cap;     // [cap] candidate keys (i << 32) | j
 };
 int launch_pairs_join(const PairsJoinArgs& a, hipStream_t st);
+// sets a.T, a.pairs and the join's grid (0: no rows); `who` names the caller in the messages (pairs.hip; clusters.hip joins by it too)
+int pairs_join_plan(PairsJoinArgs& a, const char* who, long* wgs);
 // fp32 score of candidates [0, n); those >= thr appended to out_keys ((i << b) | j) / out_scores, count in *kept
 int launch_pairs_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, float thr, int b,
                          unsigned long long* kept, uint64_t* out_keys, float* out_scores, hipStream_t st);
 int launch_pairs_emit(const uint64_t* keys, const float* vals, long n, int b, long long* pairs, float* scores, hipStream_t st);
+// ---- duplicate clusters (revo_gallery_clusters; clusters.hip): the pairs join with a union-find
+// (unionfind.h) in its epilogue -- certain edges are merged in place, only the pairs inside the rounding bound are stored
+struct ClustersJoinArgs {
+    PairsJoinArgs j;              // the pairs join's arguments (cnt / keys / cap: the AMBIGUOUS pairs)
+    uint32_t* parent;             // [N + 1] the union-find, parent[r] <= r; parent[N]: the device error word (a union-find
+                                  // loop hit its trip limit) -- one pointer: the join has no scalar register to spare
+};
+int launch_clusters_init(uint32_t* parent, uint32_t* sizes, long N, unsigned long long* ctr4, hipStream_t st);
+int launch_clusters_join(const ClustersJoinArgs& a, hipStream_t st);
+// fp32 score of the ambiguous pairs [0, n); those >= thr are united
+int launch_clusters_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, float thr, uint32_t* parent,
+                            long N, hipStream_t st);
+// labels[r] = root of r (-1: not allowed), sizes[root] = rows of its component; then the rows of components of >= 2 rows as
+// keys (label << b) | row (count: ctr4[0]; clusters: ctr4[1]; ctr4[2] = the error word)
+int launch_clusters_labels(uint32_t* parent, const uint32_t* allow, long N, int b, long long* labels, uint32_t* sizes,
+                           uint64_t* keys, unsigned long long* ctr4, hipStream_t st);
+// sorted keys -> members; rank [n] workspace; offsets [n_clusters + 1]
+int launch_clusters_emit(const uint64_t* keys, long n, long n_clusters, int b, unsigned long long* rank, long long* members,
+                         long long* offsets, hipStream_t st);
 // ---- range search (revo_search_range; range.hip): the join runs the 256 x 256 scan's work plan, with a
 // bound per query
 constexpr int RANGE_CHUNK = 1024;            // queries per candidate pass (fewer when the sort key would pass 64 bits)

@@ -17,18 +17,7 @@
 
 namespace revo {
 
-// The bf16-score bound of the join.  A row's bf16 copy gb_i has ||gb_i|| <= ||g_i|| + ||gb_i - g_i|| <= G + Eg, so a row used
-// as the query of cert_eps has e_q <= Eg and n_qb <= G + Eg; cert_eps increases in both, so this eps bounds the error of
-// every row-against-row score.  fl(thr - eps) lowered by its rounding: every pair with fp32 score >= thr has bf16 score >= lb.
-__device__ __forceinline__ float pairs_lb(const uint32_t* gstat, float thr, int D) {
-    const float G = __uint_as_float(gstat[0]), Eg = __uint_as_float(gstat[1]);
-    const float eps = cert_eps(Eg, G + Eg, G, Eg, D);
-    return score_down(thr - eps, thr);
-}
-
-// first tile pair of row tile ti in the row-major linearisation of the upper triangle (ti <= tj < T)
-__device__ __forceinline__ long pairs_row_start(long ti, long T) { return ti * T - ti * (ti - 1) / 2; }
-
+// (the join's bf16-score bound pairs_lb and the triangle's linearisation pairs_row_start: candidates.h, shared with clusters.hip)
 // -------------------------------------------------------------------------- join ----
 // Workgroup w takes the contiguous range [p0, p1) of the linearised tile pairs (equal counts: every pair is one full tile
 // of MFMA work); consecutive pairs share the A tile.  Rows past N read as zeros and are never appended.
@@ -142,11 +131,12 @@ __global__ __launch_bounds__(256) void pairs_emit_kernel(const uint64_t* __restr
 }
 
 // ------------------------------------------------------------------------ launchers ----
-int launch_pairs_join(const PairsJoinArgs& a_in, hipStream_t st) {
-    PairsJoinArgs a = a_in;
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldg % 8 == 0, "gallery_pairs: D must be a multiple of 64");
-    REVO_REQUIRE(a.N < (1ll << 31), "gallery_pairs: row indices must fit in 31 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31), "gallery_pairs: row too long for the DMA window");
+// T, pairs and the grid of a join (`who`: the caller's name in the messages; no rows: a grid of 0): shared with clusters.hip
+int pairs_join_plan(PairsJoinArgs& a, const char* who, long* wgs_out) {
+    REVO_REQUIRE(a.D % 64 == 0 && a.ldg % 8 == 0, std::string(who) + ": D must be a multiple of 64");
+    REVO_REQUIRE(a.N < (1ll << 31), std::string(who) + ": row indices must fit in 31 bits");
+    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31), std::string(who) + ": row too long for the DMA window");
+    *wgs_out = 0;
     if (a.N <= 0) return 0;
     a.T = (a.N + 255) / 256;
     a.pairs = a.T * (a.T + 1) / 2;
@@ -157,6 +147,14 @@ int launch_pairs_join(const PairsJoinArgs& a_in, hipStream_t st) {
     long wgs = cus > 0 ? cus : 256;
     if (wgs < (a.pairs >> 30) + 1) wgs = (a.pairs >> 30) + 1;
     if (wgs > a.pairs) wgs = a.pairs;
+    *wgs_out = wgs;
+    return 0;
+}
+int launch_pairs_join(const PairsJoinArgs& a_in, hipStream_t st) {
+    PairsJoinArgs a = a_in;
+    long wgs = 0;
+    { const int rc = pairs_join_plan(a, "gallery_pairs", &wgs); if (rc) return rc; }
+    if (wgs == 0) return 0;
     REVO_FUNC_LDS(pairs_join_kernel, G256_LDS);
     hipLaunchKernelGGL(pairs_join_kernel, dim3((unsigned)wgs), dim3(G256_THREADS), G256_LDS, st, a);
     REVO_HIP_CHECK(hipGetLastError());

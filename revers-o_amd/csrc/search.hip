@@ -184,11 +184,17 @@ struct revo_gallery {
     DeviceBuffer<> csr; int64_t csr_rows = -1; long csr_groups = 0, csr_grouped = 0;
     int32_t* csr_gid = nullptr; uint32_t *csr_off = nullptr, *csr_row = nullptr, *csr_pos = nullptr;
     DeviceBuffer<float> maxsim_s;
+    // revo_gallery_clusters: its workspace (counters | union-find and error word | sizes | member keys and the sort's buffers),
+    // and the last result ([clusters_rows] labels, [clusters_n + 1] offsets, [clusters_members] rows), valid until the rows
+    // change
+    DeviceBuffer<> cbuf;
+    DeviceBuffer<long long> cl_labels, cl_off, cl_members;
+    int64_t clusters_rows = 0, clusters_n = 0, clusters_members = 0; bool clusters_valid = false;
     // revo_gallery_remove: per-chunk counts | first removed rows | the copy of a host bitmap; revo_gallery_update: the row map
     DeviceBuffer<> edit;
     // the rows change: results held in the handle and the two-phase candidate state go
     void rows_changed() {
-        pairs_valid = false; range_valid = false;
+        pairs_valid = false; range_valid = false; clusters_valid = false;
         cand = nullptr; cand_Q = 0; cand_ksel = 0; nsegs = 0; prelist = nullptr; cand_estimated = false;
     }
     revo::CertArgs cert_args(float* cert_out) const {
@@ -306,6 +312,7 @@ extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     g->size = 0;
     g->pairs_valid = false;
     g->range_valid = false;
+    g->clusters_valid = false;
     g->csr_rows = -1;
     return 0;
 }
@@ -320,6 +327,7 @@ extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64
     hipStream_t st = (hipStream_t)stream;
     g->pairs_valid = false;
     g->range_valid = false;
+    g->clusters_valid = false;
     g->csr_rows = -1;
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
@@ -1054,6 +1062,102 @@ extern "C" int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64
     const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     REVO_HIP_CHECK(hipMemcpy(pairs, g->pair_idx.p + start * 2, (size_t)n * 16, kind));
     REVO_HIP_CHECK(hipMemcpy(scores, g->pair_score.p + start, (size_t)n * 4, kind));
+    return 0;
+    API_END
+}
+
+// ---- duplicate clusters of one gallery (include/revo.h revo_gallery_clusters; clusters.hip)
+extern "C" int32_t revo_gallery_clusters(revo_gallery* g, float threshold, int64_t* n_clusters, int64_t* n_members, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_clusters && n_members, "gallery_clusters: null argument");
+    REVO_REQUIRE(!std::isnan(threshold), "gallery_clusters: threshold is NaN");
+    REVO_REQUIRE(g->keep_f32, "gallery_clusters: the gallery was created without the fp32 master copy (keep_f32 = 0)");
+    REVO_REQUIRE(g->size < (1ll << 31), "gallery_clusters: row indices must fit in 31 bits");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    g->clusters_valid = false;
+    const long N = g->size;
+    const int D = g->D;
+    const int b = row_index_bits(N);
+    // the handle's counters (revo_search_stats): this call's alone
+    CHECK_RC(search_grow_queries(g, 1, st));
+    REVO_REQUIRE(g->xw.ctr, "gallery_clusters: no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, CTR_SLOTS * sizeof(int), st));
+    // the union-find and the finish step's arrays: a buffer of their own, so the candidate workspace's regrow leaves parent[] be
+    const size_t rows = (size_t)(N > 0 ? N : 1);
+    uint32_t *parent = nullptr, *sizes = nullptr, *hist = nullptr;
+    unsigned long long *ctr4 = nullptr, *rank = nullptr;
+    uint64_t *keys = nullptr, *keys_alt = nullptr;
+    float *vals = nullptr, *vals_alt = nullptr;
+    CHECK_RC(carve_buffer(g->cbuf, st, [&](Layout& l) {
+        ctr4 = l.take<unsigned long long>(4);
+        parent = l.take<uint32_t>(rows + 1); sizes = l.take<uint32_t>(rows);      // parent[N]: the error word
+        keys = l.take<uint64_t>(rows); keys_alt = l.take<uint64_t>(rows);
+        vals = l.take<float>(rows); vals_alt = l.take<float>(rows);       // (the sort moves a value with every key: unused here)
+        rank = l.take<unsigned long long>(rows);
+        hist = l.take<uint32_t>(256l * SORT_MAX_BLOCKS);
+    }));
+    CHECK_RC(g->cl_labels.grow(rows * 8, st));
+    CHECK_RC(launch_clusters_init(parent, sizes, N, ctr4, st));
+    CandidateWs ws{g->pbuf, g->pairs_cap};
+    CHECK_RC(ws.carve(g->pairs_cap > PAIRS_WS_KEYS ? g->pairs_cap : PAIRS_WS_KEYS, st));
+    ClustersJoinArgs ja{};
+    ja.j.Gb = g->gb.p; ja.j.ldg = D; ja.j.N = N; ja.j.D = D; ja.j.gstat = g->gstat.p; ja.j.thr = threshold; ja.j.allow = allow;
+    ja.parent = parent;
+    // (a second join repeats the first one's merges: parent[] is not reset between the passes)
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        ja.j.cnt = ws.cnt; ja.j.keys = ws.cand; ja.j.cap = ws.cap;
+        ProfScope ps("clusters_join", st);
+        return launch_clusters_join(ja, st);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)PAIRS_MAX_CAND,
+                     "gallery_clusters: " + std::to_string(n_cand) + " pairs inside the rounding bound of the threshold exceed the "
+                     "limit of " + std::to_string(PAIRS_MAX_CAND) + " (move the threshold)");
+        return 0;
+    }, "gallery_clusters: the candidate count changed between two joins"));
+    { ProfScope ps("clusters_rescore", st);
+      CHECK_RC(launch_clusters_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, threshold, parent, N, st)); }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    { ProfScope ps("clusters_finish", st);
+      CHECK_RC(launch_clusters_labels(parent, allow, N, b, g->cl_labels.p, sizes, keys, ctr4, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(h, ctr4, sizeof(h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[2] != 0) {
+        revo_set_error("clusters: union-find did not converge");
+        return -4;
+    }
+    const long n_mem = (long)h[0], n_cl = (long)h[1];
+    REVO_REQUIRE(n_mem <= N && n_cl <= n_mem / 2, "gallery_clusters: internal: inconsistent counts");
+    CHECK_RC(g->cl_off.grow((size_t)(n_cl + 1) * 8, st));
+    CHECK_RC(g->cl_members.grow((size_t)(n_mem > 0 ? n_mem : 1) * 8, st));
+    {
+        ProfScope ps("clusters_finish", st);
+        uint64_t* sk = nullptr; float* sv = nullptr;
+        CHECK_RC(launch_sort_keys_u64(keys, vals, keys_alt, vals_alt, n_mem, 2 * b, hist, &sk, &sv, st));
+        CHECK_RC(launch_clusters_emit(sk, n_mem, n_cl, b, rank, g->cl_members.p, g->cl_off.p, st));
+    }
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.passes, st));
+    g->clusters_rows = N; g->clusters_n = n_cl; g->clusters_members = n_mem;
+    g->clusters_valid = true;
+    *n_clusters = n_cl;
+    *n_members = n_mem;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, int64_t* offsets, int64_t* members,
+                                              int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_clusters_read: null handle");
+    REVO_REQUIRE(g->clusters_valid, "gallery_clusters_read: no result (call revo_gallery_clusters again after the rows change)");
+    if (!labels && !offsets && !members) return 0;
+    REVO_ON_DEVICE(g->device);
+    const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (labels && g->clusters_rows > 0) REVO_HIP_CHECK(hipMemcpy(labels, g->cl_labels.p, (size_t)g->clusters_rows * 8, kind));
+    if (offsets) REVO_HIP_CHECK(hipMemcpy(offsets, g->cl_off.p, (size_t)(g->clusters_n + 1) * 8, kind));
+    if (members && g->clusters_members > 0)
+        REVO_HIP_CHECK(hipMemcpy(members, g->cl_members.p, (size_t)g->clusters_members * 8, kind));
     return 0;
     API_END
 }

@@ -359,6 +359,24 @@ class Gallery:
                        "revo_gallery_pairs_read")
         return pairs, scores
 
+    def clusters(self, threshold, allow=None):
+        """Duplicate clusters of the gallery (include/revo.h, CLUSTERS): the connected components of the graph whose edges
+        are the pairs of :meth:`pairs` at ``threshold``, computed on the device without storing those pairs, so a cluster's
+        size sets no limit.  Returns ``(labels [len] int64, offsets [n_clusters + 1] int64, members [n_members] int64)``
+        device tensors: ``labels[r]`` is the lowest row of r's component (-1: ``allow`` excludes r), cluster c (a component of
+        at least two rows; clusters ordered by their lowest row) is ``members[offsets[c]:offsets[c + 1]]``, ascending.
+        Synchronous."""
+        nc, nm = C.c_int64(), C.c_int64()
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_gallery_clusters(self._h, float(threshold), C.byref(nc), C.byref(nm),
+                                                       _lib.current_stream()), "revo_gallery_clusters")
+            labels = torch.empty((len(self),), dtype=torch.int64, device=self.device)
+            offsets = torch.empty((int(nc.value) + 1,), dtype=torch.int64, device=self.device)
+            members = torch.empty((int(nm.value),), dtype=torch.int64, device=self.device)
+            _lib.check(self._lib.revo_gallery_clusters_read(self._h, _lib.ptr(labels), _lib.ptr(offsets), _lib.ptr(members), 1),
+                       "revo_gallery_clusters_read")
+        return labels, offsets, members
+
     def search_range(self, queries, score_threshold, index_offset=0, allow=None):
         """Range search (include/revo.h, RANGE): for each query every row (allowed by ``allow``, as in :meth:`search`) whose
         fp32 score reaches ``score_threshold`` -- the reference's threshold without its ``limit``.  Returns ``(offsets [Q + 1]

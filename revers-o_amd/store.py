@@ -242,6 +242,18 @@ def connected_groups(pairs, n):
     return [groups[root] for root in sorted(groups) if len(groups[root]) >= 2]
 
 
+def split_clusters(offsets, members):
+    """The CSR ``(offsets [n + 1], members)`` of ``Gallery.clusters`` as a list of lists of rows."""
+    offsets = np.asarray(offsets, dtype=np.int64).tolist()
+    members = np.asarray(members, dtype=np.int64).tolist()
+    return [members[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+def largest_first(groups):
+    """``groups`` (lists of rows, each ascending) ordered by (size descending, first row ascending)."""
+    return sorted(groups, key=lambda g: (-len(g), g[0]))
+
+
 def average_vector_query(positive, negative=None):
     """The query vector of Qdrant's ``average_vector`` recommendation strategy (host, numpy): with the examples normalised,
     ``mean(positive) + (mean(positive) - mean(negative))``, or ``mean(positive)`` alone without negatives.  fp32 ``[dim]``."""
@@ -626,6 +638,19 @@ class GalleryStore:
         """:meth:`duplicate_groups` as lists of row indices (the places of the points in ``ids`` / ``payloads``)."""
         pairs, _ = self._pairs(score_threshold, query_filter)
         return connected_groups(pairs, len(self))
+
+    def duplicate_row_clusters(self, score_threshold, query_filter=None):
+        """The lists :meth:`duplicate_row_groups` returns, from the device route (include/revo.h, CLUSTERS): the components
+        are found on the device without materialising the pairs, so a group may be of any size (a static shot of 30 000
+        frames is one group; its 4.5e8 pairs are more than :meth:`duplicate_pairs` will return)."""
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        _, offsets, members = self.gallery.clusters(float(score_threshold), allow=allow)
+        return split_clusters(offsets.cpu().numpy(), members.cpu().numpy())
+
+    def duplicate_clusters(self, score_threshold, query_filter=None):
+        """The lists :meth:`duplicate_groups` returns (point ids; members in row order, groups ordered by their first row),
+        from the device route of :meth:`duplicate_row_clusters`."""
+        return [[self.ids[r] for r in grp] for grp in self.duplicate_row_clusters(score_threshold, query_filter)]
 
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
