@@ -59,6 +59,12 @@ def ratio(got, ref, bound):
 #   fp32: O and l summed over S keys     <= 2 S U_F32 sum_j p^_j |v_j|,  1 / l and the product: 2^-21 of the same
 #   p's own error (p and l share it)     <= 2 max_j eps_j sum_j p^_j |v_j|,  eps_j = ln 2 (c (hd + 1) U_F32 (|q|.|k_j|)
 #                                           + 2^-22 |s_j c|) + 2^-22  (score sum, s c - m, exp2)
+# The reference m is not part of the result: p / l is the same softmax against any m.  A move of m (the optimistic softmax's
+# rare path) multiplies l and every O by alpha = exp2(m - m_new): alpha's own error is a common factor of l and O and
+# cancels in O / l; what stays is one fp32 rounding of each product per move, at most one move per key tile: S / 64 U_F32
+# relative, inside the 2 S U_F32 of the summation term (which counts one rounding per KEY and per accumulator).  Terms the
+# move scales below fp32's range are lost with a weight below 2^-126 / l.  So the bound needs no term for the moves;
+# Attention.emulate_optimistic (the kernel's rule, move by move) stays at <= 0.68 of it on the planted cases below.
 def attention_qkv(B, S, H, hd, ld=None, seed=None):
     """The test input: a [B S, ld] bf16 buffer of q | k | v rows (CPU), the seed test_attention uses."""
     W = H * hd
@@ -112,6 +118,105 @@ class Attention:
         l = p.sum(-1, keepdim=True)
         o = p.bfloat16().float() @ v.float()
         return (o * (1.0 / l)).bfloat16().double()
+
+    @staticmethod
+    def emulate_optimistic(q, k, v, k_lo, group=32, parts=2, mutate=None):
+        """fp32 model of the kernels' optimistic softmax (attention.hip attn_fwd_kernel; parts = 4: attn16_fwd_kernel).
+
+        Key rows [k_lo, S) in 64-key tiles; k_lo = 1: the class-token key as the prelude (m = s_cls c, l = 1, O = v_cls) and
+        the query rows in rotated order (1 .. S - 1, 0).  Per tile p = exp2(fma(s, c, -m)) against the running reference m
+        with no maximum taken.  A lane sums the keys of the tile it holds -- key i of the tile belongs to part
+        (i >> 2) & (parts - 1): the 32 keys (i & 3) + 8 (i >> 2) + 4 hh of each 32-key block pair for the 32x32x16 kernel's
+        two halves, the 16 keys 16 mb + 4 lq + i for the 16x16x32 kernel's four lanes -- and a row triggers when a part
+        sum is not < 2^80 (inf, NaN and m = -inf included).  The trigger is shared by the `group` rows of a wave (consecutive
+        rows in the kernel's row order; both kernels: 32, attn16's two query blocks share one __all).  On a trigger every row
+        of the group takes its OWN m_new = max(m, tile max c), alpha = exp2(m - m_new), scales l and O (the P.V of the
+        previous tile included) by alpha and redoes the exponentials.  P is rounded to bf16 for P.V; out = bf16(O (1 / l)).
+
+        Returns {"out": fp64 [pairs, S, hd], "moved" / "own" / "overflow": bool [pairs, S, tiles] (the row's reference moved / the row
+        itself triggered / the first pass's p was not finite), "alpha": the factor applied (1 where not moved), "m_before":
+        m ahead of each tile, "l": l at the end}.  mutate: one of HDR_MUTATION_NAMES, the model with that bug in it."""
+        P, S, hd = q.shape
+        c = float(np.float32(np.float32(1.0) / np.sqrt(np.float32(hd))) * np.float32(LOG2E))
+        dev = q.device
+        s = q.float() @ k.float().transpose(-1, -2)                 # [P, S, S], exact bf16 products summed in fp32
+        vf = v.float()
+        order = torch.arange(S, device=dev)
+        if k_lo:
+            order = torch.cat([order[1:], order[:1]])
+        pos = torch.empty(S, dtype=torch.long, device=dev)
+        pos[order] = torch.arange(S, device=dev)
+        gid = pos // group                                          # wave group of each sequence row
+        ngroups = (S + group - 1) // group
+        nt = (S - k_lo + 63) // 64
+        m = torch.full((P, S), -math.inf, dtype=torch.float32, device=dev)
+        l = torch.zeros(P, S, parts, dtype=torch.float32, device=dev)
+        O = torch.zeros(P, S, hd, dtype=torch.float32, device=dev)
+        if k_lo:
+            m = s[:, :, 0] * c
+            l[..., 0] = 1.0
+            O = vf[:, :1, :].expand(P, S, hd).clone()
+        pending = torch.zeros_like(O)                               # the previous tile's P.V
+        moved = torch.zeros(P, S, nt, dtype=torch.bool, device=dev)
+        own = torch.zeros_like(moved)
+        alphas = torch.ones(P, S, nt, dtype=torch.float32, device=dev)
+        m_before = torch.zeros(P, S, nt, dtype=torch.float32, device=dev)
+        overflow = torch.zeros_like(moved)                          # the first pass's p held an inf or a NaN
+        part_of = (torch.arange(64, device=dev) >> 2) & (parts - 1)
+
+        def exps(sc, m):
+            return torch.exp2((sc.double() * c - m.double()[..., None]).float())      # one rounding: v_pk_fma_f32
+
+        def part_sums(p):
+            return torch.stack([p[..., part_of == j].sum(-1) for j in range(parts)], dim=-1)
+
+        for t in range(nt):
+            k0 = k_lo + 64 * t
+            n = min(64, S - k0)
+            sc = torch.full((P, S, 64), -math.inf, dtype=torch.float32, device=dev)   # masked past the last key
+            sc[..., :n] = s[:, :, k0:k0 + n]
+            m_before[..., t] = m
+            p = exps(sc, m)
+            ps = part_sums(p)
+            trig_row = ~((ps < 2.0 ** 80).all(-1))
+            trig = torch.zeros(P, ngroups, device=dev).index_add_(1, gid, trig_row.float())[:, gid] > 0
+            a_o = torch.ones_like(m)
+            a_l = torch.ones_like(m)
+            if bool(trig.any()):
+                m_new = torch.maximum(m, sc.amax(-1) * c)
+                alpha = torch.exp2(m - m_new)                        # 0 when m was -inf
+                if mutate == "alpha of the triggering row for the whole wave":
+                    first = torch.where(trig_row, pos[None, :].expand(P, S), torch.full((P, S), S, device=dev))
+                    for g in range(ngroups):
+                        rows = (gid == g).nonzero().flatten()
+                        src = order[first[:, rows].amin(1).clamp_max(S - 1)]            # [P] the group's first triggering row
+                        alpha[:, rows] = alpha[torch.arange(P, device=dev), src][:, None].expand(P, len(rows))
+                elif mutate == "wave mates: m moved, alpha forced to 1":
+                    alpha = torch.where(trig_row, alpha, torch.ones_like(alpha))
+                elif mutate == "class-token term dropped on the tile-0 move" and k_lo and t == 0:
+                    alpha = torch.zeros_like(alpha)
+                moved[..., t] = trig
+                overflow[..., t] = trig & ~torch.isfinite(p).all(-1)
+                own[..., t] = trig_row
+                alphas[..., t] = torch.where(trig, alpha, torch.ones_like(alpha))
+                m = torch.where(trig, m_new, m)
+                if mutate != "O not rescaled on a move":
+                    a_o = alphas[..., t]
+                if mutate != "l not rescaled on a move":
+                    a_l = alphas[..., t]
+                if mutate != "exponentials not redone after a move":
+                    p = torch.where(trig[..., None], exps(sc, m), p)
+                    ps = part_sums(p)
+            if mutate == "previous tile's P.V applied after the rescale":
+                O = O * a_o[..., None] + pending
+            else:
+                O = (O + pending) * a_o[..., None]
+            l = l * a_l[..., None] + ps
+            pending = p[..., :n].bfloat16().float() @ vf[:, k0:k0 + n]
+        O = O + pending
+        out = (O * (1.0 / l.sum(-1))[..., None]).bfloat16().double()
+        return {"out": out, "moved": moved, "own": own, "alpha": alphas, "m_before": m_before, "overflow": overflow,
+                "l": l.sum(-1)}
 
 
 def _drop_key(which):
@@ -1135,3 +1240,267 @@ GEMM_FORM_CASES = [
     ("forced no 192-row tiles", "resid", _L, 1024, 1024, dict(variant=1 << 3), ["256P", "128_64"]),
 ] + [(f"{m}x{n}x{k} {e}", e, m, n, k, {}, [f]) for e in ("f32", "resid") for (m, n, k), f in zip(
     GEMM_CASES, ["128_128", "SKINNY_444", "SKINNY_411", "SKINNY_444", "SKINNY_411", "SKINNY_411", "SKINNY_411", "SKINNY_411"])]
+
+
+# ============================================== attention: planted high dynamic range ====
+# The randn cases above move the optimistic softmax's reference once (tile 0, from -inf) or never (class-token prelude).
+# These cases plant logit steps so that the reference moves late, more than once, for one row of a wave only (its 31 wave
+# mates then rescale accumulators whose every term still counts), or stays put with l near 2^75.  A step goes through one
+# coordinate d of a head: q[row, d] = 16 on the boosted query rows, k[key, d] = beta on the planted keys and 0 on every
+# other key, so a boosted row's score on a planted key is the randn score of the other coordinates + 16 beta, i.e.
+# 16 beta c octaves (c = hd^-0.5 log2 e: 0.1803 at head_dim 64, 0.1472 at 96) over its other scores, which stay within a
+# few octaves of 0.  beta = bf16(lag / (16 c)): 8 significant bits, every planted value exact in bf16.  The other query
+# rows keep their randn q[row, d] ~ N(0, 1): a planted key moves their score by N(0, 1) beta c, a few octaves either way.
+#
+# Which branch a case takes is a property of the data, checked on the CPU by Attention.emulate_optimistic
+# (tests/test_kernel_bounds_teeth.py: every head's predicted move schedule is the one stated here); the GPU test cannot
+# observe the path.
+HDR_Q = 16.0
+HDR_MUTATION_NAMES = [
+    "O not rescaled on a move",
+    "l not rescaled on a move",
+    "exponentials not redone after a move",
+    "alpha of the triggering row for the whole wave",
+    "wave mates: m moved, alpha forced to 1",
+    "previous tile's P.V applied after the rescale",
+    "class-token term dropped on the tile-0 move",
+]
+
+
+def attention_k_lo(S, has_cls=True):
+    """launch_attention_ex: the class-token key is split off when that saves a key tile (S = 1 mod 64)"""
+    return 1 if (has_cls and S > 1 and (S - 1 + 63) // 64 < (S + 63) // 64) else 0
+
+
+def attention_row_of_pos(pos, S, k_lo):
+    """sequence row at position pos of the kernel's row order (rotated by one when the class-token key is split off)"""
+    return (pos + 1) % S if k_lo else pos
+
+
+def hdr_beta(lag, hd):
+    """the planted key value that puts a boosted row's score `lag` octaves up: bf16(lag / (16 c))"""
+    return float(torch.tensor(lag / (HDR_Q * hd ** -0.5 * LOG2E)).bfloat16())
+
+
+def _hdr_mutation(name):
+    def f(q, k, v):
+        return Attention.emulate_optimistic(q, k, v, attention_k_lo(k.shape[-2]), mutate=name)["out"]
+    return f
+
+
+Attention.HDR_MUTATIONS = [(name, _hdr_mutation(name), 3.0) for name in HDR_MUTATION_NAMES]
+
+
+def _plant(qpos, keys, moves, coord=0):
+    """coordinate `coord`: query positions qpos (kernel row order) boosted; keys = [(key indices counted from k_lo, lag in
+    octaves)]; moves = the tiles at which the boosted rows themselves must trigger a move (beyond the first one from -inf)"""
+    return dict(coord=coord, qpos=list(qpos), keys=keys, moves=tuple(moves))
+
+
+def _tile(t, offs=range(64)):
+    return [64 * t + o for o in offs]
+
+
+def _head(name, plants, cls=None, quiet=False, mates=False, others_plain=False):
+    """cls: lag in octaves (signed) of the class-token key for the boosted rows, through plants[0]'s coordinate; quiet: no
+    row's reference moves at all (beyond the first move from -inf); mates: at least 20 % of the boosted rows' wave mates
+    move with 0 < alpha < 1; others_plain: the rows that are not boosted get 0 in the planted coordinates (with many
+    coordinates planted their randn values would make every row of the head peaked on the planted keys)"""
+    return dict(name=name, plants=plants, cls=cls, quiet=quiet, mates=mates, others_plain=others_plain)
+
+
+# Every step but the ragged tiles' sits on 8 keys (both halves of a tile, all four lanes of attn16's split).  A row whose
+# weight sits on two keys takes P's and the output's bf16 roundings without any averaging, and since U_BF16 is the relative
+# half ulp at the bottom of a binade the bound is nearly attained there by construction -- by Attention.emulate with the
+# true maximum as much as by the optimistic model (0.77 of the bound on a two-key row of an earlier draft of these cases).
+# That is the bound's tightness, not a property of the moves, so the cases keep away from it.
+_K8 = (1, 6, 12, 19, 27, 36, 46, 57)
+
+
+def _every(r0, S):
+    return range(r0, S, 32)
+
+
+def _hdr_cases():
+    cases = []
+
+    def add(label, B, S, hd, h0, h1):
+        cases.append(dict(label=label, B=B, S=S, H=2, hd=hd, heads=[h0, h1]))
+
+    # ---- S577 hd64: class-token prelude, 9 full tiles, 19 wave groups in 3 workgroups (waves 0-3 and 4-7 both), q_rot
+    S = 577
+    add("S577 hd64 late rise tile 1 / mates tile 4", 2, S, 64,
+        _head("late rise, tile 1 full", [_plant(_every(5, S), [(_tile(1), 96)], [1])], mates=True),
+        _head("wave mates, 8 keys of tile 4", [_plant(_every(17, S), [(_tile(4, _K8), 96)], [4])], mates=True))
+    add("S577 hd64 late rise tile 4 / staircase", 1, S, 64,
+        _head("late rise, middle tile full", [_plant(_every(31, S), [(_tile(4), 96)], [4])], mates=True),
+        _head("staircase +60, 112, +200", [_plant(_every(0, S), [(_tile(2, _K8), 60), (_tile(5, _K8), 112),
+                                                                   (_tile(7, _K8), 312)], [5, 7])], mates=True))
+    add("S577 hd64 late rise last tile / whole group", 1, S, 64,
+        _head("late rise, last tile full", [_plant(_every(12, S), [(_tile(8), 96)], [8])], mates=True),
+        _head("group 5 boosted, each row in its own tile",
+              [_plant([160 + i for i in range(32) if i % 9 == j], [(_tile(j, _K8), 96)], [j], coord=j) for j in range(9)],
+              mates=True, others_plain=True))
+    add("S577 hd64 just below / class token far above", 1, S, 64,
+        _head("just below the trigger", [_plant(_every(9, S), [(_tile(3, range(20, 30)), 72)], [])], quiet=True),
+        _head("class token 150 octaves above", [_plant(_every(22, S), [], [])], cls=150, quiet=True))
+    add("S577 hd64 class token far below / mates tile 0", 1, S, 64,
+        _head("class token 150 octaves below", [_plant(_every(3, S), [], [0])], cls=-150, mates=True),
+        _head("wave mates, 8 keys of tile 0", [_plant(_every(26, S), [(_tile(0, _K8), 96)], [0])], mates=True))
+    # ---- S197 hd64: no prelude, 4 tiles, 5 keys in the last; 7 wave groups (waves 0-3 and 4-6), the last of 5 rows
+    S = 197
+    add("S197 hd64 ragged / mates tile 1", 2, S, 64,
+        _head("row maximum on the last real key", [_plant(_every(3, S), [([196], 96)], [3])], mates=True),
+        _head("wave mates, 8 keys of tile 1", [_plant(_every(20, S), [(_tile(1, _K8), 96)], [1])], mates=True))
+    add("S197 hd64 staircase / late rise tile 1", 1, S, 64,
+        _head("staircase +60, 112, +200", [_plant(_every(2, S), [(_tile(1, _K8), 63), (_tile(2, _K8), 115),
+                                                                   (_tile(3, range(5)), 315)], [2, 3])], mates=True),
+        _head("late rise, tile 1 full", [_plant(_every(30, S), [(_tile(1), 99)], [1])], mates=True))
+    add("S197 hd64 just below / late rise tile 2", 1, S, 64,
+        _head("just below the trigger", [_plant(_every(1, S), [(_tile(2, range(30, 40)), 75)], [])], quiet=True),
+        _head("late rise, middle tile full", [_plant(_every(4, S), [(_tile(2), 99)], [2])], mates=True))
+    # ---- S257 hd96: prelude, 4 full tiles, 9 wave groups in 2 workgroups
+    S = 257
+    add("S257 hd96 mates tile 2 / class token far below", 2, S, 96,
+        _head("wave mates, 8 keys of tile 2", [_plant(_every(9, S), [(_tile(2, _K8), 96)], [2])], mates=True),
+        _head("class token 150 octaves below", [_plant(_every(28, S), [], [0])], cls=-150, mates=True))
+    add("S257 hd96 staircase / class token far above", 1, S, 96,
+        _head("staircase +60, 112, +200", [_plant(_every(14, S), [(_tile(1, _K8), 60), (_tile(2, _K8), 112),
+                                                                    (_tile(3, _K8), 312)], [2, 3])], mates=True),
+        _head("class token 150 octaves above", [_plant(_every(6, S), [], [])], cls=150, quiet=True))
+    # ---- S130 hd96: no prelude, 3 tiles, 2 keys in the last; 5 wave groups (waves 0-4), the last of 2 rows
+    S = 130
+    add("S130 hd96 ragged / mates tile 1", 2, S, 96,
+        _head("row maximum on the last real key", [_plant(_every(1, S), [([129], 99)], [2])], mates=True),
+        _head("wave mates, 8 keys of tile 1", [_plant(_every(0, S), [(_tile(1, _K8), 99)], [1])], mates=True))
+    add("S130 hd96 just below / late rise last tile", 1, S, 96,
+        _head("just below the trigger", [_plant(_every(0, S), [(_tile(1, range(0, 10)), 75)], [])], quiet=True),
+        _head("late rise, last tile full", [_plant(_every(1, S), [(_tile(2, (0, 1)), 99)], [2])], mates=True))
+    return cases
+
+
+ATTENTION_HDR_CASES = _hdr_cases()
+
+
+def attention_hdr_qkv(case):
+    """attention_qkv's randn buffer [B S, 3W] (bf16, CPU) with the case's steps planted; every planted value is exact in bf16"""
+    B, S, H, hd = case["B"], case["S"], case["H"], case["hd"]
+    k_lo = attention_k_lo(S)
+    x = attention_qkv(B, S, H, hd).float().reshape(B, S, 3, H, hd)
+    for h, head in enumerate(case["heads"]):
+        coords = [p["coord"] for p in head["plants"]]
+        x[:, :, 1, h, coords] = 0.0                                  # every key is plain in the planted coordinates ...
+        if head["others_plain"]:
+            x[:, :, 0, h, coords] = 0.0
+        for p in head["plants"]:
+            rows = [attention_row_of_pos(pos, S, k_lo) for pos in p["qpos"]]
+            for d in coords:
+                x[:, rows, 0, h, d] = HDR_Q if d == p["coord"] else 0.0
+            for keys, lag in p["keys"]:                              # ... but the planted ones
+                assert max(keys) < S - k_lo
+                x[:, [k_lo + j for j in keys], 1, h, p["coord"]] = hdr_beta(lag, hd)
+        if head["cls"] is not None:
+            assert k_lo == 1
+            x[:, 0, 1, h, coords[0]] = math.copysign(hdr_beta(abs(head["cls"]), hd), head["cls"])
+    qkv = x.reshape(B * S, 3 * H * hd).bfloat16()
+    assert torch.equal(qkv.float(), x.reshape(B * S, 3 * H * hd))   # nothing planted was rounded
+    return qkv
+
+
+def attention_hdr_schedule(case, h, em):
+    """What Attention.emulate_optimistic (em, on the pairs of head h: one per image) predicts for head h, against what the
+    case states.  Returns (facts, failures, text): facts feed NOT_CAUGHT's predicates."""
+    S, k_lo = case["S"], attention_k_lo(case["S"])
+    head = case["heads"][h]
+    start = torch.isfinite(em["m_before"])                          # a move from -inf scales zeros: not a rescale
+    moved, own, alpha = em["moved"] & start, em["own"] & start, em["alpha"]
+    nt = moved.shape[-1]
+    failures, boosted, parts = [], [], []
+    for p in head["plants"]:
+        rows = [attention_row_of_pos(pos, S, k_lo) for pos in p["qpos"]]
+        boosted += rows
+        want = torch.zeros(nt, dtype=torch.bool)
+        want[list(p["moves"])] = True
+        got = own[:, rows]
+        if not bool((got == want).all()):
+            failures.append(f"boosted rows of coordinate {p['coord']} trigger at tiles "
+                            f"{sorted(set(got.nonzero()[:, -1].tolist()))}, stated {list(p['moves'])}")
+        parts.append(f"boosted x{len(rows)} move at {list(p['moves'])}")
+    others = torch.ones(S, dtype=torch.bool)
+    others[boosted] = False
+    if bool(own[:, others].any()):
+        failures.append("a row that is not boosted triggers a move")
+    partial = moved & ~own & (alpha > 0) & (alpha < 1)               # a mate whose earlier terms are scaled, not dropped
+    mate_rows = (moved & ~own).any(-1)
+    n_mates, n_partial = int(mate_rows.sum()), int(partial.any(-1).sum())
+    frac = n_partial / max(n_mates, 1)
+    if head["quiet"] and bool(moved.any()):
+        failures.append(f"stated quiet, but moves at tiles {sorted(set(moved.nonzero()[:, -1].tolist()))}")
+    if head["mates"] and frac < 0.2:
+        failures.append(f"only {n_partial} of {n_mates} wave mates move with 0 < alpha < 1")
+    weighty = moved & (alpha > 2.0 ** -20)                            # the earlier terms keep weight through the move
+    # a mate's partial move still shows at the end only if the row does not move by itself later (that wipes the earlier terms)
+    later_own = torch.flip(torch.cumsum(torch.flip(own, [-1]), -1), [-1]) - own.long() > 0
+    lasting = bool((partial & ~later_own).any())
+    facts = dict(S=S, moves=bool(moved.any()), late_moves=bool(moved[..., 1:].any()), mates=lasting,
+                 mates_any=bool((moved & ~own & ~later_own).any()), cls_head=head["cls"] is not None,
+                 cls_move=bool(k_lo and (weighty & ~later_own)[..., 0].any()), overflow=bool(em["overflow"].any()))
+    text = (f"{head['name']}: " + "; ".join(parts) + f"; mates moved {n_mates}, with 0 < alpha < 1 {n_partial} ({frac:.0%})"
+            + f"; l max 2^{float(torch.log2(em['l'].max())):.1f}")
+    return facts, failures, text
+
+
+_NO_MOVE = "no row's reference moves in this head: the model with the bug in it is the model"
+NOT_CAUGHT.update({
+    ("attention hdr", name): (lambda c: not c["moves"], _NO_MOVE) for name in HDR_MUTATION_NAMES})
+NOT_CAUGHT.update({
+    ("attention hdr", "alpha of the triggering row for the whole wave"):
+        (lambda c: not c["mates_any"], "no row shares another row's trigger and keeps what it held: the boosted rows use their "
+                                       "own alpha either way"),
+    ("attention hdr", "wave mates: m moved, alpha forced to 1"):
+        (lambda c: not c["mates"], "no wave mate moves with 0 < alpha < 1"),
+    ("attention hdr", "previous tile's P.V applied after the rescale"):
+        (lambda c: not c["late_moves"], "every move is at tile 0, where no earlier tile's P.V is pending"),
+    ("attention hdr", "class-token term dropped on the tile-0 move"):
+        (lambda c: not c["cls_move"], "no prelude, or no tile-0 move that leaves the class-token term a weight above 2^-20 in a row "
+                                      "that does not wipe it by a move of its own later"),
+    ("attention hdr", "exponentials not redone after a move"):
+        (lambda c: not (c["mates"] or c["overflow"]),
+         "p against the old reference is finite for every row that moves and no wave mate keeps a partial move: a boosted row's "
+         "stale p is the same softmax against another reference"),
+    ("attention hdr", "l not rescaled on a move"):
+        (lambda c: not c["moves"] or (c["cls_head"] and not c["late_moves"] and c["S"] >= 512),
+         "every move is the tile-0 move over a class token far below: what is not scaled is the prelude's l = 1, one key's "
+         "worth against the row sum of 576 plain keys"),
+    ("attention hdr", "softmax scale x 1.01"): (lambda c: c["S"] == 1, "one key"),
+})
+
+
+# ---- the data of test_attention_huge_logits and test_attention_peaked_softmax (tests/test_gpu_kernels.py), shared with the
+# CPU teeth test that decides which of them the per-element bound can be asked of
+HUGE_LOGITS_CASES = [(577, 64, 8.0), (260, 64, 12.0), (257, 96, 8.0), (577, 64, 30.0)]
+
+
+def attention_huge_logits_qkv(S, hd, scale, B=2, H=2):
+    W = H * hd
+    g = torch.Generator(device="cpu").manual_seed(S + hd)
+    qkv = torch.randn(B * S, 3 * W, generator=g)
+    qkv[:, : 2 * W] *= scale
+    # ascending scores along the key axis for the first head: the maximum keeps moving
+    qkv[:, W:W + hd] += torch.linspace(0, scale, B * S)[:, None] * torch.sign(qkv[0, :hd])[None]
+    return qkv.bfloat16()
+
+
+def attention_peaked_qkv():
+    """[577, 3 * 64] bf16, one head: one key dominates per query (key 500 aligned with query 3)"""
+    S, hd = 577, 64
+    g = torch.Generator(device="cpu").manual_seed(11)
+    x = torch.randn(S, 3, hd, generator=g)
+    x[:, 0] *= 0.1
+    x[500, 1] = x[:, 0].mean(0) * 0 + 8.0 * torch.sign(x[3, 0])
+    return x.reshape(S, 3 * hd).bfloat16()
+
+
+# whether the per-element bound is asserted on that data (the model stays within 0.75 of it on the CPU: the teeth test)
+HUGE_LOGITS_BOUND = {c: True for c in HUGE_LOGITS_CASES}
+PEAKED_BOUND = True

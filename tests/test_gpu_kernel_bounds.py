@@ -44,6 +44,28 @@ def test_attention_within_bound(plib, dev, case):
     _report("attention", label, worst)
 
 
+@pytest.mark.parametrize("case", kb.ATTENTION_HDR_CASES, ids=[c["label"] for c in kb.ATTENTION_HDR_CASES])
+def test_attention_hdr_within_bound(plib, dev, case):
+    """The planted high-dynamic-range inputs (kb.ATTENTION_HDR_CASES): the optimistic softmax's reference moves late, more
+    than once, for one row of a wave with its 31 mates rescaling accumulators that still count, or not at all with l near
+    2^75 -- the path each head takes is asserted on the CPU (tests/test_kernel_bounds_teeth.py).  Every output finite and
+    within the fp64 per-element bound, every (image, head) pair."""
+    B, S, H, hd = case["B"], case["S"], case["H"], case["hd"]
+    W = H * hd
+    qkv = kb.attention_hdr_qkv(case).to(dev)
+    out = torch.full((B * S, W), float("nan"), device=dev, dtype=torch.bfloat16)
+    _lib.check(plib.revo_op_attention(_lib.ptr(qkv), 3 * W, _lib.ptr(out), W, B, S, H, hd, _lib.current_stream()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(out.float()).all()
+    q, k, v = kb.attention_split(qkv, B, S, H, hd)
+    got = kb.attention_unsplit(out, B, S, H, hd)
+    ref, bound = kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v)
+    for h in range(H):
+        pairs = [b * H + h for b in range(B)]
+        print(f"[attention hdr {case['label']} h{h}] max |got - ref| / bound = {kb.ratio(got[pairs], ref[pairs], bound[pairs]):.3f}")
+    _report("attention hdr", case["label"], kb.ratio(got, ref, bound))
+
+
 @pytest.mark.parametrize("case", kb.ROPE_CASES, ids=[c[0] for c in kb.ROPE_CASES])
 def test_rope_within_bound(plib, dev, case):
     label, grid, H, hd, cls, B = case

@@ -271,11 +271,7 @@ def test_attention(lib, dev, B, S, H, hd):
 def test_attention_peaked_softmax(lib, dev):
     # one key dominates per query (forces the running max to jump late in the key sweep)
     B, S, H, hd = 1, 577, 1, 64
-    g = torch.Generator(device="cpu").manual_seed(11)
-    x = torch.randn(B * S, 3, hd, generator=g)
-    x[:, 0] *= 0.1
-    x[500, 1] = x[:, 0].mean(0) * 0 + 8.0 * torch.sign(x[3, 0])   # key 500 aligned with query 3
-    qkv = x.reshape(B * S, 3 * hd).to(dev).bfloat16()
+    qkv = kb.attention_peaked_qkv().to(dev)                       # key 500 aligned with query 3
     out = torch.zeros(B * S, hd, device=dev, dtype=torch.bfloat16)
     _lib.check(lib.revo_op_attention(_lib.ptr(qkv), 3 * hd, _lib.ptr(out), hd, B, S, H, hd, _lib.current_stream()))
     torch.cuda.synchronize()
@@ -283,21 +279,23 @@ def test_attention_peaked_softmax(lib, dev):
     att = torch.softmax(xf[:, 0] @ xf[:, 1].T * hd ** -0.5, dim=-1)
     ref = att @ xf[:, 2]
     assert (out.float() - ref).abs().max().item() <= 0.03
+    # and the fp64 per-element bound: the model of the optimistic softmax stays at 0.34 of it on this data
+    # (test_kernel_bounds_teeth.py::test_attention_peaked_model_against_the_bound)
+    assert kb.PEAKED_BOUND
+    q, k, v = kb.attention_split(qkv, B, S, H, hd)
+    r = kb.ratio(kb.attention_unsplit(out, B, S, H, hd), kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+    print(f"[attention peaked] max |got - ref| / bound = {r:.3f}")
+    assert r <= 1.0, r
 
 
-@pytest.mark.parametrize("S,hd,scale", [(577, 64, 8.0), (260, 64, 12.0), (257, 96, 8.0), (577, 64, 30.0)])
+@pytest.mark.parametrize("S,hd,scale", kb.HUGE_LOGITS_CASES)
 def test_attention_huge_logits(lib, dev, S, hd, scale):
     """Scores spread over hundreds of octaves (|s| up to ~scale^2 * 8): the optimistic softmax's
     reference must be moved (overflow guard) and rows whose early keys are far below the final
     maximum must still come out exact.  Compared with an fp64 softmax."""
     B, H = 2, 2
     W = H * hd
-    g = torch.Generator(device="cpu").manual_seed(S + hd)
-    qkv = torch.randn(B * S, 3 * W, generator=g)
-    qkv[:, : 2 * W] *= scale
-    # ascending scores along the key axis for the first head: the maximum keeps moving
-    qkv[:, W:W + hd] += torch.linspace(0, scale, B * S)[:, None] * torch.sign(qkv[0, :hd])[None]
-    qkv = qkv.to(dev).bfloat16()
+    qkv = kb.attention_huge_logits_qkv(S, hd, scale, B, H).to(dev)
     out = torch.full((B * S, W), float("nan"), device=dev, dtype=torch.bfloat16)
     _lib.check(lib.revo_op_attention(_lib.ptr(qkv), 3 * W, _lib.ptr(out), W, B, S, H, hd, _lib.current_stream()))
     torch.cuda.synchronize()
@@ -308,27 +306,41 @@ def test_attention_huge_logits(lib, dev, S, hd, scale):
     assert torch.isfinite(out.float()).all()
     err = (out.double() - ref).abs().max().item()
     assert err <= 0.04, err
+    # and the fp64 per-element bound, where the model of the optimistic softmax stays within 0.75 of it on the CPU (all four:
+    # 0.63 / 0.36 / 0.49 / 0.08, test_kernel_bounds_teeth.py::test_attention_huge_logits_model_against_the_bound)
+    if kb.HUGE_LOGITS_BOUND[(S, hd, scale)]:
+        q, k, v = kb.attention_split(qkv, B, S, H, hd)
+        r = kb.ratio(kb.attention_unsplit(out, B, S, H, hd), kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+        print(f"[attention huge logits S{S} hd{hd} x{scale}] max |got - ref| / bound = {r:.3f}")
+        assert r <= 1.0, r
 
 
 @pytest.mark.parametrize("B,S,H,scale", [(2, 577, 2, 0), (1, 197, 3, 0), (3, 17, 2, 0), (1, 64, 1, 0), (1, 65, 1, 0), (2, 128, 2, 0), (1, 129, 1, 0),
                                          (1, 1, 1, 0), (1, 1024, 2, 0), (2, 16, 2, 0), (64, 577, 16, 0),
-                                         (2, 577, 2, 8.0), (2, 260, 2, 12.0), (2, 577, 2, 30.0)])
+                                         (2, 577, 2, 8.0), (2, 260, 2, 12.0), (2, 577, 2, 30.0)]
+                         + [(c["B"], c["S"], c["H"], "hdr: " + c["label"]) for c in kb.ATTENTION_HDR_CASES if c["hd"] == 64])
 def test_attention_mfma_16x16x32_kernel(dev, gemm_tile, B, S, H, scale):
     """attn16_fwd_kernel (round 6's MFMA-shape experiment: head_dim 64 on v_mfma_f32_16x16x32_bf16 -- a query's scores in four
     lanes, probabilities fed back as the B operand in key-slot order, V rows swizzled for 4 x 16 transposing reads) against an fp64
     softmax, on every shape the 32x32x16 kernel is tested on (ragged last key tile, one row, class-token prelude, the rotated
-    row order, logits over hundreds of octaves: the reference-moving rare path) and against that kernel itself."""
+    row order, logits over hundreds of octaves: the reference-moving rare path) and against that kernel itself.  On the planted
+    high-dynamic-range cases (scale = "hdr: <label>", kb.ATTENTION_HDR_CASES at head_dim 64: its two references per lane move
+    for one row of a wave, late and more than once) it is also held to the fp64 per-element bound."""
     if gemm_tile != 0:
         pytest.skip("runs once: the switch lives in librevo_exp.so")
     lib = _lib.load_exp()
     hd = 64
     W = H * hd
-    g = torch.Generator(device="cpu").manual_seed(S * 31 + H)
-    qkv = torch.randn(B * S, 3 * W, generator=g)
-    if scale:
-        qkv[:, : 2 * W] *= scale
-        qkv[:, W:W + hd] += torch.linspace(0, scale, B * S)[:, None] * torch.sign(qkv[0, :hd])[None]
-    qkv = qkv.to(dev).bfloat16()
+    hdr = isinstance(scale, str)
+    if hdr:
+        qkv = kb.attention_hdr_qkv(next(c for c in kb.ATTENTION_HDR_CASES if "hdr: " + c["label"] == scale)).to(dev)
+    else:
+        g = torch.Generator(device="cpu").manual_seed(S * 31 + H)
+        qkv = torch.randn(B * S, 3 * W, generator=g)
+        if scale:
+            qkv[:, : 2 * W] *= scale
+            qkv[:, W:W + hd] += torch.linspace(0, scale, B * S)[:, None] * torch.sign(qkv[0, :hd])[None]
+        qkv = qkv.to(dev).bfloat16()
     outs = {}
     try:
         for flag in (0, 1 << 20):
@@ -348,6 +360,11 @@ def test_attention_mfma_16x16x32_kernel(dev, gemm_tile, B, S, H, scale):
     tol = 0.04 if scale else 0.03
     assert (new[: nb * S].double() - ref).abs().max().item() <= tol
     assert (new.float() - old.float()).abs().max().item() <= tol           # the whole batch against the shipped kernel
+    if hdr:
+        q, k, v = kb.attention_split(qkv, B, S, H, hd)
+        r = kb.ratio(kb.attention_unsplit(new, B, S, H, hd), kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+        print(f"[attention 16x16x32 {scale}] max |got - ref| / bound = {r:.3f}")
+        assert r <= 1.0, r
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 1024, 1024), (64, 4096, 1024), (64, 1024, 4096), (1, 256, 256), (7, 260, 512),

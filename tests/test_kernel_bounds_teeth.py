@@ -6,7 +6,9 @@ required ratio somewhere (3x; 1.5x for the softmax scale off by 1 %), and the em
 bound is per element, so the large attention shapes are checked on a sample of (image, head) pairs.  The GEMM family
 (GemmF32, GemmResid, GemmRope, GemmLnIn, LnStats, SplitkResidLn) runs at the GPU cases' N, K, slot counts, S and head_dim
 with M cut to a few hundred rows; the rounding-direction statistic and the coverage of the launch-form record are checked
-here too."""
+here too.  The planted high-dynamic-range attention cases (kb.ATTENTION_HDR_CASES) are checked head by head against a model
+of the kernel's optimistic softmax: the predicted move schedule is the stated one, and every way of getting a move wrong
+leaves the bound."""
 import pytest
 import torch
 
@@ -48,6 +50,95 @@ def test_attention_bound_has_teeth(case):
     ref, bound = A.reference(q, k, v), A.bound(q, k, v)
     _check("attention", label, {"S": S}, ref, bound, A.emulate(q, k, v),
            [(name, f(q, k, v), need) for name, f, need in A.MUTATIONS])
+
+
+def _hdr_ids():
+    return [f"{c['label']} h{h}" for c in kb.ATTENTION_HDR_CASES for h in range(c["H"])]
+
+
+@pytest.mark.parametrize("case,h", [(c, h) for c in kb.ATTENTION_HDR_CASES for h in range(c["H"])], ids=_hdr_ids())
+def test_attention_hdr_takes_its_path_and_the_bound_has_teeth(case, h):
+    """Each head of each planted high-dynamic-range case: the fp32 model of the kernel's optimistic softmax predicts the
+    move schedule the case states (the GPU test cannot observe the path: this condition on the inputs stands in for it),
+    stays within EMULATION_MAX of the fp64 bound, and every way of getting a move wrong leaves the bound by 3 x."""
+    B, S, H, hd = case["B"], case["S"], case["H"], case["hd"]
+    qkv = kb.attention_hdr_qkv(case)
+    q, k, v = kb.attention_split(qkv, B, S, H, hd, [b * H + h for b in range(B)])
+    A = kb.Attention
+    em = A.emulate_optimistic(q, k, v, kb.attention_k_lo(S))
+    facts, failures, text = kb.attention_hdr_schedule(case, h, em)
+    print(f"[attention hdr {case['label']} h{h}] predicted schedule: {text}")
+    assert not failures, (case["label"], h, failures)
+    _check("attention hdr", f"{case['label']} h{h}", facts, A.reference(q, k, v), A.bound(q, k, v), em["out"],
+           [(name, f(q, k, v), need) for name, f, need in A.HDR_MUTATIONS + A.MUTATIONS])
+
+
+def test_attention_hdr_cases_cover_what_they_claim():
+    """Structure of the family: the four shapes with their prelude / ragged tile, the wave-mates pattern on each, boosted
+    rows in wave groups served by waves 0-3 and by waves 4-7, late rises in tile 1, a middle tile and the last tile."""
+    shapes = {(c["S"], c["hd"]) for c in kb.ATTENTION_HDR_CASES}
+    assert shapes == {(577, 64), (197, 64), (257, 96), (130, 96)}
+    assert [kb.attention_k_lo(S) for S in (577, 197, 257, 130)] == [1, 0, 1, 0]
+    late = set()
+    for c in kb.ATTENTION_HDR_CASES:
+        assert c["B"] <= 2 and c["H"] == 2
+        nt = (c["S"] - kb.attention_k_lo(c["S"]) + 63) // 64
+        for head in c["heads"]:
+            for p in head["plants"]:
+                if head["name"].startswith("late rise"):
+                    late.add("tile 1" if p["moves"] == (1,) else "last" if p["moves"] == (nt - 1,) else "middle")
+    assert late == {"tile 1", "middle", "last"}
+    for S, hd in shapes:
+        mates = [head for c in kb.ATTENTION_HDR_CASES if (c["S"], c["hd"]) == (S, hd) for head in c["heads"]
+                 if head["name"].startswith("wave mates")]
+        assert mates, (S, hd)
+        waves = {(pos // 32) % 8 for head in mates for p in head["plants"] for pos in p["qpos"]}
+        assert waves & {0, 1, 2, 3} and waves & {4, 5, 6, 7}, (S, hd, waves)
+        for head in mates:                                            # exactly one boosted row per 32-row wave group
+            groups = [pos // 32 for p in head["plants"] for pos in p["qpos"]]
+            assert len(groups) == len(set(groups))
+
+
+@pytest.mark.parametrize("parts", [2, 4], ids=["32x32x16", "16x16x32"])
+def test_attention_hdr_model_of_both_kernels(parts):
+    """attn16_fwd_kernel sums 16 keys per lane where attn_fwd_kernel sums 32 (four partial sums against the 2^80 test
+    instead of two); the wave group is 32 rows in both.  On the head_dim-64 cases both models take the stated path and stay
+    inside the bound."""
+    for case in kb.ATTENTION_HDR_CASES:
+        if case["hd"] != 64:
+            continue
+        B, S, H, hd = case["B"], case["S"], case["H"], case["hd"]
+        qkv = kb.attention_hdr_qkv(case)
+        for h in range(H):
+            q, k, v = kb.attention_split(qkv, B, S, H, hd, [h])
+            em = kb.Attention.emulate_optimistic(q, k, v, kb.attention_k_lo(S), parts=parts)
+            _, failures, _ = kb.attention_hdr_schedule(case, h, em)
+            assert not failures, (case["label"], h, parts, failures)
+            r = kb.ratio(em["out"], kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+            assert r <= EMULATION_MAX, (case["label"], h, parts, r)
+
+
+@pytest.mark.parametrize("S,hd,scale", kb.HUGE_LOGITS_CASES)
+def test_attention_huge_logits_model_against_the_bound(S, hd, scale):
+    """The data of test_attention_huge_logits: where the model of the optimistic softmax stays within EMULATION_MAX of the
+    fp64 bound, the GPU test asserts the bound next to its absolute tolerance (kb.HUGE_LOGITS_BOUND)."""
+    B, H = 2, 2
+    qkv = kb.attention_huge_logits_qkv(S, hd, scale, B, H)
+    q, k, v = kb.attention_split(qkv, B, S, H, hd)
+    em = kb.Attention.emulate_optimistic(q, k, v, kb.attention_k_lo(S))
+    r = kb.ratio(em["out"], kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+    moves = (em["moved"] & torch.isfinite(em["m_before"])).any(1).sum(-1).float().mean()
+    print(f"[attention huge logits S{S} hd{hd} x{scale}] emulation/bound max {r:.3f}; {float(moves):.1f} tiles with a move per pair")
+    assert (r <= EMULATION_MAX) == kb.HUGE_LOGITS_BOUND[(S, hd, scale)], r
+
+
+def test_attention_peaked_model_against_the_bound():
+    qkv = kb.attention_peaked_qkv()
+    q, k, v = kb.attention_split(qkv, 1, 577, 1, 64)
+    em = kb.Attention.emulate_optimistic(q, k, v, 1)
+    r = kb.ratio(em["out"], kb.Attention.reference(q, k, v), kb.Attention.bound(q, k, v))
+    print(f"[attention peaked] emulation/bound max {r:.3f}")
+    assert (r <= EMULATION_MAX) == kb.PEAKED_BOUND, r
 
 
 @pytest.mark.parametrize("case", kb.ROPE_CASES, ids=[c[0] for c in kb.ROPE_CASES])
