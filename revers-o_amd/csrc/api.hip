@@ -1,5 +1,5 @@
-// C ABI of librevo (include/revo.h), except the gallery and the search (search.hip): error state, the per-kernel-class
-// profiler, the model handle with its embed forward schedule, and the single-kernel ops.
+// C ABI of librevo (include/revo.h), except the gallery and the searches (gallery.hip, search.hip, candidate_search.hip):
+// error state, the per-kernel-class profiler, the model handle with its embed forward schedule, and the single-kernel ops.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// Plumbing shared by api.hip and search.hip (not part of the C ABI): status guards, device guard, profiler scope.
+// Plumbing shared by api.hip, gallery.hip, search.hip and candidate_search.hip (not part of the C ABI): status guards, device guard, profiler scope.
 #pragma once
 #include "common.h"
 

@@ -1,0 +1,615 @@
+// C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, range, recommend,
+// discover, MaxSim and MMR, with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
+#include <algorithm>
+
+#include "gallery_internal.h"
+
+namespace {
+// The host side of the candidate pipeline (pairs, range and recommend searches): its workspace in one
+// buffer of the handle and the steps between its kernels (synchronous: the host reads the candidate and the kept count).
+struct CandidateWs {
+    DeviceBuffer<>& buf;
+    long& cap;                           // candidate keys the workspace holds (a handle remembers it: once grown, it stays grown)
+    unsigned long long* cnt = nullptr;   // [4] device counters: [0] candidates (counts past cap), [1] kept, [2], [3] the search's own
+    uint64_t *cand = nullptr, *kept_k = nullptr;   // [cap] candidate keys (then the sort's second key buffer), kept sort keys
+    float *kept_v = nullptr, *alt_v = nullptr;     // [cap] kept scores, the sort's second score buffer
+    uint32_t* hist = nullptr;            // the sort's digit counts
+    unsigned long long h[4] = {0, 0, 0, 0}, n_cand = 0, n_kept = 0;   // cnt as read behind the join; candidates, kept entries
+    int passes = 0;                      // joins run: 1, or 2 after a regrow
+    uint64_t* sk = nullptr; float* sv = nullptr;   // the sorted kept entries
+    // the layout for n candidate keys; extra(Layout&) takes the arrays a search adds behind it
+    template <class Extra> int carve(long n, hipStream_t st, Extra&& extra) {
+        CHECK_RC(carve_buffer(buf, st, [&](Layout& l) {
+            cnt = l.take<unsigned long long>(4);
+            cand = l.take<uint64_t>(n); kept_k = l.take<uint64_t>(n);
+            kept_v = l.take<float>(n); alt_v = l.take<float>(n);
+            hist = l.take<uint32_t>(256l * revo::SORT_MAX_BLOCKS);
+            extra(l);
+        }));
+        cap = n;
+        return 0;
+    }
+    int carve(long n, hipStream_t st) { return carve(n, st, [](Layout&) {}); }
+    // Clears the counters, runs join() and reads them; limit(candidates) is the caller's check.  A count past the workspace's
+    // end: carved again for the counted size, joined once more (`changed`: the error text if that does not fit either).
+    template <class Join, class Limit> int join_until_it_fits(hipStream_t st, Join&& join, Limit&& limit, const char* changed) {
+        for (passes = 0;;) {
+            REVO_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(h), st));
+            CHECK_RC(join());
+            ++passes;
+            REVO_HIP_CHECK(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st));
+            REVO_HIP_CHECK(hipStreamSynchronize(st));
+            n_cand = h[0];
+            CHECK_RC(limit(n_cand));
+            if (n_cand <= (unsigned long long)cap) return 0;
+            REVO_REQUIRE(passes == 1, changed);
+            CHECK_RC(carve((long)n_cand, st));
+        }
+    }
+    // behind the re-score (it counted into cnt[1]): the kept count, the kept entries sorted over key_bits bits -> n_kept, sk, sv
+    int sort_kept(const char* prof, int key_bits, hipStream_t st) {
+        n_kept = 0;
+        if (n_cand > 0) {
+            REVO_HIP_CHECK(hipMemcpyAsync(&n_kept, cnt + 1, sizeof(n_kept), hipMemcpyDeviceToHost, st));
+            REVO_HIP_CHECK(hipStreamSynchronize(st));
+        }
+        ProfScope ps(prof, st);
+        return revo::launch_sort_keys_u64(kept_k, kept_v, cand, alt_v, (long)n_kept, key_bits, hist, &sk, &sv, st);
+    }
+};
+// revo_search_stats slot 3 = candidates re-scored, slot 7 = candidate passes; the call ends synchronised
+int publish_candidate_stats(int* ctr, unsigned long long candidates, int passes, hipStream_t st) {
+    const int stats[2] = {(int)candidates, passes};
+    REVO_HIP_CHECK(hipMemcpyAsync(ctr + revo::CTR_COLLECTED, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(ctr + revo::CTR_PAIR_PASSES, &stats[1], sizeof(int), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+// the bits of the largest row index of N rows (at least 1): the row field of a sort key
+int row_index_bits(long N) {
+    int b = 1;
+    while (N > 1 && (1l << b) < N) ++b;
+    return b;
+}
+
+// The start of a candidate search: the handle's per-query arrays hold `rows` rows, and its counters (revo_search_stats) are
+// this call's alone
+int begin_counted(revo_gallery* g, int rows, const char* who, hipStream_t st) {
+    CHECK_RC(search_grow_queries(g, rows, st));
+    REVO_REQUIRE(g->xw.ctr, std::string(who) + ": no counter workspace");
+    REVO_HIP_CHECK(hipMemsetAsync(g->xw.ctr, 0, revo::CTR_SLOTS * sizeof(int), st));
+    return 0;
+}
+
+// ---- the two joins of the gallery with itself (pairs, clusters) behind their null checks: the remaining argument checks ...
+int self_join_checks(const revo_gallery* g, float threshold, const char* who, const uint32_t** allow) {
+    CHECK_RC(require_threshold(1, threshold, who));
+    CHECK_RC(require_f32_rows(g, who));
+    REVO_REQUIRE(g->size < (1ll << 31), std::string(who) + ": row indices must fit in 31 bits");
+    return search_filter(g, allow);
+}
+// ... and, on the handle's device, the counters (the two-phase state stays: these calls do not write the handle's query rows),
+// prepare() (what has to be on the stream before the join and survive the workspace's regrow), the candidate workspace and the
+// join: launch(PairsJoinArgs) under the profile class <cls>_join; `what` and `advice` are the limit message's two halves
+template <class Prepare, class Launch>
+int self_join(revo_gallery* g, CandidateWs& ws, float threshold, const uint32_t* allow, const char* who, const char* cls,
+              const char* what, const char* advice, hipStream_t st, Prepare&& prepare, Launch&& launch) {
+    using namespace revo;
+    CHECK_RC(begin_counted(g, 1, who, st));
+    CHECK_RC(prepare());
+    CHECK_RC(ws.carve(ws.cap > PAIRS_WS_KEYS ? ws.cap : PAIRS_WS_KEYS, st));
+    PairsJoinArgs ja{};
+    ja.Gb = g->gb.p; ja.ldg = g->D; ja.N = g->size; ja.D = g->D; ja.gstat = g->gstat.p; ja.thr = threshold; ja.allow = allow;
+    const std::string name = who, prof = std::string(cls) + "_join";
+    return ws.join_until_it_fits(st, [&]() -> int {
+        ja.cnt = ws.cnt; ja.keys = ws.cand; ja.cap = ws.cap;
+        ProfScope ps(prof.c_str(), st);
+        return launch(ja);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)PAIRS_MAX_CAND,
+                     name + ": " + std::to_string(n_cand) + what + std::to_string(PAIRS_MAX_CAND) + advice);
+        return 0;
+    }, (name + ": the candidate count changed between two joins").c_str());
+}
+}  // namespace
+
+// ---- near-duplicate pairs of one gallery (include/revo.h revo_gallery_pairs; pairs.hip)
+extern "C" int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_pairs, "gallery_pairs: null argument");
+    const uint32_t* allow; CHECK_RC(self_join_checks(g, threshold, "gallery_pairs", &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    g->pairs.valid = false;
+    const long N = g->size;
+    const int D = g->D;
+    CandidateWs ws{g->pbuf, g->pairs.cap};
+    CHECK_RC(self_join(g, ws, threshold, allow, "gallery_pairs", "pairs", " candidate pairs exceed the limit of ",
+                       " (raise the threshold)", st, [] { return 0; },
+                       [&](const PairsJoinArgs& ja) { return launch_pairs_join(ja, st); }));
+    // fp32 re-score; the kept entries as (i << b) | j
+    const int b = row_index_bits(N);
+    { ProfScope ps("pairs_rescore", st);
+      CHECK_RC(launch_pairs_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, threshold, b, ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    CHECK_RC(ws.sort_kept("pairs_sort", 2 * b, st));
+    const unsigned long long n_kept = ws.n_kept;
+    CHECK_RC(g->pairs.idx.grow((size_t)(n_kept > 0 ? n_kept : 1) * 16, st));
+    CHECK_RC(g->pairs.score.grow((size_t)(n_kept > 0 ? n_kept : 1) * 4, st));
+    CHECK_RC(launch_pairs_emit(ws.sk, ws.sv, (long)n_kept, b, g->pairs.idx.p, g->pairs.score.p, st));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.passes, st));
+    g->pairs.n = (int64_t)n_kept;
+    g->pairs.valid = true;
+    *n_pairs = (int64_t)n_kept;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,
+                                           int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_pairs_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "gallery_pairs_read: negative start or count");
+    REVO_REQUIRE((pairs && scores) || n == 0, "gallery_pairs_read: null argument");
+    REVO_REQUIRE(g->pairs.valid, "gallery_pairs_read: no result (call revo_gallery_pairs again after the rows change)");
+    REVO_REQUIRE(start + n <= g->pairs.n, "gallery_pairs_read: range past the result's " + std::to_string(g->pairs.n) + " pairs");
+    if (n == 0) return 0;
+    REVO_ON_DEVICE(g->device);
+    CHECK_RC(copy_out(pairs, g->pairs.idx.p + start * 2, (size_t)n * 2, dst_on_device));
+    return copy_out(scores, g->pairs.score.p + start, (size_t)n, dst_on_device);
+    API_END
+}
+
+// ---- duplicate clusters of one gallery (include/revo.h revo_gallery_clusters; clusters.hip)
+extern "C" int32_t revo_gallery_clusters(revo_gallery* g, float threshold, int64_t* n_clusters, int64_t* n_members, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_clusters && n_members, "gallery_clusters: null argument");
+    const uint32_t* allow; CHECK_RC(self_join_checks(g, threshold, "gallery_clusters", &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    ClustersResult& cl = g->clusters;
+    cl.valid = false;
+    const long N = g->size;
+    const int D = g->D;
+    const int b = row_index_bits(N);
+    const size_t rows = (size_t)(N > 0 ? N : 1);
+    uint32_t *parent = nullptr, *sizes = nullptr, *hist = nullptr;
+    unsigned long long *ctr4 = nullptr, *rank = nullptr;
+    uint64_t *keys = nullptr, *keys_alt = nullptr;
+    float *vals = nullptr, *vals_alt = nullptr;
+    // the union-find and the finish step's arrays: a buffer of their own, so the candidate workspace's regrow leaves parent[] be
+    auto prepare = [&]() -> int {
+        CHECK_RC(carve_buffer(cl.ws, st, [&](Layout& l) {
+            ctr4 = l.take<unsigned long long>(4);
+            parent = l.take<uint32_t>(rows + 1); sizes = l.take<uint32_t>(rows);      // parent[N]: the error word
+            keys = l.take<uint64_t>(rows); keys_alt = l.take<uint64_t>(rows);
+            vals = l.take<float>(rows); vals_alt = l.take<float>(rows);       // (the sort moves a value with every key: unused here)
+            rank = l.take<unsigned long long>(rows);
+            hist = l.take<uint32_t>(256l * SORT_MAX_BLOCKS);
+        }));
+        CHECK_RC(cl.labels.grow(rows * 8, st));
+        return launch_clusters_init(parent, sizes, N, ctr4, st);
+    };
+    // (a second join repeats the first one's merges: parent[] is not reset between the passes)
+    auto join = [&](const PairsJoinArgs& j) -> int {
+        ClustersJoinArgs ja{}; ja.j = j; ja.parent = parent;
+        return launch_clusters_join(ja, st);
+    };
+    CandidateWs ws{g->pbuf, g->pairs.cap};
+    CHECK_RC(self_join(g, ws, threshold, allow, "gallery_clusters", "clusters", " pairs inside the rounding bound of the threshold "
+                       "exceed the limit of ", " (move the threshold)", st, prepare, join));
+    { ProfScope ps("clusters_rescore", st);
+      CHECK_RC(launch_clusters_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, threshold, parent, N, st)); }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    { ProfScope ps("clusters_finish", st);
+      CHECK_RC(launch_clusters_labels(parent, allow, N, b, cl.labels.p, sizes, keys, ctr4, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(h, ctr4, sizeof(h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[2] != 0) {
+        revo_set_error("clusters: union-find did not converge");
+        return -4;
+    }
+    const long n_mem = (long)h[0], n_cl = (long)h[1];
+    REVO_REQUIRE(n_mem <= N && n_cl <= n_mem / 2, "gallery_clusters: internal: inconsistent counts");
+    CHECK_RC(cl.off.grow((size_t)(n_cl + 1) * 8, st));
+    CHECK_RC(cl.members.grow((size_t)(n_mem > 0 ? n_mem : 1) * 8, st));
+    {
+        ProfScope ps("clusters_finish", st);
+        uint64_t* sk = nullptr; float* sv = nullptr;
+        CHECK_RC(launch_sort_keys_u64(keys, vals, keys_alt, vals_alt, n_mem, 2 * b, hist, &sk, &sv, st));
+        CHECK_RC(launch_clusters_emit(sk, n_mem, n_cl, b, rank, cl.members.p, cl.off.p, st));
+    }
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.passes, st));
+    cl.rows = N; cl.n = n_cl; cl.n_members = n_mem;
+    cl.valid = true;
+    *n_clusters = n_cl;
+    *n_members = n_mem;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, int64_t* offsets, int64_t* members,
+                                              int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_clusters_read: null handle");
+    const ClustersResult& cl = g->clusters;
+    REVO_REQUIRE(cl.valid, "gallery_clusters_read: no result (call revo_gallery_clusters again after the rows change)");
+    if (!labels && !offsets && !members) return 0;
+    REVO_ON_DEVICE(g->device);
+    if (labels && cl.rows > 0) CHECK_RC(copy_out(labels, cl.labels.p, (size_t)cl.rows, dst_on_device));
+    if (offsets) CHECK_RC(copy_out(offsets, cl.off.p, (size_t)(cl.n + 1), dst_on_device));
+    if (members && cl.n_members > 0) CHECK_RC(copy_out(members, cl.members.p, (size_t)cl.n_members, dst_on_device));
+    return 0;
+    API_END
+}
+
+// ---- range search (include/revo.h revo_search_range; range.hip)
+extern "C" int32_t revo_search_range(revo_gallery* g, const float* queries, int32_t Q, float thr, int64_t index_offset,
+                                     int64_t* n_results, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_results && (queries || Q == 0), "search_range: null argument");
+    REVO_REQUIRE(Q >= 0, "search_range: negative query count");
+    CHECK_RC(require_threshold(1, thr, "search_range"));
+    CHECK_RC(require_f32_rows(g, "search_range"));
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    g->range.valid = false;
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    // sort keys (query << (32 + b)) | (score << b) | row in 64 bits: at most 2^(32 - b) queries per chunk
+    const int b = row_index_bits(N);
+    int QC = Q < RANGE_CHUNK ? Q : RANGE_CHUNK;
+    if ((long)QC > (1l << (32 - b))) QC = (int)(1l << (32 - b));
+    int qbits = 0;
+    while ((1l << qbits) < QC) ++qbits;
+    g->drop_two_phase();
+    CHECK_RC(begin_counted(g, QC > 0 ? QC : 1, "search_range", st));
+    // offsets: off[1 + q] collects query q's count, then the prefix sums make them the CSR offsets (off[0] = 0)
+    CHECK_RC(g->range.off.grow((size_t)(Q + 1) * 8, st));
+    REVO_HIP_CHECK(hipMemsetAsync(g->range.off.p, 0, (size_t)(Q + 1) * 8, st));
+    unsigned long long* off = g->range.off.p;
+    CandidateWs ws{g->pbuf, g->range.cap};
+    long total = 0;
+    unsigned long long cand_total = 0;
+    int max_passes = 0;
+    if (N > 0 && Q > 0) {
+        const long cap0 = (long)QC * RANGE_WS_PER_QUERY;
+        CHECK_RC(ws.carve(g->range.cap > cap0 ? g->range.cap : cap0, st));
+        for (int c0 = 0; c0 < Q; c0 += QC) {
+            const int Qc = Q - c0 < QC ? Q - c0 : QC;
+            { ProfScope ps("search_prep", st);
+              CHECK_RC(launch_l2norm_rows(queries + (size_t)c0 * D, D, g->qf.p, D, g->qb.p, D, Qc, D, st, 1, g->qstat.p)); }
+            RangeJoinArgs ja{};
+            ja.Qb = g->qb.p; ja.ldq = D; ja.Gb = g->gb.p; ja.ldg = D; ja.Q = Qc; ja.N = N; ja.D = D;
+            ja.qstat = g->qstat.p; ja.gstat = g->gstat.p; ja.thr = thr; ja.allow = allow;
+            CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+                ja.cnt = ws.cnt; ja.keys = ws.cand; ja.cap = ws.cap;
+                ProfScope ps("range_join", st);
+                return launch_range_join(ja, st);
+            }, [&](unsigned long long n_cand) -> int {
+                REVO_REQUIRE(cand_total + n_cand <= (unsigned long long)RANGE_MAX_CAND,
+                             "search_range: " + std::to_string(cand_total + n_cand) + " candidates exceed the limit of " +
+                                 std::to_string(RANGE_MAX_CAND) + " (raise the threshold or search fewer queries per call)");
+                return 0;
+            }, "search_range: the candidate count changed between two passes"));
+            cand_total += ws.n_cand;
+            max_passes = ws.passes > max_passes ? ws.passes : max_passes;
+            { ProfScope ps("range_rescore", st);
+              CHECK_RC(launch_range_rescore(ws.cand, (long)ws.n_cand, g->qf.p, D, g->gf.p, D, D, thr, b, ws.cnt + 1, off + 1 + c0,
+                                            ws.kept_k, ws.kept_v, st)); }
+            CHECK_RC(ws.sort_kept("range_sort", qbits + 32 + b, st));
+            const long n_kept = (long)ws.n_kept;
+            const size_t need = (size_t)(total + n_kept > 0 ? total + n_kept : 1);
+            CHECK_RC(g->range.idx.grow_keep(need * 8, (size_t)total * 8, st));
+            CHECK_RC(g->range.score.grow_keep(need * 4, (size_t)total * 4, st));
+            CHECK_RC(launch_range_emit(ws.sk, ws.sv, n_kept, b, index_offset, g->range.idx.p + total, g->range.score.p + total, st));
+            total += n_kept;
+        }
+        CHECK_RC(launch_inclusive_sums_u64(off + 1, Q, st));
+    }
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, cand_total, max_passes, st));
+    g->range.n = total;
+    g->range.q = Q;
+    g->range.valid = true;
+    *n_results = total;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int64_t start, int64_t n, int64_t* indices,
+                                          float* scores, int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_range_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "search_range_read: negative start or count");
+    REVO_REQUIRE((indices && scores) || n == 0, "search_range_read: null argument");
+    REVO_REQUIRE(g->range.valid, "search_range_read: no result (call revo_search_range again after the rows change)");
+    REVO_REQUIRE(start + n <= g->range.n,
+                 "search_range_read: range past the result's " + std::to_string(g->range.n) + " entries");
+    REVO_ON_DEVICE(g->device);
+    if (offsets) CHECK_RC(copy_out(offsets, g->range.off.p, (size_t)(g->range.q + 1), dst_on_device));
+    if (n == 0) return 0;
+    CHECK_RC(copy_out(indices, g->range.idx.p + start, (size_t)n, dst_on_device));
+    return copy_out(scores, g->range.score.p + start, (size_t)n, dst_on_device);
+    API_END
+}
+
+// ---- search by examples: one host skeleton under revo_search_recommend (recommend.hip) and
+// revo_search_discover (discover.hip, section 4m).  name: "recommend" / "discover" (messages search_<name>, profile classes
+// <name>_sample, _pass, _rescore, _sort); tile_rows: the rows the example tile takes in the handle; n_examples: the example rows
+// that size the sample; pa: the pass's arguments (RecommendPassArgs / DiscoverPassArgs) with the search's own fields set -- the
+// skeleton sets those the two share.  normalise() fills the example tile, pass(pa, sample, st) launches the sample or the
+// candidate pass, rescore(cand, n, b, kept, out_keys, out_scores) the fp32 re-score.
+template <class PassArgs, class Normalise, class Rescore>
+static int search_by_examples(revo_gallery* g, const char* name, int tile_rows, int n_examples, PassArgs pa, int k, int has_thr,
+                              float thr, long index_offset, float* scores, long long* indices, int* counts, const uint32_t* allow,
+                              hipStream_t st, Normalise&& normalise, int (*pass)(const PassArgs&, int, hipStream_t), Rescore&& rescore) {
+    using namespace revo;
+    const long N = g->size;
+    const int D = g->D;
+    const std::string cls = name, who = "search_" + cls;
+    g->drop_two_phase();
+    CHECK_RC(begin_counted(g, tile_rows, who.c_str(), st));
+    if (N == 0) {
+        CHECK_RC(launch_topk_fill_empty(scores, indices, counts, 1, k, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    // the sample: the rows revo_search_topk_large's sample pass covers (none in a small gallery: tau = -inf or the threshold)
+    const long n_s = large_sample_rows(n_examples, N, k);
+    // candidates are rows (32-bit indices in the key array), at most N: sized once; counter [2] = allowed rows the pass met
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *tau = nullptr, *lb = nullptr;
+    CHECK_RC(ws.carve(N, st, [&](Layout& l) { tau = l.take<float>(1); lb = l.take<float>(n_s > 0 ? n_s : 1); }));
+    uint32_t* cand = (uint32_t*)ws.cand;
+    { ProfScope ps("search_prep", st);
+      CHECK_RC(normalise()); }
+    pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.D = D;
+    pa.qstat = g->qstat.p; pa.gstat = g->gstat.p; pa.allow = allow;
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        { ProfScope ps((cls + "_sample").c_str(), st);
+          if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(pass(pa, 1, st)); }
+          CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
+        ProfScope ps((cls + "_pass").c_str(), st);
+        pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = ws.cnt; pa.rows = cand; pa.cap = N;
+        return pass(pa, 0, st);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)N, who + ": more candidates than rows");
+        return 0;
+    }, (who + ": the candidate count changed between two passes").c_str()));
+    const int b = row_index_bits(N);
+    { ProfScope ps((cls + "_rescore").c_str(), st);
+      CHECK_RC(rescore(cand, (long)ws.n_cand, b, ws.cnt + 1, ws.kept_k, ws.kept_v)); }
+    CHECK_RC(ws.sort_kept((cls + "_sort").c_str(), 32 + b, st));
+    CHECK_RC(launch_recommend_emit(ws.sk, ws.sv, (long)ws.n_kept, k, b, index_offset, scores, indices, counts, st));
+    return publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.h[2] > 0 ? 1 : 0, st);   // (no allowed row: no candidate pass counted)
+}
+extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t P, int32_t Nn, int32_t k, int32_t has_thr,
+                                         float thr, int64_t index_offset, float* scores, int64_t* indices, int32_t* counts,
+                                         void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && examples && scores && indices && counts, "search_recommend: null argument");
+    REVO_REQUIRE(P >= 1, "search_recommend: needs at least one positive example");
+    REVO_REQUIRE(Nn >= 0, "search_recommend: negative count of negative examples");
+    REVO_REQUIRE((int64_t)P + Nn <= revo::RECOMMEND_MAX_EXAMPLES, "search_recommend: at most 128 examples (n_positive + n_negative)");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_recommend: k must be in [1, 1024]");
+    CHECK_RC(require_threshold(has_thr, thr, "search_recommend"));
+    CHECK_RC(require_f32_rows(g, "search_recommend"));
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const int D = g->D, E = P + Nn;
+    RecommendPassArgs pa{};
+    pa.P = P; pa.Nn = Nn;
+    auto normalise = [&]() -> int { return launch_l2norm_rows(examples, D, g->qf.p, D, g->qb.p, D, E, D, st, 1, g->qstat.p); };
+    auto rescore = [&](const uint32_t* cand, long n, int b, unsigned long long* kept, uint64_t* out_keys, float* out_scores) -> int {
+        return launch_recommend_rescore(cand, n, g->qf.p, D, P, Nn, g->gf.p, D, D, has_thr, thr, b, kept, out_keys, out_scores, st);
+    };
+    return search_by_examples(g, "recommend", E, E, pa, k, has_thr, thr, index_offset, scores, (long long*)indices, counts, allow, st,
+                              normalise, launch_recommend_pass, rescore);
+    API_END
+}
+extern "C" int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
+                                        int32_t n_pairs, int32_t k, int32_t has_thr, float thr, int64_t index_offset, float* scores,
+                                        int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts, "search_discover: null argument");
+    if (target) REVO_REQUIRE(n_pairs >= 0 && n_pairs <= revo::DISCOVER_MAX_PAIRS - 1,
+                             "search_discover: n_pairs must be in [0, 63] with a target");
+    else REVO_REQUIRE(n_pairs >= 1 && n_pairs <= revo::DISCOVER_MAX_PAIRS,
+                      "search_discover: n_pairs must be in [1, 64] without a target (context search)");
+    REVO_REQUIRE(n_pairs == 0 || (positives && negatives), "search_discover: null positives or negatives");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_discover: k must be in [1, 1024]");
+    CHECK_RC(require_threshold(has_thr, thr, "search_discover"));
+    CHECK_RC(require_f32_rows(g, "search_discover"));
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const int D = g->D;
+    const int has_target = target ? 1 : 0;
+    const int rows = discover_tile_rows(n_pairs, has_target), half = rows / 2;
+    DiscoverPassArgs pa{};
+    pa.n_pairs = n_pairs; pa.has_target = has_target;
+    auto normalise = [&]() -> int {
+        // the example tile: zero rows, then positive i -> row i, negative i -> row half + i, the target -> row half - 1
+        REVO_HIP_CHECK(hipMemsetAsync(g->qb.p, 0, (size_t)rows * D * sizeof(bf16_t), st));
+        CHECK_RC(launch_l2norm_rows(positives, D, g->qf.p, D, g->qb.p, D, n_pairs, D, st, 1, g->qstat.p));
+        CHECK_RC(launch_l2norm_rows(negatives, D, g->qf.p + (size_t)half * D, D, g->qb.p + (size_t)half * D, D, n_pairs, D, st, 1,
+                                    g->qstat.p + 2 * half));
+        if (has_target)
+            CHECK_RC(launch_l2norm_rows(target, D, g->qf.p + (size_t)(half - 1) * D, D, g->qb.p + (size_t)(half - 1) * D, D, 1, D, st,
+                                        1, g->qstat.p + 2 * (half - 1)));
+        return 0;
+    };
+    auto rescore = [&](const uint32_t* cand, long n, int b, unsigned long long* kept, uint64_t* out_keys, float* out_scores) -> int {
+        return launch_discover_rescore(cand, n, g->qf.p, D, half, n_pairs, has_target, g->gf.p, D, D, has_thr, thr, b, kept, out_keys,
+                                       out_scores, st);
+    };
+    return search_by_examples(g, "discover", rows, 2 * n_pairs + has_target, pa, k, has_thr, thr, index_offset, scores,
+                              (long long*)indices, counts, allow, st, normalise, launch_discover_pass, rescore);
+    API_END
+}
+
+// ---- multi-vector search (include/revo.h revo_search_maxsim; maxsim.hip)
+// the CSR of the handle's group ids, built for the gallery's current rows (N >= 1)
+static int maxsim_build_index(revo_gallery* g, hipStream_t st) {
+    using namespace revo;
+    const long N = g->size;
+    g->maxsim.rows = -1;
+    CHECK_RC(carve_buffer(g->maxsim.csr, st, [&](Layout& l) {
+        g->maxsim.gid = l.take<int32_t>(N); g->maxsim.off = l.take<uint32_t>(N + 1); g->maxsim.row = l.take<uint32_t>(N);
+        g->maxsim.pos = l.take<uint32_t>(N);
+    }));
+    // (scratch of the build: the candidate pipeline's buffer, carved again by the next search that uses it)
+    uint64_t *keys = nullptr, *keys_alt = nullptr; float *vals = nullptr, *vals_alt = nullptr; uint32_t* hist = nullptr;
+    unsigned long long *flags = nullptr, *meta = nullptr;
+    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+        keys = l.take<uint64_t>(N); keys_alt = l.take<uint64_t>(N); vals = l.take<float>(N); vals_alt = l.take<float>(N);
+        hist = l.take<uint32_t>(256l * SORT_MAX_BLOCKS); flags = l.take<unsigned long long>(N); meta = l.take<unsigned long long>(2);
+    }));
+    ProfScope ps("maxsim_index", st);
+    CHECK_RC(launch_maxsim_index(g->groups.p, N, keys, keys_alt, vals, vals_alt, hist, flags, meta, g->maxsim.gid, g->maxsim.off,
+                                 g->maxsim.row, g->maxsim.pos, st));
+    unsigned long long h[2] = {0, 0};
+    REVO_HIP_CHECK(hipMemcpyAsync(h, meta, sizeof(h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    REVO_REQUIRE(h[0] <= h[1] && h[1] <= (unsigned long long)N, "search_maxsim: inconsistent group index");
+    g->maxsim.groups = (long)h[0]; g->maxsim.grouped = (long)h[1]; g->maxsim.rows = N;
+    return 0;
+}
+extern "C" int32_t revo_search_maxsim(revo_gallery* g, const float* queries, int32_t n, int32_t k, int32_t has_thr, float thr,
+                                      int64_t index_offset, float* scores, int32_t* group_ids, int32_t* counts, float* part_scores,
+                                      int64_t* part_rows_out, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g, "search_maxsim: null handle");
+    REVO_REQUIRE(queries, "search_maxsim: null queries");
+    REVO_REQUIRE(scores, "search_maxsim: null scores");
+    REVO_REQUIRE(group_ids, "search_maxsim: null group_ids");
+    REVO_REQUIRE(counts, "search_maxsim: null counts");
+    REVO_REQUIRE(n >= 1 && n <= revo::MAXSIM_MAX_VECTORS, "search_maxsim: n_vectors must be in [1, 64]");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_maxsim: k must be in [1, 1024]");
+    CHECK_RC(require_threshold(has_thr, thr, "search_maxsim"));
+    CHECK_RC(require_f32_rows(g, "search_maxsim"));
+    REVO_REQUIRE(g->groups_rows >= 0, "search_maxsim: no group ids (revo_search_set_groups)");
+    REVO_REQUIRE(g->groups_rows == g->size,
+                 "search_maxsim: the group ids were set for " + std::to_string(g->groups_rows) + " rows but the gallery holds " +
+                     std::to_string(g->size) + " (set them again after appending)");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    long long* part_rows = (long long*)part_rows_out;
+    const long N = g->size;
+    const int D = g->D;
+    const int n_pad = (n + 3) / 4 * 4;
+    g->drop_two_phase();
+    CHECK_RC(begin_counted(g, n, "search_maxsim", st));
+    MaxsimGroupArgs ga{};
+    ga.n = n; ga.n_pad = n_pad; ga.lanes = maxsim_group_lanes(n_pad); ga.allow = allow; ga.D = D;
+    if (N > 0 && g->maxsim.rows != N) CHECK_RC(maxsim_build_index(g, st));
+    const long G = N > 0 ? g->maxsim.groups : 0, n_grouped = N > 0 ? g->maxsim.grouped : 0;
+    if (G == 0) {
+        // an empty gallery, or no row with a group: all padding
+        CHECK_RC(launch_maxsim_emit(ga, nullptr, nullptr, 0, k, n, index_offset, scores, group_ids, counts, part_scores, part_rows, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    REVO_REQUIRE(G < (1l << 31), "search_maxsim: too many groups");
+    const size_t s_bytes = (size_t)N * n_pad * sizeof(float);
+    if (g->maxsim.s.bytes < s_bytes && g->maxsim.s.grow(s_bytes, st) != 0) {
+        (void)hipGetLastError();
+        revo_set_error("search_maxsim: could not allocate the score workspace of " + std::to_string(s_bytes) + " bytes (rows x " +
+                       std::to_string(n_pad) + " x 4)");
+        return -3;
+    }
+    // the candidate pipeline's workspace over GROUPS (kept keys, sort buffers), and behind it the bounds and the candidate lists
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *tau = nullptr, *lb = nullptr, *ub = nullptr; uint32_t *acnt = nullptr, *cgroups = nullptr, *crows = nullptr;
+    CHECK_RC(ws.carve(G, st, [&](Layout& l) {
+        tau = l.take<float>(1); lb = l.take<float>(G); ub = l.take<float>(G); acnt = l.take<uint32_t>(G);
+        cgroups = l.take<uint32_t>(G); crows = l.take<uint32_t>(n_grouped);
+    }));
+    { ProfScope ps("search_prep", st);
+      CHECK_RC(launch_l2norm_rows(queries, D, g->qf.p, D, g->qb.p, D, n, D, st, 1, g->qstat.p));
+      REVO_HIP_CHECK(hipMemsetAsync(ws.cnt, 0, sizeof(ws.h), st)); }
+    ga.S = g->maxsim.s.p; ga.gid = g->maxsim.gid; ga.off = g->maxsim.off; ga.rows = g->maxsim.row; ga.G = G;
+    ga.qstat = g->qstat.p; ga.gstat = g->gstat.p;
+    { ProfScope ps("maxsim_pass", st);
+      MaxsimPassArgs pa{};
+      pa.Qb = g->qb.p; pa.ldq = D; pa.Gb = g->gb.p; pa.ldg = D; pa.n = n; pa.n_pad = n_pad; pa.N = N; pa.D = D; pa.allow = allow;
+      pa.S = g->maxsim.s.p;
+      CHECK_RC(launch_maxsim_pass(pa, st)); }
+    { ProfScope ps("maxsim_bounds", st);
+      CHECK_RC(launch_maxsim_bounds(ga, lb, ub, acnt, ws.cnt, st)); }
+    { ProfScope ps("maxsim_level", st);
+      CHECK_RC(launch_recommend_level(lb, (int)G, k, has_thr, thr, tau, st));
+      CHECK_RC(launch_maxsim_select(ga, n_grouped, g->maxsim.pos, ub, acnt, tau, ws.cnt, crows, cgroups, st)); }
+    // counters: [0] candidate rows, [1] kept groups, [2] groups with an allowed row, [3] candidate groups
+    REVO_HIP_CHECK(hipMemcpyAsync(ws.h, ws.cnt, sizeof(ws.h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    REVO_REQUIRE(ws.h[0] <= (unsigned long long)n_grouped && ws.h[3] <= (unsigned long long)G, "search_maxsim: more candidates than rows");
+    { ProfScope ps("maxsim_rescore", st);
+      CHECK_RC(launch_maxsim_rescore(crows, (long)ws.h[0], g->qf.p, D, n, n_pad, g->gf.p, D, D, g->maxsim.s.p, st)); }
+    { ProfScope ps("maxsim_reduce", st);
+      CHECK_RC(launch_maxsim_reduce(ga, cgroups, (long)ws.h[3], has_thr, thr, ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    ws.n_cand = ws.h[3];
+    CHECK_RC(ws.sort_kept("maxsim_sort", 64, st));   // (the score sits above all 32 bits of the group position)
+    { ProfScope ps("maxsim_emit", st);
+      CHECK_RC(launch_maxsim_emit(ga, ws.sk, ws.sv, (long)ws.n_kept, k, n, index_offset, scores, group_ids, counts, part_scores,
+                                  part_rows, st)); }
+    return publish_candidate_stats(g->xw.ctr, ws.h[0], ws.h[2] > 0 ? 1 : 0, st);
+    API_END
+}
+
+// ---- diverse search (include/revo.h revo_search_mmr; mmr.hip)
+constexpr size_t MMR_GRAM_BYTES = 256ul << 20;   // the similarity matrices of one chunk of queries
+extern "C" int32_t revo_search_mmr(revo_gallery* g, const float* queries, int32_t Q, int32_t k, int32_t C, float diversity,
+                                   int32_t has_thr, float thr, int64_t index_offset, float* scores, float* mmr_values,
+                                   int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (queries || Q == 0), "search_mmr: null argument");
+    REVO_REQUIRE(Q >= 0, "search_mmr: negative query count");
+    REVO_REQUIRE(C >= 1 && C <= revo::LARGE_K_MAX, "search_mmr: candidates must be in [1, 1024]");
+    REVO_REQUIRE(k >= 1 && k <= C, "search_mmr: k must be in [1, candidates]");
+    REVO_REQUIRE(diversity >= 0.f && diversity <= 1.f, "search_mmr: diversity must be in [0, 1] (and not NaN)");
+    CHECK_RC(require_threshold(has_thr, thr, "search_mmr"));
+    CHECK_RC(require_f32_rows(g, "search_mmr"));
+    if (Q == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const size_t per_query = (size_t)C * C * sizeof(float);
+    const int QC = (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, MMR_GRAM_BYTES / per_query));
+    float *rel = nullptr, *gram = nullptr; long long* cand = nullptr; int* n_cand = nullptr;
+    CHECK_RC(carve_buffer(g->pbuf, st, [&](Layout& l) {
+        rel = l.take<float>((size_t)Q * C); cand = l.take<long long>((size_t)Q * C); n_cand = l.take<int>(Q);
+        gram = l.take<float>((size_t)QC * C * C);
+    }));
+    // the candidates: the large-k search's own lists (it clears and fills the handle's counters, and drops the two-phase state)
+    CHECK_RC(search_topk_large(g, queries, Q, C, has_thr, thr, 0, rel, cand, n_cand, allow, st));
+    int tile = 8;
+#ifdef REVO_EXPERIMENTS
+    if (const char* e = getenv("REVO_MMR_TILE")) tile = atoi(e) == 4 ? 4 : 8;                // tile shape study (scripts/)
+#endif
+    for (int c0 = 0; c0 < Q; c0 += QC) {
+        const int Qc = Q - c0 < QC ? Q - c0 : QC;
+        MmrGramArgs ga{};
+        ga.Gf = g->gf.p; ga.ldg = g->D; ga.N = g->size; ga.D = g->D; ga.cand = cand + (size_t)c0 * C; ga.counts = n_cand + c0;
+        ga.gram = gram; ga.Q = Qc; ga.C = C; ga.tile = tile;
+        { ProfScope ps("mmr_gram", st);
+          CHECK_RC(launch_mmr_gram(ga, st)); }
+        MmrSelectArgs sa{};
+        sa.rel = rel + (size_t)c0 * C; sa.cand = ga.cand; sa.counts = ga.counts; sa.gram = gram; sa.C = C; sa.k = k;
+        sa.lam = 1.0f - diversity; sa.diversity = diversity; sa.idx_offset = index_offset;
+        sa.scores = scores + (size_t)c0 * k; sa.mmr = mmr_values ? mmr_values + (size_t)c0 * k : nullptr;
+        sa.idx = (long long*)indices + (size_t)c0 * k; sa.out_counts = counts + c0;
+        { ProfScope ps("mmr_select", st);
+          CHECK_RC(launch_mmr_select(sa, Qc, st)); }
+    }
+    return 0;
+    API_END
+}

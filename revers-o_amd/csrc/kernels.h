@@ -418,7 +418,7 @@ int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* 
                                int* out_counts, const uint32_t* allow, hipStream_t st);
 // ------------------------------------------------- candidate pipeline ----
 // Pairs, range and recommend searches: join on the 256 x 256 main loop -> counted candidate buffer,
-// fp32 re-score -> 64-bit sort keys, sort, emit.  Shared device code: candidates.h; host side: search.hip's CandidateWs.
+// fp32 re-score -> 64-bit sort keys, sort, emit.  Shared device code: candidates.h; host side: candidate_search.hip's CandidateWs.
 // ---- the sort and the prefix sum (radix_sort.hip)
 constexpr int SORT_MAX_BLOCKS = 2048;        // at most this many blocks per radix pass (the offsets scan is one workgroup)
 // ascending sort of n (key, value) entries over the low key_bits bits; cnt: 256 * SORT_MAX_BLOCKS words; the result is in

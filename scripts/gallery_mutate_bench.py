@@ -55,7 +55,7 @@ def copy_rate():
 
 
 def remove_traffic(mask):
-    """bytes revo_gallery_remove reads plus writes for this mask: the plan of search.hip's chunk loop, on the host"""
+    """bytes revo_gallery_remove reads plus writes for this mask: the plan of gallery.hip's chunk loop, on the host"""
     chunk = min(65536, max(32, (64 << 20) // (D * 4) // 32 * 32))
     m = mask.cpu()
     row_bytes = D * 4 + D * 2

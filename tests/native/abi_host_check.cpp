@@ -1,8 +1,8 @@
 // Host-side paths of the C ABI (include/revo.h) under AddressSanitizer + UBSan, with no GPU: argument validation,
 // the checkpoint name / size map of revo_vit_create, error strings, and the graceful failure of everything that
-// needs a device (status != 0 and a message, never a crash).  Built by `make -C revers-o_amd/csrc asan` (api.hip and
-// search.hip are compiled with -fsanitize=address,undefined on the host side; GPU sanitizers are not available on this
-// pool) and run by tests/test_abi.py in the CPU tier.
+// needs a device (status != 0 and a message, never a crash).  Built by `make -C revers-o_amd/csrc asan` (api.hip, gallery.hip,
+// search.hip and candidate_search.hip are compiled with -fsanitize=address,undefined on the host side; GPU sanitizers are
+// not available on this pool) and run by tests/test_abi.py in the CPU tier.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

@@ -71,8 +71,8 @@ def test_product_has_no_oracle_import():
 
 
 def test_host_paths_under_address_and_ub_sanitizers():
-    """The host code of api.hip and search.hip (argument validation, the checkpoint name / size map, error strings,
-    handle lifetime, graceful failure without a device) compiled with -fsanitize=address,undefined and driven through
+    """The host code of api.hip, gallery.hip, search.hip and candidate_search.hip (argument validation, the checkpoint
+    name / size map, error strings, handle lifetime, graceful failure without a device) compiled with -fsanitize=address,undefined and driven through
     every entry point by tests/native/abi_host_check.cpp.  (GPU sanitizers are not available on this pool: CPU build only.)"""
     import subprocess
     csrc = os.path.join(ROOT, "revers-o_amd", "csrc")

@@ -639,7 +639,7 @@ def test_config4_gallery_10m_x_1536(dev):
     ms, mi, mc = engine.merge_topk(torch.stack(parts_s), torch.stack(parts_i), k)
     assert torch.equal(mi, i) and torch.equal(ms, s) and torch.equal(mc, c)
     plan = G.search_plan(Q, k)
-    assert plan["scan256"] and plan["ksel"] == 64          # 10 M rows: the wide candidate lists (search.hip SEARCH_WIDE_ROWS)
+    assert plan["scan256"] and plan["ksel"] == 64          # 10 M rows: the wide candidate lists (gallery_internal.h SEARCH_WIDE_ROWS)
     G.close()
 
 
@@ -1051,4 +1051,39 @@ def test_index_offset_at_and_above_2_31_two_phase(dev):
         assert torch.equal(out[5][sure], ref[1][sure]) and torch.equal(out[4][sure], ref[0][sure]) and torch.equal(out[6], ref[2])
         ex = exact_plain(0)
         assert torch.equal(ex[1], ref[1][q_idx.long()]) and torch.equal(ex[0], ref[0][q_idx.long()])
+    G.close()
+
+
+@pytest.mark.parametrize("N,k", [(3000, 5), (20000, 30)])
+def test_two_phase_state_survives_pairs_and_clusters_and_is_dropped_by_every_other_search(dev, N, k):
+    """Who keeps and who drops the handle's two-phase candidates between revo_search_candidates and revo_search_finish.
+    revo_gallery_pairs and revo_gallery_clusters never write the handle's query rows, the scan workspace or the gallery
+    rows: a finish behind them returns the bits of a finish straight behind the scan.  Every search that normalises its
+    own queries into the handle (range, recommend, discover, MaxSim, MMR, large k) overwrites the rows those candidates
+    refer to and drops them: the finish is refused.  N = 3000 runs the 128 x 128 scan; N = 20000 with k = 30 the
+    256 x 256 scan with the admission margin, whose segment pointers live in the handle too."""
+    from reverso_amd import _lib
+    D, Q = 64, 4
+    g = torch.Generator(device=dev).manual_seed(4100 + N)
+    rows = torch.nn.functional.normalize(torch.randn(N, D, generator=g, device=dev), dim=1)
+    q = torch.nn.functional.normalize(torch.randn(Q, D, generator=g, device=dev), dim=1)
+    groups = (torch.arange(N, device=dev) // 4).to(torch.int32)
+    G = engine.Gallery(D, N, device=0)
+    G.add(rows)
+    assert G.search_plan(Q, k)["scan256"] == (N >= 16384)
+    G.search_candidates(q, k)
+    ref = G.search_finish(Q, k)
+    for keeps in (lambda: G.pairs(0.95), lambda: G.clusters(0.95)):
+        G.search_candidates(q, k)
+        keeps()
+        out = G.search_finish(Q, k)
+        for a, b in zip(out, ref):
+            assert torch.equal(a, b)
+    for drops in (lambda: G.search_range(q, 0.5), lambda: G.recommend(q[:2], q[2:3], k=5),
+                  lambda: G.discover(q[0], q[1:2], q[2:3], k=5), lambda: G.search_maxsim(q, groups, k=5),
+                  lambda: G.search_mmr(q, k=5), lambda: G.search(q, k=100)):
+        G.search_candidates(q, k)
+        drops()
+        with pytest.raises(_lib.RevoError, match="no matching revo_search_candidates call"):
+            G.search_finish(Q, k)
     G.close()

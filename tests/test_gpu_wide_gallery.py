@@ -170,7 +170,7 @@ def test_search_without_the_fp32_rows_L(request, keep):
 # ---- range --------------------------------------------------------------------------------------------------------------
 def _range_chunk(N):
     """The queries per candidate pass of revo_search_range.  RANGE_CHUNK is read from kernels.h; row_index_bits and the clamp
-    to 2^(32 - b) are a MIRROR of search.hip's search_range written out here, not a value the library reports (it has no
+    to 2^(32 - b) are a MIRROR of candidate_search.hip's revo_search_range written out here, not a value the library reports (it has no
     hook for it): the assertion says which regime the gallery was chosen for, and would not notice a changed clamp.  That
     the chunked call is right is what the comparison with the reference checks."""
     src = open(os.path.join(HERE, "..", "revers-o_amd", "csrc", "kernels.h")).read()
