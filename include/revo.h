@@ -66,6 +66,26 @@ int32_t revo_vit_destroy(revo_vit* vit);
 int32_t revo_vit_forward(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch, float* out,
                          int32_t normalize, void* stream);
 int32_t revo_vit_seq_len(const revo_vit* vit);
+/* REGIONS: a vector per region for one forward per image (masked attention pooling).
+ * One body forward of the batch, ln_post and the pool's logits once; then for region r of image region_image[r] the head of
+ * revo_vit_forward with its softmax restricted to the tokens the region's bitmap allows: region_bits [n_regions][ceil(S / 32)]
+ * uint32, S = revo_vit_seq_len, token s allowed iff bit s & 31 of word s >> 5 is set (the layout of revo_search_set_filter);
+ * bits at or past S are ignored.  Token 0 is the class token on towers that have one, patch (gy, gx) of the g x g grid is
+ * token use_cls + gy * g + gx.  Disallowed tokens are skipped: their rows are not read, NaN or Inf in them changes nothing.
+ *   out_global  [batch, out_dim] or NULL: exactly what revo_vit_forward writes, bit for bit.
+ *   out_regions [n_regions, out_dim]: a region's row depends on its image and its bitmap alone -- not on the other regions
+ *     of the call, their order or their number; a region that allows every token has its image's out_global row, bit for
+ *     bit.  A region that allows no token gets zeros (not normalised).
+ * region_image is a HOST array, each entry in [0, batch); region_bits is in host (bits_on_device = 0) or device memory.
+ * Host arrays are copied into a pinned buffer of the handle before the call returns: the caller may free them on return.
+ * A device bitmap is read by kernels on `stream`.  Any n_regions >= 0 (0: revo_vit_forward; out_global is required then);
+ * the regions are taken in chunks that fit a fixed workspace the handle allocates on the first call with regions.
+ * Enqueued on `stream` like a forward (a call with more than 4096 regions waits for its own earlier copies in between).
+ * Status -2 before the device is touched: negative counts, null region arrays or out_regions with n_regions > 0, an image
+ * index outside [0, batch), null handle or images, batch above max_batch. */
+int32_t revo_vit_forward_regions(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch,
+                                 const int32_t* region_image, const uint32_t* region_bits, int32_t bits_on_device,
+                                 int32_t n_regions, float* out_global, float* out_regions, int32_t normalize, void* stream);
 /* Run-time telemetry of the LayerNorm folded into the GEMMs around it (batch-sized forwards: ln_1 / ln_2 are not kernels;
  * qkv / fc1 read A = bf16(x) UN-CENTRED and apply rstd * (acc - mean * csum) + b' in their epilogues).  The form is the same
  * function as LayerNorm-then-GEMM, but its rounding error grows with |mean| / std of a row (bf16(x) spends its 8 bits on
@@ -642,6 +662,13 @@ int32_t revo_op_linear_f32(int32_t epi, const float* A, int64_t lda, const float
  * (the batch only decides how many columns a lane carries): bit-identical between a batch and its images one at a time. */
 int32_t revo_op_pool_rows(const float* x, int64_t ldx, const float* logits, int32_t batch, int32_t seq, int32_t width,
                           int32_t heads, float* u, void* stream);
+/* the same sums over a region's tokens (region_pool.hip): u[(r * heads + h) * width + c] for region r of image region_image[r]
+ * (DEVICE int32, [n_regions]), softmax and sum restricted to the tokens region_bits [n_regions][ceil(seq / 32)] (device) allows,
+ * in the order of revo_op_pool_rows restricted to them: every token allowed = that function's bits; none (or an image index
+ * outside [0, batch)) = zeros.  Disallowed rows and logits are never read. */
+int32_t revo_op_pool_rows_masked(const float* x, int64_t ldx, const float* logits, const int32_t* region_image,
+                                 const uint32_t* region_bits, int32_t n_regions, int32_t batch, int32_t seq, int32_t width,
+                                 int32_t heads, float* u, void* stream);
 int32_t revo_op_rope(void* qkv_bf16, int64_t ld, const float* cos_sin, int32_t rows, int32_t seq, int32_t width,
                      int32_t heads, void* stream);
 int32_t revo_op_attention(const void* qkv_bf16, int64_t ld, void* out_bf16, int64_t ldo, int32_t batch, int32_t seq,

@@ -40,6 +40,7 @@ SIGNATURES = {
     "revo_vit_create": (_i32, [C.POINTER(VitCfg), C.POINTER(Tensor), _i32, _i32, _i32, C.POINTER(_p)]),
     "revo_vit_destroy": (_i32, [_p]),
     "revo_vit_forward": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p]),
+    "revo_vit_forward_regions": (_i32, [_p, _p, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _i32, _p]),
     "revo_vit_seq_len": (_i32, [_p]),
     "revo_vit_stats": (_i32, [_p, C.POINTER(C.c_double), _i32, _p]),
     "revo_gallery_create": (_i32, [_i32, _i64, _i32, _i32, C.POINTER(_p)]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "revo_op_layernorm_logits": (_i32, [_p, _i64, _p, _p, _f32, _i32, _i32, _p, _i64, _p, _p, _i32, _i32, _p, _p]),
     "revo_op_linear_f32": (_i32, [_i32, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "revo_op_pool_rows": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "revo_op_pool_rows_masked": (_i32, [_p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "revo_op_rope": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p]),
     "revo_op_attention": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
     "revo_op_f32_to_bf16": (_i32, [_p, _i64, _p, _i64, _i64, _i32, _p]),

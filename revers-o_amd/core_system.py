@@ -33,6 +33,7 @@ from PIL import Image, ImageDraw, ImageFont
 
 from . import filters
 from . import preprocess as pp
+from . import regions as rg
 from . import store as st
 from .config import DEFAULT_VARIANT, available_configs, get_config
 from .engine import VitEngine
@@ -77,10 +78,12 @@ class SimpleReverso:
                  detector=None, decode_workers=None, synthetic_seed=0, region_mode="global", device_resize=False,
                  checkpoint_interval_s=30.0):
         print("🚀 Initializing Simple Revers-o...")
-        if region_mode not in ("global", "crop"):
-            raise ValueError("region_mode must be 'global' (the reference's behaviour, core_system.py:406) or 'crop'")
+        if region_mode not in ("global", "crop", "pool"):
+            raise ValueError("region_mode must be 'global' (the reference's behaviour, core_system.py:406), 'crop' or 'pool'")
         # "crop": every region is cropped to its box on the device and embedded on its own -- the
         # feature the reference leaves as a placeholder (:406 "Use global for now", :687-690)
+        # "pool": one forward per IMAGE; every region is attention-pooled over the tokens its mask covers
+        # (regions.token_masks, VitEngine.embed_regions): the mask's shape counts, not just its box
         self.region_mode = region_mode
         # True: decoded frames are uploaded as they are and squash-resized by the HIP kernel
         # (same pixels as the host PIL resize, bit for bit); False: PIL resize in the decode pool
@@ -336,10 +339,50 @@ class SimpleReverso:
         """One vector per region of one image (see _embed_regions_batch)."""
         return self._embed_regions_batch([(pil, metas)])
 
+    def _pool_bits(self, regions, kept):
+        """pool mode: the token bitmap of every kept region (uint32 [len(kept), words]).  A processed mask is pooled over
+        the tokens it covers (regions.token_masks; binarised as _region_metadata does); a region without a mask gets every
+        token, class token included -- its image's global vector bit for bit, the reference's own fallback
+        (core_system.py:367-389)."""
+        cfg = self.pe_model.cfg
+        out = np.zeros((len(kept), rg.words_per_region(cfg)), dtype=np.uint32)
+        by_shape = {}                                  # masks of one shape (the usual case: the image's) share the cell tables
+        for j, i in enumerate(kept):
+            mask = regions.mask[i] if getattr(regions, "mask", None) is not None and i < len(regions.mask) else None
+            if mask is None:
+                out[j] = rg.full_mask(cfg, include_cls=True)
+                continue
+            m = np.asarray(mask)
+            m = (m > 0.5) if np.issubdtype(m.dtype, np.floating) else (m.astype(np.uint8) != 0)
+            by_shape.setdefault(m.shape, []).append((j, m))
+        for (h, w), items in by_shape.items():
+            out[[j for j, _ in items]] = rg.token_masks(cfg, [m for _, m in items], w, h)
+        return out
+
+    def _embed_pool_batch(self, u8, bits_per_image, to_host=True):
+        """pool mode: u8 [n, 3, size, size] device frames at the model resolution, bits_per_image: a bitmap array per
+        frame.  One forward per frame, one vector per region in frame order."""
+        region_image = np.concatenate([np.full(len(b), j, dtype=np.int64) for j, b in enumerate(bits_per_image)])
+        with self._lock:
+            _, emb = self.pe_model.embed_regions(u8, region_image, np.concatenate(list(bits_per_image)), with_global=False)
+        return emb.cpu() if to_host else emb
+
+    def _frames_u8(self, pils):
+        """PIL images -> device uint8 [n, 3, size, size] at the model resolution (the pixels _embed_pils embeds)"""
+        size = self.pe_model.cfg.image_size
+        if self.device_resize:
+            frames = [torch.from_numpy(np.array(pp.to_pil(im), dtype=np.uint8)).to(self.device, non_blocking=True)
+                      for im in pils]
+            with self._lock:
+                return pp.crop_resize_device(frames, None, size)
+        u8 = torch.stack(list(self._decode_pool.map(lambda im: pp.resize_u8(im, size), pils)))
+        return u8.to(self.device, non_blocking=True)
+
     def extract_embeddings(self, image):
         """core_system.py:320-429: one forward of the full image, every kept region receives
         the global embedding (:406) with its own mask-derived metadata.  With
-        ``region_mode="crop"`` every region is embedded from its own crop instead."""
+        ``region_mode="crop"`` every region is embedded from its own crop instead, with ``region_mode="pool"`` from the
+        tokens of that one forward which its mask covers."""
         if not self.detected_regions or len(self.detected_regions) == 0:
             print("❌ No regions detected")
             return [], []
@@ -347,6 +390,11 @@ class SimpleReverso:
         kept, metas = self._region_metadata(pil, self.detected_regions)
         if self.region_mode == "crop":
             embeddings = list(self._embed_regions(pil, metas))
+        elif self.region_mode == "pool":
+            if not kept:
+                embeddings = []
+            else:
+                embeddings = list(self._embed_pool_batch(self._frames_u8([pil]), [self._pool_bits(self.detected_regions, kept)]))
         else:
             g = self._embed_pils([pil])[0]
             embeddings = [g.clone() for _ in kept]
@@ -623,7 +671,11 @@ class SimpleReverso:
         # pinned buffer behind an event), and this thread does the per-image bookkeeping of batch i-1.
         last_ckpt = time.monotonic()
         crop_mode = self.region_mode == "crop" and not use_direct_pe
-        pipelined = host_resize and not crop_mode
+        # pool mode (the simple route: detect the batch's regions, then one embed_regions per batch): like the crop mode it
+        # stores one vector per region, queued with its batch
+        pool_mode = self.region_mode == "pool" and not use_direct_pe
+        per_region = crop_mode or pool_mode
+        pipelined = host_resize and not per_region
         stage = None
         if pipelined:
             stage = [torch.zeros((B, 3, model_size, model_size), dtype=torch.uint8).pin_memory() for _ in range(NSLOT)]
@@ -654,7 +706,8 @@ class SimpleReverso:
                     det.append(None)
                     continue
                 n_reg = self.detect_regions(im, text_prompt)
-                det.append((n_reg, self._region_metadata(im, self.detected_regions)[1] if n_reg else []))
+                kept, metas = self._region_metadata(im, self.detected_regions) if n_reg else ([], [])
+                det.append((n_reg, metas, self._pool_bits(self.detected_regions, kept) if pool_mode and metas else None))
             return det
 
         def finalize(item):
@@ -674,7 +727,7 @@ class SimpleReverso:
                     failed += 1
                     continue
                 row = None
-                if dev_emb is not None and not crop_mode:
+                if dev_emb is not None and not per_region:
                     row = j if by_file else gi                # staged batches have one row per file, the others one per decoded file
                     gi += 1
                 if use_direct_pe:
@@ -683,7 +736,7 @@ class SimpleReverso:
                     log_status(f"✅ Extracted global embedding for {filename}")
                 else:
                     if det is not None:
-                        n_reg, metas = det[j]                 # crop mode: detected when the batch was queued
+                        n_reg, metas = det[j][:2]             # crop / pool mode: detected when the batch was queued
                     else:
                         n_reg = self.detect_regions(im, text_prompt)
                         metas = self._region_metadata(im, self.detected_regions)[1] if n_reg else []
@@ -699,7 +752,7 @@ class SimpleReverso:
                     m["original_region_id"] = m.get("region_id", _uuid4())
                     m["region_id"] = _uuid4()
                 batch_items.append((path, im, metas, row, hosts[j]))
-            if crop_mode:
+            if per_region:
                 store(batch_items, dev_emb, None, last)       # one vector per region, in item order (queued with the batch)
                 return
             store(batch_items, None, dev_emb, last)
@@ -771,6 +824,20 @@ class SimpleReverso:
                                                                                         [hosts[j] for j in with_regions]))
                         frames_done[it % NSLOT] = torch.cuda.Event()
                         frames_done[it % NSLOT].record()
+            elif pool_mode:
+                det = detect_batch(pils)
+                with_regions = [j for j, d in enumerate(det) if d is not None and d[1]]
+                if with_regions:
+                    with torch.cuda.device(self.device):
+                        if host_resize:
+                            u8 = torch.stack([hosts[j] for j in with_regions]).to(self.device, non_blocking=True)
+                        else:
+                            with self._lock:
+                                frames = upload_frames(slabs[it % NSLOT], [hosts[j] for j in with_regions])
+                                frames_done[it % NSLOT] = torch.cuda.Event()
+                                frames_done[it % NSLOT].record()
+                                u8 = pp.crop_resize_device(frames, None, model_size)
+                        dev_emb = self._embed_pool_batch(u8, [det[j][2] for j in with_regions], to_host=False)
             elif good:
                 if pipelined:
                     # every file of the batch has its row in the staging buffer (a failed file's row keeps whatever it

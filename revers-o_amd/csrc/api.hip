@@ -149,6 +149,12 @@ struct revo_vit {
     float2* ln_stats = nullptr;        // [rows][width / 256] (mean, M2) per 256-column slice: the folded LayerNorm's row statistics
     int ln_parts = 0;                  // width / 256 when the fold applies (width % 256 == 0, <= 6 slices), else 0
     unsigned long long* ln_tele = nullptr;   // [4] telemetry of the folded LayerNorm's consumers (kernels.h GemmArgs::lnc_tele; revo_vit_stats)
+    // region head (revo_vit_forward_regions): allocated by the first call with regions, a fixed size whatever n_regions is.
+    // REGION_CHUNK rows of the head's buffers; image indices and bitmaps of REGION_STAGE regions on the device, filled
+    // through one pinned host buffer (rg_ev: the last copy out of it)
+    float *rg_u = nullptr, *rg_att = nullptr, *rg_o = nullptr, *rg_h = nullptr, *rg_m = nullptr, *rg_feat = nullptr;
+    int32_t* rg_img = nullptr; uint32_t* rg_bits = nullptr;
+    uint32_t* rg_pin = nullptr; hipEvent_t rg_ev = nullptr; bool rg_ev_pending = false;
 
     template <class T> int dalloc(T** out, size_t count) {
         void* p = nullptr;
@@ -159,6 +165,8 @@ struct revo_vit {
     }
     ~revo_vit() {
         for (void* p : owned) (void)hipFree(p);
+        if (rg_pin) (void)hipHostFree(rg_pin);
+        if (rg_ev) (void)hipEventDestroy(rg_ev);
     }
 };
 
@@ -491,10 +499,36 @@ int gemm(const char* cls, int epi, const bf16_t* A, long lda, const bf16_t* B, l
 }
 }  // namespace
 
+// The head behind the pooled rows u [R][pool_heads][W]: value and output projection, the pool's LayerNorm and MLP, proj, L2 --
+// for the R images of a forward or for R regions (revo_vit_forward_regions).  A row's result does not depend on R or on
+// the other rows (head.hip: the skinny GEMM cuts K the same way whatever M is).
+static int pool_head_tail(revo_vit* v, int R, const float* u, float* att, float* o, float* h, float* m, float* feat_ws,
+                          float* out, int32_t normalize, hipStream_t st) {
+    using namespace revo;
+    const revo_vit_cfg& c = v->cfg;
+    const int W = c.width, D = c.out_dim, PM = v->PM, PH = c.pool_heads;
+    { ProfScope ps("gemm_pool", st);
+      // values: head h's output columns from head h's pooled row
+      CHECK_RC(launch_gemm_f32_skinny(0, u, (long)PH * W, W, v->phd, v->w_v, W, v->b_v, R, W, W, att, W, st));
+      CHECK_RC(launch_gemm_f32_skinny(0, att, W, 0, 0, v->w_po, W, v->b_po, R, W, W, o, W, st)); }
+    { ProfScope ps("layernorm", st);
+      CHECK_RC(launch_layernorm(o, W, v->pln_w, v->pln_b, c.ln_eps, R, W, h, W, 0, st)); }
+    float* feat = normalize ? feat_ws : out;
+    { ProfScope ps("gemm_pool", st);
+      CHECK_RC(launch_gemm_f32_skinny(1, h, W, 0, 0, v->w_pfc1, W, v->b_pfc1, R, PM, W, m, PM, st));
+      CHECK_RC(launch_gemm_f32_skinny(2, m, PM, 0, 0, v->w_pfc2, PM, v->b_pfc2, R, W, PM, o, W, st));
+      CHECK_RC(launch_gemm_f32_skinny(0, o, W, 0, 0, v->w_projT, W, nullptr, R, D, W, feat, D, st)); }
+    if (normalize) {
+        ProfScope ps("l2norm", st);
+        CHECK_RC(launch_l2norm_rows(feat_ws, D, out, D, nullptr, 0, R, D, st));
+    }
+    return 0;
+}
+
 // Forward of images [b0, b0 + B) of the call's batch on stream st; every workspace buffer is
 // addressed at the rows of those images.
 static int vit_forward_range(revo_vit* vv, const void* images_all, int32_t image_dtype, int b0, int B, float* out_all,
-                             int32_t normalize, hipStream_t st) {
+                             int32_t normalize, hipStream_t st, bool with_head = true) {
     const revo_vit_cfg& c = vv->cfg;
     const int W = c.width, Md = c.mlp_dim, D = c.out_dim, S = vv->S, PM = vv->PM;
     const int rows = B * S;
@@ -515,7 +549,7 @@ static int vit_forward_range(revo_vit* vv, const void* images_all, int32_t image
     w.feat = vv->feat + (size_t)b0 * D;
     const size_t img_elems = (size_t)3 * c.image_size * c.image_size;
     const void* images = (const char*)images_all + (size_t)b0 * img_elems * (image_dtype == 1 ? 1 : 4);
-    float* out = out_all + (size_t)b0 * D;
+    float* out = out_all ? out_all + (size_t)b0 * D : nullptr;
     struct FW {
         // names used by the schedule below: workspace from the view, everything else from the handle
         bf16_t *patches, *h, *qkv, *att, *mlp;
@@ -636,23 +670,10 @@ static int vit_forward_range(revo_vit* vv, const void* images_all, int32_t image
       // (the pool's logits come out of the same kernel: the normalised row is in registers there)
       const LnLogits lg{v->qk, v->ck, v->pool_logits, PH, S};
       CHECK_RC(launch_layernorm(v->x, W, v->lnpost_w, v->lnpost_b, c.ln_eps, rows, W, v->x, W, 0, st, &lg)); }
+    if (!with_head) return 0;             // revo_vit_forward_regions without out_global: the rows and the logits are all it needs
     { ProfScope ps("pool_attention", st);
       CHECK_RC(launch_pool_head_rows(v->x, W, B, S, W, PH, v->pool_logits, v->pool_u, st)); }
-    { ProfScope ps("gemm_pool", st);
-      // values: head h's output columns from head h's pooled row
-      CHECK_RC(launch_gemm_f32_skinny(0, v->pool_u, (long)PH * W, W, v->phd, v->w_v, W, v->b_v, B, W, W, v->pool_att, W, st));
-      CHECK_RC(launch_gemm_f32_skinny(0, v->pool_att, W, 0, 0, v->w_po, W, v->b_po, B, W, W, v->pool_o, W, st)); }
-    { ProfScope ps("layernorm", st);
-      CHECK_RC(launch_layernorm(v->pool_o, W, v->pln_w, v->pln_b, c.ln_eps, B, W, v->pool_h, W, 0, st)); }
-    float* feat = normalize ? v->feat : out;
-    { ProfScope ps("gemm_pool", st);
-      CHECK_RC(launch_gemm_f32_skinny(1, v->pool_h, W, 0, 0, v->w_pfc1, W, v->b_pfc1, B, PM, W, v->pool_m, PM, st));
-      CHECK_RC(launch_gemm_f32_skinny(2, v->pool_m, PM, 0, 0, v->w_pfc2, PM, v->b_pfc2, B, W, PM, v->pool_o, W, st));
-      CHECK_RC(launch_gemm_f32_skinny(0, v->pool_o, W, 0, 0, v->w_projT, W, nullptr, B, D, W, feat, D, st)); }
-    if (normalize) {
-        ProfScope ps("l2norm", st);
-        CHECK_RC(launch_l2norm_rows(v->feat, D, out, D, nullptr, 0, B, D, st));
-    }
+    CHECK_RC(pool_head_tail(vv, B, v->pool_u, v->pool_att, v->pool_o, v->pool_h, v->pool_m, v->feat, out, normalize, st));
     return 0;
 }
 
@@ -665,6 +686,85 @@ extern "C" int32_t revo_vit_forward(revo_vit* v, const void* images, int32_t ima
     REVO_ON_DEVICE(v->device);
     hipStream_t st = (hipStream_t)stream;
     return vit_forward_range(v, images, image_dtype, 0, batch, out, normalize, st);
+    API_END
+}
+
+// ------------------------------------------------------- region embeddings ----
+constexpr int REGION_CHUNK = 512;      // regions per pass of the head (its buffers: 16 MiB of pooled rows for L14)
+constexpr int REGION_STAGE = 4096;     // regions whose image indices and bitmaps are on the device at a time
+
+static int region_workspace(revo_vit* v) {
+    if (v->rg_u) return 0;
+    const revo_vit_cfg& c = v->cfg;
+    const size_t W = c.width, R = REGION_CHUNK, words = ((size_t)v->S + 31) / 32;
+    CHECK_RC(v->dalloc(&v->rg_img, (size_t)REGION_STAGE));
+    CHECK_RC(v->dalloc(&v->rg_bits, (size_t)REGION_STAGE * words));
+    CHECK_RC(v->dalloc(&v->rg_att, R * W));
+    CHECK_RC(v->dalloc(&v->rg_o, R * W));
+    CHECK_RC(v->dalloc(&v->rg_h, R * W));
+    CHECK_RC(v->dalloc(&v->rg_m, R * (size_t)v->PM));
+    CHECK_RC(v->dalloc(&v->rg_feat, R * (size_t)c.out_dim));
+    REVO_HIP_CHECK(hipHostMalloc((void**)&v->rg_pin, (size_t)REGION_STAGE * (1 + words) * 4, hipHostMallocDefault));
+    REVO_HIP_CHECK(hipEventCreateWithFlags(&v->rg_ev, hipEventDisableTiming));
+    CHECK_RC(v->dalloc(&v->rg_u, R * (size_t)c.pool_heads * W));      // last: marks the workspace complete
+    return 0;
+}
+
+extern "C" int32_t revo_vit_forward_regions(revo_vit* v, const void* images, int32_t image_dtype, int32_t batch,
+                                            const int32_t* region_image, const uint32_t* region_bits, int32_t bits_on_device,
+                                            int32_t n_regions, float* out_global, float* out_regions, int32_t normalize,
+                                            void* stream) {
+    API_BEGIN
+    // everything that can be refused is refused before the device is touched
+    REVO_REQUIRE(batch >= 0 && n_regions >= 0, "vit_forward_regions: negative batch or region count");
+    REVO_REQUIRE(n_regions == 0 || (region_image && region_bits && out_regions),
+                 "vit_forward_regions: null region_image, region_bits or out_regions with n_regions > 0");
+    for (int32_t r = 0; r < n_regions; ++r)
+        if (region_image[r] < 0 || region_image[r] >= batch) {
+            revo_set_error("requirement failed: vit_forward_regions: region " + std::to_string(r) + " names image " +
+                           std::to_string(region_image[r]) + ", outside [0, batch = " + std::to_string(batch) + ")");
+            return -2;
+        }
+    REVO_REQUIRE(v && images, "vit_forward_regions: null handle or images");
+    REVO_REQUIRE(out_global || n_regions > 0, "vit_forward_regions: null out_global with no regions: nothing to compute");
+    REVO_REQUIRE(batch >= 1 && batch <= v->max_batch, "vit_forward_regions: batch exceeds max_batch of the handle");
+    REVO_REQUIRE(image_dtype == 0 || image_dtype == 1, "vit_forward_regions: image_dtype must be 0 (f32) or 1 (u8)");
+    REVO_ON_DEVICE(v->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    if (n_regions > 0) CHECK_RC(region_workspace(v));
+    // one body forward; the global head exactly as revo_vit_forward runs it, or none
+    CHECK_RC(vit_forward_range(v, images, image_dtype, 0, batch, out_global, normalize, st, out_global != nullptr));
+    if (n_regions == 0 || v->debug_layers != -1) return 0;
+    const revo_vit_cfg& c = v->cfg;
+    const int W = c.width, D = c.out_dim, S = v->S, PH = c.pool_heads;
+    const size_t words = ((size_t)S + 31) / 32;
+    for (int64_t s0 = 0; s0 < n_regions; s0 += REGION_STAGE) {
+        const int ns = (int)std::min<int64_t>(REGION_STAGE, n_regions - s0);
+        // image indices (and host bitmaps) go through the pinned buffer: the caller's arrays are read before the call returns
+        if (v->rg_ev_pending) REVO_HIP_CHECK(hipEventSynchronize(v->rg_ev));     // the previous copy out of it
+        memcpy(v->rg_pin, region_image + s0, (size_t)ns * 4);
+        REVO_HIP_CHECK(hipMemcpyAsync(v->rg_img, v->rg_pin, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+        const uint32_t* bits = region_bits + (size_t)s0 * words;
+        if (!bits_on_device) {
+            memcpy(v->rg_pin + REGION_STAGE, bits, (size_t)ns * words * 4);
+            REVO_HIP_CHECK(hipMemcpyAsync(v->rg_bits, v->rg_pin + REGION_STAGE, (size_t)ns * words * 4, hipMemcpyHostToDevice, st));
+            bits = v->rg_bits;
+        }
+        REVO_HIP_CHECK(hipEventRecord(v->rg_ev, st));
+        v->rg_ev_pending = true;
+        for (int r0 = 0; r0 < ns; r0 += REGION_CHUNK) {
+            const int R = std::min(REGION_CHUNK, ns - r0);
+            const uint32_t* cb = bits + (size_t)r0 * words;
+            float* out = out_regions + (size_t)(s0 + r0) * D;
+            { ProfScope ps("pool_regions", st);
+              CHECK_RC(launch_pool_head_rows_masked(v->x, W, batch, S, W, PH, v->pool_logits, v->rg_img + r0, cb, R, v->rg_u, st)); }
+            CHECK_RC(pool_head_tail(v, R, v->rg_u, v->rg_att, v->rg_o, v->rg_h, v->rg_m, v->rg_feat, out, normalize, st));
+            { ProfScope ps("pool_regions", st);
+              CHECK_RC(launch_zero_empty_regions(cb, R, S, D, out, st)); }
+        }
+    }
+    return 0;
     API_END
 }
 
@@ -868,6 +968,23 @@ extern "C" int32_t revo_op_pool_rows(const float* x, int64_t ldx, const float* l
     return revo::launch_pool_head_rows(x, ldx, batch, seq, width, heads, logits, u, (hipStream_t)stream);
     API_END
 }
+extern "C" int32_t revo_op_pool_rows_masked(const float* x, int64_t ldx, const float* logits, const int32_t* region_image,
+                                            const uint32_t* region_bits, int32_t n_regions, int32_t batch, int32_t seq,
+                                            int32_t width, int32_t heads, float* u, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(n_regions >= 0 && batch >= 1 && seq >= 1 && width >= 4 && heads >= 1 && ldx >= width,
+                 "op_pool_rows_masked: sizes must be positive, ldx at least width");
+    REVO_REQUIRE(n_regions == 0 || (x && logits && region_image && region_bits && u), "op_pool_rows_masked: null argument");
+    for (int32_t r0 = 0; r0 < n_regions; r0 += 32768) {
+        const int R = std::min(32768, n_regions - r0);
+        CHECK_RC(revo::launch_pool_head_rows_masked(x, ldx, batch, seq, width, heads, logits, region_image + r0,
+                                                    region_bits + (size_t)r0 * (((size_t)seq + 31) / 32), R,
+                                                    u + (size_t)r0 * heads * width, (hipStream_t)stream));
+    }
+    return 0;
+    API_END
+}
+
 extern "C" int32_t revo_op_rope(void* qkv, int64_t ld, const float* cs, int32_t rows, int32_t seq, int32_t width,
                                 int32_t heads, void* stream) {
     API_BEGIN

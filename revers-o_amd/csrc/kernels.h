@@ -135,6 +135,13 @@ int launch_probe_qk(const float* q, const float* Wk, const float* bk, int W, int
 // u [B][H][W] = softmax-weighted sums of the fp32 ln_post rows x; the logits [B][H][S] of the probe come from the
 // ln_post kernel (launch_layernorm's LnLogits)
 int launch_pool_head_rows(const float* x, long ldx, int B, int S, int W, int H, const float* logits, float* u, hipStream_t st);
+// region_pool.hip: u [R][H][W], region r pooled over the tokens its bitmap allows (region_bits [R][ceil(S / 32)], bit s & 31 of
+// word s >> 5) of image region_image[r] (device int32); every token allowed = the bits of launch_pool_head_rows; no token
+// allowed = zeros.  At most 65535 regions per launch.
+int launch_pool_head_rows_masked(const float* x, long ldx, int B, int S, int W, int H, const float* logits,
+                                 const int* region_image, const uint32_t* region_bits, int R, float* u, hipStream_t st);
+// out [R][D]: the rows of regions without an allowed token become zeros
+int launch_zero_empty_regions(const uint32_t* region_bits, int R, int S, int D, float* out, hipStream_t st);
 // C[M][N] (+)= epi(A . Wt^T + bias) in fp32, M small; epi 0 plain, 1 exact-erf GELU, 2 C += ; group_cols > 0: output
 // columns [g * group_cols, ...) read A at A + g * a_group_stride
 int launch_gemm_f32_skinny(int epi, const float* A, long lda, long a_group_stride, int group_cols, const float* Wt, long ldw,

@@ -121,6 +121,68 @@ class VitEngine:
                                                       int(bool(normalize)), st), "revo_vit_forward")
         return out
 
+    def embed_regions(self, images, region_image, token_bits, normalize=True, with_global=True):
+        """A vector per region for one forward per image (include/revo.h, REGIONS): region ``r`` is pooled over the tokens
+        of image ``region_image[r]`` that ``token_bits[r]`` allows (``regions.token_masks``: ``[R, ceil(S / 32)]`` as a
+        uint32 / int32 numpy array, or an int32 torch tensor on the host or on this device).  ``images`` as in
+        :meth:`embed`.  Returns ``(global, regions)``: fp32 ``[B, out_dim]`` (exactly :meth:`embed`'s rows; ``None``
+        without ``with_global``) and fp32 ``[R, out_dim]`` in the caller's order.  A region that allows every token has
+        its image's global vector bit for bit, one that allows none is all zeros.  Batches above ``max_batch`` are split
+        and every region goes with its image."""
+        import numpy as np
+        _require_cuda(images, "images", self.device)
+        cfg = self.cfg
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != cfg.image_size or images.shape[3] != cfg.image_size:
+            raise ValueError(f"images must be [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(images.shape)}")
+        if images.dtype == torch.uint8:
+            kind = IMAGE_U8
+        elif images.dtype == torch.float32:
+            kind = IMAGE_F32
+        else:
+            raise ValueError("images must be uint8 or float32")
+        images = images.contiguous()
+        B, words = images.shape[0], (cfg.seq + 31) // 32
+        ri = torch.as_tensor(np.asarray(region_image.cpu() if isinstance(region_image, torch.Tensor) else region_image,
+                                        dtype=np.int64).reshape(-1))
+        R = ri.shape[0]
+        if R and (int(ri.min()) < 0 or int(ri.max()) >= B):
+            raise IndexError(f"region_image must name images of the batch, 0 <= index < {B}")
+        if isinstance(token_bits, torch.Tensor):
+            if token_bits.dtype != torch.int32:
+                raise ValueError("token_bits as a tensor must be int32 (the uint32 words reinterpreted)")
+            bits = token_bits.contiguous()
+            if bits.is_cuda:
+                _require_cuda(bits, "token_bits", self.device)
+        else:
+            bits = torch.from_numpy(np.ascontiguousarray(np.asarray(token_bits)).astype(np.uint32, copy=False).view(np.int32))
+        if bits.dim() != 2 or bits.shape[0] != R or bits.shape[1] != words:
+            raise ValueError(f"token_bits must be [{R}, {words}] (one bitmap of ceil({cfg.seq} / 32) words per region), "
+                             f"got {tuple(bits.shape)}")
+        if B == 0 or (R == 0 and not with_global):
+            return (torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None,
+                    torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device))
+        out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
+        out_r = torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device)
+        with self._lock, torch.cuda.device(self.device):
+            st = _lib.current_stream()
+            for s in range(0, B, self.max_batch):
+                e = min(B, s + self.max_batch)
+                whole = s == 0 and e == B
+                sel = None if whole else torch.nonzero((ri >= s) & (ri < e)).reshape(-1)
+                n = R if whole else int(sel.shape[0])
+                if n == 0 and not with_global:
+                    continue
+                idx = (ri if whole else ri[sel] - s).to(torch.int32).contiguous()
+                cb = bits if whole else bits[sel.to(bits.device)].contiguous()
+                dst = out_r if whole else torch.empty((n, cfg.out_dim), dtype=torch.float32, device=images.device)
+                _lib.check(self._lib.revo_vit_forward_regions(
+                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(idx) if n else None, _lib.ptr(cb) if n else None,
+                    int(cb.is_cuda), n, _lib.ptr(out_g[s:e]) if with_global else None, _lib.ptr(dst) if n else None,
+                    int(bool(normalize)), st), "revo_vit_forward_regions")
+                if not whole and n:
+                    out_r.index_copy_(0, sel.to(out_r.device), dst)
+        return out_g, out_r
+
     def ln_fold_stats(self, reset=False):
         """Telemetry of the LayerNorm folded into qkv / fc1 (include/revo.h revo_vit_stats; synchronises the current stream):
         rows whose statistics the consuming GEMMs merged since the last reset, how many of them had |mean| / std above
