@@ -1238,6 +1238,30 @@ GEMM_FORM_CASES = [
     ("forced no split-K leftover", "resid", 33000, 1024, 2048, dict(variant=1 << 17), ["256P", "128R"]),
     ("forced no ring", "rope", 577, 3072, 1024, dict(tower="L14", variant=1 << 19), ["128_64"]),
     ("forced no 192-row tiles", "resid", _L, 1024, 1024, dict(variant=1 << 3), ["256P", "128_64"]),
+    # Odd numbers of K-tiles (K = 192, 320, 1088, 2112: 3, 5, 17, 33 tiles of 64; no tower has one).  gemm256_mainloop walks K
+    # two tiles per trip and peels an odd last tile into a block of its own, with its own DMA requests, wait counts and
+    # barriers: these cases run that block in every 256-tile kernel that has one, and the 128-row kernels beside them.  N is
+    # chosen for the form (1280 / 1088 columns keep the 192-row plan and the queued stores away), never K.  The leftover
+    # rows fused into the queued-stores launch (256Q_QTAIL) need K % 256 == 0 and the folded LayerNorm's consumer reads
+    # one statistics slot per 256 columns of K (LnStats): neither exists at an odd tile count.  128_64 and 128R need
+    # K >= 512 (launch_128): 1088 is the odd count they can have.
+    ("K192 resid, 256-row persistent", "resid", _L, 1280, 192, {}, ["256P"]),
+    ("K320 resid, 256-row persistent", "resid", _L, 1280, 320, {}, ["256P"]),
+    ("K192 bf16, 256-row persistent", "bf16", _L, 1088, 192, {}, ["256P"]),
+    ("K1088 bf16, 256-row persistent", "bf16", _L, 1088, 1088, {}, ["256P"]),
+    ("K192 out-proj fold, planes out", "resid_ln:out", _L, 1024, 192, {}, ["256P_192", "LN_FOLDED", "PLANES_OUT"]),
+    ("K320 out-proj fold, planes out", "resid_ln:out", _L, 1024, 320, {}, ["256P_192", "LN_FOLDED", "PLANES_OUT"]),
+    ("K1088 fc2 planes in/out", "resid_ln:inout", _L, 1024, 1088, {}, ["256P_192", "LN_FOLDED", "PLANES_IN", "PLANES_OUT"]),
+    ("K192 gelu, queued stores", "gelu", _G, 4096, 192, {}, ["256Q"]),
+    ("K1088 gelu, queued stores", "gelu", _G, 4096, 1088, {}, ["256Q"]),
+    ("K320 gelu, queued stores + leftover rows", "gelu", _L, 4096, 320, {}, ["256Q", "128_128"]),
+    ("K320 forced one workgroup per tile", "gelu", _G, 4096, 320, dict(variant=1 << 16), ["256_TILE"]),
+    ("K1088 forced one workgroup per tile", "gelu", _G, 4096, 1088, dict(variant=1 << 16), ["256_TILE"]),
+    ("K2112 b8 fc2, 256-tile split-K", "resid", 4616, 1024, 2112, {}, ["SPLITK_256"]),
+    ("K192 b1 f32", "f32", 577, 4096, 192, {}, ["128_128"]),
+    ("K192 b1 gelu", "gelu", 577, 4096, 192, {}, ["128_128"]),
+    ("K1088 b1 gelu", "gelu", 577, 4096, 1088, {}, ["128_64"]),
+    ("K1088 b1 qkv rope", "rope", 577, 3072, 1088, dict(tower="L14"), ["128R"]),
 ] + [(f"{m}x{n}x{k} {e}", e, m, n, k, {}, [f]) for e in ("f32", "resid") for (m, n, k), f in zip(
     GEMM_CASES, ["128_128", "SKINNY_444", "SKINNY_411", "SKINNY_444", "SKINNY_411", "SKINNY_411", "SKINNY_411", "SKINNY_411"])]
 

@@ -86,12 +86,13 @@ def _queries_near(rows, groups, Q, seed=2, big_first=0):
     return q
 
 
-def _oracle_groups(gal, groups, queries, L, S, thr=None, allow=None):
+def _oracle_groups(gal, groups, queries, L, S, thr=None, allow=None, sc=None):
     """Grouping of an exhaustive fp64-accumulated scoring: (scores [Q, L, S], indices, hit_counts [Q, L],
-    group_ids [Q, L], group_counts [Q]) in the layout of Gallery.search_groups."""
-    qn = osearch.normalize_rows(queries)
-    sc = osearch.cosine_scores(gal, qn)                         # [Q, N] fp32
-    Q = qn.shape[0]
+    group_ids [Q, L], group_counts [Q]) in the layout of Gallery.search_groups.  sc: that scoring [Q, N], fp64 sums
+    rounded once to fp32, where the caller has it already (gal and queries are then not read)."""
+    if sc is None:
+        sc = osearch.cosine_scores(gal, osearch.normalize_rows(queries))     # [Q, N] fp32
+    Q = sc.shape[0]
     out = (np.full((Q, L, S), -np.inf, np.float32), np.full((Q, L, S), -1, np.int64), np.zeros((Q, L), np.int32),
            np.full((Q, L), -1, np.int32), np.zeros(Q, np.int32))
     base = groups >= 0
