@@ -1528,3 +1528,335 @@ def attention_peaked_qkv():
 # whether the per-element bound is asserted on that data (the model stays within 0.75 of it on the CPU: the teeth test)
 HUGE_LOGITS_BOUND = {c: True for c in HUGE_LOGITS_CASES}
 PEAKED_BOUND = True
+
+
+# ==================================================== the front end: patch embedding ====
+# The stage every other stage reads from: patchify (elementwise.hip patchify_kernel, and patchify_band_u8_kernel writing the
+# same bytes), the weight split (head.hip split_hi_lo_hi_kernel), the split-precision patch GEMM with gemm.hip
+# gemm_epilogue<EPI_PATCH> (position add, rows remapped past the class token) and the class-token rows (cls_rows_kernel).
+#
+# Inputs as the library receives them: conv1.weight w fp32 [W, 3, P, P], positional_embedding pos fp32 [S, W], class_embedding
+# fp32 [W] or none, images uint8 or fp32 [B, 3, H, H].  Reference, fp64: tok[b, cls + g] = sum_k x_k w[:, k] + pos[cls + g] with
+# x = (2 v - 255) / 255 for uint8 pixels v and the given value for fp32 ones, k in (channel, py, px) order; row 0 = cls + pos[0].
+#
+# What the kernels do, with u_b = U_BF16 and U = U_F32:
+#   weights     ws = fl32(w fl32(1 / 255)): two fp32 roundings, |ws - w / 255| <= 2 U |w / 255| (1 + U);
+#               hi = bf16(ws), lo = bf16(ws - hi) (the difference is exact): |ws - hi - lo| <= u_b |ws - hi| <= u_b^2 |ws|
+#   u8 images   a = 2 v - 255, an odd integer of at most 8 bits: exact in bf16; the row is (a | a) against (hi | lo)
+#   f32 images  v = fl32(255 x): one rounding, U |v|; hi = bf16(v), lo = bf16(v - hi): u_b^2 |v|; the row is (hi | hi | lo)
+#               against (hi | lo | hi): (a_hi + a_lo)(w_hi + w_lo) less the product a_lo w_lo, which is <= u_b^2 (1 + u_b)^2 |v| |ws|
+# so the operands as the MFMA sees them stand for x w up to  c_op (|a| |ws|^T)  with |a| = |2 v - 255| or |fl32(255 x)| and
+#   c_op = (u_b^2 + 2 U) (1 + 2^-6) for u8,  (3 u_b^2 + 3 U) (1 + 2^-6) for f32  (1 + 2^-6 covers the cross terms: |w / 255|
+#   against |ws|, |a_hi + a_lo| against |v|, (1 + u_b)^2).
+# Accumulation: every bf16 product is exact in fp32; the sum over all parts Kp terms, in any order, is _acc_err of the operands
+# as the MFMA sees them (zero padding columns counted: an upper bound).  Epilogue: one fp32 add, U (|acc| + |pos|).  A term
+# below fp32's normal range may be flushed: parts Kp 2^-126 (only the 1e-30 pixels of the special-value fixture come near it).
+# The class row is ONE fp32 add of two inputs: bit-exact, compared with torch.equal, not with a bound.
+PATCH_TOWERS = {"T14-56": dict(image=56, P=14, W=128, cls=True), "N14-56": dict(image=56, P=14, W=192, cls=False),
+                "B16": dict(image=224, P=16, W=768, cls=True), "L14": dict(image=336, P=14, W=1024, cls=True),
+                "G14": dict(image=448, P=14, W=1536, cls=False)}
+PATCH_C_OP = {True: (U_BF16 ** 2 + 2 * U_F32) * (1 + 2.0 ** -6), False: (3 * U_BF16 ** 2 + 3 * U_F32) * (1 + 2.0 ** -6)}
+PATCH_FIXTURES = ["random", "coherent", "special"]              # special: fp32 images only
+
+
+def _split_bf16(x32):
+    hi = x32.bfloat16()
+    return hi, (x32 - hi.float()).bfloat16()
+
+
+def _pad_cols(t, Kp):
+    return torch.nn.functional.pad(t, (0, Kp - t.shape[1]))
+
+
+class PatchCase:
+    """w fp32 [W, 3, P, P], pos fp32 [S, W], cls fp32 [W] or None, images uint8 / fp32 [B, 3, H, H], all on one device."""
+
+    def __init__(self, w, pos, cls, images):
+        self.w, self.pos, self.cls, self.images = w, pos, cls, images
+        self.W, _, self.P, _ = w.shape
+        self.B, self.G = images.shape[0], images.shape[-1] // self.P
+        self.G2, self.c = self.G * self.G, 0 if cls is None else 1
+        self.S, self.M = self.G2 + self.c, self.B * self.G2
+        self.Kreal = 3 * self.P * self.P
+        self.Kp = (self.Kreal + 63) // 64 * 64
+        self.u8 = images.dtype == torch.uint8
+        assert pos.shape == (self.S, self.W) and images.shape[-1] % self.P == 0
+        self._cols = self._parts = None
+
+    def cols(self, order="cpyx"):
+        """im2col, [M, Kreal] in the images' dtype: k in (channel, py, px) order (the kernel's); "pyxc": the mutation"""
+        if order == "cpyx" and self._cols is not None:
+            return self._cols
+        B, G, P = self.B, self.G, self.P
+        x = self.images.reshape(B, 3, G, P, G, P)
+        x = x.permute(0, 2, 4, 1, 3, 5) if order == "cpyx" else x.permute(0, 2, 4, 3, 5, 1)
+        x = x.reshape(self.M, self.Kreal)
+        if order == "cpyx":
+            self._cols = x
+        return x
+
+    def x64(self, r0=0, r1=None):
+        v = self.cols()[r0:r1].double()
+        return (2 * v - 255) / 255 if self.u8 else v
+
+    def ws(self, scale=None):
+        """the fp32 weights the split sees: fl32(w fl32(1 / 255)), [W, Kreal]"""
+        s = torch.tensor(1.0 / 255.0 if scale is None else scale, dtype=torch.float32, device=self.w.device)
+        return self.w.reshape(self.W, self.Kreal) * s
+
+    def a32(self, cols, shift=True):
+        """the fp32 value patchify rounds to bf16: 2 v - 255 (exact), or fl32(255 x)"""
+        if self.u8:
+            return 2.0 * cols.float() - 255.0 if shift else cols.float()
+        return cols * torch.tensor(255.0, dtype=torch.float32, device=cols.device)
+
+    def gemm(self, r0=0, r1=None, cols=None, ws=None, shift=True):
+        """The patch GEMM's operands as the MFMA sees them, a GemmCase (bf16 A [rows, parts Kp], B [W, parts Kp]):
+        (a | a) x (hi | lo) for u8 images, (hi | hi | lo) x (hi | lo | hi) for fp32 ones, zero padded to Kp per part."""
+        cols = self.cols()[r0:r1] if cols is None else cols[r0:r1]
+        hi, lo = (_pad_cols(t, self.Kp) for t in _split_bf16(self.ws() if ws is None else ws))
+        a = self.a32(cols, shift)
+        if self.u8:
+            ah = _pad_cols(a.bfloat16(), self.Kp)
+            return GemmCase(torch.cat([ah, ah], 1), torch.cat([hi, lo], 1), None)
+        ah, al = (_pad_cols(t, self.Kp) for t in _split_bf16(a))
+        return GemmCase(torch.cat([ah, ah, al], 1), torch.cat([hi, lo, hi], 1), None)
+
+    def pos_index(self, r0=0, r1=None):
+        m = torch.arange(r0, self.M if r1 is None else r1, device=self.pos.device)
+        return self.c + m % self.G2
+
+    def pos_rows(self, r0=0, r1=None, index=None):
+        return self.pos[self.pos_index(r0, r1) if index is None else index].double()
+
+    def tokens(self, x):
+        """the token rows of a [B, S, W] output in the GEMM's row order: [M, W]"""
+        return x.reshape(self.B, self.S, self.W)[:, self.c:, :].reshape(self.M, self.W)
+
+    def part_products(self):
+        """fp64 [M, W] per part of the K axis (u8: a.hi, a.lo; f32: a_hi.w_hi, a_hi.w_lo, a_lo.w_hi)"""
+        if self._parts is None:
+            g, Kp = self.gemm(), self.Kp
+            self._parts = [g.a[:, i * Kp:(i + 1) * Kp].double() @ g.b[:, i * Kp:(i + 1) * Kp].double().T
+                           for i in range(g.K // Kp)]
+        return self._parts
+
+
+class PatchEmbed:
+    """Token rows [r0, r1) of the GEMM's row order m = b G2 + g, i.e. output rows (b, cls + g): fp64 [rows, W]."""
+
+    @staticmethod
+    def reference(c, r0=0, r1=None):
+        return c.x64(r0, r1) @ c.w.reshape(c.W, c.Kreal).double().T + c.pos_rows(r0, r1)
+
+    @staticmethod
+    def bound(c, r0=0, r1=None):
+        g = c.gemm(r0, r1)
+        pos = c.pos_rows(r0, r1)
+        a = c.a32(c.cols()[r0:r1]).double().abs()
+        return (_acc_err(g) + U_F32 * (g.acc().abs() + pos.abs()) + PATCH_C_OP[c.u8] * (a @ c.ws().double().abs().T)
+                + g.K * 2.0 ** -126)
+
+    @staticmethod
+    def emulate(c, r0=0, r1=None):
+        return (c.gemm(r0, r1).acc(dtype=torch.float32) + c.pos_rows(r0, r1).float()).double()
+
+    @staticmethod
+    def class_rows(c):
+        """fp32 [W]: the one fp32 add of cls_rows_kernel (None without a class token)"""
+        return None if c.cls is None else c.cls.float() + c.pos[0].float()
+
+
+def _pe_sum(c, keep):
+    p = c.part_products()
+    return sum(p[i] for i in keep) + c.pos_rows()
+
+
+def _pe_stride(c):
+    """the GEMM reads patch rows at stride parts Kreal where patchify wrote them at parts Kp: the zero padding is data"""
+    if c.Kp == c.Kreal:
+        return None                            # (n/a: no padding)
+    g = c.gemm()
+    parts = g.K // c.Kp
+    flat = torch.cat([g.a.double().flatten(), torch.zeros(g.K, dtype=torch.float64, device=g.a.device)])
+    idx = torch.arange(c.M, device=g.a.device)[:, None] * (parts * c.Kreal) + torch.arange(g.K, device=g.a.device)[None, :]
+    return flat[idx] @ g.b.double().T + c.pos_rows()
+
+
+def _pe_pos(index_fn, need_cls=False, need_images=1):
+    def f(c):
+        if (need_cls and not c.c) or c.B < need_images:
+            return None
+        m = torch.arange(c.M, device=c.pos.device)
+        return c.gemm().acc() + c.pos_rows(index=index_fn(c, m))
+    return f
+
+
+def _pe_row_m(c):
+    """the token of GEMM row m stored at output row m, not (m / G2) S + cls + m % G2; the class rows are written afterwards
+    and what no store reaches is taken as zero"""
+    if not c.c:
+        return None                            # (n/a: without a class token the two agree)
+    out = torch.zeros(c.B * c.S, c.W, dtype=torch.float64, device=c.pos.device)
+    out[:c.M] = c.gemm().acc() + c.pos_rows()
+    out[::c.S] = PatchEmbed.class_rows(c).double()
+    return c.tokens(out)
+
+
+def _pe_no_shift(c):
+    return c.gemm(shift=False).acc() + c.pos_rows() if c.u8 else None
+
+
+# Asserted on every fixture: wrong rows, wrong order, wrong scale.
+PatchEmbed.MUTATIONS = [
+    ("Kp padding read as data (patch rows at stride Kreal)", _pe_stride, 3.0),
+    ("pos of the neighbouring token", _pe_pos(lambda c, m: c.c + (m % c.G2 + 1) % c.G2), 3.0),
+    ("pos row g instead of cls + g", _pe_pos(lambda c, m: m % c.G2, need_cls=True), 3.0),
+    ("pos indexed by cls + m % S instead of cls + m % G2", _pe_pos(lambda c, m: (c.c + m % c.S) % c.S, True, 2), 3.0),
+    ("output row m instead of the remapped row", _pe_row_m, 3.0),
+    ("(c, py, px) order taken as (py, px, c)", lambda c: c.gemm(cols=c.cols("pyxc")).acc() + c.pos_rows(), 3.0),
+    ("x = v / 255 without the 2 v - 255 shift", _pe_no_shift, 3.0),
+    ("1 / 255 rounded to bf16", lambda c: c.gemm(ws=c.ws(float(torch.tensor(1 / 255.0).bfloat16()))).acc() + c.pos_rows(), 3.0),
+]
+# A dropped low part is u_b^2-small per term.  With random weights and pixels the dropped terms add incoherently and barely
+# clear the rigorous (linear in the term count) accumulation term: about 6 x the bound on P14 / W1024 u8, 2.4 on P16 / W768
+# fp32 images.  Asserted on the coherent fixtures, where every dropped term has one sign; printed on the others.
+PatchEmbed.PART_MUTATIONS = [
+    ("the weights' lo part dropped", lambda c: _pe_sum(c, [0] if c.u8 else [0, 2]), 3.0),
+    ("the images' lo part dropped", lambda c: None if c.u8 else _pe_sum(c, [0, 1]), 3.0),
+    ("w / 255 rounded to bf16 before the split", lambda c: c.gemm(ws=c.ws().bfloat16().float()).acc() + c.pos_rows(), 3.0),
+]
+
+
+def above_bf16(t, frac=0.45):
+    """positive fp32 values moved to `frac` of a bf16 ulp above the bf16 value below them"""
+    trunc = (t.float().contiguous().view(torch.int32) & -65536).view(torch.float32)
+    return (trunc.double() + frac * bf16_ulp(trunc)).float()
+
+
+def patch_weights(tower, fixture, seed, device="cpu", grid=None):
+    """(w, pos, cls) of a tower's front end.  random: the synthetic initialiser's distributions (N(0, 0.02^2) weights,
+    N(0, 1 / W) pos and cls).  coherent: positive weights whose w / 255 sits 0.45 of a bf16 ulp above a bf16 value (every
+    lo part has one sign).  grid: patches per side when the test cuts the image down (the teeth test)."""
+    t = PATCH_TOWERS[tower]
+    W, P = t["W"], t["P"]
+    G = grid or t["image"] // P
+    g = torch.Generator(device=device).manual_seed(seed)
+    w = torch.randn(W, 3, P, P, generator=g, device=device) * 0.02
+    if fixture == "coherent":
+        w = (above_bf16((w.abs() + 1e-3) / 255).double() * 255).float()
+    pos = torch.randn(G * G + int(t["cls"]), W, generator=g, device=device) * W ** -0.5
+    cls = torch.randn(W, generator=g, device=device) * W ** -0.5 if t["cls"] else None
+    return w, pos, cls
+
+
+def patch_images(tower, fixture, u8, B, seed, device="cpu", grid=None):
+    """random: uniform bytes, or uniform fp32 in [-1, 1).  coherent: bytes >= 128 (a > 0), or fp32 pixels whose 255 x sits
+    0.45 of a bf16 ulp above a bf16 value in [128, 255].  special (fp32): the uint8 lattice (2 v - 255) / 255 with exact 0,
+    +-1, off-lattice values, values outside [-1, 1] and values around 1e-30 mixed in; patch 0 of image 0 all zero, patch 1
+    all around 1e-30."""
+    t = PATCH_TOWERS[tower]
+    P = t["P"]
+    side = (grid or t["image"] // P) * P
+    g = torch.Generator(device=device).manual_seed(seed + 1)
+    shape = (B, 3, side, side)
+    if u8:
+        assert fixture != "special"
+        return torch.randint(128 if fixture == "coherent" else 0, 256, shape, generator=g, device=device, dtype=torch.uint8)
+    r = torch.rand(shape, generator=g, device=device)
+    if fixture == "random":
+        return r * 2 - 1
+    if fixture == "coherent":
+        return (above_bf16(r * 127 + 128).double() / 255).float()
+    v = torch.randint(0, 256, shape, generator=g, device=device).float()
+    x = (2 * v - 255) / 255
+    kind = torch.randint(0, 8, shape, generator=g, device=device)
+    sign = torch.sign(r - 0.5)
+    x = torch.where(kind == 1, torch.zeros_like(x), x)
+    x = torch.where(kind == 2, sign, x)                              # +-1
+    x = torch.where(kind == 3, r * 2 - 1, x)                         # off the lattice
+    x = torch.where(kind == 4, sign * (1 + 3 * r), x)                # outside [-1, 1]
+    x = torch.where(kind == 5, sign * 1e-30 * (1 + r), x)
+    x[0, :, :P, :P] = 0.0
+    x[0, :, :P, P:2 * P] = (sign * 1e-30 * (1 + r))[0, :, :P, P:2 * P]
+    return x
+
+
+def patch_case(tower, fixture, u8, B, seed=0, device="cpu", grid=None):
+    return PatchCase(*patch_weights(tower, fixture, seed, device, grid), patch_images(tower, fixture, u8, B, seed, device, grid))
+
+
+# The CPU teeth cases: (tower, patches per side, images) -- the real P, W and Kp with the grid cut to a few hundred rows
+# and at least two images.
+PATCH_TEETH_CASES = [("T14-56", 4, 12), ("N14-56", 4, 12), ("B16", 10, 3), ("L14", 10, 2), ("G14", 10, 2)]
+
+
+def patch_gemm_form(M, N, K):
+    """The launch form gemm.hip launch_t<EPI_PATCH> takes, restated: use_256 (M >= 1024, N >= 256, at least 100 tiles of
+    256 x 256), then the persistent kernel above 256 tiles; else launch_128's choice.  No skinny form, no tail split, no
+    split-K and no 192-row plan for this epilogue (launch_t excludes them with `if constexpr`)."""
+    up = lambda a, b: -(-a // b)
+    t256 = up(M, 256) * up(N, 256)
+    if M >= 1024 and N >= 256 and t256 >= 100:
+        return "256P" if K >= 128 and t256 > 256 else "256_TILE"
+    if up(M, 128) * up(N, 128) <= 384 and K >= 512 and N % 64 == 0:
+        return "128R" if up(M, 128) * up(N, 64) <= 256 else "128_64"
+    return "128_128"
+
+
+def patch_band(tower, u8, B, gather=False):
+    """whether launch_patchify takes patchify_band_u8_kernel (u8, side % 16 == 0, B G >= 64, not forced off)"""
+    t = PATCH_TOWERS[tower]
+    return bool(u8 and t["image"] % 16 == 0 and B * (t["image"] // t["P"]) >= 64 and not gather)
+
+
+# Every kernel launch_gemm can send EPI_PATCH through.  gemm.hip compiles the epilogue into gemm_epilogue (gemm128_kernel at
+# 128 x 128 and 128 x 64, gemm128r_kernel) and three 256-row kernels; of those, gemm256pp_kernel (phase groups, time stamps)
+# exists in the experiment build only and is entered only when a script sets phase groups or a stamp buffer, so no forward
+# reaches it.  The 192-row plan, split-K and the tail split are EPI_RESID_F32's, the queued stores the bf16 epilogues'.
+PATCH_FORMS = ["128R", "128_64", "128_128", "256_TILE", "256P"]
+
+
+def _patch_form_cases():
+    """(tower, fixture, u8, B, REVO_PATCHIFY_GATHER, form): the GPU cases of tests/test_gpu_patch_embed.py.  Batches per tower:
+    one image; either side of the band-patchify condition B G >= 64 (u8, and the band batch again with the gather form
+    forced); the largest batch of each 128-row form and the first of the next; either side of use_256 (B16 43 | 44, L14
+    10 | 11, G14 4 | 5); the smallest batch on the persistent kernel, which then walks 264 tiles with 256 workgroups (B16 112:
+    86 x 3 tiles, L14 29: 66 x 4, G14 11: 44 x 6) and L14's benchmark batch of 64.  B16 has 196 rows per image and no K
+    padding: every tile of every form holds an image boundary.  The Tiny towers (W < 256: ring kernel only) run the gather
+    patchify (56 % 16 != 0) with K padded 588 -> 640."""
+    u, f = True, False
+    rows = {
+        "T14-56": [("random", u, 1, "128R"), ("random", u, 5, "128R"), ("random", f, 1, "128R"), ("random", f, 5, "128R"),
+                   ("coherent", u, 5, "128R"), ("coherent", f, 5, "128R"), ("special", f, 5, "128R")],
+        "N14-56": [("random", u, 1, "128R"), ("random", u, 5, "128R"), ("random", f, 1, "128R"), ("random", f, 5, "128R"),
+                   ("coherent", u, 5, "128R"), ("coherent", f, 5, "128R"), ("special", f, 3, "128R")],
+        "B16": [("random", u, 1, "128R"), ("random", u, 4, "128R"), ("random", u, 5, "128R"), ("random", u, 5, "128R", True),
+                ("random", u, 13, "128R"), ("random", u, 14, "128_64"), ("random", u, 41, "128_64"), ("random", u, 43, "128_128"),
+                ("random", u, 44, "256_TILE"), ("random", u, 112, "256P"),
+                ("random", f, 1, "128R"), ("random", f, 14, "128_64"), ("random", f, 43, "128_128"),
+                ("random", f, 44, "256_TILE"), ("random", f, 112, "256P"),
+                ("coherent", u, 5, "128R"), ("coherent", u, 44, "256_TILE"), ("coherent", f, 5, "128R"),
+                ("coherent", f, 44, "256_TILE"), ("special", f, 2, "128R")],
+        "L14": [("random", u, 1, "128R"), ("random", u, 2, "128R"), ("random", u, 3, "128R"), ("random", u, 3, "128R", True),
+                ("random", u, 4, "128_64"), ("random", u, 10, "128_64"), ("random", u, 11, "256_TILE"),
+                ("random", u, 29, "256P"), ("random", u, 64, "256P"),
+                ("random", f, 1, "128R"), ("random", f, 4, "128_64"), ("random", f, 10, "128_64"),
+                ("random", f, 11, "256_TILE"), ("random", f, 29, "256P"),
+                ("coherent", u, 3, "128R"), ("coherent", u, 11, "256_TILE"), ("coherent", f, 3, "128R"),
+                ("coherent", f, 11, "256_TILE"), ("special", f, 2, "128R")],
+        "G14": [("random", u, 1, "128R"), ("random", u, 2, "128_64"), ("random", u, 2, "128_64", True),
+                ("random", u, 4, "128_64"), ("random", u, 5, "256_TILE"), ("random", u, 11, "256P"),
+                ("random", f, 1, "128R"), ("random", f, 4, "128_64"), ("random", f, 5, "256_TILE"), ("random", f, 11, "256P"),
+                ("coherent", u, 2, "128_64"), ("coherent", u, 5, "256_TILE"), ("coherent", f, 2, "128_64"),
+                ("coherent", f, 5, "256_TILE"), ("special", f, 1, "128R")],
+    }
+    return [(tower, r[0], r[1], r[2], len(r) > 4, r[3]) for tower, rs in rows.items() for r in rs]
+
+
+PATCH_FORM_CASES = _patch_form_cases()
+
+
+def patch_case_id(case):
+    tower, fixture, u8, B, gather, form = case
+    return f"{tower} {fixture} {'u8' if u8 else 'f32'} b{B}{' gather' if gather else ''}"

@@ -54,7 +54,8 @@ def test_tiny_vit_layer_by_layer(dev, fname, cname):
         assert err <= 3e-2 * np.abs(ref).max(), (name, err, np.abs(ref).max())
     if cfg.use_cls:      # the class-token row is exactly cls + pos[0] (fp32 adds, no matmul)
         ref0 = (sd["visual.class_embedding"] + sd["visual.positional_embedding"][0]).numpy()
-        assert np.abs(taps["embed"][:, 0].cpu().numpy() - ref0[None]).max() <= 1e-6
+        got0 = taps["embed"][:, 0].cpu().numpy()
+        assert np.array_equal(got0, np.broadcast_to(ref0[None], got0.shape))
     emb = eng.embed(img).cpu().numpy()
     ref = gold["embedding"]
     assert_embeddings_match(emb, ref, what=cname)

@@ -8,7 +8,9 @@ bound is per element, so the large attention shapes are checked on a sample of (
 with M cut to a few hundred rows; the rounding-direction statistic and the coverage of the launch-form record are checked
 here too.  The planted high-dynamic-range attention cases (kb.ATTENTION_HDR_CASES) are checked head by head against a model
 of the kernel's optimistic softmax: the predicted move schedule is the stated one, and every way of getting a move wrong
-leaves the bound."""
+leaves the bound.  The patch embedding (kb.PatchEmbed) runs at every tower's patch size, width and padded K with the grid cut
+to a few hundred rows of two or more images: the index, order and scale mutations on every fixture, the dropped low parts on
+the coherent fixtures (on random data they add incoherently and are printed only)."""
 import pytest
 import torch
 
@@ -268,6 +270,74 @@ def test_splitk_resid_ln_bound_has_teeth(case):
     muts.append(("a plane dropped before the normalisation",
                  H.h_reference(G.reference(c, kb._acc_drop_plane(c)).float(), eps), 3.0))
     _check("splitk ln h", label, {}, H.h_reference(x_new, eps), H.h_bound(x_new, eps), H.h_emulate(x_new, eps), muts)
+
+
+def _patch_teeth_params():
+    return [(tower, grid, B, fixture, u8) for tower, grid, B in kb.PATCH_TEETH_CASES for fixture in kb.PATCH_FIXTURES
+            for u8 in (True, False) if not (u8 and fixture == "special")]
+
+
+@pytest.mark.parametrize("tower,grid,B,fixture,u8", _patch_teeth_params(),
+                         ids=[f"{t} {f} {'u8' if u else 'f32'}" for t, _, _, f, u in _patch_teeth_params()])
+def test_patch_embed_bound_has_teeth(tower, grid, B, fixture, u8):
+    c = kb.patch_case(tower, fixture, u8, B, seed=7, grid=grid)
+    assert c.B >= 2 and 150 <= c.M <= 400 and c.Kp == (kb.PATCH_TOWERS[tower]["P"] ** 2 * 3 + 63) // 64 * 64
+    P = kb.PatchEmbed
+    ref, bound = P.reference(c), P.bound(c)
+    label = f"{tower} {fixture} {'u8' if u8 else 'f32'} images"
+    parts = [(name, f(c), need) for name, f, need in P.PART_MUTATIONS]
+    muts = [(name, f(c), need) for name, f, need in P.MUTATIONS]
+    if fixture == "coherent":
+        g = c.gemm()
+        lo_w = g.b[:, c.Kp:c.Kp + c.Kreal].float()
+        assert (lo_w > 0).all() and (c.a32(c.cols()) > 0).all()      # every dropped term has one sign
+        if not u8:
+            assert (g.a[:, 2 * c.Kp:2 * c.Kp + c.Kreal].float() > 0).all()
+        muts = muts + parts
+    else:
+        print(f"[patch embed {label}] not asserted (incoherent): "
+              + "; ".join(f"{n}: {'n/a' if m is None else format(kb.ratio(m, ref, bound), '.3g')}" for n, m, _ in parts))
+    if fixture == "special":
+        x = c.images
+        assert (x == 0).any() and (x == 1).any() and (x == -1).any() and (x.abs() > 1).any()
+        assert ((x.abs() > 0) & (x.abs() < 1e-29)).any()
+    _check("patch embed", label, {}, ref, bound, P.emulate(c), muts)
+    if c.cls is not None:                                             # one fp32 add of two inputs: the rounded exact sum
+        assert torch.equal(P.class_rows(c), (c.cls.double() + c.pos[0].double()).float())
+
+
+def test_every_patch_gemm_launch_form_has_a_gpu_case():
+    """The GPU cases of the patch embedding (kb.PATCH_FORM_CASES): each states the launch form that gemm.hip's rule
+    (kb.patch_gemm_form) gives its shape; for uint8 and for fp32 images they cover every kernel the launcher can send
+    EPI_PATCH through; every tower has a one-image forward, and the three product towers a batch just under and one just
+    at use_256, the first batch on the persistent kernel, and uint8 batches on both sides of the band-patchify condition
+    with the first band batch also forced to the gather form."""
+    cases = kb.PATCH_FORM_CASES
+    assert len(set(cases)) == len(cases)
+    forms = {}                                                        # (tower, u8) -> {batch: form}
+    for tower, fixture, u8, B, gather, form in cases:
+        t = kb.PATCH_TOWERS[tower]
+        M, Kp = B * (t["image"] // t["P"]) ** 2, (3 * t["P"] ** 2 + 63) // 64 * 64
+        assert form == kb.patch_gemm_form(M, t["W"], (2 if u8 else 3) * Kp), (tower, B)
+        assert not gather or kb.patch_band(tower, u8, B), "the gather form is forced only where the band form would run"
+        forms.setdefault((tower, u8), {})[B] = form
+    for u8 in (True, False):
+        assert {f for (_, u), d in forms.items() if u == u8 for f in d.values()} == set(kb.PATCH_FORMS)
+    for (tower, u8), d in forms.items():
+        assert 1 in d
+        if tower not in ("B16", "L14", "G14"):
+            continue
+        at256 = min(B for B, f in d.items() if f == "256_TILE")
+        assert d[at256 - 1] in ("128_64", "128_128")
+        t = kb.PATCH_TOWERS[tower]
+        G2, K = (t["image"] // t["P"]) ** 2, (2 if u8 else 3) * ((3 * t["P"] ** 2 + 63) // 64 * 64)
+        first_p = min(B for B, f in d.items() if f == "256P")         # the smallest batch on the persistent kernel
+        assert kb.patch_gemm_form((first_p - 1) * G2, t["W"], K) == "256_TILE"
+        if u8:
+            band = min(B for B in d if kb.patch_band(tower, True, B))
+            assert band - 1 in d and not kb.patch_band(tower, True, band - 1)
+            assert (tower, "random", True, band, True, d[band]) in cases
+    assert forms[("L14", True)][10] == "128_64" and forms[("L14", True)][11] == "256_TILE"
 
 
 def test_bf16_rounding_direction_statistic_has_teeth():
