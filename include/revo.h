@@ -254,6 +254,38 @@ int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64
 int32_t revo_gallery_clusters(revo_gallery* g, float threshold, int64_t* n_clusters, int64_t* n_members, void* stream);
 int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, int64_t* offsets, int64_t* members,
                                    int32_t dst_on_device);
+/* ---- exact kNN graph: every row's k nearest other rows (the database's "distance matrix" query; no counterpart in the
+ * reference's own code)
+ * KNN.  The vertices are the rows that the handle's filter allows (revo_search_set_filter, with its lifecycle: a filter set
+ * for another gallery size gives status -2).  score(i, j) is the PAIRS score: the one fma chain over the two fp32 master rows,
+ * symmetric bit for bit; wherever revo_gallery_pairs returns (i, j), the two calls give the same bits.  For every allowed row i
+ * the result is the best k allowed rows j != i, ordered by (score desc, index asc) and, with has_threshold, cut at score >=
+ * threshold: exactly what an exhaustive fp32 scoring of the allowed rows gives.  Row i itself is never returned; rows identical
+ * to it at other indices are, index-ascending.  Fewer than k qualifying rows leave the tail at -inf / -1, the number found in
+ * counts[i]; a row the filter excludes has counts 0 and an empty list, and it is nobody's neighbour.  Two calls give
+ * identical bytes: neither the level estimate, nor the workspace size, nor the number of join passes, nor the order of the
+ * device's appends changes a byte.
+ * How: the PAIRS join with a level per row.  A pass of all rows against a sample of at most 8 192 rows estimates, per row, a
+ * level that a few times k rows reach; the join keeps pair (i, j) when its bf16 score is within the certificate's rounding
+ * bound of the lower of the two levels; the candidates are re-scored in fp32, sorted by row on the device, and every row takes
+ * the best k of its entries.  A row is certified when none of its candidates was dropped for want of workspace and it has k
+ * entries at or above its level (or its level is the threshold / -inf); every other row is answered by an exhaustive fp32
+ * scoring of the allowed rows, on the device, in batches.  The estimate is never trusted: it decides speed only.  A gallery of
+ * mostly identical rows (each of n duplicates has n - 1 equal partners) is therefore slow -- one pass over the fp32 rows
+ * per row -- but correct.
+ * Limits: 1 <= k <= 64; needs the fp32 master rows (keep_f32 = 0: status -2) and row indices below 2^31.  A NaN threshold, k
+ * out of range, a null handle or a null n_rows give status -2 before the device is touched.  *n_rows receives the gallery
+ * size; an empty gallery or a filter that allows no row is not an error.  SYNCHRONOUS on `stream`, like revo_gallery_pairs.
+ * revo_search_stats after it: slot 3 = candidates re-scored in fp32, slot 6 = rows answered by the exhaustive fallback,
+ * slot 7 = join passes run (1; 0 for an empty gallery), every other slot 0.
+ * revo_gallery_knn_read copies rows [start, start + n) of the result to indices ([n][k] int64), scores ([n][k] fp32) and
+ * counts ([n] int32), host or device memory (dst_on_device); each of the three pointers may be NULL independently.  The
+ * result lives in the handle: it stays valid across revo_gallery_pairs, revo_gallery_clusters and revo_search_range, and
+ * their results across it; append, clear, remove and update invalidate it: after one, with no result, or for a range past
+ * the end, _read gives status -2. */
+int32_t revo_gallery_knn(revo_gallery* g, int32_t k, int32_t has_threshold, float threshold, int64_t* n_rows, void* stream);
+int32_t revo_gallery_knn_read(revo_gallery* g, int64_t start, int64_t n, int64_t* indices, float* scores, int32_t* counts,
+                              int32_t dst_on_device);
 /* ---- range search: every row above a threshold, per query (the reference's score_threshold without its limit,
  * core_system.py:659-664)
  * RANGE.  For each query q the result is exactly the rows the handle's filter allows (revo_search_set_filter, with its
@@ -497,7 +529,8 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
  * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_gallery_clusters see CLUSTERS, after revo_search_range see RANGE,
- * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM. */
+ * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM, after
+ * revo_gallery_knn see KNN. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */
@@ -587,6 +620,11 @@ int32_t revo_search_set_mode(revo_gallery* g, int32_t mode);
 /* rows per chunk of revo_gallery_remove (rounded up to a multiple of 32, at most 65536; 0 = the default, 64 MB of fp32 rows):
  * tests cross many chunk boundaries with a small gallery.  Same result for every value. */
 int32_t revo_debug_set_remove_chunk(int64_t rows);
+/* revo_gallery_knn's paths (tests hold every one of them to the same bytes; speed only): cap_keys = candidate keys its
+ * workspace holds (0 = the default; small enough and keys are dropped, their rows take the fallback); level_mode 0 = the
+ * estimate, 1 = every level -inf (or the threshold), 2 = every level +2.0: nothing is a candidate and every row falls back,
+ * 3 = the sample-derived level raised by a fixed 0.05: some rows come up short and some do not. */
+int32_t revo_debug_set_knn(int64_t cap_keys, int32_t level_mode);
 /* phase groups of the persistent 256 x 256 GEMM (an experiment, measured in round 5 and not adopted): 0 / 1 = off (all
  * workgroups in step), 2..4 = that many groups, a workgroup of group g doing the first (g + 1) / groups of its first tile at the start and the
  * rest of that tile last.  Result-preserving (bit-identical). */

@@ -1194,6 +1194,39 @@ class SimpleReverso:
                 rows = st.largest_first(rows)
             return self._duplicates_report(db, rows, similarity_threshold)
 
+    def similarity_graph(self, max_neighbors=5, similarity_threshold=None, query_filter=None):
+        """Every stored region's ``max_neighbors`` (at most 64) most similar other regions in the loaded database, cut at
+        ``similarity_threshold`` if given (``GalleryStore.neighbor_graph``: the exact kNN graph, a level per region rather
+        than the one threshold of :meth:`find_duplicates`).  ``query_filter`` restricts both ends to the points a
+        Qdrant-style payload filter selects.  Returns ``(text, graph)``: ``graph`` has one entry per region, in storage
+        order: ``{"filename", "image_source", "bbox", "id", "neighbors": [{"filename", "image_source", "id", "score"}]}``,
+        neighbours best first."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        try:
+            with self._lock:
+                db = self.vector_db
+                g = db.neighbor_graph(limit=int(max_neighbors), score_threshold=similarity_threshold, query_filter=query_filter)
+                payload_of = {i: p for i, p in zip(db.ids, db.payloads)}
+        except Exception as e:
+            return f"❌ Error building the similarity graph: {str(e)}", []
+        out = []
+        for i in g.ids:
+            p = payload_of[i]
+            out.append({"filename": p.get("filename", "Unknown"), "image_source": p.get("image_source", ""), "bbox": p.get("bbox"),
+                        "id": i, "neighbors": []})
+        for a, b, s in zip(g.offsets_row.tolist(), g.offsets_col.tolist(), g.scores.tolist()):
+            nb = out[b]
+            out[a]["neighbors"].append({"filename": nb["filename"], "image_source": nb["image_source"], "id": nb["id"],
+                                        "score": float(s)})
+        if not out:
+            return "No regions to relate", []
+        text = f"🎯 Neighbours of {len(out)} regions (up to {int(max_neighbors)} each):\n\n"
+        for n, it in enumerate(out):
+            near = ", ".join(f"{m['filename']} {m['score']:.3f}" for m in it["neighbors"]) or "none"
+            text += f"{n + 1}. {it['filename']}: {near}\n"
+        return text, out
+
     def delete_images(self, image_sources=None, query_filter=None):
         """Remove stored regions from the loaded database, in place: every region of the source images ``image_sources``
         (one path or a list; payload key ``image_source``) or every region a Qdrant-style ``query_filter`` selects (both

@@ -1,4 +1,4 @@
-// C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, range, recommend,
+// C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, kNN, range, recommend,
 // discover, MaxSim and MMR, with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
 #include <algorithm>
 
@@ -238,6 +238,154 @@ extern "C" int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, 
     if (labels && cl.rows > 0) CHECK_RC(copy_out(labels, cl.labels.p, (size_t)cl.rows, dst_on_device));
     if (offsets) CHECK_RC(copy_out(offsets, cl.off.p, (size_t)(cl.n + 1), dst_on_device));
     if (members && cl.n_members > 0) CHECK_RC(copy_out(members, cl.members.p, (size_t)cl.n_members, dst_on_device));
+    return 0;
+    API_END
+}
+
+// ---- exact kNN graph of one gallery (include/revo.h revo_gallery_knn; knn.hip)
+#ifdef REVO_EXPERIMENTS
+static long g_knn_cap_keys = 0;
+static int g_knn_level_mode = 0;
+extern "C" int32_t revo_debug_set_knn(int64_t cap_keys, int32_t level_mode) {
+    REVO_REQUIRE(cap_keys >= 0 && cap_keys <= revo::KNN_MAX_KEYS, "debug_set_knn: cap_keys must be in [0, 2^28]");
+    REVO_REQUIRE(level_mode >= 0 && level_mode <= 3, "debug_set_knn: level_mode must be in [0, 3]");
+    g_knn_cap_keys = (long)cap_keys;
+    g_knn_level_mode = level_mode;
+    return 0;
+}
+#endif
+extern "C" int32_t revo_gallery_knn(revo_gallery* g, int32_t k, int32_t has_threshold, float threshold, int64_t* n_rows,
+                                    void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && n_rows, "gallery_knn: null argument");
+    REVO_REQUIRE(k >= 1 && k <= revo::KNN_K_MAX, "gallery_knn: k must be in [1, 64]");
+    CHECK_RC(require_threshold(has_threshold, threshold, "gallery_knn"));
+    CHECK_RC(require_f32_rows(g, "gallery_knn"));
+    REVO_REQUIRE(g->size < (1ll << 31), "gallery_knn: row indices must fit in 31 bits");
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    KnnResult& kr = g->knn;
+    kr.valid = false;
+    const long N = g->size;
+    const int D = g->D;
+    CHECK_RC(begin_counted(g, 1, "gallery_knn", st));
+    if (N == 0) {
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        kr.n = 0; kr.k = k; kr.valid = true;
+        *n_rows = 0;
+        return 0;
+    }
+    long cap_keys = 0;
+    int level_mode = 0;
+#ifdef REVO_EXPERIMENTS
+    cap_keys = g_knn_cap_keys; level_mode = g_knn_level_mode;
+#endif
+    if (cap_keys <= 0) {
+        // about 2 k + 16 entries per row and direction and as many again inside the rounding bound; a gallery no larger than
+        // the sample has no levels: all its pairs
+        cap_keys = 2l * (2 * k + 16) * N;
+        if (N <= KNN_SAMPLE && cap_keys < N * (N - 1) / 2) cap_keys = N * (N - 1) / 2;
+        cap_keys = std::min(KNN_MAX_KEYS, std::max(KNN_MIN_KEYS, cap_keys));
+    }
+    const long T = (N + 255) / 256, rows = T * 256;
+    const long stride = (N + KNN_SAMPLE - 1) / KNN_SAMPLE, S = (N + stride - 1) / stride, sample_rows = (S + 255) / 256 * 256;
+    const bool have_pass = N > KNN_SAMPLE && level_mode != 1 && level_mode != 2;
+    CHECK_RC(kr.score.grow((size_t)N * k * 4, st));
+    CHECK_RC(kr.idx.grow((size_t)N * k * 8, st));
+    CHECK_RC(kr.counts.grow((size_t)N * 4, st));
+    // the workspace: 2 cap_keys entries (a candidate key gives at most two directed entries), the per-row arrays, the sample
+    long cap = 0;
+    CandidateWs ws{g->pbuf, cap};
+    float *level = nullptr, *lb = nullptr, *sum = nullptr, *sq = nullptr;
+    uint32_t *lost = nullptr, *sallow = nullptr;
+    bf16_t* Sb = nullptr;
+    int *fb_q = nullptr, *fb_ctr = nullptr;
+    CHECK_RC(ws.carve(2 * cap_keys, st, [&](Layout& l) {
+        level = l.take<float>(rows); lb = l.take<float>(rows); lost = l.take<uint32_t>(T * 8);
+        fb_q = l.take<int>(N); fb_ctr = l.take<int>(2);    // fb_ctr[0]: sample rows pruned; [1]: fallback rows
+        if (have_pass) {
+            sum = l.take<float>(4 * rows); sq = l.take<float>(4 * rows);
+            Sb = l.take<bf16_t>((size_t)sample_rows * D); sallow = l.take<uint32_t>(sample_rows / 32);
+        }
+    }));
+    REVO_HIP_CHECK(hipMemsetAsync(ws.cnt, 0, sizeof(ws.h), st));
+    REVO_HIP_CHECK(hipMemsetAsync(lost, 0, (size_t)T * 8 * 4, st));
+    REVO_HIP_CHECK(hipMemsetAsync(fb_ctr, 0, 2 * sizeof(int), st));
+    KnnLevelArgs la{};
+    la.Gb = g->gb.p; la.ldg = D; la.N = N; la.D = D; la.Sb = Sb; la.S = S; la.stride = stride; la.sallow = sallow;
+    la.sum = sum; la.sq = sq; la.rows = rows;
+    { ProfScope ps("knn_level", st);
+      if (have_pass) {
+          CHECK_RC(launch_knn_sample(g->gb.p, D, N, D, S, stride, allow, Sb, sallow, ws.cnt, st));
+          CHECK_RC(launch_knn_level_pass(la, st));
+      }
+      CHECK_RC(launch_knn_levels(la, allow, g->gstat.p, ws.cnt, k, has_threshold, threshold, level_mode, have_pass ? 1 : 0, 0, fb_ctr,
+                                 level, lb, st));
+      if (have_pass) {
+          // rows of dense blocks: out of the join, into the fallback, and out of the sample; the levels once more without them
+          la.lb = lb;
+          CHECK_RC(launch_knn_level_pass(la, st));
+          CHECK_RC(launch_knn_dense_rows(la, ws.cnt, k, sallow, fb_ctr, level, lb, st));
+          la.lb = nullptr;
+          CHECK_RC(launch_knn_level_pass(la, st));
+          CHECK_RC(launch_knn_levels(la, allow, g->gstat.p, ws.cnt, k, has_threshold, threshold, level_mode, 1, 1, fb_ctr, level, lb,
+                                     st));
+      } }
+    KnnJoinArgs ja{};
+    ja.j.Gb = g->gb.p; ja.j.ldg = D; ja.j.N = N; ja.j.D = D; ja.j.gstat = g->gstat.p; ja.j.allow = allow;
+    ja.j.cnt = ws.cnt; ja.j.keys = ws.cand; ja.j.cap = cap_keys; ja.lb = lb; ja.lost = lost;
+    { ProfScope ps("knn_join", st);
+      CHECK_RC(launch_knn_join(ja, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(ws.h, ws.cnt, sizeof(ws.h), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    // (a count past the workspace: the keys behind it were dropped and their rows marked lost)
+    ws.n_cand = std::min<unsigned long long>(ws.h[0], (unsigned long long)cap_keys);
+    { ProfScope ps("knn_rescore", st);
+      CHECK_RC(launch_knn_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, level, ws.cnt + 1, ws.kept_k, ws.kept_v, st)); }
+    CHECK_RC(ws.sort_kept("knn_sort", 32 + row_index_bits(N), st));
+    REVO_REQUIRE(ws.n_kept <= 2 * ws.n_cand, "gallery_knn: internal: more entries than the workspace holds");
+    { ProfScope ps("knn_select", st);
+      CHECK_RC(launch_knn_select(ws.sk, ws.sv, (long)ws.n_kept, N, k, has_threshold ? threshold : -INFINITY, level, lost, allow, fb_q,
+                                 fb_ctr, kr.score.p, kr.idx.p, kr.counts.p, st)); }
+    int fb[2] = {0, 0};
+    REVO_HIP_CHECK(hipMemcpyAsync(fb, fb_ctr, sizeof(fb), hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    const int n_fb = fb[1];
+    REVO_REQUIRE(n_fb >= 0 && n_fb <= N, "gallery_knn: internal: more fallback rows than rows");
+    if (n_fb > 0) {
+        // rows without a certificate: the large-k search's exhaustive fallback, the master row as the query, in rounds
+        long F = (long)(KNN_FB_BYTES / ((size_t)N * 4));
+        F = std::max(1l, std::min({F, 1024l, (long)n_fb}));
+        CHECK_RC(kr.fb.grow((size_t)F * N * 4, st));
+        LargeWs lw{};
+        lw.ctr = fb_ctr; lw.fb_q = fb_q; lw.fb_scores = kr.fb.p; lw.F = (int)F;
+        ProfScope ps("knn_fallback", st);
+        CHECK_RC(launch_topk_large_fallback(lw, n_fb, g->gf.p, D, g->gf.p, D, N, D, k, has_threshold, threshold, 0, kr.score.p,
+                                            kr.idx.p, kr.counts.p, allow, st, 1));
+    }
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_LARGE_FALLBACK, &n_fb, sizeof(int), hipMemcpyHostToDevice, st));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, 1, st));
+    kr.n = N; kr.k = k;
+    kr.valid = true;
+    *n_rows = N;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_knn_read(revo_gallery* g, int64_t start, int64_t n, int64_t* indices, float* scores, int32_t* counts,
+                                         int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_knn_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "gallery_knn_read: negative start or count");
+    const KnnResult& kr = g->knn;
+    REVO_REQUIRE(kr.valid, "gallery_knn_read: no result (call revo_gallery_knn again after the rows change)");
+    REVO_REQUIRE(start + n <= kr.n, "gallery_knn_read: range past the result's " + std::to_string(kr.n) + " rows");
+    if (n == 0 || (!indices && !scores && !counts)) return 0;
+    REVO_ON_DEVICE(g->device);
+    if (indices) CHECK_RC(copy_out(indices, kr.idx.p + start * kr.k, (size_t)n * kr.k, dst_on_device));
+    if (scores) CHECK_RC(copy_out(scores, kr.score.p + start * kr.k, (size_t)n * kr.k, dst_on_device));
+    if (counts) CHECK_RC(copy_out(counts, kr.counts.p + start, (size_t)n, dst_on_device));
     return 0;
     API_END
 }

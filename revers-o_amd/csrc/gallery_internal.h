@@ -93,6 +93,13 @@ struct ClustersResult {
     DeviceBuffer<long long> labels, off, members;
     int64_t rows = 0, n = 0, n_members = 0; bool valid = false;
 };
+// revo_gallery_knn: the last result ([n][k] scores and indices, [n] counts), valid until the rows change, and the score buffer of
+// its exhaustive fallback (allocated when a row first needs it)
+struct KnnResult {
+    DeviceBuffer<long long> idx; DeviceBuffer<float> score; DeviceBuffer<int> counts;
+    DeviceBuffer<float> fb;
+    int64_t n = 0; int k = 0; bool valid = false;
+};
 // revo_search_maxsim: the CSR of the group ids (gid | off | row | pos in csr; revo::launch_maxsim_index), built at the first
 // call for `rows` rows (-1: none; dropped by revo_search_set_groups, an append, a clear and a remove that moves rows), and the
 // score workspace S [N][n_pad]
@@ -137,11 +144,12 @@ struct __attribute__((visibility("default"))) revo_gallery {   // (the C ABI nam
     PairsResult pairs;
     RangeResult range;
     ClustersResult clusters;
+    KnnResult knn;
     MaxsimIndex maxsim;
     // a search overwrites the handle's query rows: the two-phase candidates that refer to them go
     void drop_two_phase() { two.cand = nullptr; two.Q = 0; two.nsegs = 0; two.prelist = nullptr; two.estimated = false; }
     // rows were added or all removed: the results held in the handle go (and, the caller's part, the group index)
-    void drop_results() { pairs.valid = false; range.valid = false; clusters.valid = false; }
+    void drop_results() { pairs.valid = false; range.valid = false; clusters.valid = false; knn.valid = false; }
     // rows left or changed in place: the results and the two-phase candidate state go
     void rows_changed() { drop_results(); two.ksel = 0; drop_two_phase(); }
     revo::CertArgs cert_args(float* cert_out) const {

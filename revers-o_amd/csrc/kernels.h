@@ -422,7 +422,8 @@ int launch_topk_large_finish(const LargeWs& ws, int max_entries, const float* Qf
                              int* out_counts, hipStream_t st);
 int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, long N,
                                int D, int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
-                               int* out_counts, const uint32_t* allow, hipStream_t st);
+                               int* out_counts, const uint32_t* allow, hipStream_t st, int skip_self = 0);
+// (skip_self: Qf IS Gf and an entry's query is a gallery row -- revo_gallery_knn: that row itself is left out, by index)
 // ------------------------------------------------- candidate pipeline ----
 // Pairs, range and recommend searches: join on the 256 x 256 main loop -> counted candidate buffer,
 // fp32 re-score -> 64-bit sort keys, sort, emit.  Shared device code: candidates.h; host side: candidate_search.hip's CandidateWs.
@@ -473,6 +474,54 @@ int launch_clusters_labels(uint32_t* parent, const uint32_t* allow, long N, int 
 // sorted keys -> members; rank [n] workspace; offsets [n_clusters + 1]
 int launch_clusters_emit(const uint64_t* keys, long n, long n_clusters, int b, unsigned long long* rank, long long* members,
                          long long* offsets, hipStream_t st);
+// ---- exact kNN graph (revo_gallery_knn; knn.hip): the pairs join with a level PER ROW.  An estimated
+// level t_r for every row (sample pass), the join keeps pair (i, j) when its bf16 score reaches min(lb_i, lb_j), the re-score
+// turns a candidate into a directed entry for every end whose level it reaches, sort by (row, score), select with a
+// certificate per row; rows without one take the exhaustive fp32 fallback of the large-k search (LargeWs)
+constexpr int KNN_K_MAX = 64;
+constexpr long KNN_SAMPLE = 8192;            // sample rows of the level pass (at most); no more allowed rows: no estimate
+constexpr long KNN_MIN_KEYS = 1l << 16;      // candidate keys of the smallest workspace
+constexpr long KNN_MAX_KEYS = 1l << 28;      // and of the largest (the workspace takes 48 bytes per key)
+constexpr size_t KNN_FB_BYTES = 256ul << 20; // the fallback's score buffer: rows of a round = this / (4 N), 1 .. 1024
+// sample row s is gallery row s * stride; S sample rows.  Sb [ST * 256][D] their bf16 rows (rows past S: zeros), sallow
+// [ST * 8] the bitmap of the ALLOWED sample rows; ctr[2] counts the allowed rows of the gallery, ctr[3] those of the sample
+int launch_knn_sample(const bf16_t* Gb, long ldg, long N, int D, long S, long stride, const uint32_t* allow, bf16_t* Sb,
+                      uint32_t* sallow, unsigned long long* ctr, hipStream_t st);
+struct KnnLevelArgs {
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    long N; int D;
+    const bf16_t* Sb; long S, stride;   // the sample (launch_knn_sample)
+    const uint32_t* sallow;
+    float *sum, *sq;              // [4][rows] per wave column: sum and sum of squares of row r's bf16 scores against the allowed
+    long rows;                    // sample rows other than r itself; rows = the gallery's rows padded to whole 256-row tiles
+    const float* lb;              // null, or the counting pass: sum = the count of those scores that reach lb[r]
+};
+int launch_knn_level_pass(const KnnLevelArgs& a, hipStream_t st);
+// behind the counting pass: rows whose bound far too many sample rows reach get level = lb = +inf (the fallback's) and leave
+// the sample (sallow; pruned[0], zeroed by the caller, counts them)
+int launch_knn_dense_rows(const KnnLevelArgs& a, const unsigned long long* ctr, int k, uint32_t* sallow, int* pruned, float* level,
+                          float* lb, hipStream_t st);
+// level[r] / lb[r] for r < rows (rows: padded to whole tiles; a row past N or not allowed: +inf / +inf).  level_mode: the
+// debug knob (include/revo.h revo_debug_set_knn); have_pass = 0: no sample pass ran, every level is the floor; keep_dense: the
+// second round -- rows launch_knn_dense_rows set to +inf stay there; pruned[0]: the sample rows it took out
+int launch_knn_levels(const KnnLevelArgs& a, const uint32_t* allow, const uint32_t* gstat, const unsigned long long* ctr, int k,
+                      int has_thr, float thr, int level_mode, int have_pass, int keep_dense, const int* pruned, float* level,
+                      float* lb, hipStream_t st);
+struct KnnJoinArgs {
+    PairsJoinArgs j;              // the pairs join's arguments (thr unused)
+    const float* lb;              // [T * 256] the rows' bf16-score bounds
+    uint32_t* lost;               // [T * 8] bit r: a candidate key of row r found no room in the workspace
+};
+int launch_knn_join(const KnnJoinArgs& a, hipStream_t st);
+// fp32 score v of candidates [0, n): a directed entry (row << 32 | ~orderable score, partner) for row i when v >= level[i] and
+// one for row j when v >= level[j]; count in *kept; out arrays hold 2 n entries
+int launch_knn_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, const float* level,
+                       unsigned long long* kept, uint64_t* out_keys, float* out_partner, hipStream_t st);
+// sorted entries -> each row's best k by (score desc, index asc), padding and counts; a row without a certificate is appended
+// to fb_q (count: fb_ctr[1]).  floor_level: the threshold or -inf
+int launch_knn_select(const uint64_t* keys, const float* partner, long n, long N, int k, float floor_level, const float* level,
+                      const uint32_t* lost, const uint32_t* allow, int* fb_q, int* fb_ctr, float* scores, long long* idx,
+                      int* counts, hipStream_t st);
 // ---- range search (revo_search_range; range.hip): the join runs the 256 x 256 scan's work plan, with a
 // bound per query
 constexpr int RANGE_CHUNK = 1024;            // queries per candidate pass (fewer when the sort key would pass 64 bits)

@@ -332,11 +332,12 @@ __global__ __launch_bounds__(1024) void topk_large_sort_kernel(LargeWs ws, int k
 // grid (LARGE_FB_SLICES, F): the fp32 score of every row of slice s for fallback entry round * F + y (NaN: not allowed)
 __global__ __launch_bounds__(1024) void topk_large_fb_score_kernel(LargeWs ws, int round, const float* __restrict__ Qf, long ldqf,
                                                                    const float* __restrict__ Gf, long ldgf, long N, int D,
-                                                                   const uint32_t* __restrict__ allow) {
+                                                                   const uint32_t* __restrict__ allow, int skip_self) {
     const int i = round * ws.F + blockIdx.y;
     if (i >= ws.ctr[1]) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float* qr = Qf + (long)ws.fb_q[i] * ldqf;
+    const long self = skip_self ? (long)ws.fb_q[i] : -1;    // the kNN graph: the query is gallery row fb_q[i], never its own neighbour
     float* out = ws.fb_scores + (long)blockIdx.y * N;
     const long per = (N + LARGE_FB_SLICES - 1) / LARGE_FB_SLICES;
     const long r0 = (long)blockIdx.x * per;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(1024) void topk_large_fb_score_kernel(LargeWs ws, i
         if (lane < 4 && r + lane < r1) {
             const long row = r + lane;
             const float v = lane == 0 ? t[0] : (lane == 1 ? t[1] : (lane == 2 ? t[2] : t[3]));
-            const bool ok = !allow || ((allow[row >> 5] >> (row & 31)) & 1u);
+            const bool ok = (!allow || ((allow[row >> 5] >> (row & 31)) & 1u)) && row != self;
             out[row] = ok ? v : __builtin_nanf("");
         }
     }
@@ -440,14 +441,14 @@ int launch_topk_large_finish(const LargeWs& ws, int max_entries, const float* Qf
 }
 int launch_topk_large_fallback(const LargeWs& ws, int max_entries, const float* Qf, long ldqf, const float* Gf, long ldgf, long N,
                                int D, int k, int has_thr, float thr, long idx_offset, float* out_scores, long long* out_idx,
-                               int* out_counts, const uint32_t* allow, hipStream_t st) {
+                               int* out_counts, const uint32_t* allow, hipStream_t st, int skip_self) {
     if (max_entries <= 0 || N <= 0) return 0;
     REVO_REQUIRE(Gf && ws.F >= 1 && k >= 1 && k <= LARGE_K_MAX && N < (1ll << 32),
                  "large-k fallback: needs the fp32 master rows, 1 <= k <= 1024, N < 2^32");
     // rounds of F entries: the score buffer holds F rows of N; a round past the device's entry count exits at once
     for (int round = 0; round * ws.F < max_entries; ++round) {
         hipLaunchKernelGGL(topk_large_fb_score_kernel, dim3(LARGE_FB_SLICES, (unsigned)ws.F), dim3(1024), 0, st, ws, round, Qf,
-                           ldqf, Gf, ldgf, N, D, allow);
+                           ldqf, Gf, ldgf, N, D, allow, skip_self);
         hipLaunchKernelGGL(topk_large_fb_select_kernel, dim3((unsigned)ws.F), dim3(1024), 0, st, ws, round, N, k, has_thr, thr,
                            idx_offset, out_scores, out_idx, out_counts);
     }

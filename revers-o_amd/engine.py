@@ -439,6 +439,25 @@ class Gallery:
                        "revo_gallery_clusters_read")
         return labels, offsets, members
 
+    def knn(self, k, score_threshold=None, allow=None):
+        """Exact kNN graph of the gallery (include/revo.h, KNN): for every row ``allow`` selects (as in :meth:`search`) its
+        best ``k <= 64`` other allowed rows by (score desc, index asc), cut at ``score_threshold`` if given.  Returns
+        ``(scores [len, k] fp32, indices [len, k] int64, counts [len] int32)`` device tensors, padded with -inf / -1 past
+        ``counts``; a row ``allow`` excludes has count 0 and is nobody's neighbour.  A score has the bits :meth:`pairs`
+        gives the same two rows; a row is never its own neighbour, identical rows at other indices are.  Synchronous."""
+        n = C.c_int64()
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_gallery_knn(self._h, int(k), int(score_threshold is not None),
+                                                  float(score_threshold if score_threshold is not None else 0.0), C.byref(n),
+                                                  _lib.current_stream()), "revo_gallery_knn")
+            n = int(n.value)
+            scores = torch.empty((n, int(k)), dtype=torch.float32, device=self.device)
+            idx = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
+            counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+            _lib.check(self._lib.revo_gallery_knn_read(self._h, 0, n, _lib.ptr(idx), _lib.ptr(scores), _lib.ptr(counts), 1),
+                       "revo_gallery_knn_read")
+        return scores, idx, counts
+
     def search_range(self, queries, score_threshold, index_offset=0, allow=None):
         """Range search (include/revo.h, RANGE): for each query every row (allowed by ``allow``, as in :meth:`search`) whose
         fp32 score reaches ``score_threshold`` -- the reference's threshold without its ``limit``.  Returns ``(offsets [Q + 1]

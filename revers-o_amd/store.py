@@ -216,6 +216,53 @@ class DuplicatePair:
     score: float
 
 
+@dataclass
+class NeighborGraph:
+    """What :meth:`GalleryStore.neighbor_graph` returns, in the shape of the database's matrix-offsets response: ``ids`` are
+    the points of the graph in storage order; edge e goes from ``ids[offsets_row[e]]`` to its neighbour
+    ``ids[offsets_col[e]]`` with ``scores[e]``.  Edges are ordered by source point, each point's neighbours best first."""
+    ids: list
+    offsets_row: np.ndarray
+    offsets_col: np.ndarray
+    scores: np.ndarray
+
+    def pairs(self):
+        """The edges as ``(id_a, id_b, score)`` tuples, in edge order (the matrix-pairs response)."""
+        return [(self.ids[a], self.ids[b], float(s))
+                for a, b, s in zip(self.offsets_row.tolist(), self.offsets_col.tolist(), self.scores.tolist())]
+
+
+def sample_mask(mask, sample, seed=0):
+    """``mask`` (bool [n]) restricted to ``sample`` of its set entries, drawn without replacement by a generator seeded with
+    ``seed`` (all of them when ``sample`` is None or not smaller than their number).  A new array."""
+    mask = np.asarray(mask, dtype=bool)
+    rows = np.flatnonzero(mask)
+    if sample is None or int(sample) >= rows.size:
+        return mask.copy()
+    if int(sample) < 0:
+        raise ValueError("sample must not be negative")
+    out = np.zeros_like(mask)
+    out[np.random.default_rng(seed).choice(rows, size=int(sample), replace=False)] = True
+    return out
+
+
+def knn_to_graph(ids, mask, scores, idx, counts):
+    """``Gallery.knn``'s arrays (host copies: scores / idx [n, k], counts [n]) over the rows ``mask`` selects, as a
+    :class:`NeighborGraph` over those rows' ids."""
+    mask = np.asarray(mask, dtype=bool)
+    rows = np.flatnonzero(mask)
+    place = np.full(mask.shape[0], -1, dtype=np.int64)
+    place[rows] = np.arange(rows.size)
+    counts = np.asarray(counts, dtype=np.int64)[rows]
+    k = scores.shape[1] if scores.ndim == 2 else 0
+    take = np.arange(k)[None, :] < counts[:, None]                    # [rows, k]: the entries that are results
+    cols = np.asarray(idx)[rows][take]
+    if cols.size and (place[cols] < 0).any():
+        raise ValueError("knn_to_graph: a neighbour outside the selected rows")
+    return NeighborGraph([ids[r] for r in rows.tolist()], np.repeat(np.arange(rows.size, dtype=np.int64), counts),
+                         place[cols].astype(np.int64), np.asarray(scores)[rows][take].astype(np.float32))
+
+
 def connected_groups(pairs, n):
     """The connected components with at least two members of the graph on rows ``0 .. n - 1`` whose edges are ``pairs``
     (int array [m, 2]): lists of rows, each in ascending order, the lists ordered by their first row.  Union-find on numpy."""
@@ -651,6 +698,21 @@ class GalleryStore:
         """The lists :meth:`duplicate_groups` returns (point ids; members in row order, groups ordered by their first row),
         from the device route of :meth:`duplicate_row_clusters`."""
         return [[self.ids[r] for r in grp] for grp in self.duplicate_row_clusters(score_threshold, query_filter)]
+
+    def neighbor_graph(self, limit=3, score_threshold=None, query_filter=None, sample=None, seed=0):
+        """The database's distance-matrix query: for every point ``query_filter`` selects (all points without one) -- or for
+        ``sample`` of them, drawn on the host with a generator seeded by ``seed`` -- its ``limit <= 64`` nearest other
+        points of that same set, cut at ``score_threshold`` if given.  Returns a :class:`NeighborGraph` (CSR arrays over the
+        set's ids, or ``.pairs()``).  Exact (include/revo.h, KNN): a point is never its own neighbour, identical vectors at
+        other points are."""
+        mask = self.filter_mask(query_filter) if query_filter is not None else np.ones(len(self), dtype=bool)
+        mask = sample_mask(mask, sample, seed)
+        restricted = query_filter is not None or sample is not None
+        if len(self) == 0 or not mask.any():
+            return NeighborGraph([], np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))
+        allow = torch.from_numpy(_filters.pack_bits(mask)).to(self.gallery.device) if restricted else None
+        scores, idx, counts = self.gallery.knn(int(limit), score_threshold=score_threshold, allow=allow)
+        return knn_to_graph(self.ids, mask, scores.cpu().numpy(), idx.cpu().numpy(), counts.cpu().numpy())
 
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
