@@ -662,6 +662,18 @@ int32_t revo_op_set_gemm_debug(int32_t flags);
  * out[0] = phases, out[1] = segment slots per query, then per phase: first block, first query tile, query tiles, slices.
  * Returns the number of workgroups of the launch (-1: bad arguments). */
 int64_t revo_debug_scan_plan(int32_t Q, int64_t rows, int64_t* out, int32_t cap);
+/* The launch plan of a GEMM (revers-o_amd/csrc/gemm_plan.h) under the library's current switches (revo_op_set_variant,
+ * revo_op_set_qstores, revo_op_set_gemm_tile ...): host logic only, no device.  epi: 0 bf16, 1 bf16 + GELU, 2 residual, 3 fp32,
+ * 4 patch embedding, 5 bf16 + RoPE (with the table's rows, the head dimension and the rotated columns).  ws_elems: the
+ * split-K workspace in fp32 elements (0: none).  offers: bit 0 a LayerNorm to fuse behind a residual GEMM, 1 the folded
+ * LayerNorm's producer outputs, 2 residual stream read from planes, 3 written to planes, 4 the folded LayerNorm's row
+ * statistics (consumer), 5 the caller prefers 256 x 256 tiles.  out (cap >= 30): [0] the GemmForm bits of the call (-1: the
+ * launcher refuses the call), [1] steps (1 or 2), then 14 values per step: kernel form bit, first row, rows, XCD
+ * arrangement gy, persistent workgroups per XCD, grid x, grid y, 192-row tile rows, how many of them tall, leftover rows
+ * fused into the launch, split-K parts, the reduce does the LayerNorm, plane format pair, folds.  Returns out[0]; -2: bad
+ * arguments. */
+int64_t revo_debug_gemm_plan(int32_t epi, int32_t m, int32_t n, int32_t k, int64_t lda, int64_t ldb, int64_t ldc, int64_t ws_elems,
+                             int32_t offers, int32_t rope_seq, int32_t rope_head_dim, int32_t rope_cols, int64_t* out, int32_t cap);
 /* 1 if a forward of `batch` images keeps the residual stream in two bf16 planes between its folded GEMMs (reporting) */
 int32_t revo_debug_stream_in_planes(const revo_vit* vit, int32_t batch);
 /* copies bytes of the handle's search workspace to host_dst (host_dst NULL: returns the workspace size) */

@@ -128,6 +128,7 @@ EXPERIMENT_SIGNATURES = {
     "revo_debug_stream_in_planes": (_i32, [_p, _i32]),
     "revo_probe_gridbar": (_i32, [_i32, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
     "revo_debug_scan_plan": (_i64, [_i32, _i64, C.POINTER(C.c_int64), _i32]),
+    "revo_debug_gemm_plan": (_i64, [_i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), _i32]),
 }
 BASE_SIGNATURES = dict(SIGNATURES)
 if os.environ.get("REVO_LIBRARY_PATH"):            # bisecting / A-B runs of another build of the same ABI

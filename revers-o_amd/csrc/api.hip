@@ -931,6 +931,15 @@ extern "C" int64_t revo_debug_scan_plan(int32_t Q, int64_t rows, int64_t* out, i
     if (Q < 1 || rows < 1 || !out || cap < 2) return -1;
     return (int64_t)revo::topk_scan256_plan_dump(Q, (long)rows, (long*)out, cap);
 }
+// the plan launch_gemm would execute for a problem under the library's current switches: host logic only, no device needed
+// (CPU-tier tests; kernels.h gemm_debug_plan has the layout of `out`)
+extern "C" int64_t revo_debug_gemm_plan(int32_t epi, int32_t m, int32_t n, int32_t k, int64_t lda, int64_t ldb, int64_t ldc,
+                                        int64_t ws_elems, int32_t offers, int32_t rope_seq, int32_t rope_head_dim, int32_t rope_cols,
+                                        int64_t* out, int32_t cap) {
+    if (epi < 0 || epi > 5 || !out) return -2;
+    return (int64_t)revo::gemm_debug_plan(epi, m, n, k, (long)lda, (long)ldb, (long)ldc, (long)ws_elems, (unsigned)offers, rope_seq,
+                                          rope_head_dim, rope_cols, (long*)out, cap);
+}
 // whether the forward keeps the residual stream in planes for this many rows of this tower (reporting / tests)
 extern "C" int32_t revo_debug_stream_in_planes(const revo_vit* v, int32_t batch) {
     if (!v || !v->xlo) return 0;

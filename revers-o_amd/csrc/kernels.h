@@ -70,8 +70,7 @@ struct GemmArgs {
 #endif
 };
 constexpr float LNC_TELE_RATIO = 8.0f;
-// true when launch_gemm would run the 256 x 256 kernel with the row-coalesced epilogue for these sizes
-bool gemm_uses_wide_epilogue(int M, int N, long lda, long ldb, long ldc);
+constexpr int LNF_SLICE = 256;      // columns per partial of the folded LayerNorm's statistics = one column tile of the 256 x 256 kernel
 int launch_gemm(int epi, const GemmArgs& a, hipStream_t st);
 // The launch forms launch_gemm can issue (bits of revo_debug_gemm_forms, librevo_exp.so; tests/test_gpu_gemm_bounds.py lists
 // them too): kernels, then properties of the launch
@@ -96,10 +95,17 @@ enum GemmForm : unsigned {
 };
 #ifdef REVO_EXPERIMENTS
 unsigned gemm_debug_forms(int reset);
+// The plan (gemm_plan.h) launch_gemm would execute under the library's current switches, for a problem given as plain values;
+// offers: bit 0 a LayerNorm to fuse, 1 the folded producer, 2 planes in, 3 planes out, 4 lnc statistics, 5 prefer256 (the
+// output strides of the offered forms are taken as ldc).  Host only.  out: [0] form bits (-1: the launcher refuses),
+// [1] steps, then 14 values per step: form, row0, rows, gy, nslot, grid x, grid y, t192 tiles, t192 tall, qtail rows, S,
+// reduce does the LayerNorm, XP, folds.  Returns the form bits, -1 for a refusal, -2 when `cap` is too small.
+long gemm_debug_plan(int epi, int M, int N, int K, long lda, long ldb, long ldc, long ws_elems, unsigned offers, int rope_S,
+                     int rope_hd, int rope_cols, long* out, int cap);
 #endif
 // EPI_F32 on 128 x 64 ring tiles whatever the tile count (few rows x very many columns: the search pre-pass of few queries)
 int launch_gemm_f32_ring(const GemmArgs& a, hipStream_t st);
-// true when launch_gemm(EPI_RESID_F32) would take one of the two launch forms that can fold the LayerNorm behind it (and
+// true when the plan of launch_gemm(EPI_RESID_F32) (gemm_plan.h) is one of the two that can fold the LayerNorm behind it (and
 // keep the residual stream in planes): the persistent 256-row kernel over ALL rows
 bool gemm_resid_folds(int M, int N, int K, long lda, long ldb, long ldc);
 // residual stream planes <-> fp32 (format changes at the ends of a forward's folded stretch; parity hooks)

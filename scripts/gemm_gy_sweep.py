@@ -1,6 +1,6 @@
 """XCD arrangement (gy = N stripes per 8 XCDs) of the persistent body GEMMs, per layer shape, alternated in one process:
     REVO_EXPERIMENTS=1 python scripts/gemm_gy_sweep.py > gpurun_out/gemm_gy_sweep.json
-The launchers' rule (gemm.hip launch_256p / launch_256q) is set from this table."""
+The launch plan's rule (gemm_plan.h gemm_xcd_stripes) is set from this table."""
 import json
 import os
 import sys

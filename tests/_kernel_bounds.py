@@ -1244,7 +1244,7 @@ GEMM_FORM_CASES = [
     # chosen for the form (1280 / 1088 columns keep the 192-row plan and the queued stores away), never K.  The leftover
     # rows fused into the queued-stores launch (256Q_QTAIL) need K % 256 == 0 and the folded LayerNorm's consumer reads
     # one statistics slot per 256 columns of K (LnStats): neither exists at an odd tile count.  128_64 and 128R need
-    # K >= 512 (launch_128): 1088 is the odd count they can have.
+    # K >= 512 (gemm_plan.h gemm_plan_128): 1088 is the odd count they can have.
     ("K192 resid, 256-row persistent", "resid", _L, 1280, 192, {}, ["256P"]),
     ("K320 resid, 256-row persistent", "resid", _L, 1280, 320, {}, ["256P"]),
     ("K192 bf16, 256-row persistent", "bf16", _L, 1088, 192, {}, ["256P"]),
@@ -1792,9 +1792,10 @@ PATCH_TEETH_CASES = [("T14-56", 4, 12), ("N14-56", 4, 12), ("B16", 10, 3), ("L14
 
 
 def patch_gemm_form(M, N, K):
-    """The launch form gemm.hip launch_t<EPI_PATCH> takes, restated: use_256 (M >= 1024, N >= 256, at least 100 tiles of
-    256 x 256), then the persistent kernel above 256 tiles; else launch_128's choice.  No skinny form, no tail split, no
-    split-K and no 192-row plan for this epilogue (launch_t excludes them with `if constexpr`)."""
+    """The launch form the plan (csrc/gemm_plan.h gemm_plan) gives EPI_PATCH, restated: gemm_use_256 (M >= 1024, N >= 256, at
+    least 100 tiles of 256 x 256), then the persistent kernel above 256 tiles; else gemm_plan_128's choice.  No skinny form,
+    no tail split, no split-K and no 192-row plan for this epilogue (gemm_plan_rows excludes them; tests/test_gemm_plan.py
+    holds the plan to this restatement over its sweep)."""
     up = lambda a, b: -(-a // b)
     t256 = up(M, 256) * up(N, 256)
     if M >= 1024 and N >= 256 and t256 >= 100:
