@@ -143,6 +143,41 @@ int32_t revo_gallery_remove(revo_gallery* g, const uint32_t* remove_bits, int64_
 int32_t revo_gallery_update(revo_gallery* g, const int64_t* row_idx, const float* vecs, int64_t n, int32_t normalize,
                             int32_t src_on_device, void* stream);
 
+/* ---- DEDUP: the deduplicating append (insert-time dedup of a points database)
+ * The gallery holds rows 0 .. N - 1; the call brings n vectors x_0 .. x_{n-1} (vecs: [n, dim] fp32, host or device, as
+ * revo_gallery_append takes them) and a threshold t.  m_j is the fp32 master row an ordinary append would write for x_j: the
+ * same normalisation arithmetic, the same bits.  s(a, b) is the PAIRS score of two fp32 master rows: the one fma chain, the
+ * bits revo_gallery_pairs reports, symmetric bit for bit.  The rows are decided in order j = 0, 1, ...:
+ *   D_j = { gallery rows i < N with s(i, m_j) >= t }  united with  { batch rows j' < j that were KEPT and have s(m_j', m_j) >= t }
+ *   D_j empty: x_j is KEPT and becomes row N + (number of rows kept before it);
+ *   otherwise x_j is DROPPED, and its representative is the member of D_j with the lowest final row index: first seen wins,
+ *   gallery rows come before batch rows.
+ * A dropped row never suppresses a later one: a greedy leader selection in index order, not connected components.
+ * Outputs, n entries each, host or device memory (dst_on_device): rows[j] (int64) = the row's own new row index, or its
+ * representative's; scores[j] (fp32) = -inf for a kept row, else the PAIRS bits of s(representative, m_j); *n_kept (host).
+ * Consequences:
+ *   - after the call every entry point of this library returns, byte for byte, what it returns on a gallery to which only
+ *     the kept vectors were appended in order (the wording of revo_gallery_remove's contract; as there, the certificate's
+ *     running row maxima may stay looser upper bounds: they include the dropped rows');
+ *   - revo_gallery_pairs(t) afterwards holds no pair with an end >= N;
+ *   - splitting the batch into consecutive calls, down to one row per call, gives the same rows, scores and gallery;
+ *   - two calls on equal galleries give identical bytes;
+ *   - the number of duplicate pairs imposes no limit: nothing proportional to the certain edges is stored (16 384 identical
+ *     rows are one call).  Only pairs whose bf16 score lies INSIDE the rounding bound of t are stored for the fp32 re-score;
+ *     more than 2^28 of those give status -2 (move the threshold).
+ * SYNCHRONOUS on `stream`, like revo_gallery_remove: the host needs the new size.  Needs the fp32 master rows (keep_f32 = 0:
+ * status -2) and row indices below 2^31, as PAIRS.  0 <= n <= 16 384 per call (larger inputs: consecutive calls, which the
+ * semantics make equivalent).  CAPACITY: room for N + n rows is required even if few are kept -- every row of the batch is
+ * first written behind the gallery's end.  Status -2 with a message, before the device is touched and with nothing written:
+ * a null handle or pointer (vecs may be null at n = 0), a negative or too-large n, a NaN threshold, keep_f32 = 0,
+ * insufficient capacity.  On any failure the gallery is as before, with size N.  The handle's filter is NOT consulted (an
+ * append invalidates it anyway).  The call invalidates whatever an append invalidates: held pairs, clusters, knn and range
+ * results, the two-phase candidate state, the multi-vector index, and filter or group ids sized for N (when a row was kept).
+ * revo_search_stats afterwards: slot 3 = ambiguous pairs re-scored in fp32, slot 7 = join passes, every other slot 0. */
+int32_t revo_gallery_append_unique(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device,
+                                   float threshold, int64_t* rows, float* scores, int32_t dst_on_device,
+                                   int64_t* n_kept, void* stream);
+
 /* ---- search: replaces vector_db.search(query_vector, limit, score_threshold) (core_system.py:659-664)
  * queries: [n_queries, dim] fp32 on the device (normalised internally, cosine semantics).
  * Results, best first under (score desc, index asc): scores [n_queries, k] fp32, indices

@@ -51,6 +51,7 @@ SIGNATURES = {
     "revo_gallery_read": (_i32, [_p, _i64, _i64, _p, _i32]),
     "revo_gallery_remove": (_i32, [_p, _p, _i64, _i32, C.POINTER(C.c_int64), _p]),
     "revo_gallery_update": (_i32, [_p, _p, _p, _i64, _i32, _i32, _p]),
+    "revo_gallery_append_unique": (_i32, [_p, _p, _i64, _i32, _i32, _f32, _p, _p, _i32, C.POINTER(C.c_int64), _p]),
     "revo_gallery_pairs": (_i32, [_p, _f32, C.POINTER(C.c_int64), _p]),
     "revo_gallery_pairs_read": (_i32, [_p, _i64, _i64, _p, _p, _i32]),
     "revo_gallery_clusters": (_i32, [_p, _f32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _p]),

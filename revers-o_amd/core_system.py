@@ -76,7 +76,7 @@ class SimpleReverso:
 
     def __init__(self, model_name=DEFAULT_VARIANT, checkpoint=None, device=0, db_root=DB_ROOT, max_batch=64,
                  detector=None, decode_workers=None, synthetic_seed=0, region_mode="global", device_resize=False,
-                 checkpoint_interval_s=30.0):
+                 checkpoint_interval_s=30.0, skip_duplicates=None):
         print("🚀 Initializing Simple Revers-o...")
         if region_mode not in ("global", "crop", "pool"):
             raise ValueError("region_mode must be 'global' (the reference's behaviour, core_system.py:406), 'crop' or 'pool'")
@@ -85,6 +85,13 @@ class SimpleReverso:
         # "pool": one forward per IMAGE; every region is attention-pooled over the tokens its mask covers
         # (regions.token_masks, VitEngine.embed_regions): the mask's shape counts, not just its box
         self.region_mode = region_mode
+        # a score threshold: create_database stores a vector only if no stored vector and no earlier kept vector of its batch
+        # scores that high against it (GalleryStore.upsert(skip_duplicates=...): frames of a static camera or a slow pan)
+        if skip_duplicates is not None:
+            skip_duplicates = float(skip_duplicates)
+            if skip_duplicates != skip_duplicates:
+                raise ValueError("skip_duplicates must be a score threshold or None, not NaN")
+        self.skip_duplicates = skip_duplicates
         # True: decoded frames are uploaded as they are and squash-resized by the HIP kernel
         # (same pixels as the host PIL resize, bit for bit); False: PIL resize in the decode pool
         self.device_resize = bool(device_resize)
@@ -436,6 +443,14 @@ class SimpleReverso:
 
     def _create_database(self, folder_path, database_name, text_prompt, use_direct_pe, progress_callback,
                          resume_from_checkpoint, include_subfolders):
+        if self.skip_duplicates is not None and self.region_mode == "global" and not use_direct_pe:
+            # every region of an image stores the image's global vector (core_system.py:406-408): all but the first would
+            # be "duplicates" of it
+            msg = ("❌ skip_duplicates needs one vector per stored point: with the detector in region_mode='global' every "
+                   "region of an image shares the image's vector (use use_direct_pe=True, region_mode='crop' or 'pool')")
+            if progress_callback:
+                progress_callback(msg, None)
+            return msg
         status_messages = []
 
         class _Log(str):
@@ -498,7 +513,8 @@ class SimpleReverso:
         """What a collection is made from and how: written into the build's manifest header, compared on resume."""
         return {"folder_path": os.path.abspath(folder_path), "model": self.pe_model.cfg.name,
                 "use_ls": bool(self.pe_model.cfg.use_ls), "region_mode": self.region_mode,
-                "use_direct_pe": bool(use_direct_pe), "include_subfolders": bool(include_subfolders)}
+                "use_direct_pe": bool(use_direct_pe), "include_subfolders": bool(include_subfolders),
+                "skip_duplicates": self.skip_duplicates}      # (an older manifest has no such key: the same as None)
 
     def _create_database_body(self, folder_path, database_name, text_prompt, use_direct_pe, resume_from_checkpoint,
                               include_subfolders, log_status, status_messages, db_path, ckpt_base, processed_files):
@@ -563,7 +579,7 @@ class SimpleReverso:
         model_size = self.pe_model.cfg.image_size
 
         stats = {"images": len(image_files), "decode_thread_s": 0.0, "wait_decode_s": 0.0, "wait_device_s": 0.0, "launch_s": 0.0,
-                 "bookkeeping_s": 0.0, "flush_s": 0.0}
+                 "bookkeeping_s": 0.0, "flush_s": 0.0, "duplicates_skipped": 0}
         self.last_ingest_stats = stats
         t_start = time.perf_counter()
 
@@ -779,7 +795,12 @@ class SimpleReverso:
                         vec = dev_emb
                     else:
                         vec = dev_emb.index_select(0, torch.tensor(rows, dtype=torch.int64, device=dev_emb.device))
-                    store_db.upsert(vec, [m["region_id"] for m in metas_all], metas_all, files=list(done_files))
+                    rep = store_db.upsert(vec, [m["region_id"] for m in metas_all], metas_all, files=list(done_files),
+                                          skip_duplicates=self.skip_duplicates)
+                    if rep and rep["dropped"]:
+                        stats["duplicates_skipped"] += len(rep["dropped"])
+                        log_status(f"♻️ Skipped {len(rep['dropped'])} near-duplicates of stored vectors "
+                                   f"(score >= {self.skip_duplicates:g}); {rep['kept']} of the batch stored")
             else:
                 store_db.upsert(torch.zeros((0, store_db.dim)), [], [], files=list(done_files))
             processed_files.update(done_files)

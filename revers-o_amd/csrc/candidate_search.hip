@@ -242,6 +242,84 @@ extern "C" int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, 
     API_END
 }
 
+// ---- deduplicating append (include/revo.h revo_gallery_append_unique; dedup.hip)
+extern "C" int32_t revo_gallery_append_unique(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device,
+                                              float threshold, int64_t* rows, float* scores, int32_t dst_on_device,
+                                              int64_t* n_kept, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && rows && scores && n_kept && (vecs || n == 0), "gallery_append_unique: null argument");
+    REVO_REQUIRE(n >= 0, "gallery_append_unique: negative row count");
+    REVO_REQUIRE(n <= revo::DEDUP_MAX_BATCH, "gallery_append_unique: at most " + std::to_string(revo::DEDUP_MAX_BATCH) +
+                                                 " rows per call (split the batch: consecutive calls give the same result)");
+    CHECK_RC(require_threshold(1, threshold, "gallery_append_unique"));
+    REVO_REQUIRE(g->size + n <= g->capacity, "gallery_append_unique: exceeds the capacity given at create (room for every row "
+                                             "of the batch is needed, however few are kept)");
+    CHECK_RC(require_f32_rows(g, "gallery_append_unique"));
+    REVO_REQUIRE(g->size + n < (1ll << 31), "gallery_append_unique: row indices must fit in 31 bits");
+    if (n == 0) { *n_kept = 0; return 0; }
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    // what an append invalidates; the gallery's size stays N0 until the last step has been enqueued and waited for: a failure
+    // on the way leaves the gallery as it was (the provisional rows lie behind its end)
+    g->rows_changed(); g->maxsim.rows = -1;
+    const long N0 = g->size, nb = (long)n, R0 = N0 & ~31l, nwords = (N0 - R0 + nb + 63) / 64 * 2;
+    const int D = g->D;
+    CHECK_RC(begin_counted(g, 1, "gallery_append_unique", st));
+    uint32_t *edges = nullptr, *rep = nullptr, *kept_dev = nullptr, *bits = nullptr, *cnt = nullptr, *first = nullptr;
+    long long* rows_dev = nullptr;
+    float* scores_dev = nullptr;
+    CHECK_RC(carve_buffer(g->dedup, st, [&](Layout& l) {
+        edges = l.take<uint32_t>(dedup_edge_words(nb));
+        rep = l.take<uint32_t>(nb); rows_dev = l.take<long long>(nb); scores_dev = l.take<float>(nb);
+        kept_dev = l.take<uint32_t>(1); bits = l.take<uint32_t>(nwords); cnt = l.take<uint32_t>(1); first = l.take<uint32_t>(1);
+    }));
+    // provisional append: the fp32 master and the bf16 row of every batch row, with the bits an append writes
+    CHECK_RC(gallery_write_rows(g, vecs, n, normalize, src_on_device, N0, nullptr, "dedup_write", st));
+    REVO_HIP_CHECK(hipMemsetAsync(edges, 0xff, (size_t)dedup_pad(nb) * 4, st));
+    REVO_HIP_CHECK(hipMemsetAsync(edges + dedup_pad(nb), 0, (size_t)nb * dedup_words(nb) * 4, st));
+    CandidateWs ws{g->pbuf, g->pairs.cap};
+    CHECK_RC(ws.carve(ws.cap > PAIRS_WS_KEYS ? ws.cap : PAIRS_WS_KEYS, st));
+    DedupJoinArgs ja{};
+    ja.j.Gb = g->gb.p; ja.j.ldg = D; ja.j.N = N0 + nb; ja.j.D = D; ja.j.gstat = g->gstat.p; ja.j.thr = threshold;
+    ja.N0 = (uint32_t)N0; ja.edges = edges;
+    CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+        ja.j.cnt = ws.cnt; ja.j.keys = ws.cand; ja.j.cap = ws.cap;
+        ProfScope ps("dedup_join", st);
+        return launch_dedup_join(ja, st);
+    }, [&](unsigned long long n_cand) -> int {
+        REVO_REQUIRE(n_cand <= (unsigned long long)PAIRS_MAX_CAND,
+                     "gallery_append_unique: " + std::to_string(n_cand) + " pairs inside the rounding bound of the threshold exceed "
+                     "the limit of " + std::to_string(PAIRS_MAX_CAND) + " (move the threshold)");
+        return 0;
+    }, "gallery_append_unique: the candidate count changed between two joins"));
+    { ProfScope ps("dedup_rescore", st);
+      CHECK_RC(launch_dedup_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, D, threshold, edges, N0, nb, st)); }
+    {
+        ProfScope ps("dedup_select", st);
+        DedupSelectArgs sa{};
+        sa.edges = edges; sa.n = nb; sa.N0 = N0; sa.rep = rep; sa.rows = rows_dev; sa.n_kept = kept_dev;
+        CHECK_RC(launch_dedup_select(sa, st));
+        CHECK_RC(launch_dedup_finish(rep, nb, N0, g->gf.p, D, D, scores_dev, bits, nwords, st));
+    }
+    // the tail compacted through the remove path: one chunk (the batch and the at most 31 gallery rows in front of it that
+    // share its first bitmap word); only rows >= N0 move
+    long kept_rows = 0;
+    const long len = N0 - R0 + nb, chunk = (len + 31) / 32 * 32;
+    CHECK_RC(gallery_compact_rows(g, bits, R0, len, chunk, cnt, first, "dedup_compact", st, &kept_rows));
+    uint32_t kept_h = 0;
+    REVO_HIP_CHECK(hipMemcpyAsync(&kept_h, kept_dev, 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    REVO_REQUIRE((long)kept_h == kept_rows - (N0 - R0) && (long)kept_h <= nb, "gallery_append_unique: internal: inconsistent kept counts");
+    CHECK_RC(copy_out(rows, rows_dev, (size_t)nb, dst_on_device));
+    CHECK_RC(copy_out(scores, scores_dev, (size_t)nb, dst_on_device));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.passes, st));
+    g->size = N0 + (long)kept_h;
+    *n_kept = (int64_t)kept_h;
+    return 0;
+    API_END
+}
+
 // ---- exact kNN graph of one gallery (include/revo.h revo_gallery_knn; knn.hip)
 #ifdef REVO_EXPERIMENTS
 static long g_knn_cap_keys = 0;

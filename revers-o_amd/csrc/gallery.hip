@@ -118,8 +118,8 @@ extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
 // Rows come in from `vecs` (host rows: staged in chunks of 64 MB) through one kernel: fp32 master row, bf16 scan row, and the
 // row's share of the certificate's maxima (max ||g||, max ||bf16(g) - g||; with normalize = 0 the rows are stored as given,
 // whatever their length).  Row i goes to row row0 + i or, with a map (device [n]), to row map[i]: the same bits either way.
-static int write_rows(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device, int64_t row0,
-                      const long long* map, const char* prof, hipStream_t st) {
+int gallery_write_rows(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device, int64_t row0,
+                       const long long* map, const char* prof, hipStream_t st) {
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
     for (int64_t done = 0; done < n; done += chunk_rows) {
@@ -148,7 +148,7 @@ extern "C" int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64
     REVO_ON_DEVICE(g->device);
     hipStream_t st = (hipStream_t)stream;
     g->drop_results(); g->maxsim.rows = -1;
-    CHECK_RC(write_rows(g, vecs, n, normalize, src_on_device, g->size, nullptr, "gallery_append", st));
+    CHECK_RC(gallery_write_rows(g, vecs, n, normalize, src_on_device, g->size, nullptr, "gallery_append", st));
     g->size += n;
     return 0;
     API_END
@@ -174,6 +174,51 @@ extern "C" int32_t revo_debug_set_remove_chunk(int64_t rows) {
     return 0;
 }
 #endif
+// The rows [R0, R0 + N) of the gallery (R0 a multiple of 32) compacted by a device bitmap over them -- bit p: row R0 + p leaves
+// -- in chunks of `chunk` rows; cnt / first: [chunks] device words.  *kept_out = the rows that stay (rows R0 .. R0 + kept - 1
+// afterwards).  Enqueued on `st` behind one synchronisation (the host reads the chunks' counts).
+int gallery_compact_rows(revo_gallery* g, const uint32_t* bits, long R0, long N, long chunk, uint32_t* cnt, uint32_t* first,
+                         const char* prof, hipStream_t st, long* kept_out) {
+    const int D = g->D;
+    const long nchunks = (N + chunk - 1) / chunk;
+    std::vector<uint32_t> h_cnt(nchunks), h_first(nchunks);
+    { ProfScope ps(prof, st);
+      CHECK_RC(revo::launch_remove_count(bits, N, chunk, cnt, first, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), cnt, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(h_first.data(), first, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    // Chunk after chunk, front to back, everything ordered on the stream.  The kept rows of chunk c go to rows
+    // [base, base + cnt) with base <= row0 and base + cnt <= row0 + len: below every later chunk's rows.  Where that range
+    // ends at or before row0 the gather writes it directly (source and destination rows are disjoint); otherwise it gathers
+    // into staging memory, and a copy ordered behind it brings the run down.  No launch writes a row it also reads.
+    long base = 0;
+    {
+        ProfScope ps(prof, st);
+        for (long c = 0; c < nchunks; ++c) {
+            const long row0 = c * chunk, len = std::min(chunk, N - row0), kept = (long)h_cnt[c];
+            REVO_REQUIRE(kept <= len && base <= row0, std::string(prof) + ": internal: inconsistent chunk counts");
+            // rows in front of the first removed row of the whole range stay where they are
+            const long j0 = base == row0 ? std::min<long>((long)h_first[c], kept) : 0;
+            if (kept > j0) {
+                const bool direct = base + kept <= row0;
+                if (!direct) CHECK_RC(g->stage.grow((size_t)chunk * D * 4, st));
+                for (int which = g->keep_f32 ? 0 : 1; which < 2; ++which) {
+                    const int u4 = which == 0 ? D / 4 : D / 8;       // 16-byte units of a row (D % 64 == 0)
+                    uint4* arr = (which == 0 ? (uint4*)g->gf.p : (uint4*)g->gb.p) + R0 * u4;
+                    uint4* dst = direct ? arr + base * u4 : (uint4*)g->stage.p;
+                    CHECK_RC(revo::launch_remove_gather(bits, N, row0, len, j0, arr, dst, u4, st));
+                    if (!direct)
+                        REVO_HIP_CHECK(hipMemcpyAsync(arr + (base + j0) * u4, dst + j0 * u4, (size_t)(kept - j0) * u4 * 16,
+                                                      hipMemcpyDeviceToDevice, st));
+                }
+            }
+            base += kept;
+        }
+    }
+    *kept_out = base;
+    return 0;
+}
+
 extern "C" int32_t revo_gallery_remove(revo_gallery* g, const uint32_t* remove_bits, int64_t rows, int32_t src_on_device,
                                        int64_t* n_removed, void* stream) {
     API_BEGIN
@@ -204,43 +249,11 @@ extern "C" int32_t revo_gallery_remove(revo_gallery* g, const uint32_t* remove_b
         REVO_HIP_CHECK(hipMemcpyAsync(own_bits, remove_bits, (size_t)nwords * 4, hipMemcpyHostToDevice, st));
         bits = own_bits;
     }
-    std::vector<uint32_t> h_cnt(nchunks), h_first(nchunks);
-    { ProfScope ps("gallery_remove", st);
-      CHECK_RC(revo::launch_remove_count(bits, N, chunk, cnt, first, st)); }
-    REVO_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), cnt, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
-    REVO_HIP_CHECK(hipMemcpyAsync(h_first.data(), first, (size_t)nchunks * 4, hipMemcpyDeviceToHost, st));
-    REVO_HIP_CHECK(hipStreamSynchronize(st));
-    // Chunk after chunk, front to back, everything ordered on the stream.  The kept rows of chunk c go to rows
-    // [base, base + cnt) with base <= row0 and base + cnt <= row0 + len: below every later chunk's rows.  Where that range
-    // ends at or before row0 the gather writes it directly (source and destination rows are disjoint); otherwise it gathers
-    // into staging memory, and a copy ordered behind it brings the run down.  No launch writes a row it also reads.
     long base = 0;
-    {
-        ProfScope ps("gallery_remove", st);
-        for (long c = 0; c < nchunks; ++c) {
-            const long row0 = c * chunk, len = std::min(chunk, N - row0), kept = (long)h_cnt[c];
-            REVO_REQUIRE(kept <= len && base <= row0, "gallery_remove: internal: inconsistent chunk counts");
-            // rows in front of the first removed row of the whole gallery stay where they are
-            const long j0 = base == row0 ? std::min<long>((long)h_first[c], kept) : 0;
-            if (kept > j0) {
-                const bool direct = base + kept <= row0;
-                if (!direct) CHECK_RC(g->stage.grow((size_t)chunk * D * 4, st));
-                for (int which = g->keep_f32 ? 0 : 1; which < 2; ++which) {
-                    const int u4 = which == 0 ? D / 4 : D / 8;       // 16-byte units of a row (D % 64 == 0)
-                    uint4* arr = which == 0 ? (uint4*)g->gf.p : (uint4*)g->gb.p;
-                    uint4* dst = direct ? arr + base * u4 : (uint4*)g->stage.p;
-                    CHECK_RC(revo::launch_remove_gather(bits, N, row0, len, j0, arr, dst, u4, st));
-                    if (!direct)
-                        REVO_HIP_CHECK(hipMemcpyAsync(arr + (base + j0) * u4, dst + j0 * u4, (size_t)(kept - j0) * u4 * 16,
-                                                      hipMemcpyDeviceToDevice, st));
-                }
-            }
-            base += kept;
-        }
-        // an emptied gallery starts its certificate maxima over, as revo_gallery_clear does; otherwise they stay: maxima over
-        // more rows are upper bounds still
-        if (base == 0) REVO_HIP_CHECK(hipMemsetAsync(g->gstat.p, 0, 8, st));
-    }
+    CHECK_RC(gallery_compact_rows(g, bits, 0, N, chunk, cnt, first, "gallery_remove", st, &base));
+    // an emptied gallery starts its certificate maxima over, as revo_gallery_clear does; otherwise they stay: maxima over
+    // more rows are upper bounds still
+    if (base == 0) REVO_HIP_CHECK(hipMemsetAsync(g->gstat.p, 0, 8, st));
     REVO_HIP_CHECK(hipStreamSynchronize(st));
     if (base < N) g->maxsim.rows = -1;
     g->size = base;
@@ -273,6 +286,6 @@ extern "C" int32_t revo_gallery_update(revo_gallery* g, const int64_t* row_idx, 
     long long* map = (long long*)g->edit.p;
     REVO_HIP_CHECK(hipMemcpyAsync(map, row_idx, (size_t)n * 8, hipMemcpyHostToDevice, st));
     REVO_HIP_CHECK(hipStreamSynchronize(st));             // the caller may free its host array on return
-    return write_rows(g, vecs, n, normalize, src_on_device, 0, map, "gallery_update", st);
+    return gallery_write_rows(g, vecs, n, normalize, src_on_device, 0, map, "gallery_update", st);
     API_END
 }

@@ -140,6 +140,9 @@ struct __attribute__((visibility("default"))) revo_gallery {   // (the C ABI nam
     DeviceBuffer<> pbuf;
     // revo_gallery_remove: per-chunk counts | first removed rows | the copy of a host bitmap; revo_gallery_update: the row map
     DeviceBuffer<> edit;
+    // revo_gallery_append_unique: edges (first_old | bit matrix) | representatives | rows | scores | kept count | the
+    // remove-bitmap of the dropped rows and its chunk words; allocated at the first call, grown with the batch size
+    DeviceBuffer<> dedup;
     TwoPhaseState two;
     PairsResult pairs;
     RangeResult range;
@@ -181,6 +184,12 @@ template <class T> int copy_out(void* dst, const T* src, size_t count, int dst_o
 // ---- host helpers that cross the files (`allow`: what search_filter gave; the device of the handle is current)
 // gallery.hip: the allow-bitmap the next search of this handle runs with (null: none)
 int search_filter(const revo_gallery* g, const uint32_t** out);
+// gallery.hip: the row writer of append and update (row i of vecs -> row row0 + i, or map[i]), and the in-place compaction of
+// the rows [R0, R0 + N) behind revo_gallery_remove
+int gallery_write_rows(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device, int64_t row0,
+                       const long long* map, const char* prof, hipStream_t st);
+int gallery_compact_rows(revo_gallery* g, const uint32_t* bits, long R0, long N, long chunk, uint32_t* cnt, uint32_t* first,
+                         const char* prof, hipStream_t st, long* kept_out);
 // search.hip: the handle's per-query arrays, grown to hold Q queries; the rows of the large-k sample; revo_search_topk_large
 // behind its argument checks (search_prepass_rows and search_topk stay inside search.hip: nothing else calls them)
 int search_grow_queries(revo_gallery* g, int Q, hipStream_t st);

@@ -480,6 +480,36 @@ int launch_clusters_labels(uint32_t* parent, const uint32_t* allow, long N, int 
 // sorted keys -> members; rank [n] workspace; offsets [n_clusters + 1]
 int launch_clusters_emit(const uint64_t* keys, long n, long n_clusters, int b, unsigned long long* rank, long long* members,
                          long long* offsets, hipStream_t st);
+// ---- deduplicating append (revo_gallery_append_unique; dedup.hip): the pairs join restricted to the tile
+// pairs whose column tile holds a batch row (dedup_plan.h), certain edges applied in place, a one-workgroup greedy selection
+constexpr long DEDUP_MAX_BATCH = 16384;      // batch rows of one call (the n x n bit matrix: 32 MB; the kept bitmap: 2 KB of LDS)
+constexpr uint32_t DEDUP_NONE = 0xffffffffu; // first_old / rep: no row
+// the edges of one call, one array of words: first_old [dedup_pad(n)] | mat [n][dedup_words(n)].  first_old[j]: the lowest
+// gallery row that is a neighbour of batch row j (DEDUP_NONE: none); bit i of mat row j: batch rows i < j are neighbours.
+// (One pointer, the sizes derived from n: the join has no scalar register to spare.)
+__host__ __device__ inline uint32_t dedup_words(long n) { return (uint32_t)((n + 63) / 64 * 2); }   // even: read as 64-bit words
+__host__ __device__ inline uint32_t dedup_pad(long n) { return (uint32_t)((n + 63) / 64 * 64); }
+inline size_t dedup_edge_words(long n) { return (size_t)dedup_pad(n) + (size_t)n * dedup_words(n); }
+struct DedupJoinArgs {
+    PairsJoinArgs j;              // the pairs join's arguments over all N0 + n rows (allow unused; cnt / keys / cap: the AMBIGUOUS pairs)
+    uint32_t N0;                  // gallery rows in front of the batch
+    uint32_t* edges;
+};
+int launch_dedup_join(const DedupJoinArgs& a, hipStream_t st);
+// fp32 score of the ambiguous pairs [0, n); those >= thr become edges (nb: batch rows)
+int launch_dedup_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, int D, float thr, uint32_t* edges, long N0,
+                         long nb, hipStream_t st);
+struct DedupSelectArgs {
+    const uint32_t* edges;
+    long n, N0;
+    uint32_t* rep;                // [n] the representative's row BEFORE the compaction (batch row i: N0 + i); DEDUP_NONE: kept
+    long long* rows;              // [n] the row's own final row, or its representative's
+    uint32_t* n_kept;             // [1]
+};
+int launch_dedup_select(const DedupSelectArgs& a, hipStream_t st);
+// scores [n] (-inf: kept) and the remove-bitmap (nwords words) of the dropped rows over the rows from N0 & ~31 on
+int launch_dedup_finish(const uint32_t* rep, long n, long N0, const float* Gf, long ldg, int D, float* scores, uint32_t* bits,
+                        long nwords, hipStream_t st);
 // ---- exact kNN graph (revo_gallery_knn; knn.hip): the pairs join with a level PER ROW.  An estimated
 // level t_r for every row (sample pass), the join keeps pair (i, j) when its bf16 score reaches min(lb_i, lb_j), the re-score
 // turns a candidate into a directed entry for every end whose level it reaches, sort by (row, score), select with a

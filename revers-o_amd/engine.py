@@ -289,6 +289,31 @@ class Gallery:
                                                      int(v.is_cuda), _lib.current_stream()), "revo_gallery_append")
         return start
 
+    ADD_UNIQUE_MAX = 16384                        # rows of one revo_gallery_append_unique call (DEDUP_MAX_BATCH, kernels.h)
+
+    def add_unique(self, vectors, threshold, normalize=True):
+        """Append only the rows that are no near-duplicate (include/revo.h, DEDUP): row by row, a vector whose exact fp32
+        score against a gallery row or an earlier kept row of ``vectors`` reaches ``threshold`` is dropped.  Returns
+        ``(rows int64 [n], scores fp32 [n], kept bool [n])`` on the device: a kept row's new row index and -inf, a dropped
+        row's representative (the first such row) and its score.  The gallery needs room for every row of a call, kept or
+        not; inputs above ``ADD_UNIQUE_MAX`` rows go in consecutive calls, which gives the same result.  Synchronous."""
+        v = vectors.detach().to(torch.float32).contiguous()
+        if v.dim() != 2 or v.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [n, {self.dim}], got {tuple(v.shape)}")
+        if v.is_cuda:
+            _require_cuda(v, "vectors", self.device)
+        n = int(v.shape[0])
+        rows = torch.empty((n,), dtype=torch.int64, device=self.device)
+        scores = torch.empty((n,), dtype=torch.float32, device=self.device)
+        kept = C.c_int64()
+        with self._lock, torch.cuda.device(self.device):
+            for a in range(0, n, self.ADD_UNIQUE_MAX):
+                b = min(n, a + self.ADD_UNIQUE_MAX)
+                _lib.check(self._lib.revo_gallery_append_unique(
+                    self._h, _lib.ptr(v[a:b]), b - a, int(bool(normalize)), int(v.is_cuda), float(threshold), _lib.ptr(rows[a:b]),
+                    _lib.ptr(scores[a:b]), 1, C.byref(kept), _lib.current_stream()), "revo_gallery_append_unique")
+        return rows, scores, torch.isinf(scores) & (scores < 0)
+
     def remove(self, rows):
         """Take rows out in place (include/revo.h, EDIT): ``rows`` is a ``bool [len]`` mask, a packed int32 bitmap
         ``[ceil(len / 32)]`` (bit ``r & 31`` of word ``r >> 5``) or an int64 index tensor, on the device or the host.  The

@@ -358,14 +358,25 @@ class GalleryStore:
         old.close()
         self.gallery = new
 
-    def upsert(self, vectors, ids, payloads, files=None, replace_existing=False):
+    def upsert(self, vectors, ids, payloads, files=None, replace_existing=False, skip_duplicates=None):
         """vectors: [n, dim] fp32 tensor, host or DEVICE (an ingest appends its embeddings where they are: they never
         visit the host); rows are normalised at insert.  ``files``: source files these rows complete (resume bookkeeping).
         ``replace_existing=True`` is the database's own upsert: a point whose id is already in the store gets the new vector
         and payload in place, the others are appended (of an id given twice in one call the last entry counts).  The
-        default appends every row, whatever its id."""
+        default appends every row, whatever its id.
+        ``skip_duplicates=t`` (a float) is the insert-time dedup (include/revo.h, DEDUP): in order, a point whose vector
+        scores >= t against a stored point or an earlier kept point of this call is not stored.  Only kept points enter the
+        ids, the payloads and the shards; ``files`` is recorded as ever (a file whose rows were all dropped is done).  The call
+        then returns ``{"kept": n, "dropped": [(id, representative id, score), ...]}``.  Not with ``replace_existing``."""
+        if skip_duplicates is not None:
+            if replace_existing:
+                raise ValueError("upsert: skip_duplicates and replace_existing exclude each other (a replaced point keeps its row)")
+            skip_duplicates = float(skip_duplicates)
+            if skip_duplicates != skip_duplicates:
+                raise ValueError("upsert: skip_duplicates is NaN")
         vectors = torch.as_tensor(vectors, dtype=torch.float32)
         assert vectors.shape[0] == len(ids) == len(payloads)
+        report = None if skip_duplicates is None else {"kept": 0, "dropped": []}
         if replace_existing and vectors.shape[0]:
             last = {pid: i for i, pid in enumerate(ids)}
             have = self._id_row_map()
@@ -375,13 +386,23 @@ class GalleryStore:
                 self._update([ids[i] for i in old], vectors[old], [payloads[i] for i in old])
             vectors, ids, payloads = vectors[new], [ids[i] for i in new], [payloads[i] for i in new]
         if vectors.shape[0]:
-            self._grow(len(self) + vectors.shape[0])
-            self.gallery.add(vectors, normalize=True)
+            self._grow(len(self) + vectors.shape[0])           # (room for every row of the call, kept or not)
+            if skip_duplicates is None:
+                self.gallery.add(vectors, normalize=True)
+            else:
+                rows, scores, kept = (a.cpu().tolist() for a in self.gallery.add_unique(vectors, skip_duplicates))
+                base = len(self.ids)
+                kept_ids = [pid for pid, k in zip(ids, kept) if k]
+                report["kept"] = len(kept_ids)
+                report["dropped"] = [(pid, self.ids[r] if r < base else kept_ids[r - base], s)
+                                     for pid, r, s, k in zip(ids, rows, scores, kept) if not k]
+                ids, payloads = kept_ids, [p for p, k in zip(payloads, kept) if k]
             self.ids.extend(ids)
             self.payloads.extend(payloads)
         if files:
             self._files_pending.extend(files)
         self.complete = False
+        return report
 
     # -- changes of stored points (include/revo.h, EDIT): on the device in place, on disk one manifest line each ------
     def _id_row_map(self):
