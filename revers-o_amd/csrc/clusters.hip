@@ -2,7 +2,7 @@
 // components of the graph whose edges are the pairs of revo_gallery_pairs, without storing those pairs.
 //
 //   join     the pairs join (pairs.hip: same walk over the upper triangle of row-tile pairs, operands, main loop, column mask,
-//            diagonal rule) with three-way scores: v >= ub = fl(thr + eps) raised by its rounding is certainly an edge (the
+//            diagonal rule; tile_walk.h) with three-way scores: v >= ub = fl(thr + eps) raised by its rounding is certainly an edge (the
 //            fp32 score is >= v - eps >= thr) and is merged into the union-find (unionfind.h) in place; lb <= v < ub is
 //            ambiguous and appended as the key (i << 32) | j; v < lb is certainly no edge
 //   rescore  the fp32 score of every ambiguous pair; those >= thr are merged.  Nothing is kept, nothing is sorted
@@ -13,6 +13,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 #include "unionfind.h"
 
@@ -28,133 +29,26 @@ __global__ __launch_bounds__(256) void clusters_init_kernel(uint32_t* __restrict
 }
 
 // -------------------------------------------------------------------------- join ----
-// pairs_join_kernel's walk.  Per tile a lane classifies its 8 x 16 scores into bit masks without a branch per score (a
-// branch per score kept so many lane masks alive that the scalar spills took a second VGPR and the main loop spilled):
-// ambiguous ones are appended as the pairs join appends its candidates, certain ones are merged in one loop behind the
-// rows: the row's root stays in a register across the row's columns, and a column whose parent is that root costs one load.
+// tile_walk.h's tile-pair frame over the triangle and its three-way classification; a certain edge is merged: the row's
+// root stays in a register across the row's columns, and a column whose parent is that root costs one load.
 __global__ __launch_bounds__(G256_THREADS, 2) void clusters_join_kernel(ClustersJoinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PairsJoinArgs& p = a.j;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int lane = tid & 63;
-    const long per = p.pairs / gridDim.x, rem = p.pairs - per * gridDim.x;
-    const long w = blockIdx.x;
-    const long p0 = w * per + (w < rem ? w : rem);
-    const int n_my = (int)(per + (w < rem ? 1 : 0));
-    if (n_my <= 0) return;
     const float lb = pairs_lb(p.gstat, p.thr, p.D), ub = pairs_ub(p.gstat, p.thr, p.D);
-    // the row tile of p0: the largest ti with pairs_row_start(ti) <= p0
-    int lo = 0, hi = (int)p.T - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs_row_start(mid, p.T) <= p0) lo = mid; else hi = mid - 1;
-    }
-    int ti = lo, tj = (int)(lo + (p0 - pairs_row_start(lo, p.T)));
-    G256Operand A, B;
-    g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-    g256_issue_prologue(A, B, smem, p.D, wave);
-    for (int it = 0; it < n_my; ++it) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop(A, B, smem, p.D, wave, lane, acc);
-        const int ci = ti, cj = tj;                         // this tile's pair; the next one's DMA overlaps the epilogue
-        if (++tj == (int)p.T) { ++ti; tj = ti; }
-        if (it + 1 < n_my) {
-            if (ti != ci) g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-            g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-            g256_issue_prologue(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
-        const int lr = lane & 15, lq = lane >> 4;
-        const int rbase = (wave >> 2) * 128 + lr;
-        const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
-        const long n0 = (long)cj * 256;
-        const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed column
-        const uint64_t bits = fm >> (lq * 4);
-        const bool diag = ci == cj;
-        // the rows of the tile with a score that reaches lb (wave-uniform): most tiles have none
-        uint32_t hot = 0u;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, acc[m][n][j]);
-            if (__ballot(mx >= lb) != 0ull) hot |= 1u << m;
-        }
-        if (hot == 0u) continue;
-        // bit c = n * 4 + j of the masks below: this lane's column cw + n * 16 + lq * 4 + j
-        uint32_t colm = 0u;                                 // columns that exist and are allowed
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) colm |= ((uint32_t)(bits >> (n * 16 + j)) & 1u) << (n * 4 + j);
-        const int dl = rbase - cw - lq * 4;                 // row - column = dl + m * 16 - (n * 16 + j)
-        const unsigned long long below = lanes_below(lane);
-        uint64_t sure0 = 0ull, sure1 = 0ull;                // bit (m & 3) * 16 + c: score [m][c] is a certain edge
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (!((hot >> m) & 1u)) continue;               // wave-uniform
-            const int row = rbase + m * 16;
-            const long gi = (long)ci * 256 + row;
-            const bool rok = gi < p.N && (!p.allow || ((p.allow[gi >> 5] >> (gi & 31)) & 1u));
-            uint32_t pm = rok ? colm : 0u;                  // the pairs of this row that count: on the diagonal, column > row
-            if (diag) {
-                uint32_t gt = 0u;
-#pragma unroll
-                for (int c = 0; c < 16; ++c) gt |= ((uint32_t)(dl + m * 16 - ((c >> 2) * 16 + (c & 3))) >> 31) << c;
-                pm &= gt;
-            }
-            uint32_t ge_lb = 0u, ge_ub = 0u;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = acc[m][n][j];
-                    ge_lb |= v >= lb ? 1u << (n * 4 + j) : 0u;
-                    ge_ub |= v >= ub ? 1u << (n * 4 + j) : 0u;
-                }
-            const uint32_t sure = pm & ge_lb & ge_ub, amb = pm & ge_lb & ~ge_ub;
-            if (m < 4) sure0 |= (uint64_t)sure << (m * 16); else sure1 |= (uint64_t)sure << ((m - 4) * 16);
-            if (__ballot(amb != 0u) == 0ull) continue;      // wave-uniform
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const bool take = (amb >> c) & 1u;
-                const unsigned long long mk = __ballot(take);
-                if (mk == 0ull) continue;                   // wave-uniform
-                const unsigned long long pos = wave_append(mk, p.cnt, lane, below);
-                if (take && pos < (unsigned long long)p.cap)
-                    p.keys[pos] = ((uint64_t)gi << 32) | (uint64_t)(n0 + cw + (c >> 2) * 16 + lq * 4 + (c & 3));
-            }
-        }
-        // the merges: per lane, rows in order
+    tile_pair_frame(p, TriangleWalk{p.T}, smem, [&](int ci, int cj, long n0, bool diag, int wave, int lane, const f32x4 (&acc)[8][4]) {
+        const uint64_t fm = tile_column_mask(p.N, n0, (wave & 3) * 64, p.allow);
         const UfLimits lim = uf_limits(p.N);
-        uint32_t* const err = a.parent + p.N;           // (the error word sits behind the last row's parent)
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-            uint64_t mk = h ? sure1 : sure0;
-            int last = -1;
-            uint32_t ri = 0u;
-            while (mk != 0ull) {
-                const int bit = __ffsll((long long)mk) - 1;
-                mk &= mk - 1ull;
-                const int m = h * 4 + (bit >> 4), c = bit & 15;
-                const uint32_t gi = (uint32_t)(ci * 256 + rbase + m * 16);
-                const uint32_t gj = (uint32_t)(n0 + cw + (c >> 2) * 16 + lq * 4 + (c & 3));
-                if (m != last) { ri = uf_find(a.parent, gi, lim.walk, err); last = m; }
-                if (UF_LOAD(a.parent + gj) == ri) continue; // same component (true whenever seen: links are never removed)
-                ri = uf_unite(a.parent, ri, gj, lim, err);
-                if (UF_LOAD(err) != 0u) { mk = 0ull; h = 2; }   // a trip limit was hit somewhere: leave
-            }
-        }
-    }
+        uint32_t* const err = a.parent + p.N;               // (the error word sits behind the last row's parent)
+        uint32_t ri = 0u;
+        classify_tile3(p, fm, lb, ub, ci, n0, diag, wave, lane, acc,
+                       [&](long gi) { return !p.allow || ((p.allow[gi >> 5] >> (gi & 31)) & 1u); },
+                       [&](uint32_t gi, uint32_t gj, bool new_row) {
+                           if (new_row) ri = uf_find(a.parent, gi, lim.walk, err);
+                           if (UF_LOAD(a.parent + gj) == ri) return true;   // same component (true whenever seen: links are never removed)
+                           ri = uf_unite(a.parent, ri, gj, lim, err);
+                           return UF_LOAD(err) == 0u;       // a trip limit was hit somewhere: leave
+                       });
+    });
 }
 
 // ----------------------------------------------------------------------- rescore ----

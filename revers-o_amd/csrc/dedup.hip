@@ -16,6 +16,7 @@
 #include "dedup_plan.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -41,122 +42,28 @@ __device__ __forceinline__ uint32_t dedup_wave_min(uint32_t v) {
 }  // namespace
 
 // -------------------------------------------------------------------------- join ----
-// clusters_join_kernel's epilogue on dedup_plan.h's walk: A is the row tile ti (it changes with every pair), B the column tile
-// tj (the same rows across a column's pairs, from L2).  Both operands are set up again for every pair: keeping B's set-up
-// behind `if (tj != cj)` cost 8 spilled VGPRs (hipcc's resource report; tests/test_dedup_host.py holds the kernel to 0).
+// tile_walk.h's tile-pair frame on dedup_plan.h's walk, with its three-way classification: A is the row tile ti (it changes
+// with every pair), B the column tile tj (the same rows across a column's pairs, from L2), so both operands are set up
+// again for every pair (tests/test_dedup_host.py holds the kernel to 0 spilled VGPRs).
 // The wave's columns are those of [N0, N): a tile that straddles N0 ignores its old columns.
+struct DedupWalk {
+    static constexpr bool kInitBoth = true;
+    long tj0, T;
+    __device__ __forceinline__ void locate(long p0, int& ti, int& tj) const { dedup_locate(p0, tj0, T, ti, tj); }
+    __device__ __forceinline__ void next(int& ti, int& tj) const { dedup_next(ti, tj); }
+};
 __global__ __launch_bounds__(G256_THREADS, 2) void dedup_join_kernel(DedupJoinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PairsJoinArgs& p = a.j;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int lane = tid & 63;
-    const long per = p.pairs / gridDim.x, rem = p.pairs - per * gridDim.x;
-    const long w = blockIdx.x;
-    const long p0 = w * per + (w < rem ? w : rem);
-    const int n_my = (int)(per + (w < rem ? 1 : 0));
-    if (n_my <= 0) return;
     const float lb = pairs_lb(p.gstat, p.thr, p.D), ub = pairs_ub(p.gstat, p.thr, p.D);
-    int ti, tj;
-    dedup_locate(p0, (long)(a.N0 >> 8), p.T, ti, tj);
-    G256Operand A, B;
-    g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-    g256_issue_prologue(A, B, smem, p.D, wave);
-    for (int it = 0; it < n_my; ++it) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop(A, B, smem, p.D, wave, lane, acc);
-        const int ci = ti, cj = tj;                         // this tile's pair; the next one's DMA overlaps the epilogue
-        dedup_next(ti, tj);
-        if (it + 1 < n_my) {
-            g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-            g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-            g256_issue_prologue(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
-        const int lr = lane & 15, lq = lane >> 4;
-        const int rbase = (wave >> 2) * 128 + lr;
-        const int cw = (wave & 3) * 64;                     // the wave's 64 columns
-        const long n0 = (long)cj * 256;
+    tile_pair_frame(p, DedupWalk{(long)(a.N0 >> 8), p.T}, smem, [&](int ci, int cj, long n0, bool diag, int wave, int lane, const f32x4 (&acc)[8][4]) {
+        const int cw = (wave & 3) * 64;
         // columns that exist (< N) and are batch rows (>= N0)
         const uint64_t fm = tile_column_mask(p.N, n0, cw, nullptr) & ~tile_column_mask((long)a.N0, n0, cw, nullptr);
-        if (fm == 0ull) continue;                           // wave-uniform: no batch column
-        const uint64_t bits = fm >> (lq * 4);
-        const bool diag = ci == cj;
-        // the rows of the tile with a score that reaches lb (wave-uniform): most tiles have none
-        uint32_t hot = 0u;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, acc[m][n][j]);
-            if (__ballot(mx >= lb) != 0ull) hot |= 1u << m;
-        }
-        if (hot == 0u) continue;
-        // bit c = n * 4 + j of the masks below: this lane's column cw + n * 16 + lq * 4 + j
-        uint32_t colm = 0u;
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) colm |= ((uint32_t)(bits >> (n * 16 + j)) & 1u) << (n * 4 + j);
-        const int dl = rbase - cw - lq * 4;                 // row - column = dl + m * 16 - (n * 16 + j)
-        const unsigned long long below = lanes_below(lane);
-        uint64_t sure0 = 0ull, sure1 = 0ull;                // bit (m & 3) * 16 + c: score [m][c] is a certain edge
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (!((hot >> m) & 1u)) continue;               // wave-uniform
-            const int row = rbase + m * 16;
-            const long gi = (long)ci * 256 + row;
-            uint32_t pm = gi < p.N ? colm : 0u;             // the pairs of this row that count: on the diagonal, column > row
-            if (diag) {
-                uint32_t gt = 0u;
-#pragma unroll
-                for (int c = 0; c < 16; ++c) gt |= ((uint32_t)(dl + m * 16 - ((c >> 2) * 16 + (c & 3))) >> 31) << c;
-                pm &= gt;
-            }
-            uint32_t ge_lb = 0u, ge_ub = 0u;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = acc[m][n][j];
-                    ge_lb |= v >= lb ? 1u << (n * 4 + j) : 0u;
-                    ge_ub |= v >= ub ? 1u << (n * 4 + j) : 0u;
-                }
-            const uint32_t sure = pm & ge_lb & ge_ub, amb = pm & ge_lb & ~ge_ub;
-            if (m < 4) sure0 |= (uint64_t)sure << (m * 16); else sure1 |= (uint64_t)sure << ((m - 4) * 16);
-            if (__ballot(amb != 0u) == 0ull) continue;      // wave-uniform
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const bool take = (amb >> c) & 1u;
-                const unsigned long long mk = __ballot(take);
-                if (mk == 0ull) continue;                   // wave-uniform
-                const unsigned long long pos = wave_append(mk, p.cnt, lane, below);
-                if (take && pos < (unsigned long long)p.cap)
-                    p.keys[pos] = ((uint64_t)gi << 32) | (uint64_t)(n0 + cw + (c >> 2) * 16 + lq * 4 + (c & 3));
-            }
-        }
-        // the certain edges: per lane, rows in order
         const uint32_t n_pad = dedup_pad(p.N - a.N0), W = dedup_words(p.N - a.N0);
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-            uint64_t mk = h ? sure1 : sure0;
-            while (mk != 0ull) {
-                const int bit = __ffsll((long long)mk) - 1;
-                mk &= mk - 1ull;
-                const int m = h * 4 + (bit >> 4), c = bit & 15;
-                const uint32_t gi = (uint32_t)(ci * 256 + rbase + m * 16);
-                const uint32_t gj = (uint32_t)(n0 + cw + (c >> 2) * 16 + lq * 4 + (c & 3));
-                dedup_edge(a.edges, a.N0, n_pad, W, gi, gj);
-            }
-        }
-    }
+        classify_tile3(p, fm, lb, ub, ci, n0, diag, wave, lane, acc, [](long) { return true; },
+                       [&](uint32_t gi, uint32_t gj, bool) { dedup_edge(a.edges, a.N0, n_pad, W, gi, gj); return true; });
+    });
 }
 
 // ----------------------------------------------------------------------- rescore ----

@@ -37,6 +37,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -94,7 +95,7 @@ __device__ __forceinline__ bool disc_row_used(int q, int half, int n_pairs, int 
 }
 
 // -------------------------------------------------------------------------- pass ----
-// recommend_pass_kernel's frame: workgroup s takes slice s of the gallery tiles; waves 0..3 hold every example row of their
+// recommend_pass_kernel's tile loop: workgroup s takes slice s of the gallery tiles; waves 0..3 hold every example row of their
 // 64 columns, waves 4..7 only move data.  SAMPLE: write lb of every row instead of appending candidates.  TARGET: discovery
 // (integer counts and the target's score cross the lanes), else context (two float sums do).
 template <int ROWS, bool SAMPLE, bool TARGET>
@@ -107,11 +108,8 @@ __global__ __launch_bounds__(G256_THREADS, 2) void discover_pass_kernel(Discover
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lane = tid & 63;
     const int nsl = (int)gridDim.x, sl = (int)blockIdx.x;
-    const int tiles = (int)((p.N + 255) / 256);
-    const int per = __builtin_amdgcn_readfirstlane(tiles / nsl), rem = tiles - per * nsl;
-    const int t0 = sl * per + (sl < rem ? sl : rem);
-    const int t1 = t0 + per + (sl < rem ? 1 : 0);
-    if (t0 >= t1) return;
+    int t0, t1;
+    if (!tile_slice((int)((p.N + 255) / 256), nsl, sl, t0, t1)) return;
     const int np = p.n_pairs;
     if (wave == 0) {
         // e: the largest error bound over the examples

@@ -12,7 +12,7 @@
 //            the row's bound: a row with far too many (a block of near-identical rows) gets t_i = +inf and goes to the
 //            fallback without flooding the workspace; it also leaves the sample, and a third pass estimates the other
 //            rows' levels again without the block's weight in their sigma.
-//   join     pairs_join_kernel's walk over the upper triangle of 256 x 256 tiles.  Pair (i, j) is a candidate when its bf16
+//   join     the pairs join's walk over the upper triangle of 256 x 256 tiles (tile_walk.h).  Pair (i, j) is a candidate when its bf16
 //            score reaches min(lb_i, lb_j), lb_r = fl(t_r - eps) lowered by its rounding, eps the row-against-row cert_eps of
 //            pairs_lb.  A key that finds no room in the workspace is dropped and BOTH its rows are marked lost.
 //   rescore  the fp32 PAIRS score v of every candidate (rescore_group4, the pairs row functor): a directed entry for row i
@@ -36,6 +36,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void knn_sample_kernel(const bf16_t* __restric
 }
 
 // ------------------------------------------------------------------------- level ----
-// Workgroup ti: row tile ti against every sample tile, the pairs join's loop with the A tile fixed.  Per tile a lane folds its
+// Workgroup ti: row tile ti against every sample tile (tile_walk.h's slice frame, B the sample).  Per tile a lane folds its
 // 8 x 16 scores into sum / sum of squares per row, the four lanes of a row meet, and the wave adds its share to the slot
 // (wave column, row) of the zeroed sum / sq arrays (no atomics, no registers held across the main loop: launch_knn_levels
 // adds the four wave columns in a fixed order).  With p.lb (the second pass) it counts instead, into `sum`: the allowed sample
@@ -92,28 +93,13 @@ __global__ __launch_bounds__(G256_THREADS, 2) void knn_level_kernel(KnnLevelArgs
     const long ti = blockIdx.x;
     const int ST = (int)((p.S + 255) / 256);
     const bool counting = p.lb != nullptr;
-    G256Operand A, B;
+    G256Operand A;
     g256_operand_init(A, p.Gb + ti * 256 * p.ldg, p.ldg, p.N - ti * 256, 0, wave, lane);
-    g256_operand_init(B, p.Sb, p.D, p.S, 0, wave, lane);
-    g256_issue_prologue(A, B, smem, p.D, wave);
-    for (int sj = 0; sj < ST; ++sj) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop(A, B, smem, p.D, wave, lane, acc);
-        if (sj + 1 < ST) {                                  // the next tile's DMA overlaps the epilogue
-            g256_operand_init(B, p.Sb + (long)(sj + 1) * 256 * p.D, p.D, p.S - (long)(sj + 1) * 256, 0, wave, lane);
-            g256_issue_prologue(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
-        const int lr = lane & 15, lq = lane >> 4;
-        const int rbase = (wave >> 2) * 128 + lr;
-        const int cw = (wave & 3) * 64;
-        const long n0 = (long)sj * 256;
+    tile_slice_frame<0, false, 0>(A, p.Sb, p.D, p.S, 0, ST, smem, p.D, wave, lane, [&](long n0, int lane, const f32x4 (&acc)[8][4]) {
+        const TileLane tl = tile_lane(wave, lane);
+        const int lq = tl.lq, rbase = tl.rbase, cw = tl.cw;
         const uint64_t fm = tile_column_mask(p.S, n0, cw, p.sallow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed sample row
+        if (fm == 0ull) return;                             // wave-uniform: no allowed sample row
         const uint64_t bits = fm >> (lq * 4);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -145,7 +131,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void knn_level_kernel(KnnLevelArgs
                 p.sq[slot] += b;
             }
         }
-    }
+    });
 }
 
 // the upper normal quantile of p in (0, 0.5] (Abramowitz & Stegun 26.2.23, |error| < 4.5e-4)
@@ -217,58 +203,22 @@ __global__ __launch_bounds__(256) void knn_dense_rows_kernel(KnnLevelArgs p, con
 }
 
 // -------------------------------------------------------------------------- join ----
-// pairs_join_kernel with the bound min(lb_i, lb_j).  Per tile a lane reads the lb of ONE of the wave's 64 columns (the others
+// pairs_join_kernel (tile_walk.h's tile-pair frame over the triangle) with the bound min(lb_i, lb_j).  Per tile a lane reads the lb of ONE of the wave's 64 columns (the others
 // come by a lane shuffle where a row gets past the wave-uniform test) and of its 8 rows; the test per 16-row block is the
 // block's best score against min(lb of the lane's row, the smallest lb of the wave's columns).
 __global__ __launch_bounds__(G256_THREADS, 2) void knn_join_kernel(KnnJoinArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const PairsJoinArgs& p = a.j;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int lane = tid & 63;
-    const long per = p.pairs / gridDim.x, rem = p.pairs - per * gridDim.x;
-    const long w = blockIdx.x;
-    const long p0 = w * per + (w < rem ? w : rem);
-    const int n_my = (int)(per + (w < rem ? 1 : 0));
-    if (n_my <= 0) return;
-    // the row tile of p0: the largest ti with pairs_row_start(ti) <= p0
-    int lo = 0, hi = (int)p.T - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs_row_start(mid, p.T) <= p0) lo = mid; else hi = mid - 1;
-    }
-    int ti = lo, tj = (int)(lo + (p0 - pairs_row_start(lo, p.T)));
-    G256Operand A, B;
-    g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-    g256_issue_prologue(A, B, smem, p.D, wave);
-    for (int it = 0; it < n_my; ++it) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop(A, B, smem, p.D, wave, lane, acc);
-        const int ci = ti, cj = tj;                         // this tile's pair; the next one's DMA overlaps the epilogue
-        if (++tj == (int)p.T) { ++ti; tj = ti; }
-        if (it + 1 < n_my) {
-            if (ti != ci) g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-            g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-            g256_issue_prologue(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
-        const int lr = lane & 15, lq = lane >> 4;
-        const int rbase = (wave >> 2) * 128 + lr;
-        const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
-        const long n0 = (long)cj * 256;
+    tile_pair_frame(p, TriangleWalk{p.T}, smem, [&](int ci, int cj, long n0, bool diag, int wave, int lane, const f32x4 (&acc)[8][4]) {
+        const TileLane t = tile_lane(wave, lane);
+        const int lq = t.lq, rbase = t.rbase, cw = t.cw;
         const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed column
+        if (fm == 0ull) return;                             // wave-uniform: no allowed column
         const float lbc = a.lb[n0 + cw + lane];             // column cw + lane (lb holds whole tiles: +inf past N)
         float cmin = lbc;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) cmin = fminf(cmin, __shfl_xor(cmin, o, 64));
         const uint64_t bits = fm >> (lq * 4);
-        const bool diag = ci == cj;
         const unsigned long long below = lanes_below(lane);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -305,7 +255,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void knn_join_kernel(KnnJoinArgs a
                     }
                 }
         }
-    }
+    });
 }
 
 // ----------------------------------------------------------------------- rescore ----

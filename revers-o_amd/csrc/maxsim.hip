@@ -19,6 +19,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -71,35 +72,17 @@ __global__ __launch_bounds__(G256_THREADS, 2) void maxsim_pass_kernel(MaxsimPass
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lane = tid & 63;
     const int nsl = (int)gridDim.x, sl = (int)blockIdx.x;
-    const int tiles = (int)((p.N + 255) / 256);
-    const int per = __builtin_amdgcn_readfirstlane(tiles / nsl), rem = tiles - per * nsl;
-    const int t0 = sl * per + (sl < rem ? sl : rem);
-    const int t1 = t0 + per + (sl < rem ? 1 : 0);
-    if (t0 >= t1) return;
+    int t0, t1;
+    if (!tile_slice((int)((p.N + 255) / 256), nsl, sl, t0, t1)) return;
 
-    G256Operand A, B;
+    G256Operand A;
     g256_operand_init(A, p.Qb, p.ldq, p.n, 0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)t0 * 256 * p.ldg, p.ldg, p.N - (long)t0 * 256, 0, wave, lane);
-    g256_issue_prologue_deep<2>(A, B, smem, p.D, wave);
-    for (int t = t0; t < t1; ++t) {
-        const long n0 = (long)t * 256;
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop<64, false, true, 0, 2>(A, B, smem, p.D, wave, lane, acc);
-        if (t + 1 < t1) {
-            // next gallery tile: DMA in flight during the epilogue
-            g256_operand_init(B, p.Gb + (n0 + 256) * p.ldg, p.ldg, p.N - (n0 + 256), 0, wave, lane);
-            g256_issue_prologue_deep<2>(A, B, smem, p.D, wave);
-        }
-        if (wave >= 4) continue;                            // no query vectors in the second wave-row
-        asm volatile("" : "+v"(lane) :: "memory");
+    tile_slice_frame<64, true, 2>(A, p.Gb, p.ldg, p.N, t0, t1, smem, p.D, wave, lane, [&](long n0, int lane, const f32x4 (&acc)[8][4]) {
+        if (wave >= 4) return;                              // no query vectors in the second wave-row
         const int lr = lane & 15, lq = lane >> 4;
         const int cw = wave * 64;                           // the wave's 64 columns: bits of one 64-bit word of the bitmap
         const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed column inside the gallery
+        if (fm == 0ull) return;                             // wave-uniform: no allowed column inside the gallery
         // bit c of fm set: row n0 + cw + c is below N (and allowed), so its S row exists; v < n_pad: the slot exists
         float* srow = p.S + (n0 + cw + lq * 4) * (long)p.n_pad + lr;
 #pragma unroll
@@ -112,7 +95,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void maxsim_pass_kernel(MaxsimPass
                 for (int j = 0; j < 4; ++j)
                     if ((fm >> (n * 16 + lq * 4 + j)) & 1ull) srow[(long)(n * 16 + j) * p.n_pad + m * 16] = acc[m][n][j];
         }
-    }
+    });
 }
 
 // ------------------------------------------------------------------ group reduction ----

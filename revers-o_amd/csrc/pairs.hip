@@ -2,8 +2,8 @@
 // of allowed rows whose fp32 score reaches a threshold, sorted by (i, j).  eps is the certificate's rigorous bound of
 // |bf16 score - fp32 score| (cert_eps, kernels.h), here for a gallery row against a gallery row.
 //
-//   join     the 256 x 256 main loop over the upper triangle of row-tile pairs (ti <= tj), both operands the gallery's
-//            bf16 rows; every score v >= lb = fl(thr - eps) lowered by its rounding is a candidate; keys (i << 32) | j are
+//   join     the 256 x 256 main loop over the upper triangle of row-tile pairs (ti <= tj; tile_walk.h), both operands the
+//            gallery's bf16 rows; every score v >= lb = fl(thr - eps) lowered by its rounding is a candidate; keys (i << 32) | j are
 //            appended (candidates.h wave_append)
 //   rescore  the fp32 score of every candidate (the exact_dot4 chain); those >= thr are kept, as (i << b) | j, b = the bits
 //            of the largest row index
@@ -13,59 +13,23 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
 
 // (the join's bf16-score bound pairs_lb and the triangle's linearisation pairs_row_start: candidates.h, shared with clusters.hip)
 // -------------------------------------------------------------------------- join ----
-// Workgroup w takes the contiguous range [p0, p1) of the linearised tile pairs (equal counts: every pair is one full tile
-// of MFMA work); consecutive pairs share the A tile.  Rows past N read as zeros and are never appended.
+// tile_walk.h's tile-pair frame over the triangle; rows past N read as zeros and are never appended.
 __global__ __launch_bounds__(G256_THREADS, 2) void pairs_join_kernel(PairsJoinArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int lane = tid & 63;
-    const long per = p.pairs / gridDim.x, rem = p.pairs - per * gridDim.x;
-    const long w = blockIdx.x;
-    const long p0 = w * per + (w < rem ? w : rem);
-    const int n_my = (int)(per + (w < rem ? 1 : 0));
-    if (n_my <= 0) return;
     const float lb = pairs_lb(p.gstat, p.thr, p.D);
-    // the row tile of p0: the largest ti with pairs_row_start(ti) <= p0
-    int lo = 0, hi = (int)p.T - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pairs_row_start(mid, p.T) <= p0) lo = mid; else hi = mid - 1;
-    }
-    int ti = lo, tj = (int)(lo + (p0 - pairs_row_start(lo, p.T)));
-    G256Operand A, B;
-    g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-    g256_issue_prologue(A, B, smem, p.D, wave);
-    for (int it = 0; it < n_my; ++it) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop(A, B, smem, p.D, wave, lane, acc);
-        const int ci = ti, cj = tj;                         // this tile's pair; the next one's DMA overlaps the epilogue
-        if (++tj == (int)p.T) { ++ti; tj = ti; }
-        if (it + 1 < n_my) {
-            if (ti != ci) g256_operand_init(A, p.Gb + (long)ti * 256 * p.ldg, p.ldg, p.N - (long)ti * 256, 0, wave, lane);
-            g256_operand_init(B, p.Gb + (long)tj * 256 * p.ldg, p.ldg, p.N - (long)tj * 256, 0, wave, lane);
-            g256_issue_prologue(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
-        const int lr = lane & 15, lq = lane >> 4;
-        const int rbase = (wave >> 2) * 128 + lr;
-        const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
-        const long n0 = (long)cj * 256;
+    tile_pair_frame(p, TriangleWalk{p.T}, smem, [&](int ci, int cj, long n0, bool diag, int wave, int lane, const f32x4 (&acc)[8][4]) {
+        const TileLane t = tile_lane(wave, lane);
+        const int lq = t.lq, rbase = t.rbase, cw = t.cw;
         const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed column
+        if (fm == 0ull) return;                             // wave-uniform: no allowed column
         const uint64_t bits = fm >> (lq * 4);
-        const bool diag = ci == cj;
         const unsigned long long below = lanes_below(lane);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -90,7 +54,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void pairs_join_kernel(PairsJoinAr
                     if (take && pos < (unsigned long long)p.cap) p.keys[pos] = ((uint64_t)gi << 32) | (uint64_t)(n0 + col);
                 }
         }
-    }
+    });
 }
 
 // ----------------------------------------------------------------------- rescore ----

@@ -16,6 +16,7 @@
 #include "gemm256_core.h"
 #include "kernels.h"
 #include "scan_plan.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -45,11 +46,8 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
     const int q0 = (ph_q0 + (jloc - sp * ph_qn)) * 256;
     if (q0 >= p.Q) return;
     const int qvalid = (p.Q - q0) < 256 ? (p.Q - q0) : 256;
-    const int tiles = (int)((p.N + 255) / 256);
-    const int per = __builtin_amdgcn_readfirstlane(tiles / nsl), rem = tiles - per * nsl;
-    const int t0 = sp * per + (sp < rem ? sp : rem);
-    const int t1 = t0 + per + (sp < rem ? 1 : 0);
-    if (t0 >= t1) return;
+    int t0, t1;
+    if (!tile_slice((int)((p.N + 255) / 256), nsl, sp, t0, t1)) return;
     if (tid < 256) {
         // lb(q): every row with fp32 score >= thr has bf16 score >= fl(thr - eps(q)) lowered by its rounding; +inf: no query
         float lb = INFINITY;
@@ -63,29 +61,15 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
     }
     __syncthreads();
 
-    G256Operand A, B;
+    G256Operand A;
     g256_operand_init(A, p.Qb, p.ldq, p.Q, q0, wave, lane);
-    g256_operand_init(B, p.Gb + (long)t0 * 256 * p.ldg, p.ldg, p.N - (long)t0 * 256, 0, wave, lane);
-    if constexpr (DEEP) g256_issue_prologue_deep<BAUX>(A, B, smem, p.D, wave); else g256_issue_prologue<BAUX>(A, B, smem, p.D, wave);
-    for (int t = t0; t < t1; ++t) {
-        const long n0 = (long)t * 256;
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gemm256_mainloop<ROWS, false, DEEP, 0, BAUX>(A, B, smem, p.D, wave, lane, acc);
-        if (t + 1 < t1) {
-            // next gallery tile: DMA in flight during the epilogue (the query bounds sit past the main loop's LDS image)
-            g256_operand_init(B, p.Gb + (n0 + 256) * p.ldg, p.ldg, p.N - (n0 + 256), 0, wave, lane);
-            if constexpr (DEEP) g256_issue_prologue_deep<BAUX>(A, B, smem, p.D, wave); else g256_issue_prologue<BAUX>(A, B, smem, p.D, wave);
-        }
-        asm volatile("" : "+v"(lane) :: "memory");
+    // (the query bounds sit past the main loop's LDS image)
+    tile_slice_frame<ROWS, DEEP, BAUX>(A, p.Gb, p.ldg, p.N, t0, t1, smem, p.D, wave, lane, [&](long n0, int lane, const f32x4 (&acc)[8][4]) {
         const int lr = lane & 15, lq = lane >> 4;
         const int wrow = (wave >> 2) * 128;                 // the wave's first query row of the tile
         const int cw = (wave & 3) * 64;                     // the wave's 64 columns: bits of one 64-bit word of the bitmap
         const uint64_t fm = tile_column_mask(p.N, n0, cw, p.allow);
-        if (fm == 0ull) continue;                           // wave-uniform: no allowed column
+        if (fm == 0ull) return;                             // wave-uniform: no allowed column
         const uint64_t bits = fm >> (lq * 4);
         const unsigned long long below = lanes_below(lane);
 #pragma unroll
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
                     if (take && pos < (unsigned long long)p.cap) p.keys[pos] = qk | (uint64_t)(n0 + col);
                 }
         }
-    }
+    });
 }
 
 // ----------------------------------------------------------------------- rescore ----

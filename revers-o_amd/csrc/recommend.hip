@@ -20,6 +20,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -58,6 +59,7 @@ __device__ __forceinline__ float rec_row_max(float v) {
 // Workgroup s takes slice s of the gallery tiles [0, ceil(N / 256)).  ROWS = 64 / 128: the example rows fit in that many rows
 // of the tile; in both forms waves 0..3 hold every example row of their 64 columns (gemm256_mainloop: the second wave-row
 // computes nothing), waves 4..7 only move data.  SAMPLE: write lb of every row instead of appending candidates.
+// (The tile loop is tile_walk.h's slice frame, typed out: see there.)
 template <int ROWS, bool SAMPLE>
 __global__ __launch_bounds__(G256_THREADS, 2) void recommend_pass_kernel(RecommendPassArgs p) {
     static_assert(ROWS == 64 || ROWS == 128, "one wave holds every example row of a column");
@@ -67,11 +69,8 @@ __global__ __launch_bounds__(G256_THREADS, 2) void recommend_pass_kernel(Recomme
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lane = tid & 63;
     const int nsl = (int)gridDim.x, sl = (int)blockIdx.x;
-    const int tiles = (int)((p.N + 255) / 256);
-    const int per = __builtin_amdgcn_readfirstlane(tiles / nsl), rem = tiles - per * nsl;
-    const int t0 = sl * per + (sl < rem ? sl : rem);
-    const int t1 = t0 + per + (sl < rem ? 1 : 0);
-    if (t0 >= t1) return;
+    int t0, t1;
+    if (!tile_slice((int)((p.N + 255) / 256), nsl, sl, t0, t1)) return;
     const int E = p.P + p.Nn;
     if (wave == 0) {
         // e: the largest error bound over the examples

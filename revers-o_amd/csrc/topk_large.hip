@@ -19,6 +19,7 @@
 #include "candidates.h"
 #include "gemm256_core.h"
 #include "kernels.h"
+#include "tile_walk.h"
 #include "topk_util.h"
 
 namespace revo {
@@ -139,6 +140,7 @@ __global__ __launch_bounds__(256) void topk_large_sample_kernel(const float* __r
 // -------------------------------------------------------------------------- count ----
 // The collect pass's main loop and slicing (topk256.hip topk_collect256_kernel) with the append replaced by a histogram
 // count: a score v of query row q, column c, is counted when v >= lo(q) and c is an allowed row of the gallery.
+// (The tile loop inside the query-tile loop is tile_walk.h's slice frame, typed out: see there.)
 template <int ROWS>
 __global__ __launch_bounds__(G256_THREADS, 2) void topk_large_count_kernel(LargeCountArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -148,11 +150,8 @@ __global__ __launch_bounds__(G256_THREADS, 2) void topk_large_count_kernel(Large
     int lane = tid & 63;
     const int nq = p.nq;
     const int sp = blockIdx.x;
-    const long tiles = (p.N + 255) / 256;
-    const long per = tiles / p.splits, rem = tiles - per * p.splits;
-    const long t0 = sp * per + (sp < rem ? sp : rem);
-    const long t1 = t0 + per + (sp < rem ? 1 : 0);
-    if (t0 >= t1) return;
+    long t0, t1;
+    if (!tile_slice<long>((p.N + 255) / 256, p.splits, sp, t0, t1)) return;
     const long row_begin = t0 * 256;
     for (int q0 = 0; q0 < nq; q0 += 256) {
         const int qvalid = (nq - q0) < 256 ? (nq - q0) : 256;

@@ -60,6 +60,17 @@ def _clear_threshold(rows, t, delta, allow=None):
 @pytest.mark.parametrize("N", [1, 255, 1300, 4096])
 @pytest.mark.parametrize("D", [64, 256])
 def test_equals_the_pairs_route_and_the_fp64_oracle(N, D):
+    _equals_the_pairs_route_and_the_fp64_oracle(N, D)
+
+
+@pytest.mark.parametrize("N", [256, 257, 513, 5889])
+def test_equals_the_pairs_route_where_the_tile_walk_turns(N):
+    """the sizes of test_gpu_gallery_pairs.py's test of the same name: one full tile, a partial last tile with the wrap of tj,
+    three tiles, and more tile pairs (276) than workgroups"""
+    _equals_the_pairs_route_and_the_fp64_oracle(N, 64)
+
+
+def _equals_the_pairs_route_and_the_fp64_oracle(N, D):
     x = _planted(N, D, seed=3 * N + D)
     G = _gallery(x)
     rows = G.read()

@@ -25,6 +25,11 @@ DEV = torch.device("cuda", 0)
 SHAPES = [(1500, 700, 256), (300, 1000, 64), (0, 600, 128), (2000, 300, 1024), (515, 1, 320), (257, 255, 64)]
 SEEDS = {s: 11 + i for i, s in enumerate(SHAPES)}
 THRESHOLDS = [0.8, 0.9, 0.95]
+# where the join's walk over the tile pairs (csrc/tile_walk.h, dedup_plan.h) can go wrong, (old rows, batch rows, D): N0 + n = 1,
+# 255, 256, 257 and 513 rows (one tile; the diagonal tile only; a partial last tile; the next column), N0 = 100 and 300 inside a
+# tile (it straddles old and new rows), and 23 row tiles = 276 tile pairs, more than the one workgroup per CU
+WALK_SHAPES = [(0, 1, 64), (0, 255, 64), (0, 256, 64), (100, 157, 64), (300, 213, 64), (100, 5789, 64)]
+SEEDS.update({s: 31 + i for i, s in enumerate(WALK_SHAPES)})
 
 
 def _delta(D):
@@ -123,6 +128,26 @@ def test_matches_the_pairs_oracle_and_fp64(shape, t):
     assert np.array_equal(kept, ref["kept"]) and np.array_equal(rep, ref["rep"])
     d = ~kept
     assert np.abs(S[N + np.flatnonzero(d), rep[d]] - ref["score"][d]).max(initial=0.0) <= _delta(D)
+
+
+@pytest.mark.parametrize("shape", WALK_SHAPES, ids=lambda s: "N%d-n%d-D%d" % s)
+def test_matches_the_pairs_oracle_where_the_tile_walk_turns(shape):
+    N, n, D = shape
+    t = 0.9
+    g, b = _inputs(shape)
+    ref = _reference(shape, t)
+    G = _gallery(g, N + n)
+    got = G.add_unique(torch.tensor(b).to(DEV), t)
+    _expect(got, ref)
+    assert len(G) == N + int(ref["kept"].sum())
+    if n > 1:
+        assert 0 < int(ref["kept"].sum()) < n                             # some rows are dropped and some are kept
+    want = np.concatenate([ref["master"][:N], ref["master"][N:][ref["kept"]]])
+    assert G.read().cpu().numpy().tobytes() == want.tobytes()
+    p, s = G.pairs(t)                                                     # no pair with an end among the new rows is left
+    assert np.array_equal(p.cpu().numpy(), ref["old_pairs"])
+    assert np.array_equal(s.cpu().numpy().view(np.uint32), ref["old_scores"].view(np.uint32))
+    G.close()
 
 
 # ---- 3. the gallery afterwards equals a fresh one of the old and the kept vectors ---------------------------------------------

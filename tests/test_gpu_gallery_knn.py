@@ -262,7 +262,7 @@ def _raw_read(G, start, n, k):
     return rc, (s[:n], idx[:n], c[:n])
 
 
-@pytest.mark.parametrize("N", [0, 1, 2, 257])
+@pytest.mark.parametrize("N", [0, 1, 2, 255, 256, 257, 513])
 def test_small_galleries_and_padding(N):
     D, k = 64, 64 if N == 257 else 5
     x = _planted(N, D, seed=40 + N) if N else np.zeros((0, D), np.float32)
@@ -285,6 +285,18 @@ def test_small_galleries_and_padding(N):
         assert (cnt1 == 0).all() and (idx1 == -1).all() and torch.isneginf(s1).all()
         none = torch.zeros(N, dtype=torch.bool, device=DEV)
         assert (G.knn(5, allow=none)[2] == 0).all()
+    G.close()
+
+
+def test_more_tile_pairs_than_workgroups():
+    """N = 5 889: 23 row tiles, 276 tile pairs for the one workgroup per CU, so a workgroup's range of the join's walk
+    (csrc/tile_walk.h) crosses a row of the triangle.  Fewer rows than the level's sample: every pair is a candidate."""
+    N, D, k = 5889, 64, 10
+    G = _gallery(_planted(N, D, seed=77))
+    want = _expected(*_lists_from_pairs(G, N), k)
+    _same(G.knn(k), want, "N=5889")
+    st = G.search_stats()
+    assert st["large_k_fallback"] == 0
     G.close()
 
 

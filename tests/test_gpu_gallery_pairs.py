@@ -120,6 +120,19 @@ def _cluster_pairs(rows, lo=0.75):
 @pytest.mark.parametrize("N", [1, 255, 4096, 20_037])
 @pytest.mark.parametrize("D", [64, 1024, 1536])
 def test_matches_the_fp64_oracle(N, D):
+    _matches_the_fp64_oracle(N, D)
+
+
+@pytest.mark.parametrize("N", [256, 257, 513, 5889])
+def test_matches_the_fp64_oracle_where_the_tile_walk_turns(N):
+    """The join's walk over the tile pairs (csrc/tile_walk.h) at the sizes where it can go wrong, next to N = 1 and 255 above:
+    one full tile, a second tile of one row (a partial last tile, and tj wraps into the next ti), three tiles, and T = 23 row
+    tiles = 276 tile pairs, more than the one workgroup per CU of this part, so that a workgroup's range crosses a row of
+    the triangle."""
+    _matches_the_fp64_oracle(N, 64)
+
+
+def _matches_the_fp64_oracle(N, D):
     x = _planted(N, D, seed=N + D)
     G = _gallery(x)
     rows = G.read()
