@@ -210,9 +210,8 @@ __global__ __launch_bounds__(256) void dedup_bits_kernel(const uint32_t* __restr
 int launch_dedup_join(const DedupJoinArgs& a_in, hipStream_t st) {
     DedupJoinArgs a = a_in;
     PairsJoinArgs& p = a.j;
-    REVO_REQUIRE(p.D % 64 == 0 && p.ldg % 8 == 0, "gallery_append_unique: D must be a multiple of 64");
+    if (int rc = g256_check_operands("gallery_append_unique", p.D, p.ldg)) return rc;
     REVO_REQUIRE(p.N < (1ll << 31), "gallery_append_unique: row indices must fit in 31 bits");
-    REVO_REQUIRE(256l * p.ldg * 2 < (1l << 31), "gallery_append_unique: row too long for the DMA window");
     REVO_REQUIRE((long)a.N0 <= p.N && p.N - (long)a.N0 <= DEDUP_MAX_BATCH, "gallery_append_unique: internal: bad join arguments");
     const DedupPlan pl = dedup_plan((long)a.N0, p.N - (long)a.N0);
     if (pl.pairs <= 0) return 0;

@@ -305,25 +305,15 @@ __global__ __launch_bounds__(256) void discover_rescore_kernel(const uint32_t* _
 }
 
 // ------------------------------------------------------------------------ launchers ----
-// Slices of a pass over `tiles` gallery tiles: one workgroup per CU, every slice at least three tiles (recommend.hip)
-static int disc_slices(long tiles) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 0;
-    long s = cus > 0 ? cus : 256;
-    if (s > tiles / 3) s = tiles / 3;
-    return (int)(s < 1 ? 1 : s);
-}
 int discover_tile_rows(int n_pairs, int has_target) { return n_pairs + (has_target ? 1 : 0) <= 32 ? 64 : 128; }
 int launch_discover_pass(const DiscoverPassArgs& a, int sample, hipStream_t st) {
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldq % 8 == 0 && a.ldg % 8 == 0, "search_discover: D must be a multiple of 64");
+    if (int rc = g256_check_operands("search_discover", a.D, a.ldg, a.ldq)) return rc;
     REVO_REQUIRE(a.N < (1ll << 32), "search_discover: row indices must fit in 32 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31) && 256l * a.ldq * 2 < (1l << 31), "search_discover: row too long for the DMA window");
     REVO_REQUIRE(a.n_pairs >= (a.has_target ? 0 : 1) && a.n_pairs + (a.has_target ? 1 : 0) <= DISCOVER_MAX_PAIRS,
                  "search_discover: bad pair count");
     if (a.N <= 0) return 0;
     const long tiles = (a.N + 255) / 256;
-    const dim3 grid((unsigned)disc_slices(tiles)), block(G256_THREADS);
+    const dim3 grid((unsigned)pass256_slices(tiles)), block(G256_THREADS);
 #define DISC_LAUNCH(RW, SM, TG)                                                                     \
     do {                                                                                            \
         REVO_FUNC_LDS((discover_pass_kernel<RW, SM, TG>), DISC_LDS);                                \

@@ -337,6 +337,17 @@ struct Collect256Args {
     const uint32_t* allow;        // optional allow-bitmap (revo_search_set_filter; padded to whole 256-row tiles): rows whose bit is clear are skipped
 };
 int launch_topk_collect256(const Collect256Args& a, int max_queries, hipStream_t st);
+int topk_collect256_splits(long N);   // the collect pass's slicing, which the large-k count pass shares
+// Slices of a pass that walks `tiles` gallery tiles against one fixed query tile (recommend, discover, MaxSim): one workgroup
+// per CU, every slice at least three tiles (scan_plan.h: a slice costs its tiles plus about one tile time of fixed work)
+int pass256_slices(long tiles);
+// What the 256 x 256 main loop asks of its operands, checked by every launcher that runs it (`who`: the entry point's name
+// in the messages; ldq = 0: both operands are gallery rows)
+inline int g256_check_operands(const char* who, int D, long ldg, long ldq = 0) {
+    REVO_REQUIRE(D % 64 == 0 && ldq % 8 == 0 && ldg % 8 == 0, std::string(who) + ": D must be a multiple of 64");
+    REVO_REQUIRE(256l * ldg * 2 < (1l << 31) && 256l * ldq * 2 < (1l << 31), std::string(who) + ": row too long for the DMA window");
+    return 0;
+}
 // Fallback passes over the entries ws.ctr[CTR_UNCERTIFIED] (device count; launches are sized for max_entries).
 // exact_finish: fp32 re-score of every collected row, exact top-k; entries whose list overflowed go to ws.over_j.
 // bruteforce: for those, the fp32 score of EVERY gallery row (same fma chain as the re-score), exact top-k.

@@ -369,8 +369,7 @@ int launch_knn_sample(const bf16_t* Gb, long ldg, long N, int D, long S, long st
     return 0;
 }
 int launch_knn_level_pass(const KnnLevelArgs& a, hipStream_t st) {
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldg % 8 == 0, "gallery_knn: D must be a multiple of 64");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31), "gallery_knn: row too long for the DMA window");
+    if (int rc = g256_check_operands("gallery_knn", a.D, a.ldg)) return rc;
     REVO_REQUIRE(a.rows % 256 == 0 && a.rows >= a.N && a.stride >= 1 && a.S >= 1 && (a.S - 1) * a.stride < a.N,
                  "gallery_knn: internal: inconsistent sample");
     if (a.N <= 0) return 0;

@@ -294,24 +294,14 @@ int launch_maxsim_index(const int32_t* groups, long N, uint64_t* keys, uint64_t*
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }
-// Slices of the pass over `tiles` gallery tiles: one workgroup per CU, every slice at least three tiles (as the recommend pass)
-static int maxsim_slices(long tiles) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 0;
-    long s = cus > 0 ? cus : 256;
-    if (s > tiles / 3) s = tiles / 3;
-    return (int)(s < 1 ? 1 : s);
-}
 int launch_maxsim_pass(const MaxsimPassArgs& a, hipStream_t st) {
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldq % 8 == 0 && a.ldg % 8 == 0, "search_maxsim: D must be a multiple of 64");
+    if (int rc = g256_check_operands("search_maxsim", a.D, a.ldg, a.ldq)) return rc;
     REVO_REQUIRE(a.N < (1ll << 32), "search_maxsim: row indices must fit in 32 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31) && 256l * a.ldq * 2 < (1l << 31), "search_maxsim: row too long for the DMA window");
     REVO_REQUIRE(a.n >= 1 && a.n <= MAXSIM_MAX_VECTORS && a.n_pad == (a.n + 3) / 4 * 4, "search_maxsim: bad vector count");
     if (a.N <= 0) return 0;
     const long tiles = (a.N + 255) / 256;
     REVO_FUNC_LDS(maxsim_pass_kernel, G256_LDS);
-    hipLaunchKernelGGL(maxsim_pass_kernel, dim3((unsigned)maxsim_slices(tiles)), dim3(G256_THREADS), G256_LDS, st, a);
+    hipLaunchKernelGGL(maxsim_pass_kernel, dim3((unsigned)pass256_slices(tiles)), dim3(G256_THREADS), G256_LDS, st, a);
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }

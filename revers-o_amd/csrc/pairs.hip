@@ -34,11 +34,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void pairs_join_kernel(PairsJoinAr
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int row = rbase + m * 16;
-            float mx = -INFINITY;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, acc[m][n][j]);
+            const float mx = tile_row_max(acc, m);
             if (__ballot(mx >= lb) == 0ull) continue;      // wave-uniform
             const long gi = (long)ci * 256 + row;
             const bool rok = gi < p.N && (!p.allow || ((p.allow[gi >> 5] >> (gi & 31)) & 1u));
@@ -97,9 +93,8 @@ __global__ __launch_bounds__(256) void pairs_emit_kernel(const uint64_t* __restr
 // ------------------------------------------------------------------------ launchers ----
 // T, pairs and the grid of a join (`who`: the caller's name in the messages; no rows: a grid of 0): shared with clusters.hip
 int pairs_join_plan(PairsJoinArgs& a, const char* who, long* wgs_out) {
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldg % 8 == 0, std::string(who) + ": D must be a multiple of 64");
+    if (int rc = g256_check_operands(who, a.D, a.ldg)) return rc;
     REVO_REQUIRE(a.N < (1ll << 31), std::string(who) + ": row indices must fit in 31 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31), std::string(who) + ": row too long for the DMA window");
     *wgs_out = 0;
     if (a.N <= 0) return 0;
     a.T = (a.N + 255) / 256;

@@ -26,7 +26,7 @@ constexpr int RANGE_LDS = G256_LDS + 256 * 4;     // main loop | the tile's 256 
 
 // -------------------------------------------------------------------------- join ----
 // Block b of phase i -> query tile ph_q0[i] + j % ph_qn[i], slice j / ph_qn[i] of ph_ns[i] (j = b - ph_first[i]), as in the
-// scan (topk256_scan.inc).  ROWS: the scan's row forms (0, or the chunk's queries fit in 64 / 128 / 192 rows of one tile);
+// scan (topk_scan256_kernel, topk256.hip; the lookup is typed out in both kernels: see the comment there).  ROWS: the scan's row forms (0, or the chunk's queries fit in 64 / 128 / 192 rows of one tile);
 // BAUX = 2: the gallery tiles are requested non-temporally (one query tile: every gallery row is read once).
 template <int ROWS, int BAUX>
 __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinArgs p) {
@@ -77,11 +77,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void range_join_kernel(RangeJoinAr
             if (ROWS != 0 && wrow + m * 16 >= ROWS) continue;   // rows the row form never computed (no query there)
             const int row = wrow + m * 16 + lr;
             const float lb = lbs[row];
-            float mx = -INFINITY;
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, acc[m][n][j]);
+            const float mx = tile_row_max(acc, m);
             if (__ballot(mx >= lb) == 0ull) continue;      // wave-uniform: no score of these 16 queries reaches its bound
             const uint64_t qk = (uint64_t)(q0 + row) << 32;
 #pragma unroll
@@ -153,23 +149,16 @@ __global__ __launch_bounds__(256) void range_emit_kernel(const uint64_t* __restr
 // ------------------------------------------------------------------------ launchers ----
 int launch_range_join(const RangeJoinArgs& a_in, hipStream_t st) {
     RangeJoinArgs a = a_in;
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldq % 8 == 0 && a.ldg % 8 == 0, "search_range: D must be a multiple of 64");
+    if (int rc = g256_check_operands("search_range", a.D, a.ldg, a.ldq)) return rc;
     REVO_REQUIRE(a.N < (1ll << 32), "search_range: row indices must fit in 32 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31) && 256l * a.ldq * 2 < (1l << 31), "search_range: row too long for the DMA window");
     if (a.Q <= 0 || a.N <= 0) return 0;
     const long tiles = (a.N + 255) / 256;
     const int qtiles = (a.Q + 255) / 256;
     Scan256Plan pl;
     scan256_plan(qtiles, tiles, pl);
     a.nph = pl.nph;
-    long blocks = 0;
-    for (int i = 0; i < pl.nph; ++i) {
-        a.ph_first[i] = (int)blocks; a.ph_q0[i] = pl.q0[i]; a.ph_qn[i] = pl.qn[i]; a.ph_ns[i] = pl.ns[i];
-        blocks += (long)pl.qn[i] * pl.ns[i];
-        if (i + 1 < pl.nph) blocks = (blocks + 7) / 8 * 8;       // (pinned phases are multiples of 8 blocks anyway)
-    }
+    const long blocks = scan256_phase_table(pl, a.ph_first, a.ph_q0, a.ph_qn, a.ph_ns);
     REVO_REQUIRE(blocks < (1l << 31), "search_range: too many workgroups");
-    a.ph_first[pl.nph] = (int)blocks;
     const dim3 grid((unsigned)blocks), block(G256_THREADS);
 #define RANGE_LAUNCH(RW, AUX)                                                                 \
     do {                                                                                      \

@@ -276,24 +276,13 @@ __global__ __launch_bounds__(256) void recommend_emit_kernel(const uint64_t* __r
 }
 
 // ------------------------------------------------------------------------ launchers ----
-// Slices of a pass over `tiles` gallery tiles: one workgroup per CU, every slice at least three tiles (scan_plan.h: a slice
-// costs its tiles plus about one tile time of fixed work)
-static int rec_slices(long tiles) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 0;
-    long s = cus > 0 ? cus : 256;
-    if (s > tiles / 3) s = tiles / 3;
-    return (int)(s < 1 ? 1 : s);
-}
 int launch_recommend_pass(const RecommendPassArgs& a, int sample, hipStream_t st) {
-    REVO_REQUIRE(a.D % 64 == 0 && a.ldq % 8 == 0 && a.ldg % 8 == 0, "search_recommend: D must be a multiple of 64");
+    if (int rc = g256_check_operands("search_recommend", a.D, a.ldg, a.ldq)) return rc;
     REVO_REQUIRE(a.N < (1ll << 32), "search_recommend: row indices must fit in 32 bits");
-    REVO_REQUIRE(256l * a.ldg * 2 < (1l << 31) && 256l * a.ldq * 2 < (1l << 31), "search_recommend: row too long for the DMA window");
     REVO_REQUIRE(a.P >= 1 && a.Nn >= 0 && a.P + a.Nn <= RECOMMEND_MAX_EXAMPLES, "search_recommend: bad example counts");
     if (a.N <= 0) return 0;
     const long tiles = (a.N + 255) / 256;
-    const dim3 grid((unsigned)rec_slices(tiles)), block(G256_THREADS);
+    const dim3 grid((unsigned)pass256_slices(tiles)), block(G256_THREADS);
 #define REC_LAUNCH(RW, SM)                                                                      \
     do {                                                                                        \
         REVO_FUNC_LDS((recommend_pass_kernel<RW, SM>), REC_LDS);                                \

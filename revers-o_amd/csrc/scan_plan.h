@@ -57,5 +57,19 @@ static void scan256_plan(int qtiles, long tiles, Scan256Plan& pl) {
         add(qtiles - q, ns, c);
     }
 }
+// The plan as the kernels' argument blocks hold it (Scan256Args, RangeJoinArgs: plain arrays, read with constant indices):
+// phase i is the blocks [first[i], first[i + 1]) of a 1-D grid, block first[i] + j = (query tile q0[i] + j % qn[i], slice
+// j / qn[i] of ns[i]).  Every phase starts at a multiple of 8 blocks (the XCD pinning above; pinned phases are multiples of
+// 8 blocks anyway).  first has pl.nph + 1 entries.  Returns the number of blocks; the caller checks that it fits its grid.
+static long scan256_phase_table(const Scan256Plan& pl, int* first, int* q0, int* qn, int* ns) {
+    long blocks = 0;
+    for (int i = 0; i < pl.nph; ++i) {
+        first[i] = (int)blocks; q0[i] = pl.q0[i]; qn[i] = pl.qn[i]; ns[i] = pl.ns[i];
+        blocks += (long)pl.qn[i] * pl.ns[i];
+        if (i + 1 < pl.nph) blocks = (blocks + 7) / 8 * 8;
+    }
+    first[pl.nph] = (int)blocks;
+    return blocks;
+}
 
 }  // namespace revo

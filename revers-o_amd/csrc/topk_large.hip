@@ -189,11 +189,7 @@ __global__ __launch_bounds__(G256_THREADS, 2) void topk_large_count_kernel(Large
             for (int m = 0; m < 8; ++m) {
                 const int row = rbase + m * 16;
                 const float lo = lk_lds_f32(G256_LDS + row * 12);
-                float mx = -INFINITY;
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) mx = fmaxf(mx, acc[m][n][j]);
+                const float mx = tile_row_max(acc, m);
                 if (__ballot(mx >= lo) == 0ull) continue;   // wave-uniform
                 const float base = lk_lds_f32(G256_LDS + row * 12 + 4), inv = lk_lds_f32(G256_LDS + row * 12 + 8);
                 uint32_t* h = p.hist + (long)(q0 + row) * LARGE_NB;
@@ -394,12 +390,10 @@ int launch_topk_large_sample(const float* pre, long ld, int n_s, const uint32_t*
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int topk_collect256_splits(long N);   // topk256.hip: the collect pass's slicing, which the count pass shares
 int launch_topk_large_count(const bf16_t* Qb, long ldq, const bf16_t* Gb, long ldg, long N, int D, int Q, const LargeWs& ws,
                             const uint32_t* allow, hipStream_t st) {
-    REVO_REQUIRE(D % 64 == 0 && ldq % 8 == 0 && ldg % 8 == 0, "search: D must be a multiple of 64");
+    if (int rc = g256_check_operands("search", D, ldg, ldq)) return rc;
     REVO_REQUIRE(N < (1ll << 32), "search: a gallery holds at most 2^32 rows");
-    REVO_REQUIRE(256l * ldg * 2 < (1l << 31) && 256l * ldq * 2 < (1l << 31), "search: row too long for the DMA window");
     if (Q <= 0 || N <= 0) return 0;
     LargeCountArgs a{};
     a.Qb = Qb; a.ldq = ldq; a.Gb = Gb; a.ldg = ldg; a.N = N; a.D = D; a.nq = Q; a.splits = topk_collect256_splits(N);

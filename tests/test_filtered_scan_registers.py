@@ -1,75 +1,57 @@
-"""CPU: the filtered forms of the 256 x 256 scan (topk_scan256_filtered_kernel, every ksel / rows / margin form that is
-built) from hipcc's resource report: at or below the spill numbers pinned for the plain forms
-(tests/test_kernel_register_budget.py), and no scratch traffic inside the tile loop beyond what the plain forms have."""
-import os
+"""CPU: the filtered forms of the 256 x 256 scan (topk_scan256_kernel<KSEL, ROWS, MARGIN, FILTER = true>, every ksel / rows /
+margin form that is built) from hipcc's resource report: at or below the spill numbers pinned for the plain forms
+(tests/test_kernel_register_budget.py), and no scratch traffic inside the tile loop beyond what the plain forms have.  The
+report and the listing are the ones the plain forms' tests read (tests/_hipcc_report.py compiles topk256.hip once for each)."""
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "revers-o_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"]
+from _hipcc_report import listing as _listing, scratch_in_loops as _scratch_in_loops, usage as _usage
 
 # (ksel, rows, margin) -> spilled VGPRs allowed: the plain forms' pinned numbers (the 256-row margin form is not built
 # filtered: filtered searches of more than 128 queries scan without the margin)
 PINNED = {(32, 0, 0): 1, (32, 64, 0): 0, (32, 128, 0): 0, (32, 192, 0): 5,
           (64, 0, 0): 1, (64, 64, 0): 0, (64, 128, 0): 0, (64, 192, 0): 2,
           (64, 64, 1): 0, (64, 128, 1): 2}
+# the plain forms: the eight without the margin, and the margin with 64 candidates at 64, 128 and 256 rows
+PLAIN = {(ksel, rows, 0) for ksel in (32, 64) for rows in (0, 64, 128, 192)} | {(64, 0, 1), (64, 64, 1), (64, 128, 1)}
 
 
 @pytest.fixture(scope="module")
 def usage():
-    out = subprocess.run([HIPCC, *FLAGS, "-c", "topk256.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    cur, d = None, {}
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            d[cur] = {}
-            continue
-        for key, pat in (("VGPRs", r" VGPRs: (\d+)"), ("VGPRs Spill", r"VGPRs Spill: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur:
-                d[cur][key] = int(m.group(1))
-    return d
+    return _usage("topk256.hip")
 
 
 def test_filtered_scan_forms_spill_no_more_than_the_plain_forms(usage):
-    seen = set()
+    forms = {0: set(), 1: set()}                   # FILTER -> the (ksel, rows, margin) that are instantiated
     for name, u in usage.items():
-        m = re.search(r"28topk_scan256_filtered_kernelILi(\d+)ELi(\d+)ELb(\d)E", name)
+        m = re.search(r"19topk_scan256_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)E", name)
         if not m:
             continue
-        form = tuple(int(x) for x in m.groups())
-        assert form in PINNED, form
-        assert u["VGPRs"] <= 256 and u["VGPRs Spill"] <= PINNED[form], (form, u)
-        seen.add(form)
-    assert seen == set(PINNED), sorted(set(PINNED) - seen)
-    assert not [k for k in usage if "topk_scan256_filtered_kernelILi64ELi0ELb1E" in k]
-    # the plain kernels' names are untouched: the filtered form is not an instantiation of topk_scan256_kernel
-    assert not [k for k in usage if "topk_scan256_kernel" in k and "filtered" in k]
+        form = tuple(int(x) for x in m.groups()[:3])
+        forms[int(m.group(4))].add(form)
+        if int(m.group(4)):
+            assert form in PINNED, form
+            assert u["VGPRs"] <= 256 and u["VGPRs Spill"] <= PINNED[form], (form, u)
+    # exactly the 11 plain and the 10 filtered forms the launcher selects, and no other symbol that carries the scan's name
+    assert forms[1] == set(PINNED), (sorted(set(PINNED) - forms[1]), sorted(forms[1] - set(PINNED)))
+    assert forms[0] == PLAIN and len(PLAIN) == 11, (sorted(PLAIN - forms[0]), sorted(forms[0] - PLAIN))
+    assert len([k for k in usage if "topk_scan256" in k]) == 21, [k for k in usage if "topk_scan256" in k]
+    # ... so none of: a filtered 256-row margin form, a 192-row margin form, a 32-candidate margin form
+    assert (64, 0, 1) not in forms[1]
+    # the collect pass: <ROWS, FILTER>, three row forms each
+    collect = {tuple(int(x) for x in m.groups()) for m in (re.search(r"22topk_collect256_kernelILi(\d+)ELb(\d)E", k) for k in usage) if m}
+    assert collect == {(rows, flt) for rows in (0, 64, 128) for flt in (0, 1)}, sorted(collect)
+    assert len([k for k in usage if "topk_collect256" in k]) == 6
+    for flt in (0, 1):
+        assert not [f for f in forms[flt] if f[2] and f[1] == 192], forms[flt]
+        assert not [f for f in forms[flt] if f[2] and f[0] == 32], forms[flt]
 
 
 def test_filtered_scans_keep_scratch_out_of_the_hot_loops():
-    out = subprocess.run([HIPCC, *FLAGS, "-S", "--cuda-device-only", "topk256.hip", "-o", "-"], cwd=CSRC,
-                         capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-3000:]
-    asm = out.stdout
     seen = 0
-    for m in re.finditer(r"^(_ZN4revo28topk_scan256_filtered_kernelILi(\d+)ELi(\d+)ELb(\d)EEEvNS_11Scan256ArgsE):", asm,
-                         flags=re.M):
-        body = asm[m.end(): asm.index(".Lfunc_end", m.end())].splitlines()
-        depth, hot = 0, []
-        for ln in body:
-            if ln.startswith(".LBB") or ln.startswith("; %bb."):
-                dm = re.search(r"Depth=(\d+)", ln)
-                depth = int(dm.group(1)) if dm else 0
-            elif depth >= 1 and "scratch_" in ln:
-                hot.append((depth, ln.strip()))
+    for m, hot in _scratch_in_loops(_listing("topk256.hip"),
+                                    r"_ZN4revo19topk_scan256_kernelILi(\d+)ELi(\d+)ELb(\d)ELb1EEEvNS_11Scan256ArgsE"):
         seen += 1
         assert not [h for h in hot if h[0] >= 2], (m.group(1), hot)
         allowed = 1 if (int(m.group(3)) == 192 or int(m.group(4))) else 0

@@ -4,8 +4,8 @@ only the allowed rows (indices mapped back), (c) bit-for-bit equality with an ex
 filtered brute force.  Masks mix every kind of 64-bit word (all, none, random, only bit 0, only bit 63, only bits 31 and 32)
 so that the early return of s256_apply_allow, both halves of each word and every lane's shift are exercised.
 
-The scan form a case runs is named <KSEL, ROWS, MARGIN> after the template parameters of topk_scan256_filtered_kernel
-(topk256.hip): KSEL 32 for k <= 16 else 64; ROWS 64 / 128 / 192 for at most that many queries (192 only without the
+The scan form a case runs is named <KSEL, ROWS, MARGIN> after the template parameters of topk_scan256_kernel<KSEL, ROWS,
+MARGIN, FILTER = true> (topk256.hip): KSEL 32 for k <= 16 else 64; ROWS 64 / 128 / 192 for at most that many queries (192 only without the
 margin), 0 beyond; MARGIN for k > 25 with at most 128 queries (a filtered scan of more queries runs without it)."""
 import ctypes as C
 import os

@@ -134,6 +134,21 @@ def test_matches_the_fp64_oracle(Q, N, D):
     G.close()
 
 
+def test_two_phases_of_query_tiles_match_the_fp64_oracle():
+    """2304 queries are 9 query tiles: the join's launch is a pinned phase of 8 and a last phase of 1 (scan_plan.h; the phase
+    table is tests/test_scan_plan.py's test_the_two_phase_launch_of_the_small_gpu_cases).  At 0.7 a perturbed query keeps its own row and its cluster mates, about
+    2100 entries in all (fp64 on the CPU: 1884 in the first eight query tiles, 241 in the ninth): hits in both phases."""
+    Q, N, D = 2304, 1024, 64
+    x = _planted(N, D, seed=N + D + Q)
+    G = _gallery(x)
+    q = _queries(x, Q, seed=Q)
+    off, idx, sc = G.search_range(q, 0.7)
+    _check_against_oracle(off, idx, sc, _normalised(q), G.read(), 0.7, _delta(D))
+    _stats_are_the_range_search(G, idx.shape[0])
+    assert int(off[2048]) >= 100 and int(off[Q]) - int(off[2048]) >= 10, (int(off[2048]), int(off[Q]))
+    G.close()
+
+
 # ---- 2. bit for bit against the large-k search ---------------------------------------------------------------------------
 def test_equals_the_large_k_search_bit_for_bit():
     N, D = 20_037, 1024

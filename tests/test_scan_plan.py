@@ -65,6 +65,18 @@ def test_the_cases_the_design_quotes():
     assert len(phases) == 1 and phases[0][2] == 1 and 128 <= phases[0][3] <= 256
 
 
+def test_the_two_phase_launch_of_the_small_gpu_cases():
+    """The phase table has one author (scan256_phase_table, scan_plan.h) and two users; the GPU suite launches more than one
+    phase through both.  The range join scans the whole gallery: tests/test_gpu_range_search.py runs 2304 queries x 1024 rows.
+    The top-k scan skips the pre-pass rows (8192 at these sizes; N < 16 384 takes the small scan and has no phases at all):
+    tests/test_gpu_search.py's test_phases_of_query_tiles_vs_oracle runs 2300 x 70 003, 3000 x 33 000 and 2560 x 300 000."""
+    blocks, splits, phases = _plan(2304, 1024)                  # 9 query tiles x 4 gallery tiles: too few tiles to slice
+    assert phases == [(0, 0, 8, 1), (8, 8, 1, 1)] and blocks == 9 and splits == 1
+    for Q, rows, qn in ((2300, 70_003 - 8192, (8, 1)), (3000, 33_000 - 8192, (8, 4)), (2560, 300_000 - 8192, (8, 2))):
+        blocks, splits, phases = _plan(Q, rows)
+        assert tuple(p[2] for p in phases) == qn and phases[1][0] == 8 * phases[0][3], (Q, rows, phases)
+
+
 # ---- galleries past 2^24 rows: the scan's 24-bit relative row index (topk256.hip key packing; launch_topk_scan256 refuses a
 # slice of more than 2^24 rows) --------------------------------------------------------------------------------------------
 _SLICE_LIMIT = 1 << 24
