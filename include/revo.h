@@ -321,6 +321,56 @@ int32_t revo_gallery_clusters_read(revo_gallery* g, int64_t* labels, int64_t* of
 int32_t revo_gallery_knn(revo_gallery* g, int32_t k, int32_t has_threshold, float threshold, int64_t* n_rows, void* stream);
 int32_t revo_gallery_knn_read(revo_gallery* g, int64_t start, int64_t n, int64_t* indices, float* scores, int32_t* counts,
                               int32_t dst_on_device);
+/* ---- exact spherical k-means: a partition of the gallery into themes, each with a centre and a size (no counterpart in the
+ * reference's own code)
+ * KMEANS.  Input: C = n_centroids initial centroids, fp32 [C][dim], host (src_on_device = 0) or device memory.  normalize = 1:
+ * they are normalised exactly as revo_gallery_append(normalize = 1) normalises a row (the same kernel, the same bits);
+ * normalize = 0: they are used as given, bit for bit.
+ * Participants: the rows that the handle's filter allows (revo_search_set_filter, with its lifecycle: a filter set for another
+ * gallery size gives status -2).  Every other row has label -1 and score -inf and contributes to no centroid.
+ * Assignment: label[i] = the centroid with the largest score(i, c); ties go to the lowest c.  score(i, c) is the fp32 fma chain
+ * of every other re-score in this library (EXACTNESS) over q_i and the centroid's fp32 row, where q_i is the row's fp32 master
+ * row as a QUERY: passed through the normalisation every search applies to its queries (for a master row of unit length that
+ * moves an element by an ulp at most; a row stored with normalize = 0 is scaled to unit length).  scores[i] = score(i,
+ * label[i]) with exactly those bits.  So labels and scores are byte for byte what revo_search_topk(k = 1) returns for the fp32
+ * master rows as queries against a gallery that holds the centroids (appended with normalize = 0).
+ * Update: for centroid c, its members in ascending row order are split into consecutive chunks of 256; a chunk's partial sum is
+ * a plain sequential fp32 add chain over its members' fp32 master rows (as stored) starting from +0.0f; the centroid's sum is
+ * the sequential fp32 add chain of the partials in chunk order starting from +0.0f -- no fma, no trees: a numpy float32 loop
+ * reproduces it.  The new centroid is that sum normalised by the append's normalisation.  A centroid keeps its previous bits
+ * when it has no members, or when its sum has a squared norm (the normalisation's own) that is zero or not finite.
+ * Iteration: step t assigns against the centroids C_t.  If t >= 1 and no label changed: stop, *converged = 1.  Else if t =
+ * max_iter: stop, *converged = 0.  Else C_{t+1} = update(labels_t).  *n_iter = updates done.  So the returned labels are always
+ * the exact assignment against the returned centroids, max_iter = 0 is a pure assignment, and -- the update being a function of
+ * the labels alone -- a converged result is a fixed point bit for bit.
+ * Two calls give identical bytes: neither the order of the device's atomics, nor the workspace size, nor the number of passes
+ * reaches a byte.
+ * How: the centroids get a bf16 copy beside their fp32 rows; per step two MFMA passes of every row tile over the centroid tiles
+ * -- each row's best bf16 score, then every (row, centroid) whose bf16 score is within twice the certificate's rounding bound
+ * (for that row against the centroids) of it -- and an fp32 re-score of those candidates, folded per row by a maximum over
+ * (score, lowest centroid).  Every maximiser of the fp32 score is provably among a row's candidates.  The update sorts (label,
+ * row) keys on the device and sums chunks in the fixed order.
+ * The result lives in the handle, like the kNN graph's: labels [size] int32, scores [size] fp32, sizes [C] int64 (members per
+ * centroid under the returned labels) and centroids [C][dim] fp32.  revo_gallery_kmeans_read copies rows [start, start + n) of
+ * labels and scores, revo_gallery_kmeans_centroids the centroids and sizes, to host or device memory (dst_on_device); each
+ * output pointer may be NULL independently.  The result stays valid across revo_gallery_pairs, revo_gallery_clusters,
+ * revo_gallery_knn and revo_search_range, and their results across it; append, clear, remove and update invalidate it: after
+ * one, with no result, or for a range past the end, the two read calls give status -2.
+ * Limits: 1 <= n_centroids <= 65 536; 0 <= max_iter <= 1 000; dim a multiple of 64; needs the fp32 master rows (keep_f32 = 0:
+ * status -2) and row indices below 2^31.  A null pointer, n_centroids or max_iter out of range give status -2 before the device
+ * is touched.  A centroid row that is not finite, or has zero norm under normalize = 1, gives status -2 (found from the
+ * normalisation pass's statistics).  More than 2^28 candidates in one assignment give status -2.  An empty gallery or a filter
+ * that allows no row is not an error: all sizes 0, the centroids returned as normalised.  *n_rows receives the gallery size.
+ * SYNCHRONOUS on `stream`, like revo_gallery_pairs: the host reads the changed-label and candidate counts between passes.
+ * revo_search_stats after it, summed over the steps: slot 3 = (row, centroid) candidates re-scored in fp32 beyond the one score
+ * per row, slot 6 = rows whose label needed a re-score to decide (more than one candidate), slot 7 = assignment passes run
+ * (one per step, one more for each step whose candidate workspace had to grow), every other slot 0. */
+int32_t revo_gallery_kmeans(revo_gallery* g, const float* centroids, int32_t n_centroids, int32_t normalize,
+                            int32_t src_on_device, int32_t max_iter, int32_t* n_iter, int32_t* converged, int64_t* n_rows,
+                            void* stream);
+int32_t revo_gallery_kmeans_read(revo_gallery* g, int64_t start, int64_t n, int32_t* labels, float* scores,
+                                 int32_t dst_on_device);
+int32_t revo_gallery_kmeans_centroids(revo_gallery* g, float* centroids, int64_t* sizes, int32_t dst_on_device);
 /* ---- range search: every row above a threshold, per query (the reference's score_threshold without its limit,
  * core_system.py:659-664)
  * RANGE.  For each query q the result is exactly the rows the handle's filter allows (revo_search_set_filter, with its
@@ -565,7 +615,7 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
  * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_gallery_clusters see CLUSTERS, after revo_search_range see RANGE,
  * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM, after
- * revo_gallery_knn see KNN. */
+ * revo_gallery_knn see KNN, after revo_gallery_kmeans see KMEANS. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard
  * results of a row-sharded gallery) into one [n_queries, k] set, same ordering rule. */
@@ -660,6 +710,9 @@ int32_t revo_debug_set_remove_chunk(int64_t rows);
  * estimate, 1 = every level -inf (or the threshold), 2 = every level +2.0: nothing is a candidate and every row falls back,
  * 3 = the sample-derived level raised by a fixed 0.05: some rows come up short and some do not. */
 int32_t revo_debug_set_knn(int64_t cap_keys, int32_t level_mode);
+/* revo_gallery_kmeans' candidate workspace (tests hold a workspace that has to grow to the bytes of the default run; speed
+ * only): cap_keys = candidate keys it starts with (0 = the default). */
+int32_t revo_debug_set_kmeans(int64_t cap_keys);
 /* phase groups of the persistent 256 x 256 GEMM (an experiment, measured in round 5 and not adopted): 0 / 1 = off (all
  * workgroups in step), 2..4 = that many groups, a workgroup of group g doing the first (g + 1) / groups of its first tile at the start and the
  * rest of that tile last.  Result-preserving (bit-identical). */

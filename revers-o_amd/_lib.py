@@ -58,6 +58,9 @@ SIGNATURES = {
     "revo_gallery_clusters_read": (_i32, [_p, _p, _p, _p, _i32]),
     "revo_gallery_knn": (_i32, [_p, _i32, _i32, _f32, C.POINTER(C.c_int64), _p]),
     "revo_gallery_knn_read": (_i32, [_p, _i64, _i64, _p, _p, _p, _i32]),
+    "revo_gallery_kmeans": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, C.POINTER(C.c_int64), _p]),
+    "revo_gallery_kmeans_read": (_i32, [_p, _i64, _i64, _p, _p, _i32]),
+    "revo_gallery_kmeans_centroids": (_i32, [_p, _p, _p, _i32]),
     "revo_search_range": (_i32, [_p, _p, _i32, _f32, _i64, C.POINTER(C.c_int64), _p]),
     "revo_search_range_read": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32]),
     "revo_search_recommend": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
@@ -124,6 +127,7 @@ EXPERIMENT_SIGNATURES = {
     "revo_debug_scan_stats": (_i32, [C.POINTER(C.c_int64)]),
     "revo_debug_set_remove_chunk": (_i32, [_i64]),
     "revo_debug_set_knn": (_i32, [_i64, _i32]),
+    "revo_debug_set_kmeans": (_i32, [_i64]),
     "revo_debug_seed_bounds": (_i32, [_p, _p]),
     "revo_debug_read_workspace": (_i64, [_p, _i64, _i64, _p]),
     "revo_debug_stream_in_planes": (_i32, [_p, _i32]),

@@ -1248,6 +1248,36 @@ class SimpleReverso:
             text += f"{n + 1}. {it['filename']}: {near}\n"
         return text, out
 
+    def summarize_database(self, n_themes=20, max_iter=10, seed=0, query_filter=None):
+        """What is in the loaded database: its stored regions (those a Qdrant-style ``query_filter`` selects, if given)
+        partitioned into ``n_themes`` themes by exact spherical k-means (``GalleryStore.themes``), largest first.  Returns
+        ``(text, themes)``: each theme is ``{"size", "ids", "representative": {"filename", "image_source", "bbox", "id",
+        "score"}}``, the representative being the member closest to the theme's centre."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        try:
+            with self._lock:
+                db = self.vector_db
+                if len(db) == 0:
+                    return "⚠️ The database holds no regions", []
+                themes = db.themes(int(n_themes), max_iter=int(max_iter), seed=int(seed), query_filter=query_filter)
+        except Exception as e:
+            return f"❌ Error summarizing the database: {str(e)}", []
+        out = []
+        for t in themes:
+            p = t.representative_payload
+            out.append({"size": t.size, "ids": t.ids,
+                        "representative": {"filename": p.get("filename", "Unknown"), "image_source": p.get("image_source", ""),
+                                           "bbox": p.get("bbox"), "id": t.representative_id,
+                                           "score": float(t.representative_score)}})
+        if not out:
+            return "⚠️ No regions to summarize", []
+        total = sum(t["size"] for t in out)
+        text = f"🎯 {len(out)} themes over {total} regions:\n\n"
+        for n, t in enumerate(out):
+            text += f"{n + 1}. {t['size']} regions, e.g. {t['representative']['filename']} ({t['representative']['score']:.3f})\n"
+        return text, out
+
     def delete_images(self, image_sources=None, query_filter=None):
         """Remove stored regions from the loaded database, in place: every region of the source images ``image_sources``
         (one path or a list; payload key ``image_source``) or every region a Qdrant-style ``query_filter`` selects (both

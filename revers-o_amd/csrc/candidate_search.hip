@@ -1,6 +1,7 @@
-// C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, kNN, range, recommend,
-// discover, MaxSim and MMR, with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
+// C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, kNN, k-means, range,
+// recommend, discover, MaxSim and MMR, with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
 #include <algorithm>
+#include <vector>
 
 #include "gallery_internal.h"
 
@@ -464,6 +465,185 @@ extern "C" int32_t revo_gallery_knn_read(revo_gallery* g, int64_t start, int64_t
     if (indices) CHECK_RC(copy_out(indices, kr.idx.p + start * kr.k, (size_t)n * kr.k, dst_on_device));
     if (scores) CHECK_RC(copy_out(scores, kr.score.p + start * kr.k, (size_t)n * kr.k, dst_on_device));
     if (counts) CHECK_RC(copy_out(counts, kr.counts.p + start, (size_t)n, dst_on_device));
+    return 0;
+    API_END
+}
+
+// ---- exact spherical k-means over one gallery (include/revo.h revo_gallery_kmeans; kmeans.hip)
+#ifdef REVO_EXPERIMENTS
+static long g_kmeans_cap_keys = 0;
+extern "C" int32_t revo_debug_set_kmeans(int64_t cap_keys) {
+    REVO_REQUIRE(cap_keys >= 0 && cap_keys <= revo::KMEANS_MAX_CAND, "debug_set_kmeans: cap_keys must be in [0, 2^28]");
+    g_kmeans_cap_keys = (long)cap_keys;
+    return 0;
+}
+#endif
+extern "C" int32_t revo_gallery_kmeans(revo_gallery* g, const float* centroids, int32_t n_centroids, int32_t normalize,
+                                       int32_t src_on_device, int32_t max_iter, int32_t* n_iter, int32_t* converged,
+                                       int64_t* n_rows, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && centroids && n_iter && converged && n_rows, "gallery_kmeans: null argument");
+    REVO_REQUIRE(n_centroids >= 1 && n_centroids <= revo::KMEANS_MAX_CENTROIDS, "gallery_kmeans: n_centroids must be in [1, 65536]");
+    REVO_REQUIRE(max_iter >= 0 && max_iter <= revo::KMEANS_MAX_ITER, "gallery_kmeans: max_iter must be in [0, 1000]");
+    CHECK_RC(require_f32_rows(g, "gallery_kmeans"));
+    REVO_REQUIRE(g->size < (1ll << 31), "gallery_kmeans: row indices must fit in 31 bits");
+    CHECK_RC(revo::g256_check_operands("gallery_kmeans", g->D, g->D, g->D));
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    KmeansResult& kr = g->kmeans;
+    kr.valid = false;
+    const long N = g->size, C = n_centroids, Cpad = (C + 255) / 256 * 256;
+    const int D = g->D;
+    const long T = (N + 255) / 256, rows = T * 256, part_chunks = N / 256 + C;
+    const int b = row_index_bits(N);
+    CHECK_RC(begin_counted(g, 1, "gallery_kmeans", st));
+    const size_t n1 = (size_t)(N > 0 ? N : 1);
+    CHECK_RC(kr.labels.grow(n1 * 4, st));
+    CHECK_RC(kr.score.grow(n1 * 4, st));
+    CHECK_RC(kr.sizes.grow((size_t)C * 8, st));
+    for (int i = 0; i < 2; ++i) {
+        CHECK_RC(kr.cf[i].grow((size_t)Cpad * D * 4, st));
+        CHECK_RC(kr.cb[i].grow((size_t)Cpad * D * 2, st));
+        // (the rows past C of the bf16 copies are operand rows of the last centroid tile: zeros)
+        if (Cpad > C) REVO_HIP_CHECK(hipMemsetAsync(kr.cb[i].p + (size_t)C * D, 0, (size_t)(Cpad - C) * D * 2, st));
+    }
+    // the call's own arrays, in a buffer of their own: a regrow of the candidate workspace leaves them be
+    unsigned long long *ctr = nullptr, *rowkey = nullptr, *moff = nullptr, *coff = nullptr;
+    uint32_t *cstat = nullptr, *ncand = nullptr, *hist = nullptr;
+    float *cst = nullptr, *inv = nullptr, *rstat = nullptr, *best = nullptr, *thr = nullptr, *vals = nullptr, *vals_alt = nullptr,
+          *part = nullptr, *sums = nullptr;
+    uint64_t *keys = nullptr, *keys_alt = nullptr;
+    CHECK_RC(carve_buffer(kr.ws, st, [&](Layout& l) {
+        ctr = l.take<unsigned long long>(4); cstat = l.take<uint32_t>(2); cst = l.take<float>(2 * C);
+        inv = l.take<float>(n1); rstat = l.take<float>(2 * n1);
+        best = l.take<float>(4 * (rows > 0 ? rows : 256)); thr = l.take<float>(rows > 0 ? rows : 256);
+        rowkey = l.take<unsigned long long>(n1); ncand = l.take<uint32_t>(n1);
+        keys = l.take<uint64_t>(n1); keys_alt = l.take<uint64_t>(n1); vals = l.take<float>(n1); vals_alt = l.take<float>(n1);
+        hist = l.take<uint32_t>(256l * SORT_MAX_BLOCKS);
+        moff = l.take<unsigned long long>(C); coff = l.take<unsigned long long>(C);
+        part = l.take<float>((size_t)part_chunks * D); sums = l.take<float>((size_t)C * D);
+    }));
+    // the initial centroids through the append's kernel: fp32 rows, bf16 copies, the rows' statistics and their maxima
+    kr.cur = 0;
+    {
+        const float* src = centroids;
+        if (!src_on_device) {
+            CHECK_RC(g->stage.grow((size_t)C * D * 4, st));
+            REVO_HIP_CHECK(hipMemcpyAsync(g->stage.p, centroids, (size_t)C * D * 4, hipMemcpyHostToDevice, st));
+            src = g->stage.p;
+        }
+        REVO_HIP_CHECK(hipMemsetAsync(cstat, 0, 8, st));
+        ProfScope ps("kmeans_init", st);
+        CHECK_RC(launch_l2norm_rows(src, D, kr.cf[0].p, D, kr.cb[0].p, D, C, D, st, normalize ? 1 : 0, cst, cstat));
+        if (N > 0) CHECK_RC(launch_kmeans_rows(g->gf.p, g->gb.p, D, N, D, inv, rstat, st));
+    }
+    {
+        std::vector<float> h((size_t)2 * C);
+        REVO_HIP_CHECK(hipMemcpyAsync(h.data(), cst, h.size() * 4, hipMemcpyDeviceToHost, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        for (long c = 0; c < C; ++c) {
+            REVO_REQUIRE(std::isfinite(h[2 * c]) && std::isfinite(h[2 * c + 1]),
+                         "gallery_kmeans: centroid " + std::to_string(c) + " is not finite");
+            REVO_REQUIRE(!normalize || h[2 * c + 1] > 0.f, "gallery_kmeans: centroid " + std::to_string(c) + " has zero norm");
+        }
+    }
+    REVO_HIP_CHECK(hipMemsetAsync(kr.labels.p, 0xfe, n1 * 4, st));          // (no label: every row of step 0 counts as changed)
+    long cap_keys = 0;
+#ifdef REVO_EXPERIMENTS
+    cap_keys = g_kmeans_cap_keys;
+#endif
+    if (cap_keys <= 0) cap_keys = std::max({KMEANS_MIN_KEYS, 2 * N, kr.cap});   // a candidate per row and as many again in the band
+    CandidateWs ws{g->pbuf, kr.cap};
+    CHECK_RC(ws.carve(cap_keys, st));
+    KmeansAssignArgs aa{};
+    aa.Gb = g->gb.p; aa.ldg = D; aa.N = N; aa.D = D; aa.C = C; aa.rows = rows; aa.best = best; aa.thr = thr; aa.allow = allow;
+    unsigned long long extra = 0, decided = 0;
+    int passes = 0, t = 0, conv = 0;
+    for (;;) {
+        // the assignment against the centroids of step t
+        unsigned long long h[4] = {0, 0, 0, 0};
+        aa.Cb = kr.cb[kr.cur].p;
+        if (N > 0) {
+            { ProfScope ps("kmeans_best", st);
+              CHECK_RC(launch_kmeans_best(aa, st));
+              CHECK_RC(launch_kmeans_bound(aa, inv, rstat, cstat, st)); }
+            CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
+                aa.cnt = ws.cnt; aa.keys = ws.cand; aa.cap = ws.cap;
+                ProfScope ps("kmeans_decide", st);
+                return launch_kmeans_decide(aa, st);
+            }, [&](unsigned long long n_cand) -> int {
+                REVO_REQUIRE(n_cand <= (unsigned long long)KMEANS_MAX_CAND,
+                             "gallery_kmeans: " + std::to_string(n_cand) + " (row, centroid) pairs inside the rounding bound of a "
+                             "row's best score exceed the limit of " + std::to_string(KMEANS_MAX_CAND));
+                return 0;
+            }, "gallery_kmeans: the candidate count changed between two passes"));
+            passes += ws.passes;
+            REVO_HIP_CHECK(hipMemsetAsync(rowkey, 0, (size_t)N * 8, st));
+            REVO_HIP_CHECK(hipMemsetAsync(ncand, 0, (size_t)N * 4, st));
+            ProfScope ps("kmeans_rescore", st);
+            CHECK_RC(launch_kmeans_rescore(ws.cand, (long)ws.n_cand, g->gf.p, D, inv, kr.cf[kr.cur].p, D, rowkey, ncand, st));
+        }
+        REVO_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof(h), st));
+        { ProfScope ps("kmeans_finish", st);
+          CHECK_RC(launch_kmeans_finish(rowkey, ncand, N, C, kr.labels.p, kr.score.p, kr.sizes.p, ctr, st)); }
+        REVO_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        if (N > 0) {
+            REVO_REQUIRE(h[2] <= ws.n_cand && h[2] <= (unsigned long long)N, "gallery_kmeans: internal: inconsistent counts");
+            extra += ws.n_cand - h[2];
+            decided += h[1];
+        }
+        if (t >= 1 && h[0] == 0) { conv = 1; break; }
+        if (t == max_iter) break;
+        // the centroids of step t + 1 from the labels of step t
+        KmeansUpdateArgs ua{};
+        ua.labels = kr.labels.p; ua.N = N; ua.C = C; ua.D = D; ua.b = b; ua.Gf = g->gf.p; ua.ldg = D; ua.sizes = kr.sizes.p;
+        ua.keys = keys; ua.keys_alt = keys_alt; ua.vals = vals; ua.vals_alt = vals_alt; ua.hist = hist; ua.moff = moff; ua.coff = coff;
+        ua.part = part; ua.part_chunks = part_chunks; ua.sums = sums;
+        ua.Cf_old = kr.cf[kr.cur].p; ua.Cb_old = kr.cb[kr.cur].p; ua.Cf_new = kr.cf[1 - kr.cur].p; ua.Cb_new = kr.cb[1 - kr.cur].p;
+        ua.cstat = cstat;
+        { ProfScope ps("kmeans_update", st);
+          CHECK_RC(launch_kmeans_update(ua, st)); }
+        kr.cur = 1 - kr.cur;
+        ++t;
+    }
+    const int stats[2] = {(int)std::min<unsigned long long>(decided, 0x7fffffffull), 0};
+    REVO_HIP_CHECK(hipMemcpyAsync(g->xw.ctr + CTR_LARGE_FALLBACK, &stats[0], sizeof(int), hipMemcpyHostToDevice, st));
+    CHECK_RC(publish_candidate_stats(g->xw.ctr, std::min<unsigned long long>(extra, 0x7fffffffull), passes, st));
+    kr.n = N; kr.C = C;
+    kr.valid = true;
+    *n_iter = t;
+    *converged = conv;
+    *n_rows = N;
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_kmeans_read(revo_gallery* g, int64_t start, int64_t n, int32_t* labels, float* scores,
+                                            int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_kmeans_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "gallery_kmeans_read: negative start or count");
+    const KmeansResult& kr = g->kmeans;
+    REVO_REQUIRE(kr.valid, "gallery_kmeans_read: no result (call revo_gallery_kmeans again after the rows change)");
+    REVO_REQUIRE(start + n <= kr.n, "gallery_kmeans_read: range past the result's " + std::to_string(kr.n) + " rows");
+    if (n == 0 || (!labels && !scores)) return 0;
+    REVO_ON_DEVICE(g->device);
+    if (labels) CHECK_RC(copy_out(labels, kr.labels.p + start, (size_t)n, dst_on_device));
+    if (scores) CHECK_RC(copy_out(scores, kr.score.p + start, (size_t)n, dst_on_device));
+    return 0;
+    API_END
+}
+extern "C" int32_t revo_gallery_kmeans_centroids(revo_gallery* g, float* centroids, int64_t* sizes, int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(g, "gallery_kmeans_centroids: null handle");
+    const KmeansResult& kr = g->kmeans;
+    REVO_REQUIRE(kr.valid, "gallery_kmeans_centroids: no result (call revo_gallery_kmeans again after the rows change)");
+    if (!centroids && !sizes) return 0;
+    REVO_ON_DEVICE(g->device);
+    if (centroids) CHECK_RC(copy_out(centroids, kr.cf[kr.cur].p, (size_t)kr.C * g->D, dst_on_device));
+    if (sizes) CHECK_RC(copy_out(sizes, (const long long*)kr.sizes.p, (size_t)kr.C, dst_on_device));
     return 0;
     API_END
 }

@@ -100,6 +100,16 @@ struct KnnResult {
     DeviceBuffer<float> fb;
     int64_t n = 0; int k = 0; bool valid = false;
 };
+// revo_gallery_kmeans: the last result ([n] labels and scores, [C] sizes, the centroids' fp32 rows in cf[cur]), valid until the
+// rows change; the centroids' two generations (fp32 rows and bf16 copies of ceil(C / 256) * 256 rows, an update writes the other
+// one) and the call's workspace (ws: what must survive a regrow of the candidate workspace in pbuf)
+struct KmeansResult {
+    DeviceBuffer<int> labels; DeviceBuffer<float> score; DeviceBuffer<unsigned long long> sizes;
+    DeviceBuffer<float> cf[2]; DeviceBuffer<bf16_t> cb[2]; int cur = 0;
+    DeviceBuffer<> ws;
+    long cap = 0;
+    int64_t n = 0, C = 0; bool valid = false;
+};
 // revo_search_maxsim: the CSR of the group ids (gid | off | row | pos in csr; revo::launch_maxsim_index), built at the first
 // call for `rows` rows (-1: none; dropped by revo_search_set_groups, an append, a clear and a remove that moves rows), and the
 // score workspace S [N][n_pad]
@@ -148,11 +158,12 @@ struct __attribute__((visibility("default"))) revo_gallery {   // (the C ABI nam
     RangeResult range;
     ClustersResult clusters;
     KnnResult knn;
+    KmeansResult kmeans;
     MaxsimIndex maxsim;
     // a search overwrites the handle's query rows: the two-phase candidates that refer to them go
     void drop_two_phase() { two.cand = nullptr; two.Q = 0; two.nsegs = 0; two.prelist = nullptr; two.estimated = false; }
     // rows were added or all removed: the results held in the handle go (and, the caller's part, the group index)
-    void drop_results() { pairs.valid = false; range.valid = false; clusters.valid = false; knn.valid = false; }
+    void drop_results() { pairs.valid = false; range.valid = false; clusters.valid = false; knn.valid = false; kmeans.valid = false; }
     // rows left or changed in place: the results and the two-phase candidate state go
     void rows_changed() { drop_results(); two.ksel = 0; drop_two_phase(); }
     revo::CertArgs cert_args(float* cert_out) const {

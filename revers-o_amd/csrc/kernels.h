@@ -569,6 +569,53 @@ int launch_knn_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, 
 int launch_knn_select(const uint64_t* keys, const float* partner, long n, long N, int k, float floor_level, const float* level,
                       const uint32_t* lost, const uint32_t* allow, int* fb_q, int* fb_ctr, float* scores, long long* idx,
                       int* counts, hipStream_t st);
+// ---- exact spherical k-means (revo_gallery_kmeans; kmeans.hip): an assignment is two walks of every row
+// tile over the centroid tiles (best bf16 score per row; candidates inside the rounding band of it), an fp32 re-score folded
+// per row, a finish; an update is a sort by (label, row), chunked fp32 sums in a fixed order and the append's normalisation
+constexpr long KMEANS_MAX_CENTROIDS = 65536;
+constexpr int KMEANS_MAX_ITER = 1000;
+constexpr long KMEANS_MIN_KEYS = 1l << 16;   // candidate keys of the smallest workspace
+constexpr long KMEANS_MAX_CAND = 1l << 28;   // candidates an assignment may have (2 GiB of keys); more: status -2
+// per row, once per call: inv [N] = the factor the query normalisation gives the row's fp32 master row; rstat [N][2] =
+// (||inv gb - fl(g inv)||, inv ||gb||), the row's rounding norms against its own bf16 scan row
+int launch_kmeans_rows(const float* Gf, const bf16_t* Gb, long ldg, long N, int D, float* inv, float* rstat, hipStream_t st);
+struct KmeansAssignArgs {
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    long N; int D;
+    const bf16_t* Cb; long C;     // the centroids' bf16 rows, [ceil(C / 256) * 256][D], zero rows past C
+    long rows;                    // the gallery's rows padded to whole 256-row tiles
+    float* best;                  // [4][rows] per wave column: the row's largest bf16 score over the centroids
+    float* thr;                   // [rows] the candidate bound of each row (+inf: past N or not allowed)
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    unsigned long long* cnt;      // candidates found (counts past cap)
+    uint64_t* keys; long cap;     // [cap] candidate keys (row << 32) | centroid
+};
+int launch_kmeans_best(const KmeansAssignArgs& a, hipStream_t st);
+// cstat [2]: the running maxima max ||c||, max ||cb - c|| of the centroids (launch_l2norm_rows max_stats)
+int launch_kmeans_bound(const KmeansAssignArgs& a, const float* inv, const float* rstat, const uint32_t* cstat, hipStream_t st);
+int launch_kmeans_decide(const KmeansAssignArgs& a, hipStream_t st);
+// fp32 score of candidates [0, n) folded into rowkey[row] (zeroed by the caller) = max of make_key(score, centroid);
+// ncand[row] (zeroed by the caller) counts the row's candidates
+int launch_kmeans_rescore(const uint64_t* cand, long n, const float* Gf, long ldg, const float* inv, const float* Cf, int D,
+                          unsigned long long* rowkey, uint32_t* ncand, hipStream_t st);
+// labels / scores of rows [0, N) from their keys (no key: -1 / -inf); ctr[0] += labels that differ from the old ones, ctr[1] +=
+// rows with more than one candidate, ctr[2] += rows with a label; sizes [C] = members per centroid
+int launch_kmeans_finish(const unsigned long long* rowkey, const uint32_t* ncand, long N, long C, int* labels, float* scores,
+                         unsigned long long* sizes, unsigned long long* ctr, hipStream_t st);
+struct KmeansUpdateArgs {
+    const int* labels; long N; long C; int D;
+    int b;                        // bits of a row index (the row field of the sort key)
+    const float* Gf; long ldg;    // the gallery's fp32 master rows
+    const unsigned long long* sizes;        // [C] launch_kmeans_finish's
+    uint64_t *keys, *keys_alt; float *vals, *vals_alt; uint32_t* hist;   // [N] each, and the sort's digit counts
+    unsigned long long *moff, *coff;        // [C] inclusive member / chunk offsets
+    float* part; long part_chunks;          // [part_chunks][D] chunk partials, part_chunks >= N / 256 + C
+    float* sums;                  // [C][D]
+    const float* Cf_old; const bf16_t* Cb_old;   // the centroids of this step
+    float* Cf_new; bf16_t* Cb_new;          // the centroids of the next one
+    uint32_t* cstat;              // [2] running maxima of the centroids' norms (not reset: upper bounds for the kept rows too)
+};
+int launch_kmeans_update(const KmeansUpdateArgs& a, hipStream_t st);
 // ---- range search (revo_search_range; range.hip): the join runs the 256 x 256 scan's work plan, with a
 // bound per query
 constexpr int RANGE_CHUNK = 1024;            // queries per candidate pass (fewer when the sort key would pass 64 bits)

@@ -483,6 +483,36 @@ class Gallery:
                        "revo_gallery_knn_read")
         return scores, idx, counts
 
+    def kmeans(self, centroids, max_iter=10, normalize=True, allow=None):
+        """Exact spherical k-means over the gallery (include/revo.h, KMEANS): the rows ``allow`` selects (as in
+        :meth:`search`) are assigned to the best of the ``C`` centroids under the fp32 score (ties to the lowest centroid),
+        the centroids are re-computed from their members in a fixed summation order, for at most ``max_iter`` updates
+        (``max_iter=0``: a pure assignment).  ``centroids``: fp32 ``[C, dim]`` device tensor, normalised like appended rows
+        unless ``normalize=False``.  Returns ``(centroids [C, dim] fp32, labels [len] int32, scores [len] fp32, sizes [C]
+        int64, n_iter, converged)``, all tensors on the device; the labels are the exact assignment against the returned
+        centroids, a row ``allow`` excludes has label -1 and score -inf.  Labels and scores are what
+        ``search(self.read(), k=1)`` gives on a gallery of the returned centroids.  Synchronous."""
+        _require_cuda(centroids, "centroids", self.device)
+        c = centroids.detach().to(torch.float32).contiguous()
+        if c.dim() != 2 or c.shape[1] != self.dim or c.shape[0] < 1:
+            raise ValueError(f"centroids must be [C, {self.dim}] with C >= 1, got {tuple(c.shape)}")
+        n_c = int(c.shape[0])
+        n, it, conv = C.c_int64(), C.c_int32(), C.c_int32()
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_gallery_kmeans(self._h, _lib.ptr(c), n_c, int(bool(normalize)), 1, int(max_iter),
+                                                     C.byref(it), C.byref(conv), C.byref(n), _lib.current_stream()),
+                       "revo_gallery_kmeans")
+            n = int(n.value)
+            out = torch.empty((n_c, self.dim), dtype=torch.float32, device=self.device)
+            sizes = torch.empty((n_c,), dtype=torch.int64, device=self.device)
+            labels = torch.empty((n,), dtype=torch.int32, device=self.device)
+            scores = torch.empty((n,), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.revo_gallery_kmeans_centroids(self._h, _lib.ptr(out), _lib.ptr(sizes), 1),
+                       "revo_gallery_kmeans_centroids")
+            _lib.check(self._lib.revo_gallery_kmeans_read(self._h, 0, n, _lib.ptr(labels), _lib.ptr(scores), 1),
+                       "revo_gallery_kmeans_read")
+        return out, labels, scores, sizes, int(it.value), bool(conv.value)
+
     def search_range(self, queries, score_threshold, index_offset=0, allow=None):
         """Range search (include/revo.h, RANGE): for each query every row (allowed by ``allow``, as in :meth:`search`) whose
         fp32 score reaches ``score_threshold`` -- the reference's threshold without its ``limit``.  Returns ``(offsets [Q + 1]

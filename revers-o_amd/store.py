@@ -232,6 +232,52 @@ class NeighborGraph:
                 for a, b, s in zip(self.offsets_row.tolist(), self.offsets_col.tolist(), self.scores.tolist())]
 
 
+@dataclass
+class Theme:
+    """One theme of :meth:`GalleryStore.themes`: its ``size``, its members' point ids in storage order, and its
+    representative -- the member that scores highest against the theme's centre (ties: the first in storage order)."""
+    size: int
+    ids: list
+    representative_id: str
+    representative_score: float
+    representative_payload: dict
+
+
+def seed_rows(mask, n, seed=0):
+    """``n`` distinct rows of those ``mask`` (bool [len]) selects, drawn without replacement by a generator seeded with
+    ``seed``, in ascending order: the initial centroids of :meth:`GalleryStore.themes`.  Raises if fewer are selected."""
+    rows = np.flatnonzero(np.asarray(mask, dtype=bool))
+    n = int(n)
+    if n < 1:
+        raise ValueError("n_themes must be at least 1")
+    if rows.size < n:
+        raise ValueError(f"{n} themes asked of {rows.size} selected points")
+    return np.sort(np.random.default_rng(seed).choice(rows, size=n, replace=False)).astype(np.int64)
+
+
+def assemble_themes(ids, payloads, labels, sizes, representatives, scores):
+    """``Gallery.kmeans``'s host arrays as :class:`Theme` entries, largest first (equal sizes: the lower centroid first);
+    centroids without members are left out.  ``labels`` [len] (-1: not a participant), ``sizes`` [C], ``representatives`` [C]
+    the row of each centroid's representative (-1: none), ``scores`` [len]."""
+    labels = np.asarray(labels, dtype=np.int64)
+    sizes = np.asarray(sizes, dtype=np.int64)
+    order = np.argsort(labels, kind="stable")                         # members of a centroid stay in storage order
+    order = order[labels[order] >= 0]
+    ends = np.cumsum(sizes)
+    if order.size != (int(ends[-1]) if ends.size else 0):
+        raise ValueError("assemble_themes: the sizes do not add up to the labelled rows")
+    out = []
+    for c in sorted(range(sizes.size), key=lambda c: (-int(sizes[c]), c)):
+        if sizes[c] == 0:
+            continue
+        members = order[int(ends[c] - sizes[c]):int(ends[c])]
+        r = int(representatives[c])
+        if r < 0 or labels[r] != c:
+            raise ValueError("assemble_themes: a representative outside its theme")
+        out.append(Theme(int(sizes[c]), [ids[m] for m in members.tolist()], ids[r], float(scores[r]), payloads[r]))
+    return out
+
+
 def sample_mask(mask, sample, seed=0):
     """``mask`` (bool [n]) restricted to ``sample`` of its set entries, drawn without replacement by a generator seeded with
     ``seed`` (all of them when ``sample`` is None or not smaller than their number).  A new array."""
@@ -734,6 +780,32 @@ class GalleryStore:
         allow = torch.from_numpy(_filters.pack_bits(mask)).to(self.gallery.device) if restricted else None
         scores, idx, counts = self.gallery.knn(int(limit), score_threshold=score_threshold, allow=allow)
         return knn_to_graph(self.ids, mask, scores.cpu().numpy(), idx.cpu().numpy(), counts.cpu().numpy())
+
+    def themes(self, n_themes, max_iter=10, seed=0, query_filter=None):
+        """What is in this collection: the points ``query_filter`` selects (all points without one) partitioned into
+        ``n_themes`` themes by exact spherical k-means (include/revo.h, KMEANS), started from ``n_themes`` distinct selected
+        points drawn by :func:`seed_rows` with ``seed``.  Returns :class:`Theme` entries, largest first; themes that end
+        without members are left out.  Raises if fewer points are selected than themes asked."""
+        mask = self.filter_mask(query_filter) if query_filter is not None else np.ones(len(self), dtype=bool)
+        rows = seed_rows(mask, n_themes, seed)
+        dev = self.gallery.device
+        allow = torch.from_numpy(_filters.pack_bits(mask)).to(dev) if query_filter is not None else None
+        init = self.gallery.read()[torch.from_numpy(rows).to(dev)]
+        _, labels, scores, sizes, _, _ = self.gallery.kmeans(init, max_iter=int(max_iter), normalize=True, allow=allow)
+        # each theme's representative on the device: the best score of the theme, then the lowest row that has it
+        n_c = int(sizes.shape[0])
+        lab = labels.to(torch.int64)
+        ok = lab >= 0
+        best = torch.full((n_c,), float("-inf"), dtype=torch.float32, device=dev)
+        best.scatter_reduce_(0, lab[ok], scores[ok], reduce="amax", include_self=True)
+        is_best = ok.clone()
+        is_best[ok] = scores[ok] == best[lab[ok]]
+        rep = torch.full((n_c,), len(self), dtype=torch.int64, device=dev)
+        at = torch.arange(len(self), dtype=torch.int64, device=dev)
+        rep.scatter_reduce_(0, lab[is_best], at[is_best], reduce="amin", include_self=True)
+        rep = torch.where(rep >= len(self), torch.full_like(rep, -1), rep)
+        return assemble_themes(self.ids, self.payloads, labels.cpu().numpy(), sizes.cpu().numpy(), rep.cpu().numpy(),
+                               scores.cpu().numpy())
 
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
