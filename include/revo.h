@@ -99,6 +99,31 @@ int32_t revo_vit_forward_regions(revo_vit* vit, const void* images, int32_t imag
  * out4[3], the ratio that counts as large (8) }.  Synchronises `stream`; reset != 0 clears the counters. */
 int32_t revo_vit_stats(revo_vit* vit, double* out4, int32_t reset, void* stream);
 
+/* ---- TEXT: the text tower of the same CLIP checkpoint (the reference loads it at core_system.py:181 and never calls it):
+ * prompts -> vectors in the space of revo_vit_forward's, so a sentence can be a search query.
+ *   x = token_embedding[tokens] + positional_embedding[:seq_len];  pre-LN blocks with CAUSAL attention (no RoPE, no class
+ *   token);  p = ln_final(x[b, first position of the prompt's largest token id]);  out = p . text_projection, optionally
+ *   normalised.  [UPSTREAM-RECALL] for the structure; every dimension comes from the checkpoint.
+ * Tensor names are the upstream ones without a prefix: token_embedding.weight [vocab, width], positional_embedding
+ * [context, width], transformer.resblocks.{i}.{ln_1, ln_2, attn.in_proj_*, attn.out_proj.*, mlp.c_fc.*, mlp.c_proj.*,
+ * ls_1.gamma, ls_2.gamma (use_ls)}, ln_final.{weight, bias}, text_projection [width, out_dim]; anything else is refused. */
+typedef struct revo_text revo_text;
+typedef struct revo_text_cfg {
+    int32_t context_length, vocab_size, width, layers, heads, mlp_dim, out_dim, use_ls;
+    float ln_eps;
+} revo_text_cfg;
+/* Refused with a message (-2, before the device is touched): head_dim other than 64, context_length over 128, width or
+ * mlp_dim not a multiple of 64, out_dim not a multiple of 4, a missing / mis-sized / unexpected tensor. */
+int32_t revo_text_create(const revo_text_cfg* cfg, const revo_tensor* weights, int32_t n_weights, int32_t device,
+                         int32_t max_batch, revo_text** out);
+int32_t revo_text_destroy(revo_text* text);
+/* tokens: HOST int32 [batch][seq_len], 1 <= seq_len <= context_length (a shorter seq_len computes the same rows: a causal
+ * row never sees what follows it); out: device fp32 [batch, out_dim].  Every id must lie in [0, vocab_size): otherwise status
+ * -2 with a message naming the prompt and the position, before the device is touched.  The tokens are copied through a
+ * pinned buffer of the handle: the caller may free them on return.  Enqueued on `stream` like revo_vit_forward. */
+int32_t revo_text_forward(revo_text* text, const int32_t* tokens, int32_t batch, int32_t seq_len, float* out,
+                          int32_t normalize, void* stream);
+
 /* ---- gallery: replaces recreate_collection(size=D, COSINE) + upsert (core_system.py:600-622) */
 int32_t revo_gallery_create(int32_t dim, int64_t capacity, int32_t device, int32_t keep_f32, revo_gallery** out);
 int32_t revo_gallery_destroy(revo_gallery* g);
@@ -698,6 +723,10 @@ int32_t revo_vit_read_residual(revo_vit* vit, int32_t batch, float* dst, void* s
  * 1 the ln_post output after a whole forward (fp32 [batch*seq, width]: the head works in fp32), 2 the attention-pool
  * output after its MLP residual, before proj (fp32 [batch, width]) */
 int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch, void* dst, void* stream);
+/* the text tower's: n = -2 stops after the token embedding, n >= 0 after the first n blocks, -1 runs the whole forward;
+ * read_residual copies the fp32 residual stream [batch * seq_len of the last forward, width] to dst (device) */
+int32_t revo_text_set_debug_layers(revo_text* text, int32_t n_layers);
+int32_t revo_text_read_residual(revo_text* text, int32_t batch, float* dst, void* stream);
 /* how the certificate treats the handle's searches: 0 = certificate + fallback (the product library's only behaviour),
  * 1 = every query takes the collecting pass, 2 = every query takes the brute-force pass -- and every query of a grouped
  * search the grouped fp32 passes, and every query of revo_search_topk_large its exhaustive fallback (1 and 2: parity tests of the fallback against the fast path), 3 = certificate evaluated and counted but no fallback (timing only: NOT exact) */
@@ -811,6 +840,15 @@ int32_t revo_op_rope(void* qkv_bf16, int64_t ld, const float* cos_sin, int32_t r
                      int32_t heads, void* stream);
 int32_t revo_op_attention(const void* qkv_bf16, int64_t ld, void* out_bf16, int64_t ldo, int32_t batch, int32_t seq,
                           int32_t heads, int32_t head_dim, void* stream);
+/* causal attention of the text tower (text.hip) on the same qkv layout: 1 <= seq <= 128, head_dim 64, fp32 scores and a
+ * two-pass softmax with the row's real maximum.  Output row i is a function of rows 0..i of its sequence alone, bit for
+ * bit, whatever finite values the rows past i hold.  ld % 8 == 0, ldo % 4 == 0. */
+int32_t revo_op_attention_causal(const void* qkv_bf16, int64_t ld, void* out_bf16, int64_t ldo, int32_t batch, int32_t seq,
+                                 int32_t heads, int32_t head_dim, void* stream);
+/* x[(b * seq + s) * ldx + c] = table[tokens_dev[b * seq + s]][c] + pos[s][c] (one fp32 add: bit-exact); tokens_dev: DEVICE
+ * int32 [batch * seq]; an id outside [0, vocab) gives a row of NaN instead of a wild read.  width % 4 == 0, ldx % 4 == 0. */
+int32_t revo_op_embed_tokens(const int32_t* tokens_dev, const float* table, const float* pos, int32_t batch, int32_t seq,
+                             int32_t vocab, int32_t width, float* x, int64_t ldx, void* stream);
 int32_t revo_op_f32_to_bf16(const float* src, int64_t ld_src, void* dst_bf16, int64_t ld_dst, int64_t rows,
                             int32_t cols, void* stream);
 

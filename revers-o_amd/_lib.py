@@ -20,6 +20,12 @@ class VitCfg(C.Structure):
         "use_cls", "use_ls")] + [("ln_eps", C.c_float), ("rope_theta", C.c_float), ("pool_mlp_dim", C.c_int32)]
 
 
+class TextCfg(C.Structure):
+    """revo_text_cfg of include/revo.h."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "context_length", "vocab_size", "width", "layers", "heads", "mlp_dim", "out_dim", "use_ls")] + [("ln_eps", C.c_float)]
+
+
 class Tensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -43,6 +49,9 @@ SIGNATURES = {
     "revo_vit_forward_regions": (_i32, [_p, _p, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _i32, _p]),
     "revo_vit_seq_len": (_i32, [_p]),
     "revo_vit_stats": (_i32, [_p, C.POINTER(C.c_double), _i32, _p]),
+    "revo_text_create": (_i32, [C.POINTER(TextCfg), C.POINTER(Tensor), _i32, _i32, _i32, C.POINTER(_p)]),
+    "revo_text_destroy": (_i32, [_p]),
+    "revo_text_forward": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p]),
     "revo_gallery_create": (_i32, [_i32, _i64, _i32, _i32, C.POINTER(_p)]),
     "revo_gallery_destroy": (_i32, [_p]),
     "revo_gallery_append": (_i32, [_p, _p, _i64, _i32, _i32, _p]),
@@ -99,6 +108,8 @@ SIGNATURES = {
     "revo_op_pool_rows_masked": (_i32, [_p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "revo_op_rope": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p]),
     "revo_op_attention": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
+    "revo_op_attention_causal": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
+    "revo_op_embed_tokens": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _i64, _p]),
     "revo_op_f32_to_bf16": (_i32, [_p, _i64, _p, _i64, _i64, _i32, _p]),
     "revo_prof_enable": (_i32, [_i32]),
     "revo_prof_reset": (_i32, []),
@@ -114,6 +125,8 @@ EXPERIMENT_SIGNATURES = {
     "revo_vit_set_debug_layers": (_i32, [_p, _i32]),
     "revo_vit_read_residual": (_i32, [_p, _i32, _p, _p]),
     "revo_vit_read_tap": (_i32, [_p, _i32, _i32, _p, _p]),
+    "revo_text_set_debug_layers": (_i32, [_p, _i32]),
+    "revo_text_read_residual": (_i32, [_p, _i32, _p, _p]),
     "revo_search_set_mode": (_i32, [_p, _i32]),
     "revo_op_set_gemm_tile": (_i32, [_i32]),
     "revo_op_set_phase_groups": (_i32, [_i32]),

@@ -76,6 +76,47 @@ VARIANTS = {
     "PE-Tiny-N14-56": PEConfig("PE-Tiny-N14-56", 56, 14, 192, 2, 2, 384, 96, pool_heads=2, use_cls=False),
 }
 
+@dataclass(frozen=True)
+class PETextConfig:
+    """The text tower of a PE-Core CLIP: the open-CLIP text transformer (pre-LN blocks, causal attention, end-of-text
+    pooling, a bias-free projection).  [UPSTREAM-RECALL]: the table below is recalled, the checkpoint decides
+    (``weights.resolve_text_config`` takes every dimension from the tensors' shapes)."""
+    name: str
+    context_length: int
+    vocab_size: int
+    width: int
+    layers: int
+    heads: int
+    mlp_dim: int
+    out_dim: int
+    use_ls: bool = False
+    ln_eps: float = 1e-5
+
+    @property
+    def head_dim(self) -> int:
+        return self.width // self.heads
+
+    def to_dict(self):
+        return asdict(self)
+
+
+TEXT_VARIANTS = {
+    # [UPSTREAM-RECALL] keyed by the image tower's model names
+    "PE-Core-B16-224": PETextConfig("PE-Core-B16-224", 32, 49408, 1024, 24, 16, 4096, 1024),
+    "PE-Core-L14-336": PETextConfig("PE-Core-L14-336", 32, 49408, 1024, 24, 16, 4096, 1024),
+    "PE-Core-G14-448": PETextConfig("PE-Core-G14-448", 72, 49408, 1280, 24, 20, 5120, 1280),
+    # Test-only miniatures
+    "PE-Tiny-Text-16": PETextConfig("PE-Tiny-Text-16", 16, 64, 128, 2, 2, 512, 64),
+    "PE-Tiny-Text-40": PETextConfig("PE-Tiny-Text-40", 40, 300, 256, 2, 4, 768, 96, use_ls=True),
+}
+
+
+def get_text_config(name: str = "PE-Core-L14-336") -> PETextConfig:
+    if name not in TEXT_VARIANTS:
+        raise KeyError(f"unknown PE text variant {name!r}; available: {sorted(TEXT_VARIANTS)}")
+    return TEXT_VARIANTS[name]
+
+
 # The model the reference asks for first (core_system.py:177).
 DEFAULT_VARIANT = "PE-Core-L14-336"
 

@@ -17,6 +17,7 @@ What differs underneath:
 
 There is no CPU fallback: constructing the class without a GPU raises.
 """
+import dataclasses
 import json
 import os
 from datetime import datetime
@@ -35,9 +36,10 @@ from . import filters
 from . import preprocess as pp
 from . import regions as rg
 from . import store as st
-from .config import DEFAULT_VARIANT, available_configs, get_config
-from .engine import VitEngine
-from .weights import load_state_dict, synth_weights
+from .config import DEFAULT_VARIANT, TEXT_VARIANTS, available_configs, get_config, get_text_config
+from .engine import TextEngine, VitEngine
+from .tokenizer import ClipTokenizer
+from .weights import load_state_dict, load_text_state_dict, resolve_text_config, synth_text_weights, synth_weights
 
 DB_ROOT = "./simple_reverso_db"
 IMAGE_EXTENSIONS = ['.jpg', '.jpeg', '.png', '.bmp', '.tiff', '.webp']
@@ -110,6 +112,7 @@ class SimpleReverso:
         self._lock = threading.RLock()      # ui.py drives one shared instance from worker threads
         self.device = self.setup_device(device)
         self.pe_model, self.preprocess = self.load_pe_model(model_name, checkpoint, synthetic_seed)
+        self.text_model = None              # the checkpoint's text tower, built by the first text query (load_text_model)
         self.grounded_sam = None
         self.vector_db = None
         self.current_database = None
@@ -220,6 +223,7 @@ class SimpleReverso:
         configs = available_configs()
         print(f"Available PE configs: {configs}")
         checkpoint = checkpoint or os.environ.get("REVERSO_PE_CHECKPOINT")
+        self._checkpoint, self._synthetic_seed = checkpoint, synthetic_seed      # load_text_model reads the same file
         sd = load_state_dict(checkpoint) if checkpoint else None
         if sd is None:
             # no network here: pretrained weights (pe.CLIP.from_config(..., pretrained=True), :181)
@@ -937,19 +941,25 @@ class SimpleReverso:
             return "❌ No query embeddings available. Please detect/process an image first.", []
         if not self.vector_db or not self.current_database:
             return "❌ No database loaded. Please create or load a database first.", []
-        query = self.region_embeddings[0]
+        return self._search_with_query(self.region_embeddings[0], similarity_threshold, max_results, query_filter, group_by)
+
+    def _search_with_query(self, query, similarity_threshold, max_results, query_filter, group_by):
+        """The search and the result formatting of :meth:`search_similar` for a query vector (an image region's or a
+        prompt's); ``similarity_threshold`` None: no cut."""
+        score_threshold = None if similarity_threshold is None else float(similarity_threshold)
         with self._lock:
             if group_by is not None:
                 res = self.vector_db.search_groups(query, group_by, limit=int(max_results),
-                                                   score_threshold=float(similarity_threshold), query_filter=query_filter)
+                                                   score_threshold=score_threshold, query_filter=query_filter)
                 hits = [grp.hits[0] for grp in res.groups]
             elif query_filter is None:
-                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold))
+                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=score_threshold)
             else:
-                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=float(similarity_threshold),
+                hits = self.vector_db.search(query, limit=int(max_results), score_threshold=score_threshold,
                                              query_filter=query_filter)
         if not hits:
-            return f"❌ No similar regions found above threshold {similarity_threshold}", []
+            return ("❌ No similar regions found" +
+                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
         text = f"🎯 Found {len(hits)} similar regions:\n\n"
 
         def thumbnail(r):
@@ -990,6 +1000,92 @@ class SimpleReverso:
             text += f"   📍 Bounding box: {str(payload.get('bbox', '[0,0,0,0]'))}\n\n"
             items.append({"image": img, "score": r.score, "filename": filename, "bbox": payload.get("bbox")})
         return text, items
+
+    # ------------------------------------------------------------ text queries --
+    def load_text_model(self, checkpoint=None, vocab=None):
+        """The text tower of the same CLIP checkpoint (the reference loads it at core_system.py:181 and never uses it), built
+        on first use.  ``checkpoint``: the file to read it from -- by default the one the image tower came from; without
+        one: seeded random-init weights and a warning, as :meth:`load_pe_model` does.  ``vocab``: the BPE merges file
+        (``REVERSO_BPE_VOCAB`` otherwise); without one only token arrays can be embedded."""
+        with self._lock:
+            if getattr(self, "text_model", None) is not None and checkpoint is None and vocab is None:
+                return self.text_model
+            checkpoint = checkpoint or self._checkpoint or os.environ.get("REVERSO_PE_CHECKPOINT")
+            name = self.pe_model.cfg.name
+            if checkpoint:
+                sd = load_text_state_dict(checkpoint)
+                cfg = resolve_text_config(sd, name=name)
+            else:
+                print("⚠️ No checkpoint given (REVERSO_PE_CHECKPOINT): the text tower uses seeded random-init weights")
+                cfg = get_text_config(name if name in TEXT_VARIANTS else DEFAULT_VARIANT)
+                if cfg.out_dim != self.pe_model.cfg.out_dim:      # (a test miniature of the image tower: match its width)
+                    cfg = dataclasses.replace(get_text_config("PE-Tiny-Text-16"), out_dim=self.pe_model.cfg.out_dim)
+                sd = synth_text_weights(cfg, seed=self._synthetic_seed, device=self.device)
+            if cfg.out_dim != self.pe_model.cfg.out_dim:
+                raise ValueError(f"the text tower embeds into {cfg.out_dim} dimensions, the image tower into {self.pe_model.cfg.out_dim}")
+            tok = None
+            vocab = vocab or os.environ.get("REVERSO_BPE_VOCAB")
+            if vocab:
+                tok = ClipTokenizer(vocab, context_length=cfg.context_length, vocab_size=cfg.vocab_size)
+            if getattr(self, "text_model", None) is not None:
+                self.text_model.close()
+            self.text_model = TextEngine(cfg, sd, device=self.device.index or 0, tokenizer=tok)
+            print(f"✅ Loaded the text tower of {name}" + (f" from {checkpoint}" if checkpoint else ""))
+            return self.text_model
+
+    def embed_text(self, texts):
+        """Prompts (a string, a list of strings, or an integer token array ``[n, seq_len]``) -> normalised fp32 ``[n, out_dim]``
+        on the device, in the space of the image embeddings."""
+        eng = self.load_text_model()
+        if isinstance(texts, str) or (len(texts) and isinstance(texts[0], str)):
+            return eng.embed(texts)
+        return eng.embed_tokens(texts, trim=True)
+
+    def search_by_text(self, text, similarity_threshold=None, max_results=5, query_filter=None, group_by=None):
+        """:meth:`search_similar` with a prompt as the query: the same results and strings.  No default threshold: the
+        text-image cosines of a CLIP model lie far below the 0.7 that suits image-image scores."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        try:
+            query = self.embed_text([text] if isinstance(text, str) else text)[0].cpu()
+        except Exception as e:
+            return f"❌ Error embedding the text query: {str(e)}", []
+        return self._search_with_query(query, similarity_threshold, max_results, query_filter, group_by)
+
+    def label_database(self, labels, query_filter=None, members=5):
+        """Zero-shot labelling: every stored region (those a Qdrant-style ``query_filter`` selects, if given) gets the best
+        of the prompts ``labels`` -- the exact assignment of ``Gallery.kmeans(max_iter=0)`` with the prompts' embeddings as
+        centroids.  Returns ``(text, out)``: per label ``{"label", "count", "members": [{"filename", "image_source", "bbox",
+        "id", "score"}]}`` with its ``members`` best-scoring regions, in the order of ``labels``."""
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        labels = [labels] if isinstance(labels, str) else list(labels)
+        if not labels:
+            return "❌ Please provide at least one label", []
+        try:
+            with self._lock:
+                db = self.vector_db
+                if len(db) == 0:
+                    return "⚠️ The database holds no regions", []
+                lab, sc = db.assign(self.embed_text(labels), query_filter=query_filter)
+                lab, sc = lab.cpu().numpy(), sc.cpu().numpy()
+                out = []
+                for j, name in enumerate(labels):
+                    rows = np.nonzero(lab == j)[0]
+                    best = rows[np.lexsort((rows, -sc[rows]))][:int(members)]        # score desc, row asc
+                    out.append({"label": name, "count": int(rows.size),
+                                "members": [{"filename": db.payloads[r].get("filename", "Unknown"),
+                                             "image_source": db.payloads[r].get("image_source", ""),
+                                             "bbox": db.payloads[r].get("bbox"), "id": db.ids[r], "score": float(sc[r])}
+                                            for r in best.tolist()]})
+        except Exception as e:
+            return f"❌ Error labelling the database: {str(e)}", []
+        total = sum(o["count"] for o in out)
+        text = f"🎯 {total} regions over {len(out)} labels:\n\n"
+        for o in out:
+            eg = f", e.g. {o['members'][0]['filename']} ({o['members'][0]['score']:.3f})" if o["members"] else ""
+            text += f"- {o['label']}: {o['count']} regions{eg}\n"
+        return text, out
 
     def search_similar_all_regions(self, similarity_threshold=None, max_results=5, query_filter=None, group_by="image_source"):
         """"Which images contain ALL of what this image shows?": EVERY region embedding of the query image is a query

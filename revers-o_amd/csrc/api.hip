@@ -117,15 +117,7 @@ __global__ __launch_bounds__(256) void probe_q_kernel(const float* __restrict__ 
 }  // namespace revo
 
 // ------------------------------------------------------------ the model ----
-// ln_1 / ln_2 are folded into the weights of the GEMM that follows them: w_qkv = bf16(ln_1.weight . W),
-// b_qkv = b + W ln_1.bias, c_qkv[j] = sum_k w_qkv[j][k]; the same for fc1 with ln_2.  The forward feeds those GEMMs either
-// bf16(x) with the row statistics (folded form) or the normalised row without gain and shift (LayerNorm kernel).
-struct LayerW {
-    bf16_t *w_qkv, *w_o, *w_fc1, *w_fc2;
-    float *b_qkv, *b_o, *b_fc1, *b_fc2, *c_qkv, *c_fc1, *ls1, *ls2;
-};
-
-constexpr size_t SPLITK_WS_ELEMS = 16u << 20;     // 64 MiB of fp32
+// (LayerW, the weight upload helpers, the gemm() wrapper and the block loop that both towers run: api_internal.h)
 struct revo_vit {
     revo_vit_cfg cfg;
     int device = 0, max_batch = 0, S = 0, G2 = 0, Kp = 0, hd = 0, phd = 0, PM = 0, debug_layers = -1;
@@ -169,57 +161,6 @@ struct revo_vit {
         if (rg_ev) (void)hipEventDestroy(rg_ev);
     }
 };
-
-namespace {
-struct WeightMap {
-    std::map<std::string, const revo_tensor*> m;
-    const revo_tensor* get(const std::string& name, int64_t numel) {
-        auto it = m.find(name);
-        if (it == m.end()) { revo_set_error("missing weight tensor: " + name); return nullptr; }
-        if (it->second->numel != numel) {
-            revo_set_error("weight " + name + ": expected " + std::to_string(numel) + " elements, got " +
-                           std::to_string(it->second->numel));
-            return nullptr;
-        }
-        return it->second;
-    }
-};
-
-// fp32 (host or device) -> device fp32
-int up_f32(revo_vit* v, WeightMap& wm, const std::string& name, int64_t numel, float** out) {
-    const revo_tensor* t = wm.get(name, numel);
-    if (!t) return -2;
-    CHECK_RC(v->dalloc(out, (size_t)numel));
-    REVO_HIP_CHECK(hipMemcpy(*out, t->data, (size_t)numel * 4, hipMemcpyDefault));
-    return 0;
-}
-// linear layer behind a LayerNorm: fp32 [rows][cols] weights, [cols] gain / shift, [rows] bias (host or device) ->
-// bf16(gamma . W), column sums of the rounded weights, bias + W beta
-int up_folded(revo_vit* v, WeightMap& wm, float* stage, float* gb, const std::string& wname, const std::string& bname,
-              const std::string& ln, int64_t rows, int64_t cols, bf16_t** w_out, float** c_out, float** b_out) {
-    const revo_tensor *tw = wm.get(wname, rows * cols), *tb = wm.get(bname, rows), *tg = wm.get(ln + ".weight", cols),
-                      *te = wm.get(ln + ".bias", cols);
-    if (!tw || !tb || !tg || !te) return -2;
-    CHECK_RC(v->dalloc(w_out, (size_t)(rows * cols)));
-    CHECK_RC(v->dalloc(c_out, (size_t)rows));
-    CHECK_RC(v->dalloc(b_out, (size_t)rows));
-    REVO_HIP_CHECK(hipMemcpy(stage, tw->data, (size_t)(rows * cols) * 4, hipMemcpyDefault));
-    REVO_HIP_CHECK(hipMemcpy(gb, tg->data, (size_t)cols * 4, hipMemcpyDefault));
-    REVO_HIP_CHECK(hipMemcpy(gb + cols, te->data, (size_t)cols * 4, hipMemcpyDefault));
-    REVO_HIP_CHECK(hipMemcpy(gb + 2 * cols, tb->data, (size_t)rows * 4, hipMemcpyDefault));
-    CHECK_RC(revo::launch_fold_ln_linear(stage, gb, gb + cols, gb + 2 * cols, (int)rows, (int)cols, *w_out, cols, *c_out, *b_out, 0));
-    REVO_HIP_CHECK(hipStreamSynchronize(0));
-    return 0;
-}
-// fp32 [rows][cols] (host or device) -> device bf16 [rows][ld] zero padded
-int up_bf16(revo_vit* v, float* stage, const float* src, int64_t rows, int64_t cols, int64_t ld, bf16_t** out) {
-    CHECK_RC(v->dalloc(out, (size_t)(rows * ld)));
-    REVO_HIP_CHECK(hipMemcpy(stage, src, (size_t)(rows * cols) * 4, hipMemcpyDefault));
-    CHECK_RC(revo::launch_f32_to_bf16(stage, cols, *out, ld, rows, (int)cols, 0));
-    REVO_HIP_CHECK(hipStreamSynchronize(0));
-    return 0;
-}
-}  // namespace
 
 extern "C" int32_t revo_vit_create(const revo_vit_cfg* cfg, const revo_tensor* weights, int32_t n_weights,
                                    int32_t device, int32_t max_batch, revo_vit** out) {
@@ -472,33 +413,6 @@ extern "C" int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch
 }
 #endif
 
-namespace {
-// ln (optional, residual epilogue): the LayerNorm that follows; *ln_fused = 1 if the GEMM's launch form did it (kernels.h)
-// The LayerNorm behind a residual GEMM, without gain and shift (those live in the next GEMM's weights).  Whichever the
-// launch form can do: *fused = 1: `out` holds the normalised rows (one-image forms: the split-K reduce does it);
-// *folded = 1: `out` holds bf16(x) and `stats` the rows' partial statistics (folded form, kernels.h GemmArgs::lnf_*);
-// neither: the caller runs the LayerNorm kernel.
-// planes: keep the residual stream as (out, lo) = (bf16(x), bf16(x - bf16(x))) from here on (kernels.h GemmArgs::xp_*)
-struct LnAfter { float eps; bf16_t* out; long ldo; int* fused; float2* stats; int* folded; bf16_t* lo; int x_in_planes, planes_out; };
-// consumer side of the folded form: A = bf16(x), the epilogue applies rstd (acc - mean c) + bias
-struct LnBefore { const float2* stats; int parts; const float* c; float eps; };
-int gemm(const char* cls, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K, void* C,
-         long ldc, const float* bias, const float* gamma, hipStream_t st, float* ws = nullptr, long ws_elems = 0,
-         const LnAfter* ln = nullptr) {
-    revo::GemmArgs a{};
-    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.M = M; a.N = N; a.K = K; a.C = C; a.ldc = ldc;
-    a.bias = bias; a.gamma = gamma; a.ws = ws; a.ws_elems = ws_elems;
-    if (ln) {
-        a.ln_eps = ln->eps; a.ln_ldo = ln->ldo; a.ln_fused = ln->fused;
-        if (ln->fused) a.ln_out = ln->out;
-        if (ln->stats) { a.lnf_xb = ln->out; a.lnf_ldxb = ln->ldo; a.lnf_stats = ln->stats; a.lnf_done = ln->folded; }
-        if (ln->lo) { a.xp_hi = ln->out; a.xp_lo = ln->lo; a.xp_ld = ln->ldo; a.xp_in = ln->x_in_planes; a.xp_out = ln->planes_out; }
-    }
-    ProfScope ps(cls, st);
-    return revo::launch_gemm(epi, a, st);
-}
-}  // namespace
-
 // The head behind the pooled rows u [R][pool_heads][W]: value and output projection, the pool's LayerNorm and MLP, proj, L2 --
 // for the R images of a forward or for R regions (revo_vit_forward_regions).  A row's result does not depend on R or on
 // the other rows (head.hip: the skinny GEMM cuts K the same way whatever M is).
@@ -581,88 +495,23 @@ static int vit_forward_range(revo_vit* vv, const void* images_all, int32_t image
     { ProfScope ps("layernorm", st);
       CHECK_RC(launch_layernorm(v->x, W, v->lnpre_w, v->lnpre_b, c.ln_eps, rows, W, v->x, W, 0, st)); }
 
-    const int nl = v->debug_layers < 0 ? c.layers : std::min(v->debug_layers, c.layers);
-    // ln_1 / ln_2 live in the weights of qkv / fc1 (LayerW): what those GEMMs read from `h` is, depending on what the
-    // residual GEMM in front of them could do,
-    //   H_XB    bf16(x) + the rows' partial statistics in ln_stats: the folded form (batch-sized forwards: the residual
-    //           epilogue that holds the new row writes both; the consuming epilogue applies rstd (acc - mean c) + b'),
-    //   H_NORM  the normalised rows (one-image forwards: the split-K reduce of the residual GEMM normalises its rows;
-    //           otherwise the LayerNorm kernel, which is also what block 0's ln_1 takes behind ln_pre).
-    enum { H_NONE = 0, H_NORM = 1, H_XB = 2 };
-    int h_state = H_NONE;
-    float2* stats = vv->ln_parts ? vv->ln_stats + r0 * vv->ln_parts : nullptr;
-    // Between folded residual GEMMs the stream itself lives in two bf16 planes, (h, xlo) = (bf16(x), bf16(x - bf16(x))):
-    // the high plane IS the next GEMM's A operand, so the residual epilogues move 4 + 4 bytes per element instead of fp32
-    // rows plus a bf16 copy (4 + 4 + 2).  Entered by the first folding out-proj (fp32 in, planes out), left by the last
-    // fc2 (planes in, fp32 out: ln_post and the head read fp32); only when both residual GEMMs of a block fold.
-    bf16_t* xlo = (vv->xlo && gemm_ln_planes_enabled() && gemm_resid_folds(rows, W, W, W, W, W) && gemm_resid_folds(rows, W, Md, Md, Md, W))
-                      ? vv->xlo + r0 * W : nullptr;
-    bool x_planes = false;
-    auto ln_before = [&](const float* csum, GemmArgs& a) {
-        if (h_state == H_XB) { a.lnc_stats = stats; a.lnc_parts = vv->ln_parts; a.lnc_c = csum; a.lnc_eps = c.ln_eps; a.lnc_tele = vv->ln_tele; }
-    };
-    auto normalise_if_needed = [&]() -> int {
-        if (h_state != H_NONE) return 0;
-        if (x_planes) { revo_set_error("vit_forward: internal: a LayerNorm kernel was asked for while the stream is in planes"); return -3; }
-        ProfScope ps("layernorm", st);
-        CHECK_RC(launch_layernorm(v->x, W, nullptr, nullptr, c.ln_eps, rows, W, v->h, W, 1, st));
-        h_state = H_NORM;
-        return 0;
-    };
-    for (int i = 0; i < nl; ++i) {
-        const LayerW& L = v->layers[i];
-        CHECK_RC(normalise_if_needed());
-        {
-            // K4 + K5: bias and the 2-D rotary embedding of q and k in the GEMM epilogue (every tile shape)
-            GemmArgs a{};
-            a.A = v->h; a.lda = W; a.B = L.w_qkv; a.ldb = W; a.M = rows; a.N = 3 * W; a.K = W; a.C = v->qkv;
-            a.ldc = 3 * W; a.bias = L.b_qkv; a.rope_cs = v->rope_cs; a.rope_S = S; a.rope_hd = v->hd;
-            a.rope_cols = 2 * W;
-            ln_before(L.c_qkv, a);
-            ProfScope ps("gemm_qkv", st);
-            CHECK_RC(launch_gemm(EPI_BF16_ROPE, a, st));
-        }
-        { ProfScope ps("attention", st);
-          CHECK_RC(launch_attention_ex(v->qkv, 3 * W, v->att, W, B, S, c.heads, v->hd, c.use_cls, st)); }
-        int fused = 0, folded = 0;
-        const LnAfter ln2{c.ln_eps, v->h, W, &fused, stats, &folded, xlo, x_planes ? 1 : 0, xlo ? 1 : 0};
-        CHECK_RC(gemm("gemm_out", EPI_RESID_F32, v->att, W, L.w_o, W, rows, W, W, v->x, W, L.b_o, L.ls1, st, vv->splitk_ws,
-                      (long)SPLITK_WS_ELEMS, &ln2));
-        h_state = folded ? H_XB : (fused ? H_NORM : H_NONE);
-        x_planes = xlo && folded;
-#ifdef REVO_EXPERIMENTS
-        // cache-state experiment: re-touch bf16(x) (a device copy into the dead qkv buffer) before the GEMM that streams it
-        if (folded && getenv("REVO_LNFOLD_TOUCH")) {
-            ProfScope ps("touch", st);
-            REVO_HIP_CHECK(hipMemcpyAsync(v->qkv, v->h, (size_t)rows * W * 2, hipMemcpyDeviceToDevice, st));
-        }
-#endif
-        CHECK_RC(normalise_if_needed());
-        {
-            GemmArgs a{};
-            a.A = v->h; a.lda = W; a.B = L.w_fc1; a.ldb = W; a.M = rows; a.N = Md; a.K = W; a.C = v->mlp; a.ldc = Md;
-            a.bias = L.b_fc1;
-            ln_before(L.c_fc1, a);
-            ProfScope ps("gemm_fc1", st);
-            CHECK_RC(launch_gemm(EPI_BF16_GELU, a, st));
-        }
-        // (splitk_ws: scratch for the split-K forms of fc2 -- leftover rows at large batch, the whole GEMM at small batch)
-        fused = 0; folded = 0;
-        const bool last = i + 1 >= nl;
-        // the last fc2 has no LayerNorm of the body behind it: it brings the stream back to fp32 rows (ln_post, the taps)
-        const LnAfter ln1n{c.ln_eps, v->h, W, last ? nullptr : &fused, last ? nullptr : stats, last ? nullptr : &folded, xlo,
-                           x_planes ? 1 : 0, (xlo && !last) ? 1 : 0};
-        CHECK_RC(gemm("gemm_fc2", EPI_RESID_F32, v->mlp, Md, L.w_fc2, Md, rows, W, Md, v->x, W, L.b_fc2, L.ls2, st,
-                      vv->splitk_ws, (long)SPLITK_WS_ELEMS, (!last || x_planes) ? &ln1n : nullptr));
-        h_state = last ? H_NONE : (folded ? H_XB : (fused ? H_NORM : H_NONE));
-        x_planes = !last && xlo && folded;
-#ifdef REVO_EXPERIMENTS
-        if (folded && !last && getenv("REVO_LNFOLD_TOUCH")) {
-            ProfScope ps("touch", st);
-            REVO_HIP_CHECK(hipMemcpyAsync(v->qkv, v->h, (size_t)rows * W * 2, hipMemcpyDeviceToDevice, st));
-        }
-#endif
-    }
+    // The block loop both towers run (api_internal.h body_blocks).  This tower's two pieces of it: K4 + K5, bias and the 2-D
+    // rotary embedding of q and k in the qkv GEMM's epilogue (every tile shape), and attention over all keys
+    BodyCtx bc{};
+    bc.who = "vit_forward"; bc.layers = &v->layers;
+    bc.nl = v->debug_layers < 0 ? c.layers : std::min(v->debug_layers, c.layers);
+    bc.W = W; bc.Md = Md; bc.rows = rows; bc.eps = c.ln_eps;
+    bc.x = v->x; bc.h = v->h; bc.qkv = v->qkv; bc.att = v->att; bc.mlp = v->mlp;
+    bc.xlo = vv->xlo ? vv->xlo + r0 * W : nullptr;
+    bc.stats = vv->ln_parts ? vv->ln_stats + r0 * vv->ln_parts : nullptr;
+    bc.ln_parts = vv->ln_parts; bc.ln_tele = vv->ln_tele; bc.splitk_ws = vv->splitk_ws;
+    CHECK_RC(body_blocks(
+        bc, st,
+        [&](GemmArgs& a) {
+            a.rope_cs = v->rope_cs; a.rope_S = S; a.rope_hd = v->hd; a.rope_cols = 2 * W;
+            return (int)EPI_BF16_ROPE;
+        },
+        [&]() { return launch_attention_ex(v->qkv, 3 * W, v->att, W, B, S, c.heads, v->hd, c.use_cls, st); }));
     if (v->debug_layers >= 0) return 0;   // parity hook: residual stream only
 
     // ln_post (fp32, in place) -> attention pool -> proj -> normalise: all fp32 (head.hip says why)

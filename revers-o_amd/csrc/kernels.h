@@ -190,6 +190,15 @@ int launch_attention(const bf16_t* qkv, long ld, bf16_t* out, long ldo, int B, i
 // has_cls: row 0 is the class token and may be scheduled apart from the patch rows (same result)
 int launch_attention_ex(const bf16_t* qkv, long ld, bf16_t* out, long ldo, int B, int S, int H, int hd, int has_cls,
                         hipStream_t st);
+// ---- the text tower's kernels (text.hip)
+// causal attention on the same qkv layout: 1 <= S <= ATTC_MAX_S, hd 64; output row i depends on rows 0..i alone, bit for bit
+constexpr int ATTC_MAX_S = 128;
+int launch_attention_causal(const bf16_t* qkv, long ld, bf16_t* out, long ldo, int B, int S, int H, int hd, hipStream_t st);
+// x[b * S + s][:] = table[tokens[b * S + s]] + pos[s] (tokens: device; an id outside [0, vocab) gives a row of NaN)
+int launch_embed_tokens(const int32_t* tokens, const float* table, const float* pos, int B, int S, int vocab, int W, float* x,
+                        long ldx, hipStream_t st);
+// out[b][:] = x[b * S + p][:], p = the first position of prompt b's largest token id
+int launch_pool_eot(const int32_t* tokens, const float* x, long ldx, int B, int S, int W, float* out, hipStream_t st);
 void gemm_set_min_tiles256(int n);  // timing experiments only (default 100)
 void gemm_set_ring(int on, int max_tiles);   // timing experiments only (default on, 256 tiles)
 void gemm_set_splitk(int on);       // timing experiments only (1 = default)

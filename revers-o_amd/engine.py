@@ -16,8 +16,9 @@ import threading
 import torch
 
 from . import _lib
-from .config import PEConfig, get_config
-from .weights import check_state_dict, resolve_config, strip_non_parameters, synth_weights
+from .config import PEConfig, PETextConfig, get_config, get_text_config
+from .weights import (check_state_dict, check_text_state_dict, expected_text_shapes, resolve_config, strip_non_parameters,
+                      synth_text_weights, synth_weights)
 
 IMAGE_F32 = 0
 IMAGE_U8 = 1
@@ -233,6 +234,122 @@ class VitEngine:
             _lib.check(self._lib.revo_vit_read_tap(self._h, 2, B, _lib.ptr(pooled), st), "revo_vit_read_tap")
         out.update(ln_post=lnp, pooled=pooled, embedding=emb)
         return out
+
+
+class TextEngine:
+    """The text tower of the same CLIP checkpoint resident on one GPU (include/revo.h, TEXT): prompts -> vectors in the
+    image embeddings' space.  ``state_dict``: the tower's tensors under their upstream names without a prefix
+    (``weights.load_text_state_dict`` / ``weights.text_state_dict``)."""
+
+    def __init__(self, cfg: PETextConfig, state_dict, device=0, max_batch=256, experiments=False, tokenizer=None):
+        self.cfg = cfg
+        self.device = _as_device(device)
+        self.max_batch = int(max_batch)
+        self.tokenizer = tokenizer
+        self._lock = threading.Lock()
+        self.experiments = bool(experiments) or _lib.product_is_experiment_build()
+        lib = _lib.load_exp() if experiments else _lib.load()
+        check_text_state_dict(cfg, state_dict)
+        names = sorted(k for k in state_dict if k in expected_text_shapes(cfg))
+        keep = []          # keep converted tensors alive until create returns
+        arr = (_lib.Tensor * len(names))()
+        for i, n in enumerate(names):
+            t = state_dict[n].detach().to(torch.float32).contiguous()
+            keep.append(t)
+            arr[i].name = n.encode()
+            arr[i].data = t.data_ptr()
+            arr[i].numel = t.numel()
+        c = _lib.TextCfg(cfg.context_length, cfg.vocab_size, cfg.width, cfg.layers, cfg.heads, cfg.mlp_dim, cfg.out_dim,
+                         int(cfg.use_ls), cfg.ln_eps)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize()
+            _lib.check(lib.revo_text_create(C.byref(c), arr, len(names), self.device.index or 0, self.max_batch,
+                                            C.byref(h)), "revo_text_create")
+        self._h = h
+        self._lib = lib
+
+    @classmethod
+    def synthetic(cls, name_or_cfg="PE-Core-L14-336", seed=0, device=0, max_batch=256, experiments=False, tokenizer=None, **kw):
+        cfg = name_or_cfg if isinstance(name_or_cfg, PETextConfig) else get_text_config(name_or_cfg)
+        sd = synth_text_weights(cfg, seed=seed, device=torch.device("cuda", device), **kw)
+        return cls(cfg, sd, device=device, max_batch=max_batch, experiments=experiments, tokenizer=tokenizer)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.revo_text_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _host_tokens(tokens):
+        import numpy as np
+        if isinstance(tokens, torch.Tensor):
+            tokens = tokens.detach().cpu().numpy()
+        t = np.asarray(tokens)
+        if t.ndim != 2 or t.dtype.kind not in "iu":
+            raise ValueError(f"tokens must be an integer array [n, seq_len], got {t.dtype} {t.shape}")
+        if t.size and (t.min() < -2 ** 31 or t.max() >= 2 ** 31):
+            raise ValueError("token ids must fit int32")
+        return np.ascontiguousarray(t.astype(np.int32, copy=False))
+
+    def embed_tokens(self, tokens, normalize=True, trim=False, out=None):
+        """tokens: integer ``[n, seq_len]`` on the host, ``1 <= seq_len <= context_length``, every id in ``[0, vocab)``
+        (anything else raises, naming the prompt and the position; nothing reaches the device).  Returns fp32
+        ``[n, out_dim]`` on the device.  ``trim=True`` cuts the columns behind the batch's longest prompt (its end token:
+        the largest id) before the call -- the same rows, fewer of them."""
+        t = self._host_tokens(tokens)
+        n, L = t.shape
+        if trim and n:
+            L = int((t.argmax(axis=1)).max()) + 1
+            t = t[:, :L].copy()
+        if out is None:
+            out = torch.empty((n, self.cfg.out_dim), dtype=torch.float32, device=self.device)
+        _require_cuda(out, "out", self.device)
+        with self._lock, torch.cuda.device(self.device):
+            st = _lib.current_stream()
+            for s in range(0, n, self.max_batch):
+                e = min(n, s + self.max_batch)
+                part = t[s:e]
+                _lib.check(self._lib.revo_text_forward(self._h, C.c_void_p(part.ctypes.data), e - s, L, _lib.ptr(out[s:e]),
+                                                       int(bool(normalize)), st), "revo_text_forward")
+        return out
+
+    def embed(self, texts, normalize=True, trim=True):
+        """Prompts (a string or a list of strings) through the tokenizer and :meth:`embed_tokens`."""
+        if self.tokenizer is None:
+            from .tokenizer import ClipTokenizer
+            try:
+                self.tokenizer = ClipTokenizer(None, context_length=self.cfg.context_length, vocab_size=self.cfg.vocab_size)
+            except FileNotFoundError as exc:
+                raise _lib.RevoError(f"embedding strings needs a tokenizer: {exc}") from exc
+        return self.embed_tokens(self.tokenizer(texts, self.cfg.context_length), normalize=normalize, trim=trim)
+
+    # -- parity-test hook -----------------------------------------------------
+    def residual_after(self, tokens, n_layers):
+        """fp32 residual stream [n, seq_len, W] after the first n blocks (-2: the embedded tokens)."""
+        if not self.experiments:
+            raise _lib.RevoError("residual_after is a parity-test hook of librevo_exp.so: create the engine with experiments=True")
+        t = self._host_tokens(tokens)
+        n, L = t.shape
+        assert 1 <= n <= self.max_batch
+        x = torch.empty((n, L, self.cfg.width), dtype=torch.float32, device=self.device)
+        dummy = torch.empty((n, self.cfg.out_dim), dtype=torch.float32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            st = _lib.current_stream()
+            _lib.check(self._lib.revo_text_set_debug_layers(self._h, int(n_layers)))
+            try:
+                _lib.check(self._lib.revo_text_forward(self._h, C.c_void_p(t.ctypes.data), n, L, _lib.ptr(dummy), 0, st),
+                           "revo_text_forward")
+                _lib.check(self._lib.revo_text_read_residual(self._h, n, _lib.ptr(x), st))
+            finally:
+                self._lib.revo_text_set_debug_layers(self._h, -1)
+        return x
 
 
 class Gallery:

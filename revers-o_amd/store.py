@@ -807,6 +807,17 @@ class GalleryStore:
         return assemble_themes(self.ids, self.payloads, labels.cpu().numpy(), sizes.cpu().numpy(), rep.cpu().numpy(),
                                scores.cpu().numpy())
 
+    def assign(self, vectors, query_filter=None):
+        """The best of ``vectors`` (fp32 ``[C, dim]``, normalised like stored rows) for every point: the exact assignment of
+        ``Gallery.kmeans(max_iter=0)``.  Returns ``(labels [len] int32, scores [len] fp32)`` device tensors, label -1 and
+        score -inf for a point ``query_filter`` leaves out -- what ``search(k=1)`` over a gallery of ``vectors`` gives for
+        each stored row, ties to the lowest index."""
+        dev = self.gallery.device
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        c = torch.as_tensor(vectors, dtype=torch.float32).to(dev)
+        _, labels, scores, _, _, _ = self.gallery.kmeans(c, max_iter=0, normalize=True, allow=allow)
+        return labels, scores
+
     # -- persistence ----------------------------------------------------------
     def flush(self, path=None):
         """Write the rows (and finished source files) added since the last flush as one delta shard.  Returns the rows written."""

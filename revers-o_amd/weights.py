@@ -11,7 +11,7 @@ from dataclasses import replace
 
 import torch
 
-from .config import PEConfig
+from .config import PEConfig, PETextConfig
 
 
 def expected_shapes(cfg: PEConfig):
@@ -136,6 +136,142 @@ def resolve_config(cfg: PEConfig, sd) -> PEConfig:
 def strip_non_parameters(sd):
     """The state dict without the known non-parameter buffers (see _NON_PARAMETER)."""
     return {k: v for k, v in sd.items() if not _NON_PARAMETER.search(k)}
+
+
+# ------------------------------------------------------------------ text tower ----
+# [UPSTREAM-RECALL] the text transformer's tensors sit at the top level of the CLIP state dict (upstream `CLIP` subclasses the
+# text transformer) -- or under `text.`; which one is detected by where `token_embedding.weight` is.
+# top-level entries of a CLIP state dict that are not the text tower's arithmetic
+_TEXT_NON_PARAMETER = re.compile(r"^(attn_mask|logit_scale|logit_bias)$|\.num_batches_tracked$")
+_TEXT_LS = re.compile(r"^transformer\.resblocks\.(\d+)\.ls_([12])\.gamma$")
+
+
+def expected_text_shapes(cfg: PETextConfig):
+    W, M, D = cfg.width, cfg.mlp_dim, cfg.out_dim
+    sh = {
+        "token_embedding.weight": (cfg.vocab_size, W),
+        "positional_embedding": (cfg.context_length, W),
+        "ln_final.weight": (W,), "ln_final.bias": (W,),
+        "text_projection": (W, D),
+    }
+    for i in range(cfg.layers):
+        p = f"transformer.resblocks.{i}."
+        sh.update({
+            p + "ln_1.weight": (W,), p + "ln_1.bias": (W,),
+            p + "ln_2.weight": (W,), p + "ln_2.bias": (W,),
+            p + "attn.in_proj_weight": (3 * W, W), p + "attn.in_proj_bias": (3 * W,),
+            p + "attn.out_proj.weight": (W, W), p + "attn.out_proj.bias": (W,),
+            p + "mlp.c_fc.weight": (M, W), p + "mlp.c_fc.bias": (M,),
+            p + "mlp.c_proj.weight": (W, M), p + "mlp.c_proj.bias": (W,),
+        })
+        if cfg.use_ls:
+            sh[p + "ls_1.gamma"] = (W,)
+            sh[p + "ls_2.gamma"] = (W,)
+    return sh
+
+
+def synth_text_weights(cfg: PETextConfig, seed: int = 0, device="cpu", randomize_affine: bool = False):
+    """Seeded random-init weights of the text tower (fp32, names without a prefix), by the rules of
+    :func:`synth_weights`; the token table is ``N(0, 0.02^2)``, positions ``N(0, 0.01^2)``, the projection ``N(0, 1/W)``."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    W = cfg.width
+    out = {}
+    for name, shape in expected_text_shapes(cfg).items():
+        leaf = name.rsplit(".", 1)[-1]
+        is_ln = "ln_" in name
+        if is_ln and leaf == "weight":
+            t = torch.ones(shape)
+            if randomize_affine:
+                t = t + 0.1 * torch.randn(shape, generator=g)
+        elif is_ln and leaf == "bias":
+            t = torch.zeros(shape)
+            if randomize_affine:
+                t = 0.1 * torch.randn(shape, generator=g)
+        elif leaf in ("bias", "in_proj_bias"):
+            t = torch.zeros(shape)
+            if randomize_affine:
+                t = 0.02 * torch.randn(shape, generator=g)
+        elif leaf == "gamma":
+            t = torch.full(shape, 0.5)
+            if randomize_affine:
+                t = t + 0.1 * torch.randn(shape, generator=g)
+        elif name == "text_projection":
+            t = torch.randn(shape, generator=g) * (W ** -0.5)
+        elif name == "positional_embedding":
+            t = torch.randn(shape, generator=g) * 0.01
+        else:
+            t = torch.randn(shape, generator=g) * 0.02
+        out[name] = t.to(device)
+    return out
+
+
+def text_state_dict(sd):
+    """The text tower's tensors of a CLIP state dict, names without a prefix: the non-``visual.`` entries, taken from
+    under ``text.`` when ``text.token_embedding.weight`` is there and from the top level otherwise, without the known
+    non-parameters (``attn_mask``, ``logit_scale`` ...)."""
+    if "text.token_embedding.weight" in sd:
+        sd = {k[len("text."):]: v for k, v in sd.items() if k.startswith("text.")}
+    elif "token_embedding.weight" in sd:
+        sd = {k: v for k, v in sd.items() if not k.startswith(("visual.", "text."))}
+    else:
+        raise KeyError("checkpoint has no text tower: neither token_embedding.weight nor text.token_embedding.weight")
+    return {k: v.float() for k, v in sd.items() if not _TEXT_NON_PARAMETER.search(k)}
+
+
+def load_text_state_dict(path: str):
+    """Load a user-supplied checkpoint (safetensors or torch) and keep the text tower (:func:`text_state_dict`)."""
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        sd = load_file(path)
+    else:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if "state_dict" in sd:
+            sd = sd["state_dict"]
+    return text_state_dict(sd)
+
+
+def resolve_text_config(sd, name="text", ln_eps=1e-5) -> PETextConfig:
+    """The text tower's config from the shapes of its tensors (names without a prefix): context, vocabulary, width, layers,
+    MLP width and output width; heads = width / 64 (every known variant, and all the kernel takes); LayerScale on iff the
+    checkpoint carries ``ls_*`` gains -- for every block, or it is rejected."""
+    for k in ("token_embedding.weight", "positional_embedding", "text_projection"):
+        if k not in sd:
+            raise KeyError(f"checkpoint lacks {k}: not a text tower")
+    vocab, W = (int(v) for v in sd["token_embedding.weight"].shape)
+    ctx = int(sd["positional_embedding"].shape[0])
+    D = int(sd["text_projection"].shape[-1])
+    blocks = sorted({int(m.group(1)) for m in (re.match(r"^transformer\.resblocks\.(\d+)\.", k) for k in sd) if m})
+    if not blocks or blocks != list(range(len(blocks))):
+        raise KeyError(f"checkpoint's transformer.resblocks are not numbered 0..n-1: {blocks[:8]}")
+    L = len(blocks)
+    fc = "transformer.resblocks.0.mlp.c_fc.weight"
+    if fc not in sd:
+        raise KeyError(f"checkpoint lacks {fc}")
+    M = int(sd[fc].shape[0])
+    if W % 64:
+        raise ValueError(f"text tower width {W} is not a multiple of 64 (heads = width / 64)")
+    have = sorted((int(m.group(1)), int(m.group(2))) for m in map(_TEXT_LS.match, sd) if m)
+    want = [(i, j) for i in range(L) for j in (1, 2)]
+    if have and have != want:
+        lacking = sorted(set(want) - set(have))
+        raise KeyError(f"checkpoint has LayerScale tensors for {len(have)} of {len(want)} places"
+                       + (f": lacks ls_{lacking[0][1]}.gamma of block {lacking[0][0]}" if lacking else ""))
+    return PETextConfig(name, ctx, vocab, W, L, W // 64, M, D, use_ls=bool(have), ln_eps=ln_eps)
+
+
+def check_text_state_dict(cfg: PETextConfig, sd):
+    """Every tensor the text tower needs, with its shape, and NOTHING else (``sd``: names without a prefix)."""
+    exp = expected_text_shapes(cfg)
+    missing = [k for k in exp if k not in sd]
+    if missing:
+        raise KeyError(f"checkpoint lacks {len(missing)} text tensors, e.g. {missing[:3]}")
+    unexpected = [k for k in sd if k not in exp and not _TEXT_NON_PARAMETER.search(k)]
+    if unexpected:
+        raise KeyError(f"checkpoint has {len(unexpected)} tensors the text tower {cfg.name} does not use, e.g. "
+                       f"{sorted(unexpected)[:3]}: refusing to ignore them (a tensor the forward skips is a different model)")
+    for k, shp in exp.items():
+        if tuple(sd[k].shape) != tuple(shp):
+            raise ValueError(f"{k}: expected {shp}, got {tuple(sd[k].shape)}")
 
 
 def check_state_dict(cfg: PEConfig, sd):
