@@ -1,5 +1,5 @@
 // The text tower of the CLIP checkpoint (include/revo.h, TEXT): its three kernels -- token embedding,
-// causal attention, end-of-text pooling -- its handle and its forward.  The blocks are the image tower's (api_internal.h
+// causal attention, end-of-text pooling -- its handle and its forward.  The blocks are the image tower's (tower.h
 // body_blocks) with a plain bf16 qkv epilogue and the causal attention below; the head (ln_final on the pooled rows, the
 // projection, the normalisation) is fp32 like the image tower's.
 #include <algorithm>
@@ -10,8 +10,8 @@
 #include <vector>
 
 #include "../../include/revo.h"
-#include "api_internal.h"
 #include "kernels.h"
+#include "tower.h"
 
 namespace revo {
 
@@ -193,33 +193,15 @@ int launch_attention_causal(const bf16_t* qkv, long ld, bf16_t* out, long ldo, i
 }  // namespace revo
 
 // ------------------------------------------------------------- the handle ----
-struct revo_text {
+// (the blocks' weights, the body workspace, the allocations and their release: tower.h TowerCore)
+struct revo_text : TowerCore {
     revo_text_cfg cfg;
-    int device = 0, max_batch = 0, debug_layers = -1, last_seq = 0;
-    std::vector<void*> owned;
+    int last_seq = 0;
     float *tok_emb = nullptr, *pos = nullptr, *lnf_w = nullptr, *lnf_b = nullptr, *w_projT = nullptr;
-    std::vector<LayerW> layers;
-    // workspace for max_batch prompts of context_length positions
+    // workspace for max_batch prompts of context_length positions, beside the body's
     int32_t* tokens = nullptr;         // device copy of the call's ids
-    float *x = nullptr, *pooled = nullptr, *pooled_n = nullptr, *feat = nullptr, *splitk_ws = nullptr;
-    bf16_t *h = nullptr, *qkv = nullptr, *att = nullptr, *mlp = nullptr, *xlo = nullptr;
-    float2* ln_stats = nullptr; int ln_parts = 0;
-    unsigned long long* ln_tele = nullptr;
-    // the ids reach the device through this pinned buffer (tok_ev: the last copy out of it)
-    int32_t* tok_pin = nullptr; hipEvent_t tok_ev = nullptr; bool tok_ev_pending = false;
-
-    template <class T> int dalloc(T** out, size_t count) {
-        void* p = nullptr;
-        REVO_HIP_CHECK(hipMalloc(&p, count * sizeof(T) + 256));
-        owned.push_back(p);
-        *out = (T*)p;
-        return 0;
-    }
-    ~revo_text() {
-        for (void* p : owned) (void)hipFree(p);
-        if (tok_pin) (void)hipHostFree(tok_pin);
-        if (tok_ev) (void)hipEventDestroy(tok_ev);
-    }
+    float *pooled = nullptr, *pooled_n = nullptr, *feat = nullptr;
+    PinnedStage tok_pin;               // the ids reach the device through this pinned buffer
 };
 
 extern "C" int32_t revo_text_create(const revo_text_cfg* cfg, const revo_tensor* weights, int32_t n_weights, int32_t device,
@@ -237,102 +219,38 @@ extern "C" int32_t revo_text_create(const revo_text_cfg* cfg, const revo_tensor*
     REVO_REQUIRE((long)max_batch * c.context_length < (1l << 24), "text_create: max_batch * context_length too large");
     std::unique_ptr<revo_text> v(new revo_text());
     v->cfg = c; v->device = device; v->max_batch = max_batch;
+    v->W = c.width; v->Md = c.mlp_dim; v->ln_eps = c.ln_eps;
     const int W = c.width, M = c.mlp_dim, D = c.out_dim, S = c.context_length;
 
-    // the checkpoint is validated as a whole before the device is touched (as revo_vit_create does)
+    // the checkpoint is validated as a whole before the device is touched (tower.h check_checkpoint)
+    const std::string blocks = "transformer.resblocks.";
     WeightMap wm;
-    for (int i = 0; i < n_weights; ++i) {
-        REVO_REQUIRE(weights[i].name && weights[i].data, "text_create: weight entry with a null name or data pointer");
-        wm.m[weights[i].name] = &weights[i];
-    }
+    CHECK_RC(wm.fill("text_create", weights, n_weights));
     {
-        std::vector<std::pair<std::string, int64_t>> need = {
+        NeedList need = {
             {"token_embedding.weight", (int64_t)c.vocab_size * W}, {"positional_embedding", (int64_t)S * W},
             {"ln_final.weight", W}, {"ln_final.bias", W}, {"text_projection", (int64_t)W * D}};
-        for (int i = 0; i < c.layers; ++i) {
-            const std::string p = "transformer.resblocks." + std::to_string(i) + ".";
-            for (const char* n : {"ln_1.weight", "ln_1.bias", "ln_2.weight", "ln_2.bias", "attn.out_proj.bias", "mlp.c_proj.bias"})
-                need.push_back({p + n, W});
-            need.push_back({p + "attn.in_proj_weight", (int64_t)3 * W * W});
-            need.push_back({p + "attn.in_proj_bias", 3 * W});
-            need.push_back({p + "attn.out_proj.weight", (int64_t)W * W});
-            need.push_back({p + "mlp.c_fc.weight", (int64_t)M * W});
-            need.push_back({p + "mlp.c_fc.bias", M});
-            need.push_back({p + "mlp.c_proj.weight", (int64_t)W * M});
-            if (c.use_ls) { need.push_back({p + "ls_1.gamma", W}); need.push_back({p + "ls_2.gamma", W}); }
-        }
-        for (auto& kv : need)
-            if (!wm.get(kv.first, kv.second)) return -2;
-        if (wm.m.size() != need.size()) {
-            std::map<std::string, int64_t> want(need.begin(), need.end());
-            for (auto& kv : wm.m)
-                if (!want.count(kv.first)) {
-                    revo_set_error("unexpected weight tensor: " + kv.first + " (not read by the text tower" +
-                                   (c.use_ls ? ")" : "; LayerScale needs cfg.use_ls = 1)"));
-                    return -2;
-                }
-        }
+        need_blocks(need, blocks, c.layers, W, M, c.use_ls);
+        CHECK_RC(check_checkpoint(wm, need, "the text tower", c.use_ls));
     }
     REVO_ON_DEVICE(device);
 
-    size_t stage_elems = (size_t)std::max({(long)3 * W * W, (long)M * W, (long)W * D});
-    float* stage = nullptr;
-    REVO_HIP_CHECK(hipMalloc((void**)&stage, stage_elems * 4));
-    struct StageGuard { float* p; ~StageGuard() { (void)hipFree(p); } } sg{stage};
-    float* gb = nullptr;               // gain | shift | bias of the layer being folded
-    REVO_HIP_CHECK(hipMalloc((void**)&gb, (size_t)(2 * W + std::max(3 * W, M)) * 4));
-    StageGuard sg2{gb};
-
-    const revo_tensor* t;
+    Staging sg;
+    CHECK_RC(sg.alloc(W, M, (long)W * D));
     CHECK_RC(up_f32(v.get(), wm, "token_embedding.weight", (int64_t)c.vocab_size * W, &v->tok_emb));
     CHECK_RC(up_f32(v.get(), wm, "positional_embedding", (int64_t)S * W, &v->pos));
     CHECK_RC(up_f32(v.get(), wm, "ln_final.weight", W, &v->lnf_w));
     CHECK_RC(up_f32(v.get(), wm, "ln_final.bias", W, &v->lnf_b));
-    v->layers.resize(c.layers);
-    for (int i = 0; i < c.layers; ++i) {
-        const std::string p = "transformer.resblocks." + std::to_string(i) + ".";
-        LayerW& L = v->layers[i];
-        memset(&L, 0, sizeof(L));
-        CHECK_RC(up_folded(v.get(), wm, stage, gb, p + "attn.in_proj_weight", p + "attn.in_proj_bias", p + "ln_1", 3 * W, W,
-                           &L.w_qkv, &L.c_qkv, &L.b_qkv));
-        if (!(t = wm.get(p + "attn.out_proj.weight", (int64_t)W * W))) return -2;
-        CHECK_RC(up_bf16(v.get(), stage, t->data, W, W, W, &L.w_o));
-        CHECK_RC(up_f32(v.get(), wm, p + "attn.out_proj.bias", W, &L.b_o));
-        CHECK_RC(up_folded(v.get(), wm, stage, gb, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", p + "ln_2", M, W,
-                           &L.w_fc1, &L.c_fc1, &L.b_fc1));
-        if (!(t = wm.get(p + "mlp.c_proj.weight", (int64_t)W * M))) return -2;
-        CHECK_RC(up_bf16(v.get(), stage, t->data, W, M, M, &L.w_fc2));
-        CHECK_RC(up_f32(v.get(), wm, p + "mlp.c_proj.bias", W, &L.b_fc2));
-        if (c.use_ls) {
-            CHECK_RC(up_f32(v.get(), wm, p + "ls_1.gamma", W, &L.ls1));
-            CHECK_RC(up_f32(v.get(), wm, p + "ls_2.gamma", W, &L.ls2));
-        }
-    }
-    // text_projection is stored [W][D]; the fp32 GEMM wants [D][W]
-    if (!(t = wm.get("text_projection", (int64_t)W * D))) return -2;
-    CHECK_RC(v->dalloc(&v->w_projT, (size_t)D * W));
-    REVO_HIP_CHECK(hipMemcpy(stage, t->data, (size_t)W * D * 4, hipMemcpyDefault));
-    CHECK_RC(revo::launch_transpose_f32(stage, W, D, v->w_projT, 0));
-    REVO_HIP_CHECK(hipStreamSynchronize(0));
+    CHECK_RC(upload_blocks(v.get(), wm, sg, blocks, c.layers, c.use_ls));
+    CHECK_RC(upload_projT(v.get(), wm, sg, "text_projection", D, &v->w_projT));
 
     const size_t rows = (size_t)max_batch * S, B = (size_t)max_batch;
     CHECK_RC(v->dalloc(&v->tokens, rows));
-    CHECK_RC(v->dalloc(&v->x, rows * W));
-    CHECK_RC(v->dalloc(&v->h, rows * W));
-    CHECK_RC(v->dalloc(&v->qkv, rows * 3 * W));
-    CHECK_RC(v->dalloc(&v->att, rows * W));
-    CHECK_RC(v->dalloc(&v->mlp, rows * M));
+    CHECK_RC(alloc_body(v.get(), rows));
     CHECK_RC(v->dalloc(&v->pooled, B * W));
     CHECK_RC(v->dalloc(&v->pooled_n, B * W));
     CHECK_RC(v->dalloc(&v->feat, B * D));
-    CHECK_RC(v->dalloc(&v->splitk_ws, SPLITK_WS_ELEMS));
-    v->ln_parts = (W % 256 == 0 && W / 256 <= 6) ? W / 256 : 0;
-    if (v->ln_parts) CHECK_RC(v->dalloc(&v->ln_stats, rows * (size_t)v->ln_parts));
-    if (v->ln_parts) CHECK_RC(v->dalloc(&v->xlo, rows * W));
-    CHECK_RC(v->dalloc(&v->ln_tele, 4));
-    REVO_HIP_CHECK(hipMemset(v->ln_tele, 0, 4 * sizeof(unsigned long long)));
-    REVO_HIP_CHECK(hipHostMalloc((void**)&v->tok_pin, rows * 4, hipHostMallocDefault));
-    REVO_HIP_CHECK(hipEventCreateWithFlags(&v->tok_ev, hipEventDisableTiming));
+    CHECK_RC(v->tok_pin.alloc(rows * 4));
     REVO_HIP_CHECK(hipDeviceSynchronize());
     *out = v.release();
     return 0;
@@ -383,30 +301,23 @@ extern "C" int32_t revo_text_forward(revo_text* v, const int32_t* tokens, int32_
     REVO_ON_DEVICE(v->device);
     hipStream_t st = (hipStream_t)stream;
     using namespace revo;
-    const int W = c.width, Md = c.mlp_dim, D = c.out_dim, B = batch, S = seq_len, rows = B * S;
+    const int W = c.width, D = c.out_dim, B = batch, S = seq_len, rows = B * S;
     // the ids go through the pinned buffer: the caller's array is read before the call returns
-    if (v->tok_ev_pending) REVO_HIP_CHECK(hipEventSynchronize(v->tok_ev));     // the previous copy out of it
-    memcpy(v->tok_pin, tokens, (size_t)rows * 4);
-    REVO_HIP_CHECK(hipMemcpyAsync(v->tokens, v->tok_pin, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-    REVO_HIP_CHECK(hipEventRecord(v->tok_ev, st));
-    v->tok_ev_pending = true;
+    CHECK_RC(v->tok_pin.wait());
+    memcpy(v->tok_pin.p, tokens, (size_t)rows * 4);
+    REVO_HIP_CHECK(hipMemcpyAsync(v->tokens, v->tok_pin.p, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    CHECK_RC(v->tok_pin.record(st));
     v->last_seq = S;
 
     { ProfScope ps("embed_tokens", st);
       CHECK_RC(launch_embed_tokens(v->tokens, v->tok_emb, v->pos, B, S, c.vocab_size, W, v->x, W, st)); }
     if (v->debug_layers == -2) return 0;   // parity hook: the embedded rows
 
-    // the image tower's blocks (api_internal.h body_blocks) with a plain bf16 qkv epilogue and the causal attention; block 0
+    // the image tower's blocks (tower.h body_blocks) with a plain bf16 qkv epilogue and the causal attention; block 0
     // has no ln_pre in front of it: its ln_1 normalises the embedded rows
-    BodyCtx bc{};
-    bc.who = "text_forward"; bc.layers = &v->layers;
-    bc.nl = v->debug_layers < 0 ? c.layers : std::min(v->debug_layers, c.layers);
-    bc.W = W; bc.Md = Md; bc.rows = rows; bc.eps = c.ln_eps;
-    bc.x = v->x; bc.h = v->h; bc.qkv = v->qkv; bc.att = v->att; bc.mlp = v->mlp; bc.xlo = v->xlo;
-    bc.stats = v->ln_parts ? v->ln_stats : nullptr; bc.ln_parts = v->ln_parts; bc.ln_tele = v->ln_tele;
-    bc.splitk_ws = v->splitk_ws;
     CHECK_RC(body_blocks(
-        bc, st, [&](GemmArgs&) { return (int)EPI_BF16; },
+        *v, "text_forward", rows, v->debug_layers < 0 ? c.layers : std::min(v->debug_layers, c.layers), st,
+        [&](GemmArgs&) { return (int)EPI_BF16; },
         [&]() { return launch_attention_causal(v->qkv, 3 * W, v->att, W, B, S, c.heads, 64, st); }));
     if (v->debug_layers >= 0) return 0;    // parity hook: residual stream only
 

@@ -36,8 +36,45 @@ def _as_device(device):
     return torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
 
 
-class VitEngine:
+def _tensor_array(state_dict, names):
+    """The ``revo_tensor`` array of ``names`` for a create call, and the fp32 tensors it points into (keep them alive until
+    the call returns)."""
+    keep = []
+    arr = (_lib.Tensor * len(names))()
+    for i, n in enumerate(names):
+        t = state_dict[n].detach().to(torch.float32).contiguous()
+        keep.append(t)
+        arr[i].name = n.encode()
+        arr[i].data = t.data_ptr()
+        arr[i].numel = t.numel()
+    return arr, keep
+
+
+class _Handle:
+    """A handle of the library held by ``self._h`` in ``self._lib``, destroyed by the entry point ``_destroy`` names."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _need_hooks(engine, what):
+    if not engine.experiments:
+        raise _lib.RevoError(f"{what} is a parity-test hook of librevo_exp.so: create the engine with experiments=True")
+
+
+class VitEngine(_Handle):
     """A PE vision tower resident on one GPU (weights bf16, fp32 residual stream)."""
+
+    _destroy = "revo_vit_destroy"
 
     def __init__(self, cfg: PEConfig, state_dict, device=0, max_batch=64, experiments=False):
         # LayerScale follows the checkpoint (SURVEY.md 8(a)); unknown `visual.*` tensors are rejected by name
@@ -54,14 +91,7 @@ class VitEngine:
         # the image tower only (a whole-CLIP state dict also holds the text tower), without registered buffers
         state_dict = strip_non_parameters({k: v for k, v in state_dict.items() if k.startswith("visual.")})
         names = sorted(state_dict)
-        keep = []          # keep converted tensors alive until create returns
-        arr = (_lib.Tensor * len(names))()
-        for i, n in enumerate(names):
-            t = state_dict[n].detach().to(torch.float32).contiguous()
-            keep.append(t)
-            arr[i].name = n.encode()
-            arr[i].data = t.data_ptr()
-            arr[i].numel = t.numel()
+        arr, keep = _tensor_array(state_dict, names)          # keep: alive until create returns
         c = _lib.VitCfg(cfg.image_size, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.mlp_dim, cfg.out_dim,
                         cfg.pool_heads, int(cfg.use_cls), int(cfg.use_ls), cfg.ln_eps, cfg.rope_theta, cfg.pool_mlp_dim)
         h = C.c_void_p()
@@ -79,20 +109,19 @@ class VitEngine:
         sd = synth_weights(cfg, seed=seed, device=dev, **kw)
         return cls(cfg, sd, device=device, max_batch=max_batch, experiments=experiments)
 
-    def _need_hooks(self, what):
-        if not self.experiments:
-            raise _lib.RevoError(f"{what} is a parity-test hook of librevo_exp.so: create the engine with experiments=True")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.revo_vit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _images(self, images):
+        """``images`` validated for a forward: contiguous, and its ``image_dtype``."""
+        _require_cuda(images, "images", self.device)
+        n = self.cfg.image_size
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != n or images.shape[3] != n:
+            raise ValueError(f"images must be [B,3,{n},{n}], got {tuple(images.shape)}")
+        if images.dtype == torch.uint8:
+            kind = IMAGE_U8
+        elif images.dtype == torch.float32:
+            kind = IMAGE_F32
+        else:
+            raise ValueError("images must be uint8 or float32")
+        return images.contiguous(), kind
 
     # -- the embed entry point ------------------------------------------------
     def embed(self, images, normalize=True, out=None):
@@ -100,17 +129,8 @@ class VitEngine:
         resolution (float input already normalised to [-1,1], i.e. what
         ``self.preprocess`` yields at core_system.py:439).  Returns fp32
         ``[B, out_dim]`` on the device, L2-normalised (core_system.py:447)."""
-        _require_cuda(images, "images", self.device)
+        images, kind = self._images(images)
         cfg = self.cfg
-        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != cfg.image_size or images.shape[3] != cfg.image_size:
-            raise ValueError(f"images must be [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(images.shape)}")
-        if images.dtype == torch.uint8:
-            kind = IMAGE_U8
-        elif images.dtype == torch.float32:
-            kind = IMAGE_F32
-        else:
-            raise ValueError("images must be uint8 or float32")
-        images = images.contiguous()
         B = images.shape[0]
         if out is None:
             out = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device)
@@ -131,17 +151,8 @@ class VitEngine:
         its image's global vector bit for bit, one that allows none is all zeros.  Batches above ``max_batch`` are split
         and every region goes with its image."""
         import numpy as np
-        _require_cuda(images, "images", self.device)
+        images, kind = self._images(images)
         cfg = self.cfg
-        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != cfg.image_size or images.shape[3] != cfg.image_size:
-            raise ValueError(f"images must be [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(images.shape)}")
-        if images.dtype == torch.uint8:
-            kind = IMAGE_U8
-        elif images.dtype == torch.float32:
-            kind = IMAGE_F32
-        else:
-            raise ValueError("images must be uint8 or float32")
-        images = images.contiguous()
         B, words = images.shape[0], (cfg.seq + 31) // 32
         ri = torch.as_tensor(np.asarray(region_image.cpu() if isinstance(region_image, torch.Tensor) else region_image,
                                         dtype=np.int64).reshape(-1))
@@ -196,19 +207,18 @@ class VitEngine:
     # -- parity-test hook -----------------------------------------------------
     def residual_after(self, images, n_layers):
         """fp32 residual stream [B, S, W] after ln_pre and the first n blocks."""
-        self._need_hooks("residual_after")
-        _require_cuda(images, "images", self.device)
+        _need_hooks(self, "residual_after")
+        images, kind = self._images(images)
         B = images.shape[0]
         assert B <= self.max_batch
-        kind = IMAGE_U8 if images.dtype == torch.uint8 else IMAGE_F32
         x = torch.empty((B, self.cfg.seq, self.cfg.width), dtype=torch.float32, device=images.device)
         dummy = torch.empty((B, self.cfg.out_dim), dtype=torch.float32, device=images.device)
         with self._lock, torch.cuda.device(self.device):
             st = _lib.current_stream()
             _lib.check(self._lib.revo_vit_set_debug_layers(self._h, int(n_layers)))
             try:
-                _lib.check(self._lib.revo_vit_forward(self._h, _lib.ptr(images.contiguous()), kind, B, _lib.ptr(dummy),
-                                                      0, st), "revo_vit_forward")
+                _lib.check(self._lib.revo_vit_forward(self._h, _lib.ptr(images), kind, B, _lib.ptr(dummy), 0, st),
+                           "revo_vit_forward")
                 _lib.check(self._lib.revo_vit_read_residual(self._h, B, _lib.ptr(x), st))
             finally:
                 self._lib.revo_vit_set_debug_layers(self._h, -1)
@@ -219,7 +229,7 @@ class VitEngine:
         """Parity-test hook: intermediate activations of one forward as fp32 CPU-comparable tensors:
         ``embed`` [B,S,W] (patch embed + position + class token, before ln_pre), ``ln_post`` [B,S,W] (fp32: the head
         works in fp32), ``pooled`` [B,W] (attention-pool output before proj) and the ``embedding`` [B,D]."""
-        self._need_hooks("taps")
+        _need_hooks(self, "taps")
         _require_cuda(images, "images", self.device)
         B = images.shape[0]
         assert B <= self.max_batch
@@ -236,10 +246,12 @@ class VitEngine:
         return out
 
 
-class TextEngine:
+class TextEngine(_Handle):
     """The text tower of the same CLIP checkpoint resident on one GPU (include/revo.h, TEXT): prompts -> vectors in the
     image embeddings' space.  ``state_dict``: the tower's tensors under their upstream names without a prefix
     (``weights.load_text_state_dict`` / ``weights.text_state_dict``)."""
+
+    _destroy = "revo_text_destroy"
 
     def __init__(self, cfg: PETextConfig, state_dict, device=0, max_batch=256, experiments=False, tokenizer=None):
         self.cfg = cfg
@@ -251,14 +263,7 @@ class TextEngine:
         lib = _lib.load_exp() if experiments else _lib.load()
         check_text_state_dict(cfg, state_dict)
         names = sorted(k for k in state_dict if k in expected_text_shapes(cfg))
-        keep = []          # keep converted tensors alive until create returns
-        arr = (_lib.Tensor * len(names))()
-        for i, n in enumerate(names):
-            t = state_dict[n].detach().to(torch.float32).contiguous()
-            keep.append(t)
-            arr[i].name = n.encode()
-            arr[i].data = t.data_ptr()
-            arr[i].numel = t.numel()
+        arr, keep = _tensor_array(state_dict, names)          # keep: alive until create returns
         c = _lib.TextCfg(cfg.context_length, cfg.vocab_size, cfg.width, cfg.layers, cfg.heads, cfg.mlp_dim, cfg.out_dim,
                          int(cfg.use_ls), cfg.ln_eps)
         h = C.c_void_p()
@@ -274,17 +279,6 @@ class TextEngine:
         cfg = name_or_cfg if isinstance(name_or_cfg, PETextConfig) else get_text_config(name_or_cfg)
         sd = synth_text_weights(cfg, seed=seed, device=torch.device("cuda", device), **kw)
         return cls(cfg, sd, device=device, max_batch=max_batch, experiments=experiments, tokenizer=tokenizer)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.revo_text_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _host_tokens(tokens):
@@ -333,8 +327,7 @@ class TextEngine:
     # -- parity-test hook -----------------------------------------------------
     def residual_after(self, tokens, n_layers):
         """fp32 residual stream [n, seq_len, W] after the first n blocks (-2: the embedded tokens)."""
-        if not self.experiments:
-            raise _lib.RevoError("residual_after is a parity-test hook of librevo_exp.so: create the engine with experiments=True")
+        _need_hooks(self, "residual_after")
         t = self._host_tokens(tokens)
         n, L = t.shape
         assert 1 <= n <= self.max_batch
@@ -352,9 +345,11 @@ class TextEngine:
         return x
 
 
-class Gallery:
+class Gallery(_Handle):
     """Device-resident cosine gallery: normalised rows as bf16 (scan copy) plus an
     fp32 master copy used for exact re-scoring and persistence."""
+
+    _destroy = "revo_gallery_destroy"
 
     def __init__(self, dim, capacity, device=0, keep_f32=True, experiments=False):
         self.dim = int(dim)
@@ -371,17 +366,6 @@ class Gallery:
             _lib.check(self._lib.revo_gallery_create(self.dim, self.capacity, self.device.index or 0, int(keep_f32),
                                                      C.byref(h)), "revo_gallery_create")
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.revo_gallery_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return int(self._lib.revo_gallery_size(self._h))

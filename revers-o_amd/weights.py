@@ -14,8 +14,28 @@ import torch
 from .config import PEConfig, PETextConfig
 
 
+def _block_shapes(prefix, cfg):
+    """The transformer blocks of either tower (``prefix``: up to the block's number), in checkpoint order."""
+    W, M = cfg.width, cfg.mlp_dim
+    sh = {}
+    for i in range(cfg.layers):
+        p = f"{prefix}{i}."
+        sh.update({
+            p + "ln_1.weight": (W,), p + "ln_1.bias": (W,),
+            p + "ln_2.weight": (W,), p + "ln_2.bias": (W,),
+            p + "attn.in_proj_weight": (3 * W, W), p + "attn.in_proj_bias": (3 * W,),
+            p + "attn.out_proj.weight": (W, W), p + "attn.out_proj.bias": (W,),
+            p + "mlp.c_fc.weight": (M, W), p + "mlp.c_fc.bias": (M,),
+            p + "mlp.c_proj.weight": (W, M), p + "mlp.c_proj.bias": (W,),
+        })
+        if cfg.use_ls:
+            sh[p + "ls_1.gamma"] = (W,)
+            sh[p + "ls_2.gamma"] = (W,)
+    return sh
+
+
 def expected_shapes(cfg: PEConfig):
-    W, M, D, P, S = cfg.width, cfg.mlp_dim, cfg.out_dim, cfg.patch_size, cfg.seq
+    W, D, P, S = cfg.width, cfg.out_dim, cfg.patch_size, cfg.seq
     PM = cfg.pool_mlp_dim          # the pool head's own MLP width (4 * W upstream), not the tower's
     sh = {
         "visual.conv1.weight": (W, 3, P, P),
@@ -34,34 +54,16 @@ def expected_shapes(cfg: PEConfig):
     }
     if cfg.use_cls:
         sh["visual.class_embedding"] = (W,)
-    for i in range(cfg.layers):
-        p = f"visual.transformer.resblocks.{i}."
-        sh.update({
-            p + "ln_1.weight": (W,), p + "ln_1.bias": (W,),
-            p + "ln_2.weight": (W,), p + "ln_2.bias": (W,),
-            p + "attn.in_proj_weight": (3 * W, W), p + "attn.in_proj_bias": (3 * W,),
-            p + "attn.out_proj.weight": (W, W), p + "attn.out_proj.bias": (W,),
-            p + "mlp.c_fc.weight": (M, W), p + "mlp.c_fc.bias": (M,),
-            p + "mlp.c_proj.weight": (W, M), p + "mlp.c_proj.bias": (W,),
-        })
-        if cfg.use_ls:
-            sh[p + "ls_1.gamma"] = (W,)
-            sh[p + "ls_2.gamma"] = (W,)
+    sh.update(_block_shapes("visual.transformer.resblocks.", cfg))
     return sh
 
 
-def synth_weights(cfg: PEConfig, seed: int = 0, device="cpu", randomize_affine: bool = False):
-    """Seeded random-init weights of the variant's architecture (fp32).
-
-    ``N(0, 0.02^2)`` for linear/conv weights, LayerNorm gamma=1 beta=0, biases 0,
-    probe/cls/pos-emb/proj ``N(0, 1/W)`` (SURVEY.md §8(d)).  With
-    ``randomize_affine`` the LayerNorm affine terms, biases and LayerScale are
-    perturbed too so tests exercise every epilogue term.
-    """
+def _synth(shapes, std_of, seed, device, randomize_affine):
+    """One draw per tensor of ``shapes``, in its order, from one generator.  ``std_of``: the standard deviation of the leaves
+    (last name component) that are not ``N(0, 0.02^2)``."""
     g = torch.Generator(device="cpu").manual_seed(seed)
-    W = cfg.width
     out = {}
-    for name, shape in expected_shapes(cfg).items():
+    for name, shape in shapes.items():
         leaf = name.rsplit(".", 1)[-1]
         is_ln = ("ln_" in name or "layernorm" in name)
         if is_ln and leaf == "weight":
@@ -80,29 +82,42 @@ def synth_weights(cfg: PEConfig, seed: int = 0, device="cpu", randomize_affine: 
             t = torch.full(shape, 0.5)
             if randomize_affine:
                 t = t + 0.1 * torch.randn(shape, generator=g)
-        elif leaf in ("probe", "class_embedding", "positional_embedding", "proj"):
-            t = torch.randn(shape, generator=g) * (W ** -0.5)
         else:
-            t = torch.randn(shape, generator=g) * 0.02
+            t = torch.randn(shape, generator=g) * std_of.get(leaf, 0.02)
         out[name] = t.to(device)
     return out
+
+
+def synth_weights(cfg: PEConfig, seed: int = 0, device="cpu", randomize_affine: bool = False):
+    """Seeded random-init weights of the variant's architecture (fp32).
+
+    ``N(0, 0.02^2)`` for linear/conv weights, LayerNorm gamma=1 beta=0, biases 0,
+    probe/cls/pos-emb/proj ``N(0, 1/W)`` (SURVEY.md §8(d)).  With
+    ``randomize_affine`` the LayerNorm affine terms, biases and LayerScale are
+    perturbed too so tests exercise every epilogue term.
+    """
+    wide = cfg.width ** -0.5
+    return _synth(expected_shapes(cfg), dict(probe=wide, class_embedding=wide, positional_embedding=wide, proj=wide),
+                  seed, device, randomize_affine)
+
+
+def _read_checkpoint(path: str):
+    """The state dict of a user-supplied checkpoint file (safetensors or torch)."""
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path)
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    return sd["state_dict"] if "state_dict" in sd else sd
 
 
 def load_state_dict(path: str):
     """Load a user-supplied checkpoint (safetensors or torch) and keep the
     ``visual.*`` tensors as fp32 CPU tensors."""
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        sd = load_file(path)
-    else:
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if "state_dict" in sd:
-            sd = sd["state_dict"]
-    return {k: v.float() for k, v in sd.items() if k.startswith("visual.")}
+    return {k: v.float() for k, v in _read_checkpoint(path).items() if k.startswith("visual.")}
 
 
 # `visual.*` entries of a checkpoint that are not parameters of the arithmetic: buffers a module registers for values
-# this build derives itself (the rotary tables come from rope_theta and the grid, csrc/api.hip).  Anything else under
+# this build derives itself (the rotary tables come from rope_theta and the grid, csrc/vit.hip).  Anything else under
 # `visual.` that the architecture table does not name is an error, by name: a tensor the forward would silently ignore
 # is a different model (SURVEY.md 8(a): "LayerScale present only if the checkpoint has ls_* tensors").
 _NON_PARAMETER = re.compile(r"^visual\.(.*\.)?rope(\.\w+)*\.(freqs?|inv_freq|t_x|t_y|freqs_cis)$|\.num_batches_tracked$")
@@ -147,62 +162,22 @@ _TEXT_LS = re.compile(r"^transformer\.resblocks\.(\d+)\.ls_([12])\.gamma$")
 
 
 def expected_text_shapes(cfg: PETextConfig):
-    W, M, D = cfg.width, cfg.mlp_dim, cfg.out_dim
+    W, D = cfg.width, cfg.out_dim
     sh = {
         "token_embedding.weight": (cfg.vocab_size, W),
         "positional_embedding": (cfg.context_length, W),
         "ln_final.weight": (W,), "ln_final.bias": (W,),
         "text_projection": (W, D),
     }
-    for i in range(cfg.layers):
-        p = f"transformer.resblocks.{i}."
-        sh.update({
-            p + "ln_1.weight": (W,), p + "ln_1.bias": (W,),
-            p + "ln_2.weight": (W,), p + "ln_2.bias": (W,),
-            p + "attn.in_proj_weight": (3 * W, W), p + "attn.in_proj_bias": (3 * W,),
-            p + "attn.out_proj.weight": (W, W), p + "attn.out_proj.bias": (W,),
-            p + "mlp.c_fc.weight": (M, W), p + "mlp.c_fc.bias": (M,),
-            p + "mlp.c_proj.weight": (W, M), p + "mlp.c_proj.bias": (W,),
-        })
-        if cfg.use_ls:
-            sh[p + "ls_1.gamma"] = (W,)
-            sh[p + "ls_2.gamma"] = (W,)
+    sh.update(_block_shapes("transformer.resblocks.", cfg))
     return sh
 
 
 def synth_text_weights(cfg: PETextConfig, seed: int = 0, device="cpu", randomize_affine: bool = False):
     """Seeded random-init weights of the text tower (fp32, names without a prefix), by the rules of
     :func:`synth_weights`; the token table is ``N(0, 0.02^2)``, positions ``N(0, 0.01^2)``, the projection ``N(0, 1/W)``."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    W = cfg.width
-    out = {}
-    for name, shape in expected_text_shapes(cfg).items():
-        leaf = name.rsplit(".", 1)[-1]
-        is_ln = "ln_" in name
-        if is_ln and leaf == "weight":
-            t = torch.ones(shape)
-            if randomize_affine:
-                t = t + 0.1 * torch.randn(shape, generator=g)
-        elif is_ln and leaf == "bias":
-            t = torch.zeros(shape)
-            if randomize_affine:
-                t = 0.1 * torch.randn(shape, generator=g)
-        elif leaf in ("bias", "in_proj_bias"):
-            t = torch.zeros(shape)
-            if randomize_affine:
-                t = 0.02 * torch.randn(shape, generator=g)
-        elif leaf == "gamma":
-            t = torch.full(shape, 0.5)
-            if randomize_affine:
-                t = t + 0.1 * torch.randn(shape, generator=g)
-        elif name == "text_projection":
-            t = torch.randn(shape, generator=g) * (W ** -0.5)
-        elif name == "positional_embedding":
-            t = torch.randn(shape, generator=g) * 0.01
-        else:
-            t = torch.randn(shape, generator=g) * 0.02
-        out[name] = t.to(device)
-    return out
+    return _synth(expected_text_shapes(cfg), dict(text_projection=cfg.width ** -0.5, positional_embedding=0.01),
+                  seed, device, randomize_affine)
 
 
 def text_state_dict(sd):
@@ -220,14 +195,7 @@ def text_state_dict(sd):
 
 def load_text_state_dict(path: str):
     """Load a user-supplied checkpoint (safetensors or torch) and keep the text tower (:func:`text_state_dict`)."""
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        sd = load_file(path)
-    else:
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if "state_dict" in sd:
-            sd = sd["state_dict"]
-    return text_state_dict(sd)
+    return text_state_dict(_read_checkpoint(path))
 
 
 def resolve_text_config(sd, name="text", ln_eps=1e-5) -> PETextConfig:
@@ -259,33 +227,31 @@ def resolve_text_config(sd, name="text", ln_eps=1e-5) -> PETextConfig:
     return PETextConfig(name, ctx, vocab, W, L, W // 64, M, D, use_ls=bool(have), ln_eps=ln_eps)
 
 
-def check_text_state_dict(cfg: PETextConfig, sd):
-    """Every tensor the text tower needs, with its shape, and NOTHING else (``sd``: names without a prefix)."""
-    exp = expected_text_shapes(cfg)
+def _check_state_dict(exp, sd, unexpected, tensors, user):
+    """``sd`` holds every tensor of ``exp`` with its shape, and ``unexpected`` (the caller's: what of ``sd`` it may not
+    ignore) is empty.  ``tensors`` / ``user``: the towers' words in the messages."""
     missing = [k for k in exp if k not in sd]
     if missing:
-        raise KeyError(f"checkpoint lacks {len(missing)} text tensors, e.g. {missing[:3]}")
-    unexpected = [k for k in sd if k not in exp and not _TEXT_NON_PARAMETER.search(k)]
+        raise KeyError(f"checkpoint lacks {len(missing)} {tensors}, e.g. {missing[:3]}")
     if unexpected:
-        raise KeyError(f"checkpoint has {len(unexpected)} tensors the text tower {cfg.name} does not use, e.g. "
-                       f"{sorted(unexpected)[:3]}: refusing to ignore them (a tensor the forward skips is a different model)")
+        raise KeyError(f"checkpoint has {len(unexpected)} tensors {user} does not use, e.g. {sorted(unexpected)[:3]}: "
+                       "refusing to ignore them (a tensor the forward skips is a different model)")
     for k, shp in exp.items():
         if tuple(sd[k].shape) != tuple(shp):
             raise ValueError(f"{k}: expected {shp}, got {tuple(sd[k].shape)}")
+
+
+def check_text_state_dict(cfg: PETextConfig, sd):
+    """Every tensor the text tower needs, with its shape, and NOTHING else (``sd``: names without a prefix)."""
+    exp = expected_text_shapes(cfg)
+    _check_state_dict(exp, sd, [k for k in sd if k not in exp and not _TEXT_NON_PARAMETER.search(k)],
+                      "text tensors", f"the text tower {cfg.name}")
 
 
 def check_state_dict(cfg: PEConfig, sd):
     """Every tensor the architecture needs, with its shape, and NOTHING else under ``visual.``."""
     exp = expected_shapes(cfg)
-    missing = [k for k in exp if k not in sd]
-    if missing:
-        raise KeyError(f"checkpoint lacks {len(missing)} tensors, e.g. {missing[:3]}")
     # (only the image tower's namespace is this architecture's to judge: a whole-CLIP state dict also carries `text.*`,
     #  `logit_scale` ...; VitEngine hands the library the `visual.*` entries only)
-    unexpected = [k for k in sd if k.startswith("visual.") and k not in exp and not _NON_PARAMETER.search(k)]
-    if unexpected:
-        raise KeyError(f"checkpoint has {len(unexpected)} tensors {cfg.name} does not use, e.g. {sorted(unexpected)[:3]}: "
-                       "refusing to ignore them (a tensor the forward skips is a different model)")
-    for k, shp in exp.items():
-        if tuple(sd[k].shape) != tuple(shp):
-            raise ValueError(f"{k}: expected {shp}, got {tuple(sd[k].shape)}")
+    _check_state_dict(exp, sd, [k for k in sd if k.startswith("visual.") and k not in exp and not _NON_PARAMETER.search(k)],
+                      "tensors", cfg.name)

@@ -94,6 +94,24 @@ int main() {
         k.t[3].data = nullptr;
         EXPECT(revo_vit_create(&c, k.t.data(), (int)k.t.size(), 0, 4, &vit) == -2 && err_has("null name or data"));
     }
+    {   // a tensor the architecture does not read: refused by name
+        Ckpt k = tiny_ckpt(c, 4 * c.width);
+        k.add("text_projection", 8); k.finish();
+        EXPECT(revo_vit_create(&c, k.t.data(), (int)k.t.size(), 0, 4, &vit) == -2 && err_has("unexpected weight tensor: text_projection") &&
+               err_has("not read by this architecture"));
+    }
+    {   // LayerScale gains handed to a handle created with use_ls = 0: refused, with the hint
+        Ckpt k = tiny_ckpt(c, 4 * c.width);
+        for (int i = 0; i < c.layers; ++i)
+            for (const char* n : {".ls_1.gamma", ".ls_2.gamma"}) k.add("visual.transformer.resblocks." + std::to_string(i) + n, c.width);
+        k.finish();
+        EXPECT(revo_vit_create(&c, k.t.data(), (int)k.t.size(), 0, 4, &vit) == -2 &&
+               err_has("unexpected weight tensor: visual.transformer.resblocks.0.ls_1.gamma") && err_has("LayerScale needs cfg.use_ls = 1"));
+        revo_vit_cfg ls = c; ls.use_ls = 1;                        // the same checkpoint is what a use_ls = 1 handle needs
+        const int rc = revo_vit_create(&ls, k.t.data(), (int)k.t.size(), 0, 4, &vit);
+        EXPECT(rc == 0 || rc == -1);                                // passes validation; -1 = no device here
+        if (rc == 0) EXPECT(revo_vit_destroy(vit) == 0);
+    }
     {   // a valid checkpoint: without a GPU the create fails at the device, cleanly
         vit = nullptr;
         const int rc = revo_vit_create(&c, good.t.data(), (int)good.t.size(), 0, 4, &vit);
