@@ -18,14 +18,9 @@ What differs underneath:
 There is no CPU fallback: constructing the class without a GPU raises.
 """
 import dataclasses
-import json
 import os
-from datetime import datetime
 import shutil
 import threading
-import time
-import random
-import uuid
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -33,26 +28,18 @@ import torch
 from PIL import Image, ImageDraw, ImageFont
 
 from . import filters
+from . import ingest
 from . import preprocess as pp
 from . import regions as rg
 from . import store as st
 from .config import DEFAULT_VARIANT, TEXT_VARIANTS, available_configs, get_config, get_text_config
 from .engine import TextEngine, VitEngine
+from .ingest import BUILDING, uuid4 as _uuid4
 from .tokenizer import ClipTokenizer
 from .weights import load_state_dict, load_text_state_dict, resolve_text_config, synth_text_weights, synth_weights
 
 DB_ROOT = "./simple_reverso_db"
-IMAGE_EXTENSIONS = ['.jpg', '.jpeg', '.png', '.bmp', '.tiff', '.webp']
-BUILDING = ".building"      # suffix of the directory a collection is built in (renamed over the old one when complete)
 
-
-
-_uuid_rng = random.Random()   # ids only have to be unique (uuid4 format as upstream), not unpredictable
-
-
-def _uuid4():
-    """uuid.uuid4() without the os.urandom system call (35 us each, three per stored region)"""
-    return str(uuid.UUID(int=_uuid_rng.getrandbits(128), version=4))
 
 class Regions:
     """Minimal stand-in for ``supervision.Detections`` (xyxy, mask, confidence, class_id)."""
@@ -307,16 +294,9 @@ class SimpleReverso:
     # ----------------------------------------------------------------- embed --
     def _embed_pils(self, pils):
         """list of PIL images -> fp32 CPU tensor [n, D] (L2-normalised)."""
-        size = self.pe_model.cfg.image_size
-        if self.device_resize:
-            frames = [torch.from_numpy(np.array(pp.to_pil(im), dtype=np.uint8)).to(self.device, non_blocking=True)
-                      for im in pils]
-            with self._lock:
-                emb = self.pe_model.embed(pp.crop_resize_device(frames, None, size))
-            return emb.cpu()
-        u8 = torch.stack(list(self._decode_pool.map(lambda im: pp.resize_u8(im, size), pils)))
+        u8 = self._frames_u8(pils)
         with self._lock:
-            emb = self.pe_model.embed(u8.to(self.device, non_blocking=True))
+            emb = self.pe_model.embed(u8)
         return emb.cpu()
 
     def _embed_regions_batch(self, items, to_host=True, device_frames=None):
@@ -420,9 +400,13 @@ class SimpleReverso:
         if e.dim() != 1:
             raise ValueError(f"Unexpected feature shape: {tuple(e.shape)}")
         self.region_embeddings = [e]
-        meta = {"region_id": _uuid4(), "bbox": [0, 0, pil.width, pil.height], "area_ratio": 1.0,
+        return [e.clone()], [self._full_image_meta(pil)]
+
+    @staticmethod
+    def _full_image_meta(pil):
+        """The metadata of a direct-PE vector: the whole frame as its one region (core_system.py:449-453)"""
+        return {"region_id": _uuid4(), "bbox": [0, 0, pil.width, pil.height], "area_ratio": 1.0,
                 "detection_index": 0, "confidence": 1.0, "detected_class": "full_image"}
-        return [e.clone()], [meta]
 
     def request_stop(self):
         """core_system.py:457-459"""
@@ -455,36 +439,16 @@ class SimpleReverso:
             if progress_callback:
                 progress_callback(msg, None)
             return msg
-        status_messages = []
-
-        class _Log(str):
-            """What log_status returns: the whole log so far, joined only if somebody looks at it
-            (the reference joins on every call, which is quadratic in the number of images)."""
-            def __new__(cls, parts):
-                o = super().__new__(cls, "")
-                o._parts = parts
-                return o
-
-            def __str__(self):
-                return "\n".join(self._parts)
-
-        def log_status(message, progress_value=None):
-            status_messages.append(message)
-            if progress_callback:
-                progress_callback(message, progress_value)
-            return _Log(status_messages)
-
+        log_status = ingest.StatusLog(progress_callback)
         os.makedirs(self.db_root, exist_ok=True)
-        db_path = os.path.join(self.db_root, database_name)
-        ckpt_base = os.path.join(self.db_root, "checkpoints", f"{database_name}_checkpoint")
         processed_files = set()
         # The collection is built in <db>.building (the finished one, if any, stays searchable until the new one is
         # complete) and its manifest of delta shards is the checkpoint: a resume re-opens it.
         self._partial_embeddings, self._partial_metadata = [], []          # (kept for callers that look at them: always empty now)
-        build_path = db_path + BUILDING
+        build_path = os.path.join(self.db_root, database_name) + BUILDING
         self._build_store = None
-        build_info = self._build_info(folder_path, use_direct_pe, include_subfolders)
         if resume_from_checkpoint and os.path.exists(os.path.join(build_path, st.MANIFEST)):
+            build_info = self._build_info(folder_path, use_direct_pe, include_subfolders)
             try:
                 header = st.read_manifest(os.path.join(build_path, st.MANIFEST))[0]
                 diff = [k for k in build_info if header.get("build", {}).get(k) != build_info[k]]
@@ -502,13 +466,11 @@ class SimpleReverso:
                 log_status(f"⚠️ Error loading checkpoint: {str(e)}. Starting fresh.")
                 processed_files, self._build_store = set(), None
         try:
-            return self._create_database_body(folder_path, database_name, text_prompt, use_direct_pe, resume_from_checkpoint,
-                                              include_subfolders, log_status, status_messages, db_path, ckpt_base,
-                                              processed_files)
+            return ingest.IngestRun(self, folder_path, database_name, text_prompt, use_direct_pe, resume_from_checkpoint,
+                                    include_subfolders, log_status, processed_files).run()
         finally:
             self._stop_requested = False
-            self._partial_embeddings = []
-            self._partial_metadata = []
+            self._partial_embeddings, self._partial_metadata = [], []
             if self._build_store is not None:               # stopped or failed: the shards on disk are the checkpoint
                 self._build_store.close()
                 self._build_store = None
@@ -519,416 +481,6 @@ class SimpleReverso:
                 "use_ls": bool(self.pe_model.cfg.use_ls), "region_mode": self.region_mode,
                 "use_direct_pe": bool(use_direct_pe), "include_subfolders": bool(include_subfolders),
                 "skip_duplicates": self.skip_duplicates}      # (an older manifest has no such key: the same as None)
-
-    def _create_database_body(self, folder_path, database_name, text_prompt, use_direct_pe, resume_from_checkpoint,
-                              include_subfolders, log_status, status_messages, db_path, ckpt_base, processed_files):
-        log_status(f"📁 Creating database '{database_name}' from {folder_path}")
-        image_files = []
-        if include_subfolders:
-            for root, _, files in os.walk(folder_path):
-                image_files += [os.path.join(root, f) for f in files
-                                if any(f.lower().endswith(e) for e in IMAGE_EXTENSIONS)]
-        else:
-            image_files = [os.path.join(folder_path, f) for f in os.listdir(folder_path)
-                           if any(f.lower().endswith(e) for e in IMAGE_EXTENSIONS)]
-        image_files.sort()
-        if not image_files:
-            return str(log_status(f"❌ No images found in {folder_path}"))
-        if resume_from_checkpoint:
-            image_files = [f for f in image_files if f not in processed_files]
-            if not image_files and self._build_store is None:
-                return str(log_status("✅ All files already processed. Database is complete."))
-            if not image_files:
-                # every file was embedded before the stop / crash, but the collection was never completed: finish it
-                log_status(f"📋 All files already embedded: storing {len(self._build_store)} vectors from the checkpoint")
-        if image_files:
-            log_status(f"📊 Found {len(image_files)} images to process", 0.1)
-        if include_subfolders:
-            log_status("📂 Including images from subfolders")
-        log_status(f"🔧 Processing mode: {'Direct PE' if use_direct_pe else 'Detector + PE'}")
-        log_status(f"📂 Database will be stored at: {db_path}")
-
-        processed = failed = 0
-
-        build_path = db_path + BUILDING
-        collection_name = f"simple_reverso_{database_name}"
-        if self._build_store is None:
-            if os.path.isdir(build_path):
-                shutil.rmtree(build_path)
-            self._build_store = st.GalleryStore(self.pe_model.cfg.out_dim, device=self.device.index or 0,
-                                                capacity=max(len(image_files), 1024), collection=collection_name,
-                                                path=build_path,
-                                                build_info=self._build_info(folder_path, use_direct_pe, include_subfolders))
-        store_db = self._build_store
-
-        def checkpoint():
-            """the rows and finished files since the last one, as a delta shard of the collection being built; the small
-            JSON next to the reference's checkpoint path only says where the build lives"""
-            try:
-                t_f = time.perf_counter()
-                rows = store_db.flush()
-                stats["flush_s"] += time.perf_counter() - t_f
-                os.makedirs(os.path.dirname(ckpt_base), exist_ok=True)
-                with open(ckpt_base + ".json.tmp", "w") as f:
-                    json.dump({"database_name": database_name, "folder_path": folder_path, "build_path": build_path,
-                               "timestamp": datetime.now().isoformat(), "processed_files": len(store_db.files_done),
-                               "n_embeddings": len(store_db)}, f, indent=2)
-                os.replace(ckpt_base + ".json.tmp", ckpt_base + ".json")
-                if rows:
-                    log_status(f"💾 Checkpoint: shard {store_db._shards - 1} ({rows} vectors, {len(store_db)} in all)")
-            except Exception as e:
-                log_status(f"⚠️ Error saving checkpoint: {str(e)}")
-
-        host_resize = not self.device_resize and not (self.region_mode == "crop" and not use_direct_pe)
-        model_size = self.pe_model.cfg.image_size
-
-        stats = {"images": len(image_files), "decode_thread_s": 0.0, "wait_decode_s": 0.0, "wait_device_s": 0.0, "launch_s": 0.0,
-                 "bookkeeping_s": 0.0, "flush_s": 0.0, "duplicates_skipped": 0}
-        self.last_ingest_stats = stats
-        t_start = time.perf_counter()
-
-        def open_rgb(path, slot=None):
-            """pool task: decode (and, on the host-resize path, squash-resize) one file; with `slot` (a row of the
-            pinned staging batch) the resized image is written there instead of being returned"""
-            t_dec = time.perf_counter()
-            try:
-                return open_rgb_inner(path, slot)
-            finally:
-                stats["decode_thread_s"] += time.perf_counter() - t_dec      # (summed over the pool's threads; a float += under the GIL)
-
-        def open_rgb_inner(path, slot):
-            try:
-                im = Image.open(path).convert("RGB")
-                if not host_resize:
-                    # the decoded frame goes to the device as it is (resized / cropped there): this thread leaves it in
-                    # a pinned buffer of its batch slot, so that the upload is one asynchronous copy
-                    return im, frame_to_pinned(im, slot)
-                u8 = pp.resize_u8(im, model_size)
-                if slot is None:
-                    return im, u8
-                slot.copy_(u8)
-                return im, True
-            except Exception as e:           # per-image failure: logged and skipped (core_system.py:585-591)
-                return e, None
-
-        class FrameSlab:
-            """Pinned host memory for the decoded frames of ONE batch: the decode threads reserve ranges (a bump counter
-            under a lock) and copy their frames in; the ingest thread uploads the used prefix with one asynchronous
-            copy.  A frame that does not fit goes up from pageable memory and the slab is enlarged for the next round."""
-
-            def __init__(self):
-                # no memory yet: the first batch of a slab goes up from pageable memory (a blocking copy, but the device
-                # is idle then) and tells how much the slab needs; pinning it (tens of ms) happens when the slab comes
-                # round again, by which time the device has batches queued
-                self.buf = torch.empty(0, dtype=torch.uint8)
-                self.lock = threading.Lock()
-                self.used = 0
-                self.wanted = 0
-
-            def reset(self):
-                if self.wanted > self.buf.numel():
-                    self.buf = torch.empty(int(self.wanted * 1.25), dtype=torch.uint8).pin_memory()
-                self.used = self.wanted = 0
-
-            def put(self, arr):
-                size = (arr.size + 255) & ~255
-                with self.lock:
-                    off = self.used
-                    self.wanted += size
-                    if off + size > self.buf.numel():
-                        return None, torch.from_numpy(np.array(arr, dtype=np.uint8))
-                    self.used = off + size
-                np.copyto(self.buf[off:off + arr.size].view(arr.shape).numpy(), arr)
-                return off, arr.shape
-
-        def frame_to_pinned(im, slot):
-            arr = np.asarray(im)
-            if slot is None:
-                return None, torch.from_numpy(np.array(arr, dtype=np.uint8))
-            return slot.put(arr)
-
-        def upload_frames(slab, handles):
-            """handles: what frame_to_pinned returned for the batch's good files.  One asynchronous copy of the slab's
-            used prefix; returns the device frames (views into it), in order."""
-            dev_slab = slab.buf[:slab.used].to(self.device, non_blocking=True) if slab.used else None
-            out = []
-            for off, x in handles:
-                if off is None:
-                    out.append(x.to(self.device, non_blocking=True))            # did not fit: pageable upload
-                else:
-                    n = x[0] * x[1] * x[2]
-                    out.append(dev_slab[off:off + n].view(x))
-            return out
-
-        B = self.max_batch
-        # enough decode threads to feed the device in this mode and no more (see __init__): host resize costs 9 ms of
-        # thread time per 640 x 480 JPEG, decode alone 4 ms; crops are embedded three to an image
-        want_threads = self.decode_workers or min(os.cpu_count() or 8,
-                                                  16 if host_resize else (6 if self.region_mode == "crop" and not use_direct_pe else 8))
-        if want_threads != self._decode_pool._max_workers:
-            self._decode_pool.shutdown(wait=True)
-            self._decode_pool = ThreadPoolExecutor(max_workers=want_threads)
-
-        # The pool works DEPTH batches ahead of the one being embedded (one batch ahead left it idle between
-        # submissions: 1 650 decoded images/s in the loop against 3 700 for the pool alone).  Batch n's host buffer --
-        # staging rows or frame slab -- is number n % NSLOT: decoding (DEPTH of them) / waiting / being uploaded.
-        DEPTH = 2
-        NSLOT = DEPTH + 2
-        slabs = [FrameSlab() for _ in range(NSLOT)] if not host_resize else None
-        frames_done = [None] * NSLOT         # event behind the upload that read a slab
-
-        def submit(s0):
-            if stage is not None:            # batch s0 // B fills staging buffer (s0 // B) & 1, one row per file
-                buf = stage[(s0 // B) % NSLOT]
-                return [self._decode_pool.submit(open_rgb, p, buf[j]) for j, p in enumerate(image_files[s0:s0 + B])]
-            if not host_resize:
-                slab = slabs[(s0 // B) % NSLOT]
-                slab.reset()
-                return [self._decode_pool.submit(open_rgb, p, slab) for p in image_files[s0:s0 + B]]
-            return [self._decode_pool.submit(open_rgb, p) for p in image_files[s0:s0 + B]]
-
-        # Three things overlap: the pool decodes batch i+1, the device embeds batch i (its vectors come back through a
-        # pinned buffer behind an event), and this thread does the per-image bookkeeping of batch i-1.
-        last_ckpt = time.monotonic()
-        crop_mode = self.region_mode == "crop" and not use_direct_pe
-        # pool mode (the simple route: detect the batch's regions, then one embed_regions per batch): like the crop mode it
-        # stores one vector per region, queued with its batch
-        pool_mode = self.region_mode == "pool" and not use_direct_pe
-        per_region = crop_mode or pool_mode
-        pipelined = host_resize and not per_region
-        stage = None
-        if pipelined:
-            stage = [torch.zeros((B, 3, model_size, model_size), dtype=torch.uint8).pin_memory() for _ in range(NSLOT)]
-        h2d_done = [None] * NSLOT
-        pending = []                         # futures of the batches being decoded, oldest first
-        submitted = [0]
-
-        def top_up(it):
-            """keep the pool DEPTH batches ahead of batch `it`; a buffer is handed out again only after the upload that
-            read it (NSLOT batches ago) has left the host"""
-            while submitted[0] <= it + DEPTH and submitted[0] * B < len(image_files):
-                bn = submitted[0]
-                t_ev = time.perf_counter()
-                for ev in (h2d_done[bn % NSLOT], frames_done[bn % NSLOT]):
-                    if ev is not None:
-                        ev.synchronize()
-                stats["wait_device_s"] += time.perf_counter() - t_ev        # the device is the bottleneck while this grows
-                pending.append(submit(bn * B))
-                submitted[0] += 1
-
-        def detect_batch(pils):
-            """crop mode, as soon as a batch is decoded: detector boxes and region metadata per image (None for a file
-            that failed to decode), so that the batch's crops can be queued on the device before the bookkeeping of the
-            batch in front of it"""
-            det = []
-            for im in pils:
-                if isinstance(im, Exception):
-                    det.append(None)
-                    continue
-                n_reg = self.detect_regions(im, text_prompt)
-                kept, metas = self._region_metadata(im, self.detected_regions) if n_reg else ([], [])
-                det.append((n_reg, metas, self._pool_bits(self.detected_regions, kept) if pool_mode and metas else None))
-            return det
-
-        def finalize(item):
-            """bookkeeping of one embedded batch: metadata per image, then the batch's vectors -- still on the device --
-            go straight into the collection being built (device-to-device append; nothing visits the host)"""
-            nonlocal failed
-            s, paths, pils, hosts, dev_emb, by_file, last, det = item
-            gi = 0
-            batch_items = []                       # (path, pil, metas, row of dev_emb or None)
-            for j, (path, im) in enumerate(zip(paths, pils)):
-                i = s + j
-                filename = os.path.basename(path)
-                log_status(f"🔄 Processing {i + 1}/{len(image_files)}: {filename}", 0.1 + 0.7 * (i / len(image_files)))
-                if isinstance(im, Exception):
-                    log_status(f"❌ Error processing {filename}: {str(im)}")
-                    done_files.append(path)
-                    failed += 1
-                    continue
-                row = None
-                if dev_emb is not None and not per_region:
-                    row = j if by_file else gi                # staged batches have one row per file, the others one per decoded file
-                    gi += 1
-                if use_direct_pe:
-                    metas = [{"region_id": _uuid4(), "bbox": [0, 0, im.width, im.height], "area_ratio": 1.0,
-                              "detection_index": 0, "confidence": 1.0, "detected_class": "full_image"}]
-                    log_status(f"✅ Extracted global embedding for {filename}")
-                else:
-                    if det is not None:
-                        n_reg, metas = det[j][:2]             # crop / pool mode: detected when the batch was queued
-                    else:
-                        n_reg = self.detect_regions(im, text_prompt)
-                        metas = self._region_metadata(im, self.detected_regions)[1] if n_reg else []
-                    if n_reg == 0:
-                        log_status(f"⚠️ No regions found in {filename}, skipping")
-                        done_files.append(path)
-                        failed += 1
-                        continue
-                    log_status(f"✅ Found {n_reg} regions, extracted {len(metas)} embeddings in {filename}")
-                for m in metas:
-                    m["image_source"] = path
-                    m["filename"] = filename
-                    m["original_region_id"] = m.get("region_id", _uuid4())
-                    m["region_id"] = _uuid4()
-                batch_items.append((path, im, metas, row, hosts[j]))
-            if per_region:
-                store(batch_items, dev_emb, None, last)       # one vector per region, in item order (queued with the batch)
-                return
-            store(batch_items, None, dev_emb, last)
-
-        done_files = []                            # files finished (stored, failed or empty) since the last upsert
-
-        def store(batch_items, region_vecs, dev_emb, last):
-            """the embedded batch enters the collection (and only now counts as processed: a shard never names a file
-            whose vectors it does not hold)"""
-            nonlocal processed, last_ckpt
-            metas_all, rows = [], []
-            for path, im, metas, row, _ in batch_items:
-                metas_all.extend(metas)
-                if region_vecs is None:
-                    rows.extend([row] * len(metas))            # every region of an image stores its global vector (core_system.py:406-408)
-                done_files.append(path)
-                processed += 1
-                self._last_processed_file = path
-            if metas_all:
-                with self._lock, torch.cuda.device(self.device):
-                    if region_vecs is not None:
-                        vec = region_vecs
-                    elif rows == list(range(len(rows))) and len(rows) == dev_emb.shape[0]:
-                        vec = dev_emb
-                    else:
-                        vec = dev_emb.index_select(0, torch.tensor(rows, dtype=torch.int64, device=dev_emb.device))
-                    rep = store_db.upsert(vec, [m["region_id"] for m in metas_all], metas_all, files=list(done_files),
-                                          skip_duplicates=self.skip_duplicates)
-                    if rep and rep["dropped"]:
-                        stats["duplicates_skipped"] += len(rep["dropped"])
-                        log_status(f"♻️ Skipped {len(rep['dropped'])} near-duplicates of stored vectors "
-                                   f"(score >= {self.skip_duplicates:g}); {rep['kept']} of the batch stored")
-            else:
-                store_db.upsert(torch.zeros((0, store_db.dim)), [], [], files=list(done_files))
-            processed_files.update(done_files)
-            done_files.clear()
-            # a checkpoint writes only what is new: at most one per interval (the end of the build writes the last shard itself)
-            if time.monotonic() - last_ckpt >= self.checkpoint_interval_s and not last:
-                checkpoint()
-                last_ckpt = time.monotonic()
-
-        inflight = None
-        for it, s in enumerate(range(0, len(image_files), B)):
-            if self._stop_requested:
-                if inflight is not None:
-                    finalize(inflight)
-                    inflight = None
-                log_status("🛑 Stop requested. Saving progress...")
-                checkpoint()
-                return "\n".join(status_messages) + "\n\n⏸️ Processing stopped. You can resume later."
-            paths = image_files[s:s + B]
-            top_up(it)
-            futures = pending.pop(0)
-            t_w = time.perf_counter()
-            results = [f.result() for f in futures]
-            stats["wait_decode_s"] += time.perf_counter() - t_w
-            t_l = time.perf_counter()
-            pils = [r[0] for r in results]
-            hosts = [r[1] for r in results]
-            good = [r for r in results if not isinstance(r[0], Exception)]
-            # global vectors of the whole batch in one forward -- or, when every region is cropped, the regions' vectors
-            dev_emb = None
-            det = None
-            if crop_mode:
-                # region crops of the whole batch: boxes from the detector, the frames go up from their pinned slab (one
-                # asynchronous copy), one crop + resize launch, forwards of max_batch crops -- queued NOW, so that the
-                # device holds this batch while the thread does the bookkeeping of the one before; the vectors stay there
-                det = detect_batch(pils)
-                with_regions = [j for j, d in enumerate(det) if d is not None and d[1]]
-                if with_regions:
-                    with torch.cuda.device(self.device):
-                        dev_emb = self._embed_regions_batch([(pils[j], det[j][1]) for j in with_regions], to_host=False,
-                                                            device_frames=upload_frames(slabs[it % NSLOT],
-                                                                                        [hosts[j] for j in with_regions]))
-                        frames_done[it % NSLOT] = torch.cuda.Event()
-                        frames_done[it % NSLOT].record()
-            elif pool_mode:
-                det = detect_batch(pils)
-                with_regions = [j for j, d in enumerate(det) if d is not None and d[1]]
-                if with_regions:
-                    with torch.cuda.device(self.device):
-                        if host_resize:
-                            u8 = torch.stack([hosts[j] for j in with_regions]).to(self.device, non_blocking=True)
-                        else:
-                            with self._lock:
-                                frames = upload_frames(slabs[it % NSLOT], [hosts[j] for j in with_regions])
-                                frames_done[it % NSLOT] = torch.cuda.Event()
-                                frames_done[it % NSLOT].record()
-                                u8 = pp.crop_resize_device(frames, None, model_size)
-                        dev_emb = self._embed_pool_batch(u8, [det[j][2] for j in with_regions], to_host=False)
-            elif good:
-                if pipelined:
-                    # every file of the batch has its row in the staging buffer (a failed file's row keeps whatever it
-                    # held: embedded and never looked at)
-                    buf = stage[it % NSLOT][:len(paths)]
-                    with self._lock, torch.cuda.device(self.device):
-                        dev_in = buf.to(self.device, non_blocking=True)
-                        h2d_done[it % NSLOT] = torch.cuda.Event()
-                        h2d_done[it % NSLOT].record()
-                        dev_emb = self.pe_model.embed(dev_in)
-                else:
-                    # device resize: the decoded frames go up as they are, one crop + resize launch, one forward
-                    with self._lock, torch.cuda.device(self.device):
-                        frames = upload_frames(slabs[it % NSLOT], [h for _, h in good])
-                        frames_done[it % NSLOT] = torch.cuda.Event()
-                        frames_done[it % NSLOT].record()
-                        dev_emb = self.pe_model.embed(pp.crop_resize_device(frames, None, model_size))
-            stats["launch_s"] += time.perf_counter() - t_l
-            cur = (s, paths, pils, hosts, dev_emb, pipelined, s + B >= len(image_files), det)
-            if inflight is not None:
-                t_b = time.perf_counter()
-                finalize(inflight)
-                stats["bookkeeping_s"] += time.perf_counter() - t_b
-            inflight = cur
-        if inflight is not None:
-            t_b = time.perf_counter()
-            finalize(inflight)
-            stats["bookkeeping_s"] += time.perf_counter() - t_b
-
-        if len(store_db) == 0:
-            store_db.close()                                    # nothing to keep: no empty build directory or note stays behind
-            self._build_store = None
-            shutil.rmtree(build_path, ignore_errors=True)
-            st.remove_checkpoint(ckpt_base)
-            return str(log_status("❌ No embeddings extracted from any images"))
-
-        log_status(f"📦 Recreated collection: {collection_name}", 0.8)
-        if self._stop_requested:
-            # a stop between the last embed batch and the completion of the collection: everything is in the shards
-            log_status("🛑 Stop requested during database storage. Progress saved.")
-            checkpoint()
-            return "\n".join(status_messages) + "\n\n⏸️ Processing stopped. You can resume later."
-        with self._lock:
-            t_f = time.perf_counter()
-            store_db.save()                                     # the last delta shard + the "complete" line
-            stats["flush_s"] += time.perf_counter() - t_f
-            log_status(f"💾 Stored {len(store_db)} points in {store_db._shards} shards", 0.9)
-            if self.vector_db is not None:
-                self.vector_db.close()
-            st.swap_in(build_path, db_path)                     # recreate_collection: the new one replaces the old one only now
-            store_db.path = db_path
-            self.vector_db = store_db
-            self._build_store = None
-            self.current_database = collection_name
-        if os.path.exists(ckpt_base + ".json"):
-            st.remove_checkpoint(ckpt_base)
-            log_status("🧹 Cleaned up checkpoint file")
-        stats["total_s"] = time.perf_counter() - t_start
-        stats["vectors"] = len(self.vector_db)
-        log_status("\n📊 Final Summary:", 0.9)
-        log_status(f"✅ Successfully processed: {processed} images")
-        if failed > 0:
-            log_status(f"⚠️ Failed to process: {failed} images")
-        log_status(f"🔍 Total embeddings stored: {len(self.vector_db)}")
-        log_status(f"🎯 Database '{database_name}' ready for searching!", 1.0)
-        return "\n".join(status_messages)
 
     # ---------------------------------------------------------------- search --
     def search_similar(self, similarity_threshold=0.7, max_results=5, query_filter=None, group_by=None):

@@ -179,11 +179,8 @@ def test_region_crop_mode_embeds_each_box(tmp_path, dev):
     assert items[0]["bbox"] == metas[0]["bbox"]
 
 
-def test_pipelined_ingest_equals_one_batch(tmp_path, dev):
-    """create_database overlaps decode, embed and bookkeeping across three batches (staging and result buffers used
-    alternately, region vectors stored one batch late).  Many small batches must store exactly what one big batch
-    stores, in the same order, in every mode -- a broken file in the middle included."""
-    from reverso_amd.core_system import Regions
+def _pipelined_folder(tmp_path):
+    """21 images and a broken file in the middle of the sorted order"""
     folder = str(tmp_path / "images")
     paths = _make_jpegs(folder, n=21, seed=9)
     (tmp_path / "images" / "img_010a_broken.jpg").write_bytes(b"not a jpeg")
@@ -193,29 +190,76 @@ def test_pipelined_ingest_equals_one_batch(tmp_path, dev):
         im = Image.open(paths[j]).convert(mode)
         os.remove(paths[j])
         im.save(paths[j][:-4] + (".jpg" if mode == "CMYK" else ".png"))
+    return folder
 
-    def detector(pil, prompt):
-        w, h = pil.size
-        return Regions([[0, 0, w // 2, h // 2], [w // 4, h // 4, w - 1, h - 1], [w // 3, 0, w - 1, h // 2]],
-                       confidence=[0.9, 0.8, 0.7], class_id=[0, 1, 0], class_names=["person", "car"])
 
-    direct_runs = []
-    for kw, direct in (({}, True), ({"device_resize": True}, True), ({"detector": detector, "region_mode": "crop"}, False),
-                       ({"detector": detector}, False)):
+def _box_detector(pil, prompt):
+    from reverso_amd.core_system import Regions
+    w, h = pil.size
+    return Regions([[0, 0, w // 2, h // 2], [w // 4, h // 4, w - 1, h - 1], [w // 3, 0, w - 1, h // 2]],
+                   confidence=[0.9, 0.8, 0.7], class_id=[0, 1, 0], class_names=["person", "car"])
+
+
+def _mask_detector(pil, prompt):
+    """three masks per image, as tests/test_gpu_region_pool.py: a quadrant, a disc, a corner triangle"""
+    from reverso_amd.core_system import Regions
+    w, h = pil.size
+    masks = np.zeros((3, h, w), dtype=bool)
+    masks[0, : h // 2, : w // 2] = True
+    yy, xx = np.mgrid[0:h, 0:w]
+    masks[1] = (xx - 0.7 * w) ** 2 + (yy - 0.6 * h) ** 2 <= (0.25 * min(w, h)) ** 2
+    masks[2] = (xx + yy) > 0.72 * (w + h)
+    return Regions([[0, 0, w // 2, h // 2], [w // 3, h // 3, w - 1, h - 1], [w // 2, h // 2, w - 1, h - 1]], mask=masks,
+                   confidence=[0.9, 0.8, 0.7], class_id=[0, 1, 0], class_names=["person", "car"])
+
+
+def test_pipelined_ingest_equals_one_batch(tmp_path, dev):
+    """create_database overlaps decode, embed and bookkeeping across three batches (staging and result buffers used
+    alternately, region vectors stored one batch late).  Many small batches must store exactly what one big batch
+    stores, in the same order, in every mode and through every host buffer (staging rows, frame slabs, pageable
+    tensors) -- a broken file in the middle included."""
+    folder = _pipelined_folder(tmp_path)
+    pool = {"detector": _mask_detector, "region_mode": "pool"}
+    runs = {}
+    for name, kw, direct in (("direct", {}, True), ("direct_dev", {"device_resize": True}, True),
+                             ("crop", {"detector": _box_detector, "region_mode": "crop"}, False),
+                             ("global", {"detector": _box_detector}, False),
+                             ("pool", pool, False), ("pool_dev", dict(pool, device_resize=True), False),
+                             ("global_dev", {"detector": _box_detector, "device_resize": True}, False)):
         got = []
         for mb in (4, 64):
-            r = SimpleReverso(model_name="PE-Tiny-T14-56", db_root=str(tmp_path / f"db{len(got)}_{mb}_{len(kw)}_{direct}"),
-                              max_batch=mb, **kw)
+            r = SimpleReverso(model_name="PE-Tiny-T14-56", db_root=str(tmp_path / f"db_{name}_{mb}"), max_batch=mb, **kw)
             msg = r.create_database(folder, "p", use_direct_pe=direct)
             assert "✅" in msg and "❌ Error processing img_010a_broken.jpg" in msg
             got.append((r.vector_db.gallery.read().cpu(), [(p["filename"], p["bbox"]) for p in r.vector_db.payloads]))
         assert got[0][1] == got[1][1]
         assert len(got[0][1]) == (21 if direct else 63)
         assert torch.equal(got[0][0], got[1][0])
-        if direct:
-            direct_runs.append(got[0])
-    # host resize and device resize store the same vectors, the odd image modes included
-    assert direct_runs[0][1] == direct_runs[1][1] and torch.equal(direct_runs[0][0], direct_runs[1][0])
+        runs[name] = got[0]
+    # host resize and device resize store the same vectors (both routes produce the same u8 pixels), the odd image modes included
+    for host, device in (("direct", "direct_dev"), ("pool", "pool_dev")):
+        assert runs[host][1] == runs[device][1] and torch.equal(runs[host][0], runs[device][0])
+
+
+def test_stop_with_a_batch_in_flight_in_crop_mode_then_resume(tmp_path, dev):
+    """A stop while a per-region batch is queued on the device: that batch is finalized before the checkpoint is written,
+    and the resumed build finishes with exactly the collection of an uninterrupted one (ids aside)."""
+    folder = _pipelined_folder(tmp_path)
+    kw = dict(model_name="PE-Tiny-T14-56", max_batch=4, detector=_box_detector, region_mode="crop")
+    ref = SimpleReverso(db_root=str(tmp_path / "db_ref"), **kw)
+    assert "ready for searching" in ref.create_database(folder, "c")
+    r = SimpleReverso(db_root=str(tmp_path / "db"), **kw)
+
+    def stop_in_the_second_batch(m, v=None):
+        if m.startswith("🔄 Processing 6/"):         # (of 22: the broken file counts) logged while batch 3 is in flight
+            r.request_stop()
+    msg = r.create_database(folder, "c", progress_callback=stop_in_the_second_batch)
+    assert "⏸️ Processing stopped" in msg and "🔄 Processing 12/" in msg and "🔄 Processing 13/" not in msg
+    msg = r.create_database(folder, "c", resume_from_checkpoint=True)
+    assert "📋 Resuming from checkpoint: 12 files already processed" in msg and "ready for searching" in msg, msg[-600:]
+    assert torch.equal(r.vector_db.gallery.read().cpu(), ref.vector_db.gallery.read().cpu())
+    strip = lambda db: [{k: v for k, v in p.items() if k not in ("region_id", "original_region_id")} for p in db.payloads]
+    assert strip(r.vector_db) == strip(ref.vector_db) and len(r.vector_db) == 63
 
 
 def test_device_resize_ingest_equals_host_resize(system):
