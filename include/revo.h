@@ -849,6 +849,11 @@ int32_t revo_op_attention_causal(const void* qkv_bf16, int64_t ld, void* out_bf1
  * int32 [batch * seq]; an id outside [0, vocab) gives a row of NaN instead of a wild read.  width % 4 == 0, ldx % 4 == 0. */
 int32_t revo_op_embed_tokens(const int32_t* tokens_dev, const float* table, const float* pos, int32_t batch, int32_t seq,
                              int32_t vocab, int32_t width, float* x, int64_t ldx, void* stream);
+/* end-of-text pooling of the text tower: out[b * width + c] = x[(b * seq + s_b) * ldx + c], s_b the FIRST position of prompt
+ * b's largest id (a copy: bit-exact); tokens_dev: DEVICE int32 [batch * seq], any int32 values.  width % 4 == 0, ldx % 4 == 0,
+ * ldx >= width; out is dense [batch][width]. */
+int32_t revo_op_pool_eot(const int32_t* tokens_dev, const float* x, int64_t ldx, int32_t batch, int32_t seq, int32_t width,
+                         float* out, void* stream);
 int32_t revo_op_f32_to_bf16(const float* src, int64_t ld_src, void* dst_bf16, int64_t ld_dst, int64_t rows,
                             int32_t cols, void* stream);
 

@@ -110,6 +110,7 @@ SIGNATURES = {
     "revo_op_attention": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
     "revo_op_attention_causal": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
     "revo_op_embed_tokens": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _i64, _p]),
+    "revo_op_pool_eot": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _p, _p]),
     "revo_op_f32_to_bf16": (_i32, [_p, _i64, _p, _i64, _i64, _i32, _p]),
     "revo_prof_enable": (_i32, [_i32]),
     "revo_prof_reset": (_i32, []),

@@ -48,10 +48,12 @@ int launch_embed_tokens(const int32_t* tokens, const float* table, const float* 
 __global__ __launch_bounds__(64) void pool_eot_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ x, long ldx,
                                                       int S, int W, float* __restrict__ out) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    // (a lane without a position keeps at = S and loses every tie; a lane with one starts from its first, so that a prompt
+    //  of nothing but the smallest int32 still names position 0 and never the row after the prompt)
     int best = INT32_MIN, at = S;
     for (int s = lane; s < S; s += 64) {
         const int t = tokens[(long)b * S + s];
-        if (t > best) { best = t; at = s; }           // ascending s: the first position of the lane's largest id
+        if (t > best || s == lane) { best = t; at = s; }   // ascending s: the first position of the lane's largest id
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -352,5 +354,14 @@ extern "C" int32_t revo_op_embed_tokens(const int32_t* tokens_dev, const float* 
     REVO_REQUIRE(tokens_dev && table && pos && x, "op_embed_tokens: null argument");
     REVO_REQUIRE(batch >= 0 && seq >= 1 && (long)batch * seq < (1l << 31), "op_embed_tokens: bad batch or seq");
     return revo::launch_embed_tokens(tokens_dev, table, pos, batch, seq, vocab, width, x, ldx, (hipStream_t)stream);
+    API_END
+}
+extern "C" int32_t revo_op_pool_eot(const int32_t* tokens_dev, const float* x, int64_t ldx, int32_t batch, int32_t seq,
+                                    int32_t width, float* out, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(tokens_dev && x && out, "op_pool_eot: null argument");
+    REVO_REQUIRE(batch >= 0 && seq >= 1 && (long)batch * seq < (1l << 31), "op_pool_eot: bad batch or seq");
+    REVO_REQUIRE(width >= 4 && ldx >= width, "op_pool_eot: row stride below width");
+    return revo::launch_pool_eot(tokens_dev, x, ldx, batch, seq, width, out, (hipStream_t)stream);
     API_END
 }

@@ -534,7 +534,7 @@ ATTENTION_CASES = ([(f"S{S} H{H} hd{hd} b{B}", B, S, H, hd, None, None)
 ROPE_CASES = [("B16", 14, 12, 64, True, 3), ("L14", 24, 16, 64, True, 2), ("G14", 32, 16, 96, False, 2),
               ("Tiny-T14", 4, 2, 64, True, 5), ("Tiny-N14", 4, 2, 96, False, 5)]
 
-LAYERNORM_WIDTHS = [128, 192, 768, 1024, 1536]
+LAYERNORM_WIDTHS = [128, 192, 256, 768, 1024, 1280, 1536]
 
 # the shapes of test_gemm_epilogues and test_gemm_skinny_all_epilogues
 GEMM_CASES = [(333, 512, 256), (64, 1024, 1024), (64, 4096, 1024), (64, 1024, 4096), (1, 256, 256), (7, 260, 512),
@@ -1196,11 +1196,103 @@ def form_names(bits):
     return sorted(n for i, n in enumerate(GEMM_FORMS) if bits >> i & 1)
 
 
+# A launch is more than its form bit: the kernel of a step is compiled per epilogue, with or without the folded LayerNorm's
+# consumer, the fold and the planes, and a leftover step does pointer arithmetic of its own from row0.  The signature of a
+# step of a plan (revo_debug_gemm_plan; tests/test_gemm_plan.py `plan` gives the step dicts):
+#   (kernel form, epilogue, consumer, LayerNorm in the reduce, fold, planes mode xp, "main" / "leftover")
+GEMM_EPILOGUES = ["bf16", "gelu", "resid", "f32", "patch", "rope"]              # kernels.h, in value order
+OFFER_LN, OFFER_FOLD, OFFER_XP_IN, OFFER_XP_OUT, OFFER_CONSUMER = 1, 2, 4, 8, 16  # the offers of revo_debug_gemm_plan
+BODY_WS_ELEMS = 16 << 20                                                        # tower.h SPLITK_WS_ELEMS
+
+
+def gemm_signatures(epi, offers, steps):
+    """the signatures of the steps of one planned launch (epi: the epilogue's number)"""
+    return [(form_names(s["form"])[0], GEMM_EPILOGUES[epi], bool(offers & OFFER_CONSUMER), bool(s["reduce_ln"]), bool(s["fold"]),
+             int(s["xp"]), "leftover" if i else "main") for i, s in enumerate(steps)]
+
+
+def signature_text(sig):
+    form, epi, consumer, reduce_ln, fold, xp, step = sig
+    flags = [n for n, on in (("consumer", consumer), ("reduce-LN", reduce_ln), ("fold", fold), (f"xp {xp}", xp)) if on]
+    return f"{form} {epi} [{', '.join(flags)}] {step}"
+
+
+def body_gemm_launches(plan, W, Md, rows, layers, qkv_epi, rope=(0, 0, 0)):
+    """The launch_gemm calls of tower.h body_blocks for `layers` blocks over `rows` rows, restated; `plan` plans one
+    (tests/test_gemm_plan.py plan, passed in so that importing this module loads no library).  qkv_epi / rope: what the
+    tower's qkv_args gives (image: "rope" and (S, head_dim, 2 W); text: "bf16").
+    Returns [(launch name, block, epilogue number, N, K, offers, form bits, steps)].
+
+    What is restated: ln_stats and xlo exist when W is one to six 256-column slices (alloc_body); the stream lives in planes
+    for the whole run when both residual shapes fold (stream_in_planes: gemm_resid_folds, the bare problem with the fold
+    offered); a residual GEMM is offered the fused LayerNorm, the fold and the planes together, the last fc2 none of them
+    but the planes it must read; qkv and fc1 consume the statistics exactly when the residual GEMM in front of them folded."""
+    parts = W // 256 if W % 256 == 0 and W // 256 <= 6 else 0
+
+    def folds(N, K):
+        bits, steps = plan(2, rows, N, K, 0, OFFER_FOLD)
+        return bits >= 0 and steps[0]["fold"] == 1
+    planes = bool(parts) and folds(W, W) and folds(W, Md)
+    out, h_xb, x_planes = [], False, False
+
+    def launch(name, block, epi, N, K, ws=0, offers=0, r=(0, 0, 0)):
+        bits, steps = plan(epi, rows, N, K, ws, offers, r)
+        assert bits >= 0, f"the plan refuses {name} of block {block}: {rows} x {N} x {K}, offers {offers}"
+        out.append((name, block, epi, N, K, offers, bits, steps))
+        return steps[0]["fold"] == 1
+
+    def after(offered):
+        return (OFFER_LN | (OFFER_FOLD if parts else 0) | (OFFER_XP_OUT if planes else 0)) if offered else 0
+
+    for i in range(layers):
+        last = i + 1 >= layers
+        launch("qkv", i, GEMM_EPILOGUES.index(qkv_epi), 3 * W, W, 0, OFFER_CONSUMER if h_xb else 0, rope)
+        folded = launch("out", i, 2, W, W, BODY_WS_ELEMS, after(True) | (OFFER_XP_IN if x_planes else 0))
+        h_xb, x_planes = folded, planes and folded
+        launch("fc1", i, 1, Md, W, 0, OFFER_CONSUMER if h_xb else 0)
+        folded = launch("fc2", i, 2, W, Md, BODY_WS_ELEMS, after(not last) | (OFFER_XP_IN if x_planes else 0))
+        h_xb, x_planes = not last and folded, not last and planes and folded
+    return out
+
+
 # The GPU cases of tests/test_gpu_gemm_bounds.py: (label, kind, M, N, K, options, expected forms on librevo_exp.so).
 # kind: "f32" / "bf16" / "gelu" / "resid" (revo_op_gemm), "rope" (revo_op_gemm_rope), "ln_in:bf16" / "ln_in:gelu"
 # (revo_op_gemm_ln_in), "ln_in_rope", "resid_ln:<planes>" (revo_op_gemm_resid_ln: none = fp32 rows + bf16 copy, out, inout,
 # in), "resid_norm" (revo_op_gemm_resid_norm).  options: tower (RoPE table / S / hd), variant / qstores (forced forms: then
 # the experiment library only), pad (NaN margins past N and M), ksplit (the split-K parts the form takes, for the record).
+# One case per launch signature (gemm_signatures) the towers reach and no other case of GEMM_FORM_CASES holds, each at the fewest rows
+# (then columns, then K) of the domain of tests/test_gemm_form_coverage.py that reach it; that test prints the shape.
+# "text B x S": the text tower (plain bf16 qkv epilogue; widths 1024 / 4096 and 1280 / 5120) at B prompts of S positions.
+# Where the smallest shape of a main-step signature (256_TILE bf16 at 1537 rows, 256_TILE resid at 4865) is also the
+# main step of a two-step case, that case holds it: every case here is the only one of the table with some signature
+# (tests/test_gemm_form_coverage.py removes them one at a time).
+GEMM_SIGNATURE_CASES = [
+    ("text L14 5 x 13 last fc2, ring split-K", "resid", 65, 1024, 4096, dict(ksplit=8), ["SPLITK_RING"]),
+    ("text L14 5 x 13 qkv, ring", "bf16", 65, 3072, 1024, {}, ["128R"]),
+    ("text L14 5 x 13 fc1 gelu, ring", "gelu", 65, 4096, 1024, {}, ["128R"]),
+    ("B16 b1 out-proj, ring", "resid", 197, 768, 768, {}, ["128R"]),
+    ("text G14 9 x 57 qkv", "bf16", 513, 3840, 1280, {}, ["128_64"]),
+    ("text G14 29 x 53 out-proj", "resid", 1537, 1280, 1280, {}, ["128_64"]),
+    ("G14 b2 fc1 gelu + 128 x 64 leftover", "gelu", 2048, 8960, 1536, {}, ["256_TILE", "128_64"]),
+    ("B16 b14 qkv rope, 128 x 128", "rope", 2758, 2304, 768, dict(tower="B16"), ["128_128"]),
+    ("text G14 73 x 43 fc1 gelu + ring leftover", "gelu", 3139, 5120, 1280, {}, ["256_TILE", "128R"]),
+    ("G14 b4 qkv rope, persistent", "rope", 4096, 4608, 1536, dict(tower="G14"), ["256P"]),
+    ("text G14 65 x 67 qkv + skinny leftover", "bf16", 4355, 3840, 1280, {}, ["256_TILE", "SKINNY_411"]),
+    ("text G14 94 x 47 qkv + ring leftover", "bf16", 4418, 3840, 1280, {}, ["256_TILE", "128R"]),
+    ("text G14 139 x 35 qkv + 128 x 64 leftover", "bf16", 4865, 3840, 1280, {}, ["256_TILE", "128_64"]),
+    ("text G14 151 x 39 qkv + 128 x 128 leftover", "bf16", 5889, 3840, 1280, {}, ["256_TILE", "128_128"]),
+    ("text G14 173 x 37 fc1 gelu, queued stores + 1 fused row", "gelu", 6401, 5120, 1280, {}, ["256Q_QTAIL"]),
+    ("text G14 223 x 31 qkv, queued stores", "bf16", 6913, 3840, 1280, {}, ["256Q"]),
+    ("text G14 130 x 67 qkv, queued stores + 6 fused rows", "bf16", 8710, 3840, 1280, {}, ["256Q_QTAIL"]),
+    ("text G14 184 x 71 out-proj + skinny leftover", "resid", 13064, 1280, 1280, {}, ["256_TILE", "SKINNY_411"]),
+    ("text G14 184 x 71 fc2 + fragment skinny leftover", "resid", 13064, 1280, 5120, {}, ["256_TILE", "SKINNY_444"]),
+    ("G14 b15 out-proj + 128 x 128 leftover", "resid", 15360, 1536, 1536, {}, ["256_TILE", "128_128"]),
+    ("G14 b18 out-proj fold, planes out, 256-row tiles", "resid_ln:out", 18432, 1536, 1536, {}, ["256P", "LN_FOLDED", "PLANES_OUT"]),
+    ("G14 b18 last fc2 planes in, fp32 out, 256-row tiles", "resid_ln:in", 18432, 1536, 8960, {}, ["256P", "PLANES_IN"]),
+    ("G14 b24 fc1 gelu + fold, 128 x 64 leftover", "ln_in:gelu", 24576, 8960, 1536, {}, ["256Q", "128_64", "LN_CONSUMED"]),
+    ("L14 b50 fc1 gelu + fold, ring leftover", "ln_in:gelu", 28850, 4096, 1024, {}, ["256Q", "128R", "LN_CONSUMED"]),
+]
+
 _L, _G = 36928, 32768
 GEMM_FORM_CASES = [
     # PE-L14 at batch 64: the forward's own launches
@@ -1262,7 +1354,14 @@ GEMM_FORM_CASES = [
     ("K192 b1 gelu", "gelu", 577, 4096, 192, {}, ["128_128"]),
     ("K1088 b1 gelu", "gelu", 577, 4096, 1088, {}, ["128_64"]),
     ("K1088 b1 qkv rope", "rope", 577, 3072, 1088, dict(tower="L14"), ["128R"]),
-] + [(f"{m}x{n}x{k} {e}", e, m, n, k, {}, [f]) for e in ("f32", "resid") for (m, n, k), f in zip(
+    # the text towers' widths where the signature is held above but the arithmetic differs: one partial 128-row tile on five K
+    # parts of four K-tiles (the fewest the plan allows) with a reduce of MAXG 3 whose last group is partial; six parts of an
+    # 80-tile K (uneven); the width-1024 out-proj of a few prompts; five column tiles on the 256-tile split-K
+    ("text G14 5 x 13 out-proj + LayerNorm (MAXG 3, partial group)", "resid_norm", 65, 1280, 1280, dict(ksplit=5), ["SPLITK_RING_LN"]),
+    ("text G14 2 x 72 fc2 + LayerNorm (80 K-tiles in 6 parts)", "resid_norm", 144, 1280, 5120, dict(ksplit=6), ["SPLITK_RING_LN"]),
+    ("text L14 5 x 13 out-proj + LayerNorm", "resid_norm", 65, 1024, 1024, dict(ksplit=4), ["SPLITK_RING_LN"]),
+    ("text G14 770 rows fc2, 256-tile split-K (5 column tiles)", "resid", 770, 1280, 5120, dict(ksplit=8), ["SPLITK_256"]),
+] + GEMM_SIGNATURE_CASES + [(f"{m}x{n}x{k} {e}", e, m, n, k, {}, [f]) for e in ("f32", "resid") for (m, n, k), f in zip(
     GEMM_CASES, ["128_128", "SKINNY_444", "SKINNY_411", "SKINNY_444", "SKINNY_411", "SKINNY_411", "SKINNY_411", "SKINNY_411"])]
 
 

@@ -1,6 +1,6 @@
 // The text tower's entry points of the C ABI (include/revo.h, TEXT: revo_text_create, revo_text_forward, revo_text_destroy,
-// revo_op_attention_causal, revo_op_embed_tokens) under AddressSanitizer + UBSan: every refusal they make before the device is
-// touched, with its message; the host arrays they are given are exactly as long as the call says.  Needs no GPU: without one
+// revo_op_attention_causal, revo_op_embed_tokens, revo_op_pool_eot) under AddressSanitizer + UBSan: every refusal they make
+// before the device is touched, with its message; the host arrays they are given are exactly as long as the call says.  Needs no GPU: without one
 // a complete checkpoint gets as far as the device and fails there with -1, which is checked too.  Where a device is present
 // the refusals that need a live handle (batch above max_batch, seq_len above the context, a bad token id) run as well.
 // Built by `make -C revers-o_amd/csrc text_check` and run by tests/test_text_host.py in the CPU tier.
@@ -129,6 +129,15 @@ int main() {
         EXPECT(revo_op_embed_tokens(tok.data(), tab.data(), tab.data(), 1, 1, 64, 8, x.data(), 4, nullptr) == -2);
         EXPECT(revo_op_embed_tokens(tok.data(), tab.data(), tab.data(), 1, 1, 0, 8, x.data(), 8, nullptr) == -2);
         EXPECT(revo_op_embed_tokens(tok.data(), tab.data(), tab.data(), 0, 1, 64, 8, x.data(), 8, nullptr) == 0);
+        EXPECT(revo_op_pool_eot(nullptr, tab.data(), 8, 1, 1, 8, x.data(), nullptr) == -2 && err_has("null argument"));
+        EXPECT(revo_op_pool_eot(tok.data(), nullptr, 8, 1, 1, 8, x.data(), nullptr) == -2 && err_has("null argument"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 8, 1, 1, 8, nullptr, nullptr) == -2 && err_has("null argument"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 8, 1, 0, 8, x.data(), nullptr) == -2 && err_has("bad batch or seq"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 8, -1, 1, 8, x.data(), nullptr) == -2 && err_has("bad batch or seq"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 4, 1, 1, 8, x.data(), nullptr) == -2 && err_has("row stride below width"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 8, 1, 1, 6, x.data(), nullptr) == -2 && err_has("multiples of 4"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 10, 1, 1, 8, x.data(), nullptr) == -2 && err_has("multiples of 4"));
+        EXPECT(revo_op_pool_eot(tok.data(), tab.data(), 8, 0, 1, 8, x.data(), nullptr) == 0);
     }
 
     section("create: a complete checkpoint reaches the device");

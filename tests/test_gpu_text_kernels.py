@@ -1,9 +1,10 @@
-"""GPU: the text tower's kernels one at a time (text.hip) -- the token embedding bit for bit against torch, the causal
-attention against the fp64 reference within the per-element bound of tests/_text_reference.py (whose teeth
+"""GPU: the text tower's kernels one at a time (text.hip) -- the token embedding and the end-of-text pooling bit for bit
+against torch, the causal attention against the fp64 reference within the per-element bound of tests/_text_reference.py (whose teeth
 tests/test_text_attention_teeth.py shows on the same inputs), its prefix independence and its determinism."""
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -37,6 +38,50 @@ def test_embed_tokens_is_bit_exact(dev, lib, vocab, W, B, S, pad):
     want = (table[tok.long()] + pos[None]).reshape(B * S, W)
     assert torch.equal(x[:, :W], want)
     assert (x[:, W:] == -7.0).all()                         # nothing written between the rows
+
+
+INT32_MIN = -2 ** 31
+
+
+def _pool_prompts(S, seed):
+    """int32 [B][S]: one prompt per way the first position of the largest id can be found (or missed)"""
+    rng = np.random.default_rng(seed)
+    rows = {}
+    base = lambda: rng.integers(-1000, 40000, size=S, dtype=np.int64)
+    t = base(); t[0] = 49407; rows["maximum in column 0"] = t
+    t = base(); t[S - 1] = 49407; rows["maximum in the last column"] = t
+    t = base(); t[S // 2:] = 49407; rows["maximum repeated from the middle on: the first wins"] = t
+    t = base(); t[S // 3] = 49407; t[S - 1] = 49407; rows["maximum twice"] = t
+    if S > 64:                                               # positions s and s + 64 are the same lane's
+        t = base(); t[0] = 49407; t[64] = 49407; rows["twice in lane 0"] = t
+        t = base(); t[S - 65] = 49407; t[S - 1] = 49407; rows["twice in the last position's lane"] = t
+        t = base(); t[64] = 49407; t[63] = 49407; rows["lane 0's second position against lane 63's first"] = t
+    rows["every id equal"] = np.full(S, 7, dtype=np.int64)
+    rows["every id the smallest int32"] = np.full(S, INT32_MIN, dtype=np.int64)
+    t = np.full(S, INT32_MIN, dtype=np.int64); t[S - 1] = INT32_MIN + 1; rows["one above the smallest int32, last"] = t
+    t = -base() - 5; rows["negative ids"] = t
+    t = base(); t[S // 2] = 2 ** 31 - 1; rows["the largest int32"] = t
+    return list(rows), np.stack(list(rows.values())).astype(np.int32)
+
+
+@pytest.mark.parametrize("W,pad", [(1280, 0), (1280, 12), (256, 4), (4, 4)])
+@pytest.mark.parametrize("S", [1, 63, 64, 65, 128])
+def test_pool_eot_is_the_row_at_the_first_largest_id(dev, lib, S, W, pad):
+    names, tok = _pool_prompts(S, S + W)
+    B, ldx = tok.shape[0], W + pad
+    g = torch.Generator().manual_seed(S * 7 + W)
+    # one spare row behind the last prompt: a position S (no lane found an id above its start value) reads it, not past x
+    x = torch.randn(B * S + 1, ldx, generator=g).to(dev)
+    x[B * S] = -7.0
+    buf = torch.full((B + 2, W), 3.0, dtype=torch.float32, device=dev)          # a guard row on either side of out
+    out = buf[1:B + 1]
+    _lib.check(lib.revo_op_pool_eot(_lib.ptr(torch.from_numpy(tok).to(dev)), _lib.ptr(x), ldx, B, S, W, _lib.ptr(out),
+                                    _lib.current_stream()), "revo_op_pool_eot")
+    at = np.argmax(tok, axis=1)                              # numpy: the first occurrence of the maximum
+    want = x[torch.from_numpy(np.arange(B) * S + at).to(dev), :W]
+    for b, name in enumerate(names):
+        assert torch.equal(out[b], want[b]), f"{name} (S {S}): not the row of position {at[b]}"
+    assert (buf[0] == 3.0).all() and (buf[B + 1] == 3.0).all()                  # nothing written outside out
 
 
 def _attention(lib, qkv, B, S, H, ldo):

@@ -33,6 +33,8 @@ def test_refusals_through_the_binding():
     assert b"missing weight tensor: token_embedding.weight" in lib.revo_last_error()
     assert lib.revo_op_attention_causal(p(out), 192, p(out), 64, 1, 8, 1, 96, None) == -2
     assert lib.revo_op_embed_tokens(None, p(out), p(out), 1, 1, 64, 8, p(out), 8, None) == -2
+    assert lib.revo_op_pool_eot(None, p(out), 64, 1, 5, 64, p(out), None) == -2 and b"null argument" in lib.revo_last_error()
+    assert lib.revo_op_pool_eot(p(tok), p(out), 32, 1, 5, 64, p(out), None) == -2 and b"row stride below width" in lib.revo_last_error()
     # the hooks that stop a forward early exist in the experiment library only
     assert not hasattr(lib, "revo_text_set_debug_layers") and hasattr(_lib.load_exp(), "revo_text_set_debug_layers")
 
