@@ -86,6 +86,56 @@ int32_t revo_vit_seq_len(const revo_vit* vit);
 int32_t revo_vit_forward_regions(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch,
                                  const int32_t* region_image, const uint32_t* region_bits, int32_t bits_on_device,
                                  int32_t n_regions, float* out_global, float* out_regions, int32_t normalize, void* stream);
+/* TOKENS: a vector per token from one forward (MaskCLIP-style dense features).  out_tokens [batch * S,
+ * out_dim], S = revo_vit_seq_len: row b * S + s is, bit for bit, the row revo_vit_forward_regions writes for the region of
+ * image b whose bitmap allows token s alone (a softmax over one token is exactly 1, so the head reads the token's ln_post row
+ * itself; the head's fp32 GEMMs cut K the same way whatever the row count).  out_global [batch, out_dim] or NULL: the bits of
+ * revo_vit_forward.  Enqueued on `stream` like a forward; the rows pass through the region workspace 512 at a time.  Status -2
+ * before the device is touched: null handle, images or out_tokens, batch outside [1, max_batch], a bad image_dtype. */
+int32_t revo_vit_forward_tokens(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch, float* out_global,
+                                float* out_tokens, int32_t normalize, void* stream);
+/* DETECT: text-prompted regions on the device -- token vectors scored against prompt vectors, every cell given to the prompt
+ * that wins it, the label map cut into connected regions (the MaskCLIP construction; it stands where the reference hands
+ * its text prompt to a third-party detector, core_system.py:249-262).  The contract is numerical: nothing is claimed about
+ * detection quality on trained weights.  prompts: device [n_prompts, out_dim] fp32 (revo_text_forward's rows, or any vectors
+ * of the space), the last n_background of them background prompts; thresholds: HOST [n_prompts].  g = image_size /
+ * patch_size, c = gy * g + gx a cell, token use_cls + c of its image.
+ *   t[b, c]     the normalised token vector of cell c: revo_vit_forward_tokens' row with normalize = 1.  The class token
+ *               takes no part.
+ *   s[b, p, c]  the score of prompt p, normalised like every search query by the same kernel, against t[b, c]: the one fp32
+ *               fma chain of EXACTNESS -- the bits revo_search_range returns for prompt p against a gallery to which the
+ *               token vectors were appended with normalize = 0.
+ *   w[b, c]     the prompt with the largest s[b, ., c], compared in fp32 with -0 equal to +0; ties go to the lowest p; a NaN
+ *               score never wins (every score NaN: no winner).
+ *   label[b, c] = w if there is a winner, w < n_prompts - n_background and s[b, w, c] >= thresholds[w] (equality keeps the
+ *               cell; -inf is allowed), else -1.  Background prompts compete for cells and produce no region.
+ * A region is a maximal 4-connected set of cells of one image with equal label >= 0.  Its attributes: its prompt (the label);
+ * cells, its cell count; its inclusive cell box gx0, gy0, gx1, gy1; confidence, the largest s[b, label, c] over its cells
+ * (with +0 above -0, so that the bits are defined); first, its lowest cell index.  Regions with fewer than min_cells cells are
+ * dropped; per image the rest are ordered by (confidence desc with -0 equal to +0, first asc) and cut at max_regions; images
+ * ascend in the output.  bits [ceil(S / 32)] is the region's token bitmap in revo_vit_forward_regions' layout: only
+ * patch-token bits are set.  With with_vectors, vectors[r] is bit for bit what revo_vit_forward_regions returns for
+ * (region_image[r], bits[r]) with the same `normalize`; they come from the rows and logits of the call's one body forward.
+ * out_global [batch, out_dim] or NULL: the bits of revo_vit_forward.  Two calls give identical bytes.
+ * revo_vit_detect computes the result into the handle and writes the region count to the host *n_regions.  SYNCHRONOUS on
+ * `stream`, like revo_gallery_pairs: the host needs the count to run the regions' head.  revo_vit_detect_read copies regions
+ * [start, start + n) to host or device arrays (dst_on_device), each pointer NULL independently: region_image [n], region_prompt
+ * [n], boxes [n][4], cells [n], confidence [n], bits [n][ceil(S / 32)], vectors [n][out_dim] (status -2 when the result was
+ * computed without vectors).  revo_vit_detect_maps copies s ([batch][n_prompts][g * g]) and label ([batch][g * g]), each NULL
+ * independently.  The result lives in the handle until the next forward of any kind on it (revo_vit_forward, _regions, _tokens,
+ * _detect): after one, or with no result, both reads give status -2, as does a range past the end.
+ * Limits (status -2 before the device is touched, the outputs untouched, the message naming the argument): 1 <= n_prompts <=
+ * 64; 0 <= n_background < n_prompts; 1 <= min_cells; 1 <= max_regions <= g * g; g * g <= 1024; a NaN threshold, a null handle,
+ * images, prompts, thresholds or n_regions, a batch outside [1, max_batch].  Zero regions is not an error.  Every loop of the
+ * component labelling has a trip limit; one that is hit gives status -4 ("connected components did not converge").  The first
+ * call allocates a workspace for max_batch images (the token vectors: max_batch * S * out_dim floats). */
+int32_t revo_vit_detect(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch, const float* prompts,
+                        int32_t n_prompts, const float* thresholds, int32_t n_background, int32_t min_cells, int32_t max_regions,
+                        float* out_global, int32_t with_vectors, int32_t normalize, int64_t* n_regions, void* stream);
+int32_t revo_vit_detect_read(revo_vit* vit, int64_t start, int64_t n, int32_t* region_image, int32_t* region_prompt,
+                             int32_t* boxes, int32_t* cells, float* confidence, uint32_t* bits, float* vectors,
+                             int32_t dst_on_device);
+int32_t revo_vit_detect_maps(revo_vit* vit, float* scores, int32_t* labels, int32_t dst_on_device);
 /* Run-time telemetry of the LayerNorm folded into the GEMMs around it (batch-sized forwards: ln_1 / ln_2 are not kernels;
  * qkv / fc1 read A = bf16(x) UN-CENTRED and apply rstd * (acc - mean * csum) + b' in their epilogues).  The form is the same
  * function as LayerNorm-then-GEMM, but its rounding error grows with |mean| / std of a row (bf16(x) spends its 8 bits on
@@ -836,6 +886,21 @@ int32_t revo_op_pool_rows(const float* x, int64_t ldx, const float* logits, int3
 int32_t revo_op_pool_rows_masked(const float* x, int64_t ldx, const float* logits, const int32_t* region_image,
                                  const uint32_t* region_bits, int32_t n_regions, int32_t batch, int32_t seq, int32_t width,
                                  int32_t heads, float* u, void* stream);
+/* the kernels of revo_vit_detect without a tower (detect.hip; DETECT above is their contract):
+ *  - revo_op_detect_scores: tokens [rows][dim] and prompts [n_prompts][dim] fp32; prompts_norm [n_prompts][dim] receives the
+ *    prompts normalised as every search normalises its queries; scores[p * rows + r] = the fma chain over prompts_norm[p] and
+ *    tokens[r] (the token rows are used as given).  dim % 4 == 0, 1 <= n_prompts <= 64.  Enqueued on `stream`.
+ *  - revo_op_detect_regions: scores [batch][n_prompts][g * g] and thresholds [n_prompts] (DEVICE here) -> labels [batch][g * g],
+ *    counts [batch] (regions per image) and the regions of all images, image after image, in revo_vit_detect_read's arrays
+ *    (each sized for batch * max_regions regions; bits [.][ceil((g * g + use_cls) / 32)], cell c at bit use_cls + c); every
+ *    output but counts may be NULL.  A staging buffer lives for the length of the call, which is SYNCHRONOUS on `stream`;
+ *    status -4 as revo_vit_detect. */
+int32_t revo_op_detect_scores(const float* tokens, int64_t rows, const float* prompts, int32_t n_prompts, int32_t dim,
+                              float* prompts_norm, float* scores, void* stream);
+int32_t revo_op_detect_regions(const float* scores, int32_t batch, int32_t n_prompts, int32_t g, int32_t use_cls,
+                               const float* thresholds, int32_t n_background, int32_t min_cells, int32_t max_regions,
+                               int32_t* region_image, int32_t* region_prompt, int32_t* boxes, int32_t* cells, float* confidence,
+                               uint32_t* bits, int32_t* labels, int32_t* counts, void* stream);
 int32_t revo_op_rope(void* qkv_bf16, int64_t ld, const float* cos_sin, int32_t rows, int32_t seq, int32_t width,
                      int32_t heads, void* stream);
 int32_t revo_op_attention(const void* qkv_bf16, int64_t ld, void* out_bf16, int64_t ldo, int32_t batch, int32_t seq,

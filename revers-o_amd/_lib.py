@@ -47,6 +47,10 @@ SIGNATURES = {
     "revo_vit_destroy": (_i32, [_p]),
     "revo_vit_forward": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p]),
     "revo_vit_forward_regions": (_i32, [_p, _p, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _i32, _p]),
+    "revo_vit_forward_tokens": (_i32, [_p, _p, _i32, _i32, _p, _p, _i32, _p]),
+    "revo_vit_detect": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _i32, C.POINTER(C.c_int64), _p]),
+    "revo_vit_detect_read": (_i32, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i32]),
+    "revo_vit_detect_maps": (_i32, [_p, _p, _p, _i32]),
     "revo_vit_seq_len": (_i32, [_p]),
     "revo_vit_stats": (_i32, [_p, C.POINTER(C.c_double), _i32, _p]),
     "revo_text_create": (_i32, [C.POINTER(TextCfg), C.POINTER(Tensor), _i32, _i32, _i32, C.POINTER(_p)]),
@@ -106,6 +110,8 @@ SIGNATURES = {
     "revo_op_linear_f32": (_i32, [_i32, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "revo_op_pool_rows": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "revo_op_pool_rows_masked": (_i32, [_p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "revo_op_detect_scores": (_i32, [_p, _i64, _p, _i32, _i32, _p, _p, _p]),
+    "revo_op_detect_regions": (_i32, [_p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revo_op_rope": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p]),
     "revo_op_attention": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),
     "revo_op_attention_causal": (_i32, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i32, _p]),

@@ -13,7 +13,9 @@ What differs underneath:
 * GroundedSAM (``:205-318``) is third-party and out of scope: a detector callable can be
   injected (``detector=``); without one every image is one full-frame region, which
   is also what the reference's embedding of a region amounts to (``:406`` "Use global
-  for now": every region receives the global embedding).
+  for now": every region receives the global embedding).  ``detector="prompt"`` installs
+  the built-in ``PromptDetector`` instead: the text prompt scored against the image's
+  token vectors on the device.
 
 There is no CPU fallback: constructing the class without a GPU raises.
 """
@@ -56,6 +58,51 @@ class Regions:
         return len(self.xyxy)
 
 
+def split_prompt(text_prompt):
+    """``"person . car . building"`` -> ``["person", "car", "building"]``: the reference's prompt format (core_system.py:237,
+    :416), phrases separated by `` . ``; a closing `` .`` and empty phrases are dropped, the order and repeats are kept."""
+    text = (text_prompt or "").strip()
+    if text.endswith(" ."):
+        text = text[:-2]
+    return [p.strip() for p in text.split(" . ") if p.strip(" .")]
+
+
+class PromptDetector:
+    """The built-in detector (``SimpleReverso(detector="prompt")``): the prompt's phrases and the background prompts through
+    the text tower, then ``VitEngine.detect`` -- every patch cell goes to the phrase its token vector scores highest against,
+    the label map is cut into connected regions (include/revo.h, DETECT).  Called like any injected
+    detector, ``detector(pil, text_prompt) -> Regions``: pixel boxes, pixel masks (``regions.cell_masks``), ``class_names``
+    (the phrases), ``class_id`` and ``confidence``.  Not GroundedSAM, which stays out of scope; nothing is claimed about
+    detection quality on trained weights."""
+
+    def __init__(self, system, threshold=None, background_prompts=(), min_cells=1, max_regions=50):
+        self.system = system
+        self.threshold = None if threshold is None else float(threshold)
+        self.background_prompts = [str(p) for p in background_prompts]
+        self.min_cells, self.max_regions = int(min_cells), int(max_regions)
+        self.last = None                    # the engine-level result of the last call (cell boxes, bitmaps; device tensors)
+
+    def __call__(self, image, text_prompt):
+        s = self.system
+        pil = pp.to_pil(image)
+        phrases = split_prompt(text_prompt) or ["object"]
+        texts = phrases + self.background_prompts
+        if len(texts) > 64:
+            raise ValueError(f"a prompt holds at most 64 phrases, background prompts included (got {len(texts)})")
+        cfg = s.pe_model.cfg
+        prompts = s.embed_text(texts)
+        u8 = s._frames_u8([pil])
+        with s._lock:
+            det = s.pe_model.detect(u8, prompts, thresholds=self.threshold, n_background=len(self.background_prompts),
+                                    min_cells=self.min_cells, max_regions=min(self.max_regions, cfg.grid * cfg.grid),
+                                    with_vectors=False)
+        self.last = det
+        bits = det.bits.cpu().numpy()
+        return Regions(rg.cell_boxes(cfg, det.boxes.cpu().numpy(), pil.width, pil.height),
+                       mask=rg.cell_masks(cfg, bits, pil.width, pil.height), confidence=det.confidence.cpu().numpy(),
+                       class_id=det.prompt.cpu().numpy(), class_names=phrases)
+
+
 class SimpleReverso:
     """Simplified visual investigation system (MI355X-native hot path)."""
     # names of the databases create_database calls of this instance are building right now (two UI threads may overlap):
@@ -65,7 +112,7 @@ class SimpleReverso:
 
     def __init__(self, model_name=DEFAULT_VARIANT, checkpoint=None, device=0, db_root=DB_ROOT, max_batch=64,
                  detector=None, decode_workers=None, synthetic_seed=0, region_mode="global", device_resize=False,
-                 checkpoint_interval_s=30.0, skip_duplicates=None):
+                 checkpoint_interval_s=30.0, skip_duplicates=None, detect_threshold=None, background_prompts=()):
         print("🚀 Initializing Simple Revers-o...")
         if region_mode not in ("global", "crop", "pool"):
             raise ValueError("region_mode must be 'global' (the reference's behaviour, core_system.py:406), 'crop' or 'pool'")
@@ -87,7 +134,10 @@ class SimpleReverso:
         self.checkpoint_interval_s = float(checkpoint_interval_s)     # a checkpoint writes the vectors added since the last one (a delta shard)
         self.db_root = db_root
         self.max_batch = int(max_batch)
-        self.detector = detector
+        # a callable (image, text_prompt) -> Regions, None (every image is one full-frame region), or "prompt": the built-in
+        # PromptDetector -- the prompt's phrases scored against the image's token vectors on the device (a second forward per
+        # image in the region modes of create_database); detect_threshold and background_prompts are its settings
+        self.detector = PromptDetector(self, detect_threshold, background_prompts) if detector == "prompt" else detector
         # decode threads of a gallery build.  None = by mode (create_database): MORE threads are not better -- PIL's
         # RGBX -> RGB packing of a decoded frame runs under the GIL (0.35 ms per 640 x 480 frame), and the ingest thread,
         # which has to keep the device's queue full, waits its turn behind every thread that wants it: measured on

@@ -325,6 +325,64 @@ extern "C" int32_t revo_op_pool_rows_masked(const float* x, int64_t ldx, const f
     API_END
 }
 
+// ---- the kernels of revo_vit_detect without a tower (detect.hip)
+extern "C" int32_t revo_op_detect_scores(const float* tokens, int64_t rows, const float* prompts, int32_t n_prompts, int32_t dim,
+                                         float* prompts_norm, float* scores, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(rows >= 0 && rows < (1ll << 31), "op_detect_scores: rows must be in [0, 2^31)");
+    REVO_REQUIRE(n_prompts >= 1 && n_prompts <= revo::DETECT_MAX_PROMPTS, "op_detect_scores: n_prompts must be in [1, 64]");
+    REVO_REQUIRE(dim >= 4 && dim % 4 == 0, "op_detect_scores: dim must be a positive multiple of 4");
+    REVO_REQUIRE(prompts && prompts_norm && (rows == 0 || (tokens && scores)), "op_detect_scores: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    CHECK_RC(revo::launch_l2norm_rows(prompts, dim, prompts_norm, dim, nullptr, 0, n_prompts, dim, st));
+    return revo::launch_detect_scores(tokens, dim, (int)rows, 0, (int)rows, rows, prompts_norm, n_prompts, dim, scores, st);
+    API_END
+}
+extern "C" int32_t revo_op_detect_regions(const float* scores, int32_t batch, int32_t n_prompts, int32_t g, int32_t use_cls,
+                                          const float* thresholds, int32_t n_background, int32_t min_cells, int32_t max_regions,
+                                          int32_t* region_image, int32_t* region_prompt, int32_t* boxes, int32_t* cells,
+                                          float* confidence, uint32_t* bits, int32_t* labels, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(batch >= 0, "op_detect_regions: negative batch");
+    REVO_REQUIRE(g >= 1 && (int64_t)g * g <= revo::DETECT_MAX_CELLS, "op_detect_regions: g * g must be in [1, 1024]");
+    REVO_REQUIRE(n_prompts >= 1 && n_prompts <= revo::DETECT_MAX_PROMPTS, "op_detect_regions: n_prompts must be in [1, 64]");
+    REVO_REQUIRE(n_background >= 0 && n_background < n_prompts, "op_detect_regions: n_background must be in [0, n_prompts)");
+    REVO_REQUIRE(min_cells >= 1, "op_detect_regions: min_cells must be at least 1");
+    REVO_REQUIRE(max_regions >= 1 && max_regions <= g * g, "op_detect_regions: max_regions must be in [1, g * g]");
+    REVO_REQUIRE(use_cls == 0 || use_cls == 1, "op_detect_regions: use_cls must be 0 or 1");
+    REVO_REQUIRE(thresholds && counts && (batch == 0 || scores), "op_detect_regions: null scores, thresholds or counts");
+    if (batch == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int words = (g * g + use_cls + 31) / 32;
+    // the images' slots and the error word: a buffer for the length of the call, which ends synchronised
+    uint32_t* ws = nullptr;
+    const size_t stage_words = revo::detect_stage_words(batch, max_regions, words);
+    REVO_HIP_CHECK(hipMalloc((void**)&ws, (stage_words + 1) * 4));
+    int32_t err = 0;
+    auto run = [&]() -> int {
+        REVO_HIP_CHECK(hipMemsetAsync(ws + stage_words, 0, 4, st));
+        revo::DetectRegionArgs a{};
+        a.scores = scores; a.batch = batch; a.P = n_prompts; a.g = g; a.cls = use_cls; a.thr = thresholds; a.nbg = n_background;
+        a.min_cells = min_cells; a.max_regions = max_regions; a.labels = labels; a.counts = counts; a.stage = ws;
+        a.err = (int*)(ws + stage_words);
+        CHECK_RC(revo::launch_detect_regions(a, st));
+        CHECK_RC(revo::launch_detect_compact(counts, ws, batch, max_regions, words, region_image, region_prompt, boxes, cells,
+                                             confidence, bits, st));
+        REVO_HIP_CHECK(hipMemcpyAsync(&err, ws + stage_words, 4, hipMemcpyDeviceToHost, st));
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    };
+    const int rc = run();
+    (void)hipFree(ws);
+    if (rc) return rc;
+    if (err != 0) {
+        revo_set_error("op_detect_regions: connected components did not converge");
+        return -4;
+    }
+    return 0;
+    API_END
+}
+
 extern "C" int32_t revo_op_rope(void* qkv, int64_t ld, const float* cs, int32_t rows, int32_t seq, int32_t width,
                                 int32_t heads, void* stream) {
     API_BEGIN

@@ -791,4 +791,28 @@ int launch_topk_merge_strided(const float* scores, long score_part_stride, const
                               int Q, int k, int has_thr, float thr, float* out_scores, long long* out_idx, int* out_counts,
                               hipStream_t st, const MergeCert* mc = nullptr);
 
+// ---- text-prompted regions (revo_vit_detect; detect.hip)
+constexpr int DETECT_MAX_PROMPTS = 64;
+constexpr int DETECT_MAX_CELLS = 1024;       // g * g of the region kernel: one workgroup holds an image's cells in LDS
+// scores[(b * P + p) * cells + c] = the fp32 chain of every re-score over prompts[p] ([P][D], already normalised) and token row
+// (b * S + cls + c) of tok ([.][ldt]); rows = images * cells
+int launch_detect_scores(const float* tok, long ldt, int S, int cls, int cells, long rows, const float* prompts, int P, int D,
+                         float* scores, hipStream_t st);
+struct DetectRegionArgs {
+    const float* scores;          // [batch][P][g * g]
+    int batch, P, g, cls;
+    const float* thr;             // [P] device
+    int nbg, min_cells, max_regions;
+    int* labels;                  // [batch][g * g] out (optional)
+    int* counts;                  // [batch] out: regions emitted per image
+    uint32_t* stage;              // detect_stage_words(): the images' slots -- prompt, cells, confidence, box, bitmap of slot
+                                  // b * max_regions + k, one array after the other
+    int* err;                     // device word, zeroed by the caller: != 0 afterwards = a loop hit its trip limit
+};
+size_t detect_stage_words(int batch, int max_regions, int words);
+int launch_detect_regions(const DetectRegionArgs& a, hipStream_t st);
+// the images' slots -> consecutive result rows (images ascending); every output pointer may be null
+int launch_detect_compact(const int* counts, const uint32_t* stage, int batch, int max_regions, int words, int* r_img, int* r_prompt,
+                          int* r_box, int* r_cells, float* r_conf, uint32_t* r_bits, hipStream_t st);
+
 }  // namespace revo

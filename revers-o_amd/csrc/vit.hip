@@ -1,4 +1,5 @@
-// The image tower of the C ABI (include/revo.h): its handle, the embed forward schedule and the region embeddings.  The blocks
+// The image tower of the C ABI (include/revo.h): its handle, the embed forward schedule, the region embeddings, the dense token
+// vectors and the text-prompted regions built on them (kernels: detect.hip).  The blocks
 // are tower.h body_blocks with the 2-D rotary embedding in the qkv epilogue and attention over all keys; the head (ln_post,
 // attention pool, proj, normalisation) is fp32 (head.hip says why).
 #include <algorithm>
@@ -53,6 +54,19 @@ struct revo_vit : TowerCore {
     float *rg_u = nullptr, *rg_att = nullptr, *rg_o = nullptr, *rg_h = nullptr, *rg_m = nullptr, *rg_feat = nullptr;
     int32_t* rg_img = nullptr; uint32_t* rg_bits = nullptr;
     PinnedStage rg_pin;
+    // text-prompted regions (revo_vit_detect): allocated by the first call, sized for max_batch images, 64 prompts and g * g
+    // regions per image; the region vectors grow with the largest result
+    struct Detect {
+        float *tok = nullptr, *scores = nullptr, *prompts = nullptr, *thr = nullptr;
+        int32_t *labels = nullptr, *counts = nullptr;                 // counts[max_batch]: the region kernel's error word
+        uint32_t* stage = nullptr;
+        int32_t *r_img = nullptr, *r_prompt = nullptr, *r_box = nullptr, *r_cells = nullptr;
+        float* r_conf = nullptr; uint32_t* r_bits = nullptr;
+        float* r_vec = nullptr; size_t r_vec_rows = 0;
+        bool valid = false, has_vec = false;
+        int64_t n = 0; int batch = 0, P = 0;
+    } det;
+    ~revo_vit() { if (det.r_vec) (void)hipFree(det.r_vec); }
 };
 
 extern "C" int32_t revo_vit_create(const revo_vit_cfg* cfg, const revo_tensor* weights, int32_t n_weights,
@@ -246,14 +260,16 @@ extern "C" int32_t revo_debug_stream_in_planes(const revo_vit* v, int32_t batch)
 // The head behind the pooled rows u [R][pool_heads][W]: value and output projection, the pool's LayerNorm and MLP, proj, L2 --
 // for the R images of a forward or for R regions (revo_vit_forward_regions).  A row's result does not depend on R or on
 // the other rows (head.hip: the skinny GEMM cuts K the same way whatever M is).
-static int pool_head_tail(revo_vit* v, int R, const float* u, float* att, float* o, float* h, float* m, float* feat_ws,
-                          float* out, int32_t normalize, hipStream_t st) {
+// (u_ld / u_group: the distance between two rows of u and between two heads' rows; a one-token region's pooled row is its ln_post
+//  row for every head -- a softmax over one token is exactly 1 -- so the token vectors read the rows themselves: W and 0)
+static int pool_head_tail(revo_vit* v, int R, const float* u, long u_ld, long u_group, float* att, float* o, float* h, float* m,
+                          float* feat_ws, float* out, int32_t normalize, hipStream_t st) {
     using namespace revo;
     const revo_vit_cfg& c = v->cfg;
-    const int W = c.width, D = c.out_dim, PM = v->PM, PH = c.pool_heads;
+    const int W = c.width, D = c.out_dim, PM = v->PM;
     { ProfScope ps("gemm_pool", st);
       // values: head h's output columns from head h's pooled row
-      CHECK_RC(launch_gemm_f32_skinny(0, u, (long)PH * W, W, v->phd, v->w_v, W, v->b_v, R, W, W, att, W, st));
+      CHECK_RC(launch_gemm_f32_skinny(0, u, u_ld, u_group, v->phd, v->w_v, W, v->b_v, R, W, W, att, W, st));
       CHECK_RC(launch_gemm_f32_skinny(0, att, W, 0, 0, v->w_po, W, v->b_po, R, W, W, o, W, st)); }
     { ProfScope ps("layernorm", st);
       CHECK_RC(launch_layernorm(o, W, v->pln_w, v->pln_b, c.ln_eps, R, W, h, W, 0, st)); }
@@ -276,6 +292,7 @@ static int vit_forward(revo_vit* v, const void* images, int32_t image_dtype, int
     const int W = c.width, S = v->S, PH = c.pool_heads;
     const int rows = B * S;
     using namespace revo;
+    v->det.valid = false;                 // a detect result lives until the next forward of any kind
 
     {   // K1 + K2: patch embed GEMM in split precision (patchify_kernel: the row of a patch holds its values twice --
         // exact integers for u8 images -- or as hi | hi | lo; the weight rows are hi | lo | hi of w / 255), position add, cls row
@@ -312,7 +329,7 @@ static int vit_forward(revo_vit* v, const void* images, int32_t image_dtype, int
     if (!with_head) return 0;             // revo_vit_forward_regions without out_global: the rows and the logits are all it needs
     { ProfScope ps("pool_attention", st);
       CHECK_RC(launch_pool_head_rows(v->x, W, B, S, W, PH, v->pool_logits, v->pool_u, st)); }
-    CHECK_RC(pool_head_tail(v, B, v->pool_u, v->pool_att, v->pool_o, v->pool_h, v->pool_m, v->feat, out, normalize, st));
+    CHECK_RC(pool_head_tail(v, B, v->pool_u, (long)PH * W, W, v->pool_att, v->pool_o, v->pool_h, v->pool_m, v->feat, out, normalize, st));
     return 0;
 }
 
@@ -396,11 +413,191 @@ extern "C" int32_t revo_vit_forward_regions(revo_vit* v, const void* images, int
             float* out = out_regions + (size_t)(s0 + r0) * D;
             { ProfScope ps("pool_regions", st);
               CHECK_RC(launch_pool_head_rows_masked(v->x, W, batch, S, W, PH, v->pool_logits, v->rg_img + r0, cb, R, v->rg_u, st)); }
-            CHECK_RC(pool_head_tail(v, R, v->rg_u, v->rg_att, v->rg_o, v->rg_h, v->rg_m, v->rg_feat, out, normalize, st));
+            CHECK_RC(pool_head_tail(v, R, v->rg_u, (long)PH * W, W, v->rg_att, v->rg_o, v->rg_h, v->rg_m, v->rg_feat, out, normalize, st));
             { ProfScope ps("pool_regions", st);
               CHECK_RC(launch_zero_empty_regions(cb, R, S, D, out, st)); }
         }
     }
     return 0;
+    API_END
+}
+
+// ---------------------------------------------------------- dense token vectors ----
+// The head of `rows` consecutive ln_post rows of the last body forward, each as the one-token region it is: pool_head_tail reads
+// v->x itself, REGION_CHUNK rows at a time through the region workspace.
+static int token_head(revo_vit* v, long rows, float* out, int32_t normalize, hipStream_t st) {
+    const int W = v->cfg.width, D = v->cfg.out_dim;
+    for (long r0 = 0; r0 < rows; r0 += REGION_CHUNK) {
+        const int R = (int)std::min<long>(REGION_CHUNK, rows - r0);
+        CHECK_RC(pool_head_tail(v, R, v->x + (size_t)r0 * W, W, 0, v->rg_att, v->rg_o, v->rg_h, v->rg_m, v->rg_feat,
+                                out + (size_t)r0 * D, normalize, st));
+    }
+    return 0;
+}
+
+extern "C" int32_t revo_vit_forward_tokens(revo_vit* v, const void* images, int32_t image_dtype, int32_t batch, float* out_global,
+                                           float* out_tokens, int32_t normalize, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(v && images, "vit_forward_tokens: null handle or images");
+    REVO_REQUIRE(out_tokens, "vit_forward_tokens: null out_tokens");
+    REVO_REQUIRE(batch >= 1 && batch <= v->max_batch, "vit_forward_tokens: batch exceeds max_batch of the handle");
+    REVO_REQUIRE(image_dtype == 0 || image_dtype == 1, "vit_forward_tokens: image_dtype must be 0 (f32) or 1 (u8)");
+    REVO_ON_DEVICE(v->device);
+    hipStream_t st = (hipStream_t)stream;
+    CHECK_RC(region_workspace(v));
+    CHECK_RC(vit_forward(v, images, image_dtype, batch, out_global, normalize, st, out_global != nullptr));
+    if (v->debug_layers != -1) return 0;
+    ProfScope ps("token_head", st);
+    return token_head(v, (long)batch * v->S, out_tokens, normalize, st);
+    API_END
+}
+
+// ------------------------------------------------------- text-prompted regions ----
+static int detect_workspace(revo_vit* v) {
+    revo_vit::Detect& d = v->det;
+    if (d.r_bits) return 0;
+    const size_t B = (size_t)v->max_batch, G2 = (size_t)v->G2, D = (size_t)v->cfg.out_dim, words = ((size_t)v->S + 31) / 32;
+    const size_t Rmax = B * G2;
+    CHECK_RC(v->dalloc(&d.tok, B * v->S * D));
+    CHECK_RC(v->dalloc(&d.scores, B * revo::DETECT_MAX_PROMPTS * G2));
+    CHECK_RC(v->dalloc(&d.prompts, (size_t)revo::DETECT_MAX_PROMPTS * D));
+    CHECK_RC(v->dalloc(&d.thr, (size_t)revo::DETECT_MAX_PROMPTS));
+    CHECK_RC(v->dalloc(&d.labels, Rmax));
+    CHECK_RC(v->dalloc(&d.counts, B + 1));
+    CHECK_RC(v->dalloc(&d.stage, revo::detect_stage_words((int)B, (int)G2, (int)words)));
+    CHECK_RC(v->dalloc(&d.r_img, Rmax));
+    CHECK_RC(v->dalloc(&d.r_prompt, Rmax));
+    CHECK_RC(v->dalloc(&d.r_box, Rmax * 4));
+    CHECK_RC(v->dalloc(&d.r_cells, Rmax));
+    CHECK_RC(v->dalloc(&d.r_conf, Rmax));
+    CHECK_RC(v->dalloc(&d.r_bits, Rmax * words));           // last: marks the workspace complete
+    return 0;
+}
+
+extern "C" int32_t revo_vit_detect(revo_vit* v, const void* images, int32_t image_dtype, int32_t batch, const float* prompts,
+                                   int32_t n_prompts, const float* thresholds, int32_t n_background, int32_t min_cells,
+                                   int32_t max_regions, float* out_global, int32_t with_vectors, int32_t normalize,
+                                   int64_t* n_regions, void* stream) {
+    API_BEGIN
+    // everything that can be refused is refused before the device is touched
+    REVO_REQUIRE(v && images, "vit_detect: null handle or images");
+    REVO_REQUIRE(prompts, "vit_detect: null prompts");
+    REVO_REQUIRE(thresholds, "vit_detect: null thresholds");
+    REVO_REQUIRE(n_regions, "vit_detect: null n_regions");
+    REVO_REQUIRE(batch >= 1 && batch <= v->max_batch, "vit_detect: batch must be in [1, max_batch of the handle]");
+    REVO_REQUIRE(image_dtype == 0 || image_dtype == 1, "vit_detect: image_dtype must be 0 (f32) or 1 (u8)");
+    REVO_REQUIRE(n_prompts >= 1 && n_prompts <= revo::DETECT_MAX_PROMPTS, "vit_detect: n_prompts must be in [1, 64]");
+    REVO_REQUIRE(n_background >= 0 && n_background < n_prompts, "vit_detect: n_background must be in [0, n_prompts)");
+    REVO_REQUIRE(min_cells >= 1, "vit_detect: min_cells must be at least 1");
+    REVO_REQUIRE(v->G2 <= revo::DETECT_MAX_CELLS, "vit_detect: a grid of more than 1024 cells is not supported");
+    REVO_REQUIRE(max_regions >= 1 && max_regions <= v->G2, "vit_detect: max_regions must be in [1, g * g = " + std::to_string(v->G2) + "]");
+    for (int32_t p = 0; p < n_prompts; ++p)
+        REVO_REQUIRE(!std::isnan(thresholds[p]), "vit_detect: thresholds[" + std::to_string(p) + "] is NaN");
+    REVO_REQUIRE(v->debug_layers == -1, "vit_detect: the handle is set to stop its forward early (debug layers)");
+    REVO_ON_DEVICE(v->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    revo_vit::Detect& d = v->det;
+    d.valid = false;
+    CHECK_RC(region_workspace(v));
+    CHECK_RC(detect_workspace(v));
+    const revo_vit_cfg& c = v->cfg;
+    const int W = c.width, D = c.out_dim, S = v->S, G2 = v->G2, PH = c.pool_heads, cls = c.use_cls ? 1 : 0;
+    const int words = (S + 31) / 32;
+    // the call's one body forward (the global head as revo_vit_forward runs it, or none), then the normalised token vectors
+    CHECK_RC(vit_forward(v, images, image_dtype, batch, out_global, normalize, st, out_global != nullptr));
+    { ProfScope ps("token_head", st);
+      CHECK_RC(token_head(v, (long)batch * S, d.tok, 1, st)); }
+    // prompts through the query normalisation of every search; thresholds to the device (the call is synchronous)
+    { ProfScope ps("detect_scores", st);
+      CHECK_RC(launch_l2norm_rows(prompts, D, d.prompts, D, nullptr, 0, n_prompts, D, st));
+      REVO_HIP_CHECK(hipMemcpyAsync(d.thr, thresholds, (size_t)n_prompts * 4, hipMemcpyHostToDevice, st));
+      CHECK_RC(launch_detect_scores(d.tok, D, S, cls, G2, (long)batch * G2, d.prompts, n_prompts, D, d.scores, st)); }
+    std::vector<int32_t> h((size_t)batch + 1);
+    { ProfScope ps("detect_regions", st);
+      REVO_HIP_CHECK(hipMemsetAsync(d.counts + v->max_batch, 0, 4, st));
+      DetectRegionArgs a{};
+      a.scores = d.scores; a.batch = batch; a.P = n_prompts; a.g = c.image_size / c.patch_size; a.cls = cls; a.thr = d.thr;
+      a.nbg = n_background; a.min_cells = min_cells; a.max_regions = max_regions; a.labels = d.labels; a.counts = d.counts;
+      a.stage = d.stage; a.err = d.counts + v->max_batch;
+      CHECK_RC(launch_detect_regions(a, st));
+      CHECK_RC(launch_detect_compact(d.counts, d.stage, batch, max_regions, words, d.r_img, d.r_prompt, d.r_box, d.r_cells,
+                                     d.r_conf, d.r_bits, st)); }
+    REVO_HIP_CHECK(hipMemcpyAsync(h.data(), d.counts, (size_t)batch * 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(h.data() + batch, d.counts + v->max_batch, 4, hipMemcpyDeviceToHost, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
+    if (h[batch] != 0) {
+        revo_set_error("vit_detect: connected components did not converge");
+        return -4;
+    }
+    int64_t total = 0;
+    for (int b = 0; b < batch; ++b) {
+        REVO_REQUIRE(h[b] >= 0 && h[b] <= max_regions, "vit_detect: internal: inconsistent region counts");
+        total += h[b];
+    }
+    if (with_vectors && total > 0) {
+        // the regions' vectors from the rows and logits of the same forward: the masked pool over the device bitmaps
+        if (d.r_vec_rows < (size_t)total) {
+            if (d.r_vec) REVO_HIP_CHECK(hipFree(d.r_vec));
+            d.r_vec = nullptr; d.r_vec_rows = 0;
+            REVO_HIP_CHECK(hipMalloc((void**)&d.r_vec, (size_t)total * D * 4));
+            d.r_vec_rows = (size_t)total;
+        }
+        for (int64_t r0 = 0; r0 < total; r0 += REGION_CHUNK) {
+            const int R = (int)std::min<int64_t>(REGION_CHUNK, total - r0);
+            { ProfScope ps("pool_regions", st);
+              CHECK_RC(launch_pool_head_rows_masked(v->x, W, batch, S, W, PH, v->pool_logits, d.r_img + r0,
+                                                    d.r_bits + (size_t)r0 * words, R, v->rg_u, st)); }
+            CHECK_RC(pool_head_tail(v, R, v->rg_u, (long)PH * W, W, v->rg_att, v->rg_o, v->rg_h, v->rg_m, v->rg_feat,
+                                    d.r_vec + (size_t)r0 * D, normalize, st));
+        }
+        REVO_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    d.n = total; d.batch = batch; d.P = n_prompts; d.has_vec = with_vectors != 0;
+    d.valid = true;
+    *n_regions = total;
+    return 0;
+    API_END
+}
+
+template <class T> static int detect_copy(void* dst, const T* src, size_t count, int dst_on_device) {
+    if (!dst || count == 0) return 0;
+    REVO_HIP_CHECK(hipMemcpy(dst, src, count * sizeof(T), dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int32_t revo_vit_detect_read(revo_vit* v, int64_t start, int64_t n, int32_t* region_image, int32_t* region_prompt,
+                                        int32_t* boxes, int32_t* cells, float* confidence, uint32_t* bits, float* vectors,
+                                        int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(v, "vit_detect_read: null handle");
+    REVO_REQUIRE(start >= 0 && n >= 0, "vit_detect_read: negative start or count");
+    const revo_vit::Detect& d = v->det;
+    REVO_REQUIRE(d.valid, "vit_detect_read: no result (call revo_vit_detect again after another forward)");
+    REVO_REQUIRE(start + n <= d.n, "vit_detect_read: range past the result's " + std::to_string(d.n) + " regions");
+    REVO_REQUIRE(!vectors || d.has_vec, "vit_detect_read: the result was computed without vectors");
+    if (n == 0) return 0;
+    REVO_ON_DEVICE(v->device);
+    const size_t words = ((size_t)v->S + 31) / 32, D = (size_t)v->cfg.out_dim, s = (size_t)start, m = (size_t)n;
+    CHECK_RC(detect_copy(region_image, d.r_img + s, m, dst_on_device));
+    CHECK_RC(detect_copy(region_prompt, d.r_prompt + s, m, dst_on_device));
+    CHECK_RC(detect_copy(boxes, d.r_box + s * 4, m * 4, dst_on_device));
+    CHECK_RC(detect_copy(cells, d.r_cells + s, m, dst_on_device));
+    CHECK_RC(detect_copy(confidence, d.r_conf + s, m, dst_on_device));
+    CHECK_RC(detect_copy(bits, d.r_bits + s * words, m * words, dst_on_device));
+    if (vectors) CHECK_RC(detect_copy(vectors, d.r_vec + s * D, m * D, dst_on_device));
+    return 0;
+    API_END
+}
+
+extern "C" int32_t revo_vit_detect_maps(revo_vit* v, float* scores, int32_t* labels, int32_t dst_on_device) {
+    API_BEGIN
+    REVO_REQUIRE(v, "vit_detect_maps: null handle");
+    const revo_vit::Detect& d = v->det;
+    REVO_REQUIRE(d.valid, "vit_detect_maps: no result (call revo_vit_detect again after another forward)");
+    if (!scores && !labels) return 0;
+    REVO_ON_DEVICE(v->device);
+    CHECK_RC(detect_copy(scores, d.scores, (size_t)d.batch * d.P * v->G2, dst_on_device));
+    return detect_copy(labels, d.labels, (size_t)d.batch * v->G2, dst_on_device);
     API_END
 }

@@ -10,6 +10,7 @@ the reference does at
 """
 import contextlib
 import ctypes as C
+import dataclasses
 import json
 import threading
 
@@ -69,6 +70,28 @@ class _Handle:
 def _need_hooks(engine, what):
     if not engine.experiments:
         raise _lib.RevoError(f"{what} is a parity-test hook of librevo_exp.so: create the engine with experiments=True")
+
+
+@dataclasses.dataclass
+class Detections:
+    """The result of :meth:`VitEngine.detect` (include/revo.h, DETECT): one entry per region, images ascending, device
+    tensors.  ``image`` / ``prompt`` / ``cells`` int32 ``[n]``, ``boxes`` int32 ``[n, 4]`` (gx0, gy0, gx1, gy1, inclusive, in
+    cells), ``confidence`` fp32 ``[n]``, ``bits`` int32 ``[n, ceil(S / 32)]`` (the uint32 token bitmaps reinterpreted: what
+    :meth:`VitEngine.embed_regions` takes), ``vectors`` fp32 ``[n, out_dim]`` or ``None``; with maps, ``scores`` fp32
+    ``[B, P, g * g]`` and ``labels`` int32 ``[B, g * g]``; ``global_vectors`` fp32 ``[B, out_dim]`` when asked for."""
+    image: torch.Tensor
+    prompt: torch.Tensor
+    boxes: torch.Tensor
+    cells: torch.Tensor
+    confidence: torch.Tensor
+    bits: torch.Tensor
+    vectors: torch.Tensor = None
+    scores: torch.Tensor = None
+    labels: torch.Tensor = None
+    global_vectors: torch.Tensor = None
+
+    def __len__(self):
+        return int(self.image.shape[0])
 
 
 class VitEngine(_Handle):
@@ -194,6 +217,87 @@ class VitEngine(_Handle):
                 if not whole and n:
                     out_r.index_copy_(0, sel.to(out_r.device), dst)
         return out_g, out_r
+
+    def embed_tokens(self, images, normalize=True, with_global=True):
+        """A vector per token from one forward per image (include/revo.h, TOKENS): returns ``(global, tokens)``, fp32
+        ``[B, out_dim]`` (exactly :meth:`embed`'s rows; ``None`` without ``with_global``) and fp32 ``[B, S, out_dim]``.
+        Token ``s`` of image ``b`` has, bit for bit, the vector :meth:`embed_regions` gives the region that allows token ``s``
+        alone.  Token 0 is the class token on towers that have one; patch ``(gy, gx)`` is token ``use_cls + gy * g + gx``."""
+        images, kind = self._images(images)
+        cfg = self.cfg
+        B = images.shape[0]
+        out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
+        out_t = torch.empty((B, cfg.seq, cfg.out_dim), dtype=torch.float32, device=images.device)
+        with self._lock, torch.cuda.device(self.device):
+            st = _lib.current_stream()
+            for s in range(0, B, self.max_batch):
+                e = min(B, s + self.max_batch)
+                _lib.check(self._lib.revo_vit_forward_tokens(
+                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(out_g[s:e]) if with_global else None,
+                    _lib.ptr(out_t[s:e]), int(bool(normalize)), st), "revo_vit_forward_tokens")
+        return out_g, out_t
+
+    def detect(self, images, prompts, thresholds=None, n_background=0, min_cells=1, max_regions=50, with_vectors=True,
+               with_maps=False, normalize=True, with_global=False):
+        """Text-prompted regions (include/revo.h, DETECT): every patch cell goes to the prompt vector its token vector scores
+        highest against, and the label map is cut into 4-connected regions.  ``prompts``: fp32 ``[P, out_dim]`` on this
+        device (``TextEngine.embed``'s rows, or any vectors of the space), the last ``n_background`` of them background
+        prompts that take cells and give no region; ``thresholds``: ``None`` (-inf for every prompt), a number, or ``P``
+        numbers.  Regions of fewer than ``min_cells`` cells are dropped; per image the best ``max_regions`` by
+        (confidence, lowest cell) are kept -- 50 is the reference's region cap.  Returns a :class:`Detections`: images
+        ascending, device tensors.  Synchronous.  The contract is numerical: nothing is claimed about detection quality."""
+        import numpy as np
+        images, kind = self._images(images)
+        cfg = self.cfg
+        _require_cuda(prompts, "prompts", self.device)
+        pr = prompts.detach().to(torch.float32).contiguous()
+        if pr.dim() != 2 or pr.shape[1] != cfg.out_dim:
+            raise ValueError(f"prompts must be [P, {cfg.out_dim}], got {tuple(pr.shape)}")
+        P = pr.shape[0]
+        if thresholds is None:
+            thr = np.full(P, -np.inf, dtype=np.float32)
+        else:
+            thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, dtype=np.float32), (P,)))
+        B, words, G2 = images.shape[0], (cfg.seq + 31) // 32, cfg.grid * cfg.grid
+        if B == 0:
+            raise ValueError("detect: images holds no image")
+        dev = images.device
+        parts = []
+        out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=dev) if with_global else None
+        with self._lock, torch.cuda.device(self.device):
+            st = _lib.current_stream()
+            for s in range(0, B, self.max_batch):
+                e = min(B, s + self.max_batch)
+                n = C.c_int64()
+                _lib.check(self._lib.revo_vit_detect(
+                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(pr), P, C.c_void_p(thr.ctypes.data), int(n_background),
+                    int(min_cells), int(max_regions), _lib.ptr(out_g[s:e]) if with_global else None, int(bool(with_vectors)),
+                    int(bool(normalize)), C.byref(n), st), "revo_vit_detect")
+                n = int(n.value)
+                d = Detections(
+                    image=torch.empty((n,), dtype=torch.int32, device=dev), prompt=torch.empty((n,), dtype=torch.int32, device=dev),
+                    boxes=torch.empty((n, 4), dtype=torch.int32, device=dev), cells=torch.empty((n,), dtype=torch.int32, device=dev),
+                    confidence=torch.empty((n,), dtype=torch.float32, device=dev),
+                    bits=torch.empty((n, words), dtype=torch.int32, device=dev),
+                    vectors=torch.empty((n, cfg.out_dim), dtype=torch.float32, device=dev) if with_vectors else None)
+                if n:
+                    _lib.check(self._lib.revo_vit_detect_read(
+                        self._h, 0, n, _lib.ptr(d.image), _lib.ptr(d.prompt), _lib.ptr(d.boxes), _lib.ptr(d.cells),
+                        _lib.ptr(d.confidence), _lib.ptr(d.bits), _lib.ptr(d.vectors), 1), "revo_vit_detect_read")
+                if with_maps:
+                    d.scores = torch.empty((e - s, P, G2), dtype=torch.float32, device=dev)
+                    d.labels = torch.empty((e - s, G2), dtype=torch.int32, device=dev)
+                    _lib.check(self._lib.revo_vit_detect_maps(self._h, _lib.ptr(d.scores), _lib.ptr(d.labels), 1),
+                               "revo_vit_detect_maps")
+                d.image += s
+                parts.append(d)
+        if len(parts) == 1:
+            out = parts[0]
+        else:
+            cat = lambda name: (None if getattr(parts[0], name) is None else torch.cat([getattr(p, name) for p in parts]))
+            out = Detections(**{f.name: cat(f.name) for f in dataclasses.fields(Detections) if f.name != "global_vectors"})
+        out.global_vectors = out_g
+        return out
 
     def ln_fold_stats(self, reset=False):
         """Telemetry of the LayerNorm folded into qkv / fc1 (include/revo.h revo_vit_stats; synchronises the current stream):

@@ -19,7 +19,7 @@ import math
 
 import numpy as np
 
-__all__ = ["token_masks", "full_mask", "words_per_region"]
+__all__ = ["token_masks", "full_mask", "words_per_region", "cell_masks", "cell_boxes"]
 
 
 def words_per_region(cfg):
@@ -106,3 +106,46 @@ def token_masks(cfg, regions, width, height, min_cover=0.5, include_cls=False):
         if include_cls and cfg.use_cls:
             allow[r, 0] = True
     return _pack(allow)
+
+
+def _unpack_cells(cfg, bits):
+    """uint32 [R, ceil(S / 32)] -> bool [R, g, g]: the patch-token bits (the class token's bit is dropped)"""
+    g, first = int(cfg.grid), 1 if cfg.use_cls else 0
+    b = np.ascontiguousarray(np.asarray(bits))
+    b = b.view(np.uint32) if b.dtype == np.int32 else b.astype(np.uint32, copy=False)
+    if b.ndim != 2 or b.shape[1] != words_per_region(cfg):
+        raise ValueError(f"bits must be [R, {words_per_region(cfg)}], got {b.shape}")
+    allow = ((b[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)).astype(bool).reshape(b.shape[0], -1)
+    return allow[:, first:first + g * g].reshape(b.shape[0], g, g)
+
+
+def cell_masks(cfg, bits, width, height):
+    """The inverse of :func:`token_masks`' pixel -> cell rule: token bitmaps ``uint32 [R, ceil(S / 32)]`` (a detection's
+    ``bits``; int32 words are reinterpreted) -> boolean pixel masks ``[R, height, width]`` of a ``width x height`` source
+    image.  Pixel ``(px, py)`` is set iff cell ``(px * g // width, py * g // height)`` is; the class token's bit is ignored.
+    For ``width, height >= g`` every cell holds a pixel and ``token_masks(cfg, cell_masks(cfg, bits, w, h), w, h) == bits``
+    (patch bits).  When an axis has fewer pixels than cells, the cells no pixel maps to vanish: the mask cannot show them,
+    and a region made only of such cells gives an empty mask."""
+    width, height, g = int(width), int(height), int(cfg.grid)
+    if width <= 0 or height <= 0:
+        raise ValueError("cell_masks: width and height must be positive")
+    cells = _unpack_cells(cfg, bits)
+    cx, _ = _axis_cells(width, g)
+    cy, _ = _axis_cells(height, g)
+    return cells[:, cy[:, None], cx[None, :]]
+
+
+def cell_boxes(cfg, boxes, width, height):
+    """Inclusive cell boxes ``[R, 4]`` (gx0, gy0, gx1, gy1: a detection's ``boxes``) -> source-pixel ``xyxy`` ``int64 [R, 4]``
+    by the same integer map: ``x0`` is the first pixel of column ``gx0``, ``x1`` one past the last pixel of column ``gx1``
+    (half-open, like the full-frame box ``[0, 0, width, height]``), so the box encloses :func:`cell_masks`' pixels.  Pixel
+    ``px`` lies in column ``gx`` iff ``ceil(gx * width / g) <= px < ceil((gx + 1) * width / g)``.  When an axis has fewer
+    pixels than cells a box of cells without a pixel is empty (``x1 == x0``)."""
+    width, height, g = int(width), int(height), int(cfg.grid)
+    if width <= 0 or height <= 0:
+        raise ValueError("cell_boxes: width and height must be positive")
+    b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    if b.size and (b.min() < 0 or b.max() >= g or (b[:, 0] > b[:, 2]).any() or (b[:, 1] > b[:, 3]).any()):
+        raise ValueError(f"cell_boxes: boxes must be inclusive cell ranges inside the {g} x {g} grid")
+    start = lambda c, n: -((-c * n) // g)                     # ceil(c * n / g): the first pixel of cell c
+    return np.stack([start(b[:, 0], width), start(b[:, 1], height), start(b[:, 2] + 1, width), start(b[:, 3] + 1, height)], axis=1)
