@@ -605,6 +605,56 @@ int32_t revo_search_maxsim(revo_gallery* g, const float* queries, int32_t n_vect
 int32_t revo_search_mmr(revo_gallery* g, const float* queries, int32_t n_queries, int32_t k, int32_t candidates,
                         float diversity, int32_t has_threshold, float threshold, int64_t index_offset, float* scores,
                         float* mmr_values, int64_t* indices, int32_t* counts, void* stream);
+/* ---- hybrid queries: several searches fused into one result by rank or by normalised score (the prefetch + fusion query of
+ * the vector database the reference sits on: "frames that look like this picture AND match these words").  Text-image cosines
+ * of a CLIP model lie far below image-image cosines, so adding raw scores -- or searching with an averaged vector -- ranks by
+ * the image term alone; fusing ranks (reciprocal rank fusion, RRF) or per-list standardised scores (distribution-based score
+ * fusion, DBSF) does not.
+ * FUSION.  A fused search has m lists, 1 <= m <= 64 (n_lists); a call carries n >= 0 fused searches (n_searches), n * m < 2^31.
+ * queries: [n, m, dim] fp32 on the device, list j of search i is row i * m + j, normalised internally.  limit = C is every
+ * list's length, 1 <= C <= 1024 and m * C <= 8192; 1 <= k <= 1024 rows are returned.  method: 0 = RRF, 1 = DBSF.  rrf_k: fp32,
+ * finite and >= 0, used by RRF only.  weights: host float[m] or NULL (all 1), each finite and >= 0.  list_thresholds: host
+ * float[m] or NULL (none); -inf = no cut for that list, NaN is refused.  has_threshold / threshold cut on the fused score.
+ * List L_ij: exactly the result of revo_search_topk_large(g, q_ij, k = C, no threshold) -- the same rows, order (score desc,
+ * row asc), score bits, filter semantics (revo_search_set_filter, with its lifecycle).  An entry whose score is < t_j is
+ * dropped; a kept entry keeps its 1-based position r in the UNCUT list; the kept entries, in position order, are the list's
+ * members.
+ * Contribution of a member:
+ *   RRF   c = fl32(w_j / fl32(rrf_k + fl32(r))): two fp32 operations, the division correctly rounded.
+ *   DBSF  fp64 throughout, every operation rounded on its own, nothing contracted to an fma.  Over the members' scores in
+ *         position order (n_m of them): S = ((s_1 + s_2) + ...), mu = S / n_m, V = sum of (s - mu) * (s - mu) in the same
+ *         order, sd = sqrt(V / n_m).  If !(sd > 0): v = 0.5f; otherwise v = fl32((s - (mu - 3 * sd)) / (6 * sd)), not clamped.
+ *         c = fl32(w_j * v).
+ * Fused score F(row): the sequential fp32 sum of the row's contributions over j ascending, starting from the first one
+ * present.  A row in no list is not a candidate; a row whose only lists have weight 0 is a candidate with F = 0.
+ * Result: the candidates ordered by (F desc as fp32 numbers with -0 = +0, row asc), those with F < threshold cut, the first k.
+ * Outputs (device): scores [n, k] = F (its own bits, a -0 included), indices [n, k] = row + index_offset, counts [n]; optional
+ * (NULL allowed) ranks [n, k, m] int32 = r, or 0 where the row is no member of list j, and list_scores [n, k, m] fp32 = the
+ * row's score against q_ij under the one fma chain of EXACTNESS for every j, member or not (wherever revo_search_topk_large
+ * returns that row for that query it returns these bits).  Padding -inf / -1 / 0 / -inf.  Two calls give identical bytes.
+ * How: one inner large-k search over all n * m queries into the handle's workspace; one workgroup per fused search gathers
+ * the members as 64-bit words, sorts them in LDS (equal rows become one run), sums each run sequentially, sorts the runs by F
+ * and writes the first k; a second kernel scores the (result row, list) pairs.  Asynchronous on `stream`, no host round trip.
+ * Needs the fp32 master rows (keep_f32 = 0: status -2).  A null handle, queries (unless n = 0) or scores / indices / counts,
+ * n < 0, or m, C, m * C, k, method, rrf_k, a weight, a list threshold (NaN) or the fused threshold (NaN) outside the domains
+ * above give status -2 before the device is touched, the outputs untouched.  An empty gallery, or a filter that allows no
+ * row: counts = 0, all padding.  revo_search_stats after it: what the inner large-k search leaves.  A pairs or a range result
+ * held by the handle stays valid; the two-phase state is dropped as revo_search_topk_large drops it.
+ * revo_topk_fuse is the same fusion over lists the caller already holds -- the merged lists of a row-sharded search, lists
+ * from two galleries of the same items: scores and indices [n, m, C], counts [n, m], all on the device.  No gallery, no
+ * list_scores.  Entries past a list's count are ignored (a count above C counts as C).  Indices must lie in [0, 2^47);
+ * neither that nor duplicates are checked on the device.  Lists need not be sorted: the threshold cut is per entry, the
+ * statistics run over the kept entries in position order.  A row that occurs twice in one list contributes once per
+ * occurrence in position order, and ranks reports the first.  revo_search_fusion is this op applied to its inner lists, bit
+ * for bit.  Launches on the current device. */
+int32_t revo_search_fusion(revo_gallery* g, const float* queries, int32_t n_searches, int32_t n_lists, int32_t limit,
+                           int32_t method, float rrf_k, const float* weights, const float* list_thresholds, int32_t k,
+                           int32_t has_threshold, float threshold, int64_t index_offset, float* scores, int64_t* indices,
+                           int32_t* counts, int32_t* ranks, float* list_scores, void* stream);
+int32_t revo_topk_fuse(const float* scores, const int64_t* indices, const int32_t* counts, int32_t n_searches,
+                       int32_t n_lists, int32_t limit, int32_t method, float rrf_k, const float* weights,
+                       const float* list_thresholds, int32_t k, int32_t has_threshold, float threshold,
+                       float* out_scores, int64_t* out_indices, int32_t* out_counts, int32_t* out_ranks, void* stream);
 /* ---- the same search in two phases, for a gallery that is row-sharded over several GPUs / ranks (one shard per
  * handle).  The reference has a single process and a single collection (core_system.py:659-664); this is the
  * scale-out of that call.  Per rank:

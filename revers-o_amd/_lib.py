@@ -80,6 +80,8 @@ SIGNATURES = {
     "revo_search_discover": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
     "revo_search_maxsim": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p, _p, _p]),
     "revo_search_mmr": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i32, _f32, _i64, _p, _p, _p, _p, _p]),
+    "revo_search_fusion": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _i32, _i32, _f32, _i64, _p, _p, _p, _p, _p, _p]),
+    "revo_topk_fuse": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _i32, _i32, _f32, _p, _p, _p, _p, _p]),
     "revo_search_topk": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
     "revo_search_topk_large": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
     "revo_search_ksel": (_i32, [_i32]),

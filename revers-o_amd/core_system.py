@@ -654,6 +654,40 @@ class SimpleReverso:
             return f"❌ Error embedding the text query: {str(e)}", []
         return self._search_with_query(query, similarity_threshold, max_results, query_filter, group_by)
 
+    def search_by_text_and_image(self, text, max_results=5, candidates=100, fusion="rrf", text_weight=1.0, image_weight=1.0,
+                                 image_threshold=None, query_filter=None):
+        """"Regions that look like this picture AND match these words": the first region embedding of the query image and the
+        embedding of ``text`` (a string, or several: one list each) are searched for their best ``candidates`` regions each,
+        and the lists are fused by rank (``fusion="rrf"``) or by each list's standardised scores (``"dbsf"``) -- adding the
+        raw scores, or searching with the averaged vector, would rank by the image alone, because the text-image cosines
+        of a CLIP model lie far below the image-image ones.  ``image_threshold`` drops image-list members scoring below it;
+        the ranks in the text lists are untouched.  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox",
+        "id", "score", "ranks", "scores"}`` best first: list 0 is the image, lists 1.. the prompts; ``ranks[j]`` is the
+        region's rank in list j (0: not among its candidates), ``scores[j]`` its cosine against that query.  No thumbnails."""
+        if not self.region_embeddings:
+            return "❌ No query embeddings available. Please detect/process an image first.", []
+        if not self.vector_db or not self.current_database:
+            return "❌ No database loaded. Please create or load a database first.", []
+        try:
+            prompts = self.embed_text([text] if isinstance(text, str) else text)
+        except Exception as e:
+            return f"❌ Error embedding the text query: {str(e)}", []
+        image = torch.as_tensor(self.region_embeddings[0], dtype=torch.float32).reshape(-1)
+        n_text = int(prompts.shape[0])
+        thresholds = None if image_threshold is None else [float(image_threshold)] + [None] * n_text
+        with self._lock:
+            hits = self.vector_db.query_fusion([image] + list(prompts), limit=int(max_results), prefetch_limit=int(candidates),
+                                               fusion=fusion, weights=[float(image_weight)] + [float(text_weight)] * n_text,
+                                               prefetch_thresholds=thresholds, query_filter=query_filter)
+        if not hits:
+            return "❌ No regions found for this picture and text", []
+        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
+                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score, "ranks": r.ranks, "scores": r.scores} for r in hits]
+        out = f"🎯 Found {len(items)} regions for the picture and the text ({fusion}):\n\n"
+        for n, it in enumerate(items):
+            out += f"{n + 1}. {it['filename']}  fused {it['score']:.4f}  ranks {it['ranks']}  (Source: {it['image_source']})\n"
+        return out, items
+
     def label_database(self, labels, query_filter=None, members=5):
         """Zero-shot labelling: every stored region (those a Qdrant-style ``query_filter`` selects, if given) gets the best
         of the prompts ``labels`` -- the exact assignment of ``Gallery.kmeans(max_iter=0)`` with the prompts' embeddings as

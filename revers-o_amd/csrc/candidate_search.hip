@@ -1,5 +1,5 @@
 // C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, kNN, k-means, range,
-// recommend, discover, MaxSim and MMR, with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
+// recommend, discover, MaxSim, MMR and the hybrid queries (fusion), with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
 #include <algorithm>
 #include <vector>
 
@@ -1015,6 +1015,88 @@ extern "C" int32_t revo_search_mmr(revo_gallery* g, const float* queries, int32_
         sa.idx = (long long*)indices + (size_t)c0 * k; sa.out_counts = counts + c0;
         { ProfScope ps("mmr_select", st);
           CHECK_RC(launch_mmr_select(sa, Qc, st)); }
+    }
+    return 0;
+    API_END
+}
+
+// ---- hybrid queries (include/revo.h FUSION; fusion.hip)
+namespace {
+// the domains both entry points share, and the kernel's arguments they decide (weights and list thresholds travel by value)
+int fusion_args(const char* who, int32_t n, int32_t m, int32_t C, int32_t method, float rrf_k, const float* weights,
+                const float* list_thresholds, int32_t k, int32_t has_thr, float thr, revo::FusionArgs& a) {
+    const std::string w(who);
+    REVO_REQUIRE(n >= 0, w + ": negative search count");
+    REVO_REQUIRE(m >= 1 && m <= revo::FUSION_MAX_LISTS, w + ": lists must be in [1, 64]");
+    REVO_REQUIRE(C >= 1 && C <= revo::LARGE_K_MAX, w + ": limit must be in [1, 1024]");
+    REVO_REQUIRE(m * C <= revo::FUSION_MAX_KEYS, w + ": lists * limit must be at most 8192");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, w + ": k must be in [1, 1024]");
+    REVO_REQUIRE(method == 0 || method == 1, w + ": method must be 0 (RRF) or 1 (DBSF)");
+    REVO_REQUIRE(std::isfinite(rrf_k) && rrf_k >= 0.f, w + ": rrf_k must be finite and >= 0");
+    REVO_REQUIRE((long long)n * m <= 0x7fffffffll, w + ": searches * lists must fit 31 bits");
+    a.m = m; a.C = C; a.k = k; a.method = method; a.rrf_k = rrf_k; a.has_thr = has_thr ? 1 : 0; a.thr = thr;
+    for (int j = 0; j < revo::FUSION_MAX_LISTS; ++j) { a.w[j] = 1.f; a.t[j] = -INFINITY; }
+    for (int j = 0; j < m; ++j) {
+        if (weights) {
+            REVO_REQUIRE(std::isfinite(weights[j]) && weights[j] >= 0.f, w + ": a weight must be finite and >= 0");
+            a.w[j] = weights[j];
+        }
+        if (list_thresholds) {
+            REVO_REQUIRE(!std::isnan(list_thresholds[j]), w + ": a list threshold is NaN");
+            a.t[j] = list_thresholds[j];
+        }
+    }
+    return require_threshold(has_thr, thr, who);
+}
+}  // namespace
+
+extern "C" int32_t revo_topk_fuse(const float* scores, const int64_t* indices, const int32_t* counts, int32_t n, int32_t m,
+                                  int32_t C, int32_t method, float rrf_k, const float* weights, const float* list_thresholds,
+                                  int32_t k, int32_t has_thr, float thr, float* out_scores, int64_t* out_indices,
+                                  int32_t* out_counts, int32_t* out_ranks, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(out_scores && out_indices && out_counts && ((scores && indices && counts) || n == 0), "topk_fuse: null argument");
+    revo::FusionArgs a{};
+    CHECK_RC(fusion_args("topk_fuse", n, m, C, method, rrf_k, weights, list_thresholds, k, has_thr, thr, a));
+    if (n == 0) return 0;
+    a.scores = scores; a.idx = (const long long*)indices; a.counts = counts; a.idx_offset = 0;
+    a.out_scores = out_scores; a.out_idx = (long long*)out_indices; a.out_counts = out_counts; a.out_ranks = out_ranks;
+    ProfScope ps("fusion_fuse", (hipStream_t)stream);
+    return revo::launch_fusion_fuse(a, n, (hipStream_t)stream);
+    API_END
+}
+
+extern "C" int32_t revo_search_fusion(revo_gallery* g, const float* queries, int32_t n, int32_t m, int32_t C, int32_t method,
+                                      float rrf_k, const float* weights, const float* list_thresholds, int32_t k,
+                                      int32_t has_thr, float thr, int64_t index_offset, float* scores, int64_t* indices,
+                                      int32_t* counts, int32_t* ranks, float* list_scores, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && scores && indices && counts && (queries || n == 0), "search_fusion: null argument");
+    revo::FusionArgs a{};
+    CHECK_RC(fusion_args("search_fusion", n, m, C, method, rrf_k, weights, list_thresholds, k, has_thr, thr, a));
+    CHECK_RC(require_f32_rows(g, "search_fusion"));
+    if (n == 0) return 0;
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const int Q = n * m, D = g->D;
+    float *ls = nullptr, *qn = nullptr; long long* li = nullptr; int* lc = nullptr;
+    CHECK_RC(carve_buffer(g->fbuf, st, [&](Layout& l) {
+        ls = l.take<float>((size_t)Q * C); li = l.take<long long>((size_t)Q * C); lc = l.take<int>(Q);
+        qn = l.take<float>(list_scores ? (size_t)Q * D : 0);
+    }));
+    // the lists: the large-k search's own results (it clears and fills the handle's counters, and drops the two-phase state)
+    CHECK_RC(search_topk_large(g, queries, Q, C, 0, 0.f, 0, ls, li, lc, allow, st));
+    a.scores = ls; a.idx = li; a.counts = lc; a.idx_offset = index_offset;
+    a.out_scores = scores; a.out_idx = (long long*)indices; a.out_counts = counts; a.out_ranks = ranks;
+    { ProfScope ps("fusion_fuse", st);
+      CHECK_RC(launch_fusion_fuse(a, n, st)); }
+    if (list_scores) {
+        // the inner search normalises its queries a chunk at a time into rows it reuses: the same kernel, every row kept
+        ProfScope ps("fusion_list_scores", st);
+        CHECK_RC(launch_l2norm_rows(queries, D, qn, D, nullptr, 0, Q, D, st));
+        CHECK_RC(launch_fusion_list_scores(qn, D, g->gf.p, D, D, a.out_idx, counts, index_offset, n, m, k, list_scores, st));
     }
     return 0;
     API_END

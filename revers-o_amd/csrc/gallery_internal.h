@@ -148,6 +148,8 @@ struct __attribute__((visibility("default"))) revo_gallery {   // (the C ABI nam
     DeviceBuffer<> lbuf;
     // the candidate pipeline's workspace (CandidateWs, candidate_search.hip): every search that uses it carves its own layout
     DeviceBuffer<> pbuf;
+    // revo_search_fusion's workspace: the lists' scores | rows | counts | the normalised query rows (for list_scores)
+    DeviceBuffer<> fbuf;
     // revo_gallery_remove: per-chunk counts | first removed rows | the copy of a host bitmap; revo_gallery_update: the row map
     DeviceBuffer<> edit;
     // revo_gallery_append_unique: edges (first_old | bit matrix) | representatives | rows | scores | kept count | the

@@ -775,6 +775,30 @@ struct MmrSelectArgs {
     int* out_counts;              // [Q] out: min(k, counts[q])
 };
 int launch_mmr_select(const MmrSelectArgs& a, int Q, hipStream_t st);
+// ---- hybrid queries (revo_search_fusion, revo_topk_fuse; fusion.hip): rank / score fusion of m lists
+constexpr int FUSION_MAX_LISTS = 64;
+constexpr int FUSION_MAX_KEYS = 8192;   // m * C: what one workgroup sorts in LDS (two arrays of 64 KiB)
+struct FusionArgs {
+    const float* scores;          // [n][m][C] the lists' scores
+    const long long* idx;         // [n][m][C] their rows (index offset 0), each in [0, 2^47)
+    const int* counts;            // [n][m] entries of each list (device; more than C counts as C)
+    int m, C, k;
+    int method;                   // 0 = RRF, 1 = DBSF
+    float rrf_k;
+    float w[FUSION_MAX_LISTS];    // the lists' weights (by value: the call stays asynchronous)
+    float t[FUSION_MAX_LISTS];    // the lists' thresholds (-inf: none)
+    int has_thr; float thr;       // the cut on the fused score
+    long idx_offset;
+    float* out_scores;            // [n][k] out: F
+    long long* out_idx;           // [n][k] out: row + idx_offset
+    int* out_counts;              // [n] out
+    int* out_ranks;               // [n][k][m] out (optional): 1-based position in list j, 0 = not a member
+};
+int launch_fusion_fuse(const FusionArgs& a, int n, hipStream_t st);
+// list_scores[(i * k + e) * m + j] = the fp32 chain of every re-score over row out_idx[i][e] - idx_offset of Gf and the
+// normalised query row Qf[i * m + j], for e < out_counts[i]; -inf behind
+int launch_fusion_list_scores(const float* Qf, long ldq, const float* Gf, long ldg, int D, const long long* out_idx,
+                              const int* out_counts, long idx_offset, int n, int m, int k, float* list_scores, hipStream_t st);
 // all-padding result for an empty gallery
 int launch_topk_fill_empty(float* s, long long* i, int* c, int Q, int k, hipStream_t st);
 // merge P per-shard result lists [P][Q][k] -> [Q][k]

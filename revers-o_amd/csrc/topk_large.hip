@@ -81,18 +81,7 @@ __device__ uint64_t lk_kth_largest(KeyOf key_of, long n, int k, int passes, uint
     return prefix;
 }
 
-// Descending bitonic sort of keys[0 .. P) in LDS (P a power of two), every thread of the block.
-__device__ __forceinline__ void lk_sort_desc(uint64_t* keys, int P) {
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < (P >> 1); i += blockDim.x) {
-                const int lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), hi = lo + stride;
-                const uint64_t a = keys[lo], b = keys[hi];
-                if ((a < b) == ((lo & size) == 0)) { keys[lo] = b; keys[hi] = a; }
-            }
-            __syncthreads();
-        }
-}
+// (the block-wide LDS sort lk_sort_desc: topk_util.h, shared with fusion.hip)
 // keys[0 .. P) sorted best first (0 = empty; entries past P count as empty) -> output row `orow` (k <= blockDim.x)
 __device__ __forceinline__ void lk_write(const uint64_t* keys, int P, long orow, int k, int has_thr, float thr, long idx_offset,
                                          float* __restrict__ out_scores, long long* __restrict__ out_idx,

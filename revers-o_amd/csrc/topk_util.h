@@ -70,6 +70,20 @@ __device__ __forceinline__ uint64_t wave_fold_best64(uint64_t run, uint64_t v, i
     return wave_bitonic_merge_desc(m2, lane);
 }
 
+// ---------------------------------------------------- block-level sorting ----
+// Descending bitonic sort of keys[0 .. P) in LDS (P a power of two), every thread of the block (topk_large.hip, fusion.hip).
+__device__ __forceinline__ void lk_sort_desc(uint64_t* keys, int P) {
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = threadIdx.x; i < (P >> 1); i += blockDim.x) {
+                const int lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), hi = lo + stride;
+                const uint64_t a = keys[lo], b = keys[hi];
+                if ((a < b) == ((lo & size) == 0)) { keys[lo] = b; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+}
+
 // Exact fp32 scores of up to four gallery rows against one query row: per-lane fma chain over the elements
 // lane*4 + 256*i (+0..3, in that order), then the xor butterfly.  The four rows' loads are independent (their HBM
 // round trips overlap); every row keeps its own chain, so a row's score does not depend on what it is batched with.

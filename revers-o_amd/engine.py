@@ -869,6 +869,39 @@ class Gallery(_Handle):
                 _lib.ptr(scores), _lib.ptr(values), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_mmr")
         return scores, values, idx, counts
 
+    def search_fusion(self, queries, k=5, limit=100, method="rrf", rrf_k=60.0, weights=None, list_thresholds=None,
+                      score_threshold=None, index_offset=0, allow=None, with_ranks=True, with_list_scores=False):
+        """Hybrid query (include/revo.h, FUSION): ``queries`` is ``[n, m, dim]`` (or ``[m, dim]`` for one fused search) --
+        m query vectors of possibly different kinds, e.g. an image embedding and a text embedding.  Each is searched for its
+        best ``limit`` rows as :meth:`search` would (same filter semantics); the m lists are fused by ``method``: ``"rrf"``
+        (each member adds ``weight / (rrf_k + rank)``) or ``"dbsf"`` (each member adds ``weight * (score - (mean - 3 sd)) /
+        (6 sd)`` with the list's own mean and deviation).  ``list_thresholds[j]`` drops list j's entries below it without
+        renumbering the ranks behind them; ``score_threshold`` cuts on the fused score.  Returns ``(scores [n, k] fp32,
+        indices [n, k] int64, counts [n] int32)``, then ``ranks [n, k, m] int32`` (1-based position in list j, 0 = not in
+        it) if ``with_ranks`` and ``list_scores [n, k, m] fp32`` (the row's exact score against every one of the m queries,
+        member or not) if ``with_list_scores``; padding -inf / -1 / 0 / -inf.  Exact and asynchronous like :meth:`search`."""
+        _require_cuda(queries, "queries", self.device)
+        q = queries.detach().to(torch.float32).contiguous()
+        if q.dim() == 2:
+            q = q[None]
+        if q.dim() != 3 or q.shape[2] != self.dim:
+            raise ValueError(f"queries must be [n, m, {self.dim}], got {tuple(q.shape)}")
+        n, m = int(q.shape[0]), int(q.shape[1])
+        k = int(k)
+        w, t = _fusion_host_arrays(m, weights, list_thresholds)
+        scores = torch.empty((n, max(k, 1)), dtype=torch.float32, device=q.device)
+        idx = torch.empty((n, max(k, 1)), dtype=torch.int64, device=q.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=q.device)
+        ranks = torch.empty((n, max(k, 1), m), dtype=torch.int32, device=q.device) if with_ranks else None
+        ls = torch.empty((n, max(k, 1), m), dtype=torch.float32, device=q.device) if with_list_scores else None
+        with self._lock, torch.cuda.device(self.device), self._filter(allow):
+            _lib.check(self._lib.revo_search_fusion(
+                self._h, _lib.ptr(q), n, m, int(limit), _fusion_method(method), float(rrf_k), w, t, k,
+                int(score_threshold is not None), float(score_threshold if score_threshold is not None else 0.0),
+                int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.ptr(ranks), _lib.ptr(ls),
+                _lib.current_stream()), "revo_search_fusion")
+        return (scores, idx, counts) + ((ranks,) if with_ranks else ()) + ((ls,) if with_list_scores else ())
+
     @contextlib.contextmanager
     def _groups(self, groups):
         """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.
@@ -1078,6 +1111,59 @@ def merge_topk(part_scores, part_indices, k, score_threshold=None):
                                        _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()),
                    "revo_topk_merge")
     return scores, idx, counts
+
+
+FUSION_METHODS = {"rrf": 0, "dbsf": 1}
+
+
+def _fusion_method(method):
+    if method not in FUSION_METHODS:
+        raise ValueError(f"fusion method must be one of {sorted(FUSION_METHODS)}, got {method!r}")
+    return FUSION_METHODS[method]
+
+
+def _fusion_host_arrays(m, weights, list_thresholds):
+    """The host float[m] arrays of revo_search_fusion / revo_topk_fuse (None stays NULL; a threshold of None: -inf)."""
+    def arr(values, name, none_value):
+        if values is None:
+            return None
+        values = [none_value if v is None else float(v) for v in values]
+        if len(values) != m:
+            raise ValueError(f"{name} must have one entry per list ({m}), got {len(values)}")
+        return (C.c_float * m)(*values)
+    return arr(weights, "weights", 1.0), arr(list_thresholds, "list_thresholds", float("-inf"))
+
+
+def fuse_topk(scores, indices, counts, k=5, method="rrf", rrf_k=60.0, weights=None, list_thresholds=None, score_threshold=None,
+              with_ranks=True):
+    """Fuse result lists the caller already holds (include/revo.h, FUSION: revo_topk_fuse): ``scores`` fp32 and ``indices``
+    int64 ``[n, m, C]``, ``counts`` int32 ``[n, m]``, device tensors -- e.g. the merged lists of a row-sharded search.  The
+    arithmetic, order and outputs of :meth:`Gallery.search_fusion`: returns ``(scores [n, k], indices [n, k], counts [n])``
+    and ``ranks [n, k, m]`` if ``with_ranks``."""
+    _require_cuda(scores, "scores")
+    _require_cuda(indices, "indices", scores.device)
+    _require_cuda(counts, "counts", scores.device)
+    s = scores.detach().to(torch.float32).contiguous()
+    i = indices.detach().to(torch.int64).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    if s.dim() != 3 or i.shape != s.shape or tuple(c.shape) != tuple(s.shape[:2]):
+        raise ValueError(f"scores and indices must be [n, m, C] and counts [n, m], got {tuple(s.shape)}, {tuple(i.shape)}, "
+                         f"{tuple(c.shape)}")
+    n, m, limit = (int(x) for x in s.shape)
+    k = int(k)
+    w, t = _fusion_host_arrays(m, weights, list_thresholds)
+    out_s = torch.empty((n, max(k, 1)), dtype=torch.float32, device=s.device)
+    out_i = torch.empty((n, max(k, 1)), dtype=torch.int64, device=s.device)
+    out_c = torch.empty((n,), dtype=torch.int32, device=s.device)
+    ranks = torch.empty((n, max(k, 1), m), dtype=torch.int32, device=s.device) if with_ranks else None
+    lib = _lib.load()
+    with torch.cuda.device(s.device):
+        _lib.check(lib.revo_topk_fuse(_lib.ptr(s), _lib.ptr(i), _lib.ptr(c), n, m, limit, _fusion_method(method), float(rrf_k),
+                                      w, t, k, int(score_threshold is not None),
+                                      float(score_threshold if score_threshold is not None else 0.0), _lib.ptr(out_s),
+                                      _lib.ptr(out_i), _lib.ptr(out_c), _lib.ptr(ranks), _lib.current_stream()),
+                   "revo_topk_fuse")
+    return (out_s, out_i, out_c, ranks) if with_ranks else (out_s, out_i, out_c)
 
 
 # ---- module-level convenience API named by the north star ------------------

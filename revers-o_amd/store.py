@@ -187,6 +187,17 @@ class ScoredPoint:
 
 
 @dataclass
+class FusedPoint:
+    """One hit of a hybrid query (:meth:`GalleryStore.query_fusion`): the fused ``score``, and per fused list the point's
+    1-based rank in it (0: not in the list) and its score against that list's query."""
+    id: str
+    score: float
+    payload: dict
+    ranks: list
+    scores: list
+
+
+@dataclass
 class PointGroup:
     """One group of a grouped search (Qdrant's ``PointGroup``): the payload value ``id`` and its best hits."""
     id: object
@@ -686,6 +697,35 @@ class GalleryStore:
                                         allow=allow)
         n = int(c)
         return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
+
+    def query_fusion(self, prefetch, limit=5, prefetch_limit=100, fusion="rrf", rrf_k=60.0, weights=None, prefetch_thresholds=None,
+                     score_threshold=None, query_filter=None):
+        """Hybrid query in Qdrant's shape (``prefetch`` + ``fusion``): every entry of ``prefetch`` is a point id of the store or
+        a vector -- an image embedding and a text embedding, say -- and is searched for its best ``prefetch_limit`` points
+        (selected by ``query_filter``); the lists are fused by ``fusion``: ``"rrf"`` (reciprocal rank fusion with the constant
+        ``rrf_k``) or ``"dbsf"`` (each list's scores standardised by its own mean and deviation, then added).  ``weights``
+        and ``prefetch_thresholds`` hold one entry per prefetch (a threshold drops that list's points below it; the ranks
+        behind them stay).  Returns :class:`FusedPoint` objects, best first: ``score`` is the fused score, ``ranks[j]`` the
+        point's 1-based rank in list j (0: not in it), ``scores[j]`` its exact score against prefetch j, in the list or not.
+        Points given by id are never part of the result; an unknown id raises ``KeyError``.  Exact (include/revo.h, FUSION):
+        1 to 64 prefetches, ``prefetch_limit <= 1024`` and ``len(prefetch) * prefetch_limit <= 8192``, ``limit <= 1024``."""
+        if isinstance(prefetch, (str, bytes, int)) or (torch.is_tensor(prefetch) and prefetch.dim() == 1) or \
+                (isinstance(prefetch, np.ndarray) and prefetch.ndim == 1):
+            prefetch = [prefetch]
+        q, rows = self._example_vectors(list(prefetch))
+        if q.shape[0] < 1:
+            raise ValueError("query_fusion: needs at least one prefetch")
+        allow = None
+        if rows or query_filter is not None:
+            mask = self.filter_mask(query_filter).copy() if query_filter is not None else np.ones(len(self), dtype=bool)
+            mask[rows] = False
+            allow = torch.from_numpy(_filters.pack_bits(mask)).to(self.gallery.device)
+        s, i, c, r, ls = self.gallery.search_fusion(q[None], k=int(limit), limit=int(prefetch_limit), method=fusion, rrf_k=rrf_k,
+                                                    weights=weights, list_thresholds=prefetch_thresholds,
+                                                    score_threshold=score_threshold, allow=allow, with_list_scores=True)
+        n = int(c[0])
+        return [FusedPoint(self.ids[j], float(sc), self.payloads[j], ranks, scores)
+                for sc, j, ranks, scores in zip(s[0, :n].tolist(), i[0, :n].tolist(), r[0, :n].tolist(), ls[0, :n].tolist())]
 
     def _group_ids(self, group_by):
         key = (group_by, len(self))
