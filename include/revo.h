@@ -924,6 +924,18 @@ int32_t revo_op_layernorm_logits(const float* x, int64_t ldx, const float* w, co
  * other rows of the call, bit for bit. */
 int32_t revo_op_linear_f32(int32_t epi, const float* A, int64_t lda, const float* Wt, int64_t ldw, const float* bias, int32_t M,
                            int32_t N, int32_t K, float* C, int64_t ldc, void* stream);
+/* the same kernel with grouped A rows, as the pool's value projection runs it: output columns [g * group_cols,
+ * (g + 1) * group_cols) read row m of A at A + g * a_group_stride + m * lda (one pooled row per head).  group_cols == 0: no
+ * groups (revo_op_linear_f32); otherwise group_cols % 16 == 0 and a_group_stride % 4 == 0.  Same K split and order: the bits
+ * of revo_op_linear_f32 on group g's rows and columns. */
+int32_t revo_op_linear_f32_grouped(int32_t epi, const float* A, int64_t lda, int64_t a_group_stride, int32_t group_cols,
+                                   const float* Wt, int64_t ldw, const float* bias, int32_t M, int32_t N, int32_t K, float* C,
+                                   int64_t ldc, void* stream);
+/* the pool's probe folded into its key projection at load time (head.hip probe_qk_kernel): qk[h * width + i] = sum over the
+ * rows o of head h (o in [h * width / heads, (h + 1) * width / heads)) of q[o] * Wk[o * width + i], ck[h] = sum of q[o] * bk[o];
+ * q [width] (already scaled), Wk [width, width], bk [width], all fp32 on the device.  width % heads == 0. */
+int32_t revo_op_probe_qk(const float* q, const float* Wk, const float* bk, int32_t width, int32_t heads, float* qk, float* ck,
+                         void* stream);
 /* the attention pool's weighted row sums (K10; head.hip): u[(b * heads + h) * width + c] = sum_s softmax_s(logits[b, h, :])[s] *
  * x[b * seq + s][c], all fp32; logits [batch, heads, seq].  A column's sum is taken in one fixed order whatever the batch
  * (the batch only decides how many columns a lane carries): bit-identical between a batch and its images one at a time. */

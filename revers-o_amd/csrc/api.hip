@@ -301,6 +301,28 @@ extern "C" int32_t revo_op_linear_f32(int32_t epi, const float* A, int64_t lda, 
     return revo::launch_gemm_f32_skinny(epi, A, lda, 0, 0, Wt, ldw, bias, M, N, K, C, ldc, (hipStream_t)stream);
     API_END
 }
+// The same kernel with grouped A rows, the way the pool's value projection launches it (vit.hip): output columns
+// [g * group_cols, (g + 1) * group_cols) read their A rows at A + g * a_group_stride.  The launcher's own grouping refusals
+// (group_cols % 16, a_group_stride % 4) pass through.
+extern "C" int32_t revo_op_linear_f32_grouped(int32_t epi, const float* A, int64_t lda, int64_t a_group_stride, int32_t group_cols,
+                                              const float* Wt, int64_t ldw, const float* bias, int32_t M, int32_t N, int32_t K,
+                                              float* C, int64_t ldc, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(A && Wt && C && M >= 1 && N >= 1 && K >= 16 && lda >= K && ldw >= K && ldc >= N && group_cols >= 0 &&
+                 a_group_stride >= 0, "op_linear_f32_grouped: bad arguments");
+    return revo::launch_gemm_f32_skinny(epi, A, lda, a_group_stride, group_cols, Wt, ldw, bias, M, N, K, C, ldc, (hipStream_t)stream);
+    API_END
+}
+// The probe's keys folded into one [heads, width] matrix at load time (head.hip probe_qk_kernel): qk[h][i] = sum over the
+// head's rows o of q[o] Wk[o][i], ck[h] = sum of q[o] bk[o]
+extern "C" int32_t revo_op_probe_qk(const float* q, const float* Wk, const float* bk, int32_t width, int32_t heads, float* qk,
+                                    float* ck, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(q && Wk && bk && qk && ck, "op_probe_qk: null argument");
+    REVO_REQUIRE(width >= 1 && heads >= 1 && width % heads == 0, "op_probe_qk: width must be a positive multiple of heads");
+    return revo::launch_probe_qk(q, Wk, bk, width, heads, qk, ck, (hipStream_t)stream);
+    API_END
+}
 extern "C" int32_t revo_op_pool_rows(const float* x, int64_t ldx, const float* logits, int32_t batch, int32_t seq, int32_t width,
                                      int32_t heads, float* u, void* stream) {
     API_BEGIN

@@ -188,6 +188,26 @@ int main() {
     EXPECT(revo_op_layernorm_logits(nullptr, 0, nullptr, nullptr, 1e-5f, 1, 4, nullptr, 0, nullptr, nullptr, 1, 1, nullptr, nullptr) == -2 &&
            err_has("op_layernorm_logits"));
     EXPECT(revo_op_linear_f32(0, nullptr, 0, nullptr, 0, nullptr, 1, 1, 16, nullptr, 0, nullptr) == -2 && err_has("op_linear_f32"));
+    {
+        float f[16] = {};
+        EXPECT(revo_op_linear_f32_grouped(0, nullptr, 16, 16, 16, f, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2 &&
+               err_has("op_linear_f32_grouped"));
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 16, 16, nullptr, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2);
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 16, 16, f, 16, nullptr, 1, 16, 16, nullptr, 16, nullptr) == -2);
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 16, 16, f, 16, nullptr, 1, 16, 8, f, 16, nullptr) == -2);
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 16, -16, f, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2);
+        // the launcher's own grouping refusals, before anything touches a device
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 16, 8, f, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2 && err_has("bad A grouping"));
+        EXPECT(revo_op_linear_f32_grouped(0, f, 16, 18, 16, f, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2 && err_has("bad A grouping"));
+        EXPECT(revo_op_linear_f32_grouped(3, f, 16, 16, 16, f, 16, nullptr, 1, 16, 16, f, 16, nullptr) == -2 && err_has("epilogue"));
+        EXPECT(revo_op_probe_qk(nullptr, f, f, 4, 2, f, f, nullptr) == -2 && err_has("op_probe_qk"));
+        EXPECT(revo_op_probe_qk(f, nullptr, f, 4, 2, f, f, nullptr) == -2);
+        EXPECT(revo_op_probe_qk(f, f, nullptr, 4, 2, f, f, nullptr) == -2);
+        EXPECT(revo_op_probe_qk(f, f, f, 4, 2, nullptr, f, nullptr) == -2);
+        EXPECT(revo_op_probe_qk(f, f, f, 4, 2, f, nullptr, nullptr) == -2);
+        EXPECT(revo_op_probe_qk(f, f, f, 4, 3, f, f, nullptr) == -2 && err_has("multiple of heads"));
+        EXPECT(revo_op_probe_qk(f, f, f, 4, 0, f, f, nullptr) == -2);
+    }
 
     if (failures) { std::printf("%d check(s) failed\n", failures); return 1; }
     std::printf("ALL OK\n");

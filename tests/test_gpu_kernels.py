@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import _head_bounds as hb
 import _kernel_bounds as kb
 import reverso_amd  # noqa: F401
 from reverso_amd import _lib
@@ -140,6 +141,8 @@ def test_pool_rows_equal_the_softmax_weighted_sum_and_do_not_depend_on_the_batch
     p = torch.softmax(logits.double(), dim=-1)
     ref = torch.einsum("bhs,bsw->bhw", p, x.double().view(B, S, W))
     assert (u.double() - ref).abs().max().item() <= 2e-5
+    xs = x.view(B, S, W)
+    assert hb.ratio(u, hb.PoolRows.reference(xs, logits), hb.PoolRows.bound(xs, logits)) <= 1.0
     # image by image: the narrow form (few workgroups per image)
     for b in (0, B - 1):
         u1 = torch.zeros(1, H, W, device=dev)
@@ -166,6 +169,8 @@ def test_layernorm_with_pool_logits_batch_form_equals_the_row_form(lib, dev, B, 
     assert (out.double() - ref).abs().max().item() <= 2e-5
     ref_lg = (ref @ qk.double().T + ck.double()).view(B, S, H).permute(0, 2, 1)
     assert (lg.double() - ref_lg).abs().max().item() <= 2e-4
+    (ry, rlg), (by, blg) = hb.LnLogits.reference(x, w, b, 1e-5, qk, ck, S), hb.LnLogits.bound(x, w, b, 1e-5, qk, ck, S)
+    assert hb.ratio(out, ry, by) <= 1.0 and hb.ratio(lg, rlg, blg) <= 1.0
     for i in (0, B - 1):
         o1, l1 = torch.zeros(S, W, device=dev), torch.zeros(1, H, S, device=dev)
         _lib.check(lib.revo_op_layernorm_logits(_lib.ptr(x[i * S:(i + 1) * S]), W, _lib.ptr(w), _lib.ptr(b), 1e-5, S, W, _lib.ptr(o1), W,
@@ -194,6 +199,8 @@ def test_head_linear_f32_rows_do_not_depend_on_the_batch(lib, dev, M, N, K, epi)
     if epi == 2:
         ref = ref + c0.double()
     assert (c.double() - ref).abs().max().item() <= 1e-4 * math.sqrt(K / 1024)
+    case = hb.LinearCase(a, w, bias, c0, epi)
+    assert hb.ratio(c, hb.LinearF32.reference(case), hb.LinearF32.bound(case)) <= 1.0
     for r in (0, M // 2, M - 1):
         c1 = c0[r:r + 1].clone()
         _lib.check(lib.revo_op_linear_f32(epi, _lib.ptr(a[r:r + 1]), K, _lib.ptr(w), K, _lib.ptr(bias), 1, N, K, _lib.ptr(c1), N, st))

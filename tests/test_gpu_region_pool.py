@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _head_bounds as hb
 import reverso_amd
 from reverso_amd import _lib, engine, regions, weights
 from oracle import pe_vit
@@ -132,6 +133,8 @@ def test_masked_pool_rows_against_fp64_and_bit_for_bit_against_the_unmasked_kern
     err = (u.double() - ref).abs().max().item()
     print(f"masked pool rows B={B} S={S} W={W} H={H} R={R}: max |u - fp64| = {err:.3e}")
     assert err <= 2e-5
+    xs, masked = x.view(B, S, W), (ri_t.long(), al)
+    assert hb.ratio(u, hb.PoolRows.reference(xs, logits, masked), hb.PoolRows.bound(xs, logits, masked)) <= 1.0
 
     # exact
     u_all = torch.zeros(B, H, W, device=dev)
