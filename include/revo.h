@@ -936,6 +936,33 @@ int32_t revo_op_linear_f32_grouped(int32_t epi, const float* A, int64_t lda, int
  * q [width] (already scaled), Wk [width, width], bk [width], all fp32 on the device.  width % heads == 0. */
 int32_t revo_op_probe_qk(const float* q, const float* Wk, const float* bk, int32_t width, int32_t heads, float* qk, float* ck,
                          void* stream);
+/* the row normaliser (elementwise.hip l2norm_rows_kernel) whole: the kernel that writes every gallery row and every query,
+ * example and prompt, and measures the rounding norms the exactness certificate is built from.  All pointers device memory.
+ *   src [rows][ld_src] fp32; row r goes to row r of the outputs or, with dst_rows (int64 [rows]), to row dst_rows[r]: the
+ *   same bits either way.  dst_f32 [..][ld_f32] fp32 and dst_bf16 [..][ld_bf16] bf16 (round to nearest even of the fp32
+ *   row) are each optional (null).  normalize = 0: y = x, a bit copy.  normalize = 1: y = x * (1 / sqrt(sum x^2)), the sum
+ *   in fp32: lane l of a wave adds columns l, l + 64, ... by fma, then the xor butterfly 32 .. 1 -- one order for a row
+ *   whatever the batch, its position in it, or the form (registers up to dim 2048, a loop above).
+ *   The normalised row is within a few ulp of x / ||x|| (tests/_norm_bounds.py gives the terms) for
+ *   sqrt(dim) * 2^-62 <= ||x|| < 2^64.  From 2^64 up that fp32 sum is +inf and the row comes out as zeros.  Below the range
+ *   the sum is partly, then wholly (||x|| < 2^-63) subnormal and loses bits -- the row still comes out near unit length,
+ *   with an error that grows to a few per cent near sqrt(dim) * 2^-72 -- and once every x^2 rounds to 0 (every
+ *   |x| <= 2^-75) the row is left as it is, like an all-zero row.  e / e.norm() in fp32 does the same at both ends.
+ *   row_stats (optional) [rows][2], by SOURCE row: ||bf16(y) - y||, ||bf16(y)||.  max_stats (optional) [2]: max'ed, never
+ *   overwritten, with ||y|| and ||bf16(y) - y|| of every finite row (a NaN / Inf row is left out).  The sums of squares are
+ *   taken on the row scaled by a power of two from its largest element, so a finite row of ANY length has its norms
+ *   measured: rows stored with normalize = 0 are certified whatever their length.  (A norm past fp32's range, 2^128, is
+ *   +inf in max_stats: no search is certified against such a row.)
+ *   zero_a / zero_b (optional): zero_a_words / zero_b_words 32-bit words set to 0 by the same launch (rows >= 1).
+ * Status -2 before the device is touched: null src, rows < 0, dim < 1, a stride below dim, a null array to clear with a
+ * positive count.  rows = 0 does nothing. */
+int32_t revo_op_l2norm_rows(const float* src, int64_t ld_src, float* dst_f32, int64_t ld_f32, uint16_t* dst_bf16, int64_t ld_bf16,
+                            int64_t rows, int32_t dim, int32_t normalize, float* row_stats, float* max_stats, uint32_t* zero_a,
+                            int64_t zero_a_words, uint32_t* zero_b, int64_t zero_b_words, const int64_t* dst_rows, void* stream);
+/* the certificate's maxima of a gallery as its searches read them, to HOST out[2]: out[0] >= ||g||, out[1] >= ||bf16(g) - g||
+ * for every row g now present (running maxima over every row written since the gallery was last empty: upper bounds after a
+ * remove or an update; both 0 for an empty gallery).  Waits for `stream`.  Null argument: status -2. */
+int32_t revo_op_gallery_cert_stats(revo_gallery* g, float* out, void* stream);
 /* the attention pool's weighted row sums (K10; head.hip): u[(b * heads + h) * width + c] = sum_s softmax_s(logits[b, h, :])[s] *
  * x[b * seq + s][c], all fp32; logits [batch, heads, seq].  A column's sum is taken in one fixed order whatever the batch
  * (the batch only decides how many columns a lane carries): bit-identical between a batch and its images one at a time. */

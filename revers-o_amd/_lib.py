@@ -112,6 +112,8 @@ SIGNATURES = {
     "revo_op_linear_f32": (_i32, [_i32, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "revo_op_linear_f32_grouped": (_i32, [_i32, _p, _i64, _i64, _i32, _p, _i64, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "revo_op_probe_qk": (_i32, [_p, _p, _p, _i32, _i32, _p, _p, _p]),
+    "revo_op_l2norm_rows": (_i32, [_p, _i64, _p, _i64, _p, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _i64, _p, _p]),
+    "revo_op_gallery_cert_stats": (_i32, [_p, C.POINTER(C.c_float), _p]),
     "revo_op_pool_rows": (_i32, [_p, _i64, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "revo_op_pool_rows_masked": (_i32, [_p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),
     "revo_op_detect_scores": (_i32, [_p, _i64, _p, _i32, _i32, _p, _p, _p]),

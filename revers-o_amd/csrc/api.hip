@@ -323,6 +323,26 @@ extern "C" int32_t revo_op_probe_qk(const float* q, const float* Wk, const float
     return revo::launch_probe_qk(q, Wk, bk, width, heads, qk, ck, (hipStream_t)stream);
     API_END
 }
+// The row normaliser whole (elementwise.hip l2norm_rows_kernel: every gallery row, every query; its row_stats and max_stats
+// are the only inputs of the exactness certificate).  Every refusal comes before the device is touched.
+extern "C" int32_t revo_op_l2norm_rows(const float* src, int64_t ld_src, float* dst_f32, int64_t ld_f32, uint16_t* dst_bf16,
+                                       int64_t ld_bf16, int64_t rows, int32_t dim, int32_t normalize, float* row_stats,
+                                       float* max_stats, uint32_t* zero_a, int64_t zero_a_words, uint32_t* zero_b,
+                                       int64_t zero_b_words, const int64_t* dst_rows, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(src, "op_l2norm_rows: null src");
+    REVO_REQUIRE(rows >= 0, "op_l2norm_rows: negative rows");
+    REVO_REQUIRE(dim >= 1, "op_l2norm_rows: dim must be at least 1");
+    REVO_REQUIRE(ld_src >= dim && (!dst_f32 || ld_f32 >= dim) && (!dst_bf16 || ld_bf16 >= dim),
+                 "op_l2norm_rows: a row stride is below dim");
+    REVO_REQUIRE(zero_a_words >= 0 && zero_b_words >= 0 && (zero_a || zero_a_words == 0) && (zero_b || zero_b_words == 0),
+                 "op_l2norm_rows: a null array to clear with a positive word count");
+    static_assert(sizeof(long long) == sizeof(int64_t), "dst_rows is passed through as it is");
+    return revo::launch_l2norm_rows(src, ld_src, dst_f32, ld_f32, dst_bf16, ld_bf16, rows, dim, (hipStream_t)stream, normalize ? 1 : 0,
+                                    row_stats, (uint32_t*)max_stats, zero_a, zero_a_words, zero_b, zero_b_words,
+                                    (const long long*)dst_rows);
+    API_END
+}
 extern "C" int32_t revo_op_pool_rows(const float* x, int64_t ldx, const float* logits, int32_t batch, int32_t seq, int32_t width,
                                      int32_t heads, float* u, void* stream) {
     API_BEGIN

@@ -610,6 +610,18 @@ int launch_f32_to_bf16(const float* src, long ld_src, bf16_t* dst, long ld_dst, 
 // running maxima, as fp32 bit patterns (non-negative floats order like unsigned integers), of ||y||_2 and of
 // ||bf16(y) - y||_2 over all rows ever passed -- the quantities the search's exactness certificate is built from
 // (rigorous bound of |bf16-scan score - fp32 score|).  normalize == 0 copies the rows unscaled.
+//
+// The three sums of squares are taken on the row times 2^k, k from the exponent of its largest |y| (one wave maximum), and
+// the roots scaled back: a power of two is exact, so a row whose squares neither overflow nor underflow keeps the bits it
+// had without the scaling, and a finite row of any length -- 1e20 or 1e-20, stored as given -- has its true norms
+// measured.  Squares in plain fp32 gave +inf above ||y|| ~ 1.8e19 (the row then left the maxima: G understated) and 0
+// below ~ 1e-17 (Eg = 0).
+__device__ __forceinline__ void stat_scale(float ymax, float& sc, float& rs) {
+    const int E = (int)((__float_as_uint(ymax) >> 23) & 0xff);       // 0: zero or subnormal, 255: inf / NaN (any k will do)
+    const int k = min(126, max(-126, 127 - E));                      // ymax 2^k in [1, 2) but at the ends of the range
+    sc = __uint_as_float((uint32_t)(127 + k) << 23);
+    rs = __uint_as_float((uint32_t)(127 - k) << 23);
+}
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ src, long ld_src,
                                                           float* __restrict__ dst_f32, long ld_f32,
                                                           bf16_t* __restrict__ dst_bf16, long ld_bf16, long rows,
@@ -625,8 +637,9 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
     if (row >= rows) return;
     const float* s = src + row * ld_src;
     const long orow = dst_rows ? (long)dst_rows[row] : row;   // where the row is written (revo_gallery_update: a row of the gallery)
-    float inv = 1.0f;
-    float ny = 0.f, nb = 0.f, ne = 0.f;
+    const bool stats = row_stats || max_stats;
+    float inv = 1.0f, sc = 1.0f, rs = 1.0f;
+    float ny = 0.f, nb = 0.f, ne = 0.f;       // sums of squares of the row times sc
     constexpr int NV = 32;                    // rows of up to 64 NV = 2048 elements are held in registers
     if (D <= 64 * NV) {
         // every load of the row requested before the first is used, and the row read once: with a load inside each step of
@@ -643,6 +656,12 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
             q = wave_sum(q);
             inv = q > 0.f ? 1.0f / sqrtf(q) : 1.0f;
         }
+        if (stats) {
+            float mx = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) mx = fmaxf(mx, fabsf(v[i]));
+            stat_scale(wave_max(mx) * inv, sc, rs);       // the product is monotonic: the largest |y|
+        }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = lane + 64 * i;
@@ -652,33 +671,49 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
                 if (dst_f32) dst_f32[orow * ld_f32 + c] = y;
                 if (dst_bf16) dst_bf16[orow * ld_bf16 + c] = yb;
                 const float fb = bf16_to_f32(yb), d = fb - y;     // the difference of two neighbouring floats is exact
-                ny = fmaf(y, y, ny); nb = fmaf(fb, fb, nb); ne = fmaf(d, d, ne);
+                const float ys = y * sc, fs = fb * sc, ds = d * sc;
+                ny = fmaf(ys, ys, ny); nb = fmaf(fs, fs, nb); ne = fmaf(ds, ds, ne);
             }
         }
     } else {
+        float mx = 0.f;
         if (normalize) {
             float q = 0.f;
-            for (int c = lane; c < D; c += 64) q = fmaf(s[c], s[c], q);
+            for (int c = lane; c < D; c += 64) { const float x = s[c]; q = fmaf(x, x, q); mx = fmaxf(mx, fabsf(x)); }
             q = wave_sum(q);
             inv = q > 0.f ? 1.0f / sqrtf(q) : 1.0f;
+        } else if (stats) {
+            for (int c = lane; c < D; c += 64) mx = fmaxf(mx, fabsf(s[c]));
         }
-        for (int c = lane; c < D; c += 64) {
-            const float y = s[c] * inv;
-            const bf16_t yb = f32_to_bf16(y);
-            if (dst_f32) dst_f32[orow * ld_f32 + c] = y;
-            if (dst_bf16) dst_bf16[orow * ld_bf16 + c] = yb;
-            const float fb = bf16_to_f32(yb), d = fb - y;
-            ny = fmaf(y, y, ny); nb = fmaf(fb, fb, nb); ne = fmaf(d, d, ne);
+        if (stats) stat_scale(wave_max(mx) * inv, sc, rs);
+        // the sums in runs of NV steps, each run added to the row's total: the register form's chain for the first 2048
+        // columns (0 + run is exact), and NV + D / 2048 + 6 roundings, not D / 64 + 6, under the longest rows
+        for (int c0 = lane; c0 < D; c0 += 64 * NV) {
+            float ry = 0.f, rb = 0.f, re = 0.f;
+            const int c1 = min(D, c0 + 64 * NV);
+            for (int c = c0; c < c1; c += 64) {
+                const float y = s[c] * inv;
+                const bf16_t yb = f32_to_bf16(y);
+                if (dst_f32) dst_f32[orow * ld_f32 + c] = y;
+                if (dst_bf16) dst_bf16[orow * ld_bf16 + c] = yb;
+                const float fb = bf16_to_f32(yb), d = fb - y;
+                const float ys = y * sc, fs = fb * sc, ds = d * sc;
+                ry = fmaf(ys, ys, ry); rb = fmaf(fs, fs, rb); re = fmaf(ds, ds, re);
+            }
+            ny += ry; nb += rb; ne += re;
         }
     }
-    if (!row_stats && !max_stats) return;
-    ny = sqrtf(wave_sum(ny)); nb = sqrtf(wave_sum(nb)); ne = sqrtf(wave_sum(ne));
+    if (!stats) return;
+    const float sy = wave_sum(ny), se = wave_sum(ne);
+    ny = sqrtf(sy) * rs; nb = sqrtf(wave_sum(nb)) * rs; ne = sqrtf(se) * rs;
     if (lane == 0) {
         if (row_stats) { row_stats[row * 2] = ne; row_stats[row * 2 + 1] = nb; }
         if (max_stats) {
-            // NaN / inf rows (never produced by the embed path) would poison the maxima: they are left out
-            if (ny == ny && ny < INFINITY) atomicMax(max_stats, __float_as_uint(ny));
-            if (ne == ne && ne < INFINITY) atomicMax(max_stats + 1, __float_as_uint(ne));
+            // NaN / inf rows (never produced by the embed path) would poison the maxima: they are left out.  The sums of
+            // the scaled row tell: finite for every finite row, whatever its length (a norm past fp32's range enters as
+            // +inf: nothing is certified against such a row)
+            if (sy < INFINITY) atomicMax(max_stats, __float_as_uint(ny));
+            if (se < INFINITY) atomicMax(max_stats + 1, __float_as_uint(ne));
         }
     }
 }

@@ -165,6 +165,18 @@ extern "C" int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, 
     API_END
 }
 
+// the certificate's maxima as the handle holds them (gstat: max ||g||, max ||bf16(g) - g|| over every row written since the
+// gallery was last empty), after the work enqueued on `stream`
+extern "C" int32_t revo_op_gallery_cert_stats(revo_gallery* g, float* out, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && out, "op_gallery_cert_stats: null argument");
+    REVO_ON_DEVICE(g->device);
+    REVO_HIP_CHECK(hipMemcpyAsync(out, g->gstat.p, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+    API_END
+}
+
 // ---- rows leave and change in place (include/revo.h EDIT; gallery_edit.hip)
 #ifdef REVO_EXPERIMENTS
 static long g_remove_chunk = 0;

@@ -576,6 +576,14 @@ class Gallery(_Handle):
             _lib.check(self._lib.revo_gallery_read(self._h, start, n, _lib.ptr(out), 1), "revo_gallery_read")
         return out
 
+    def cert_stats(self):
+        """The certificate's maxima as the searches read them: ``(G, Eg)`` with ``G >= ||g||`` and ``Eg >= ||bf16(g) - g||``
+        for every row now present (include/revo.h, revo_op_gallery_cert_stats).  Synchronous."""
+        out = (C.c_float * 2)()
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self._lib.revo_op_gallery_cert_stats(self._h, out, _lib.current_stream()), "revo_op_gallery_cert_stats")
+        return float(out[0]), float(out[1])
+
     def allow_bits(self, allow):
         """The device allow-bitmap (int32 ``[ceil(len / 32)]``, bit ``r & 31`` of word ``r >> 5``) of ``allow``: a device
         tensor, either ``torch.bool [len(self)]`` or that bitmap already packed."""

@@ -207,6 +207,23 @@ int main() {
         EXPECT(revo_op_probe_qk(f, f, f, 4, 2, f, nullptr, nullptr) == -2);
         EXPECT(revo_op_probe_qk(f, f, f, 4, 3, f, f, nullptr) == -2 && err_has("multiple of heads"));
         EXPECT(revo_op_probe_qk(f, f, f, 4, 0, f, f, nullptr) == -2);
+        // the row normaliser and the gallery's certificate maxima: refused before anything touches a device
+        uint16_t h[16] = {};
+        uint32_t w[4] = {};
+        EXPECT(revo_op_l2norm_rows(nullptr, 4, f, 4, h, 4, 1, 4, 1, f, f, w, 4, w, 4, nullptr, nullptr) == -2 && err_has("op_l2norm_rows"));
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 4, -1, 4, 1, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) == -2 &&
+               err_has("negative rows"));
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 4, 1, 0, 1, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) == -2 &&
+               err_has("dim"));
+        EXPECT(revo_op_l2norm_rows(f, 3, f, 4, h, 4, 1, 4, 1, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) == -2 &&
+               err_has("stride"));
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 3, h, 4, 1, 4, 1, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) == -2);
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 3, 1, 4, 1, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) == -2);
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 4, 1, 4, 1, nullptr, nullptr, nullptr, 1, nullptr, 0, nullptr, nullptr) == -2 &&
+               err_has("null array to clear"));
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 4, 1, 4, 1, nullptr, nullptr, w, 4, nullptr, 1, nullptr, nullptr) == -2);
+        EXPECT(revo_op_l2norm_rows(f, 4, f, 4, h, 4, 1, 4, 1, nullptr, nullptr, w, -1, nullptr, 0, nullptr, nullptr) == -2);
+        EXPECT(revo_op_gallery_cert_stats(nullptr, f, nullptr) == -2 && err_has("op_gallery_cert_stats"));
     }
 
     if (failures) { std::printf("%d check(s) failed\n", failures); return 1; }
