@@ -103,6 +103,30 @@ class PromptDetector:
                        class_id=det.prompt.cpu().numpy(), class_names=phrases)
 
 
+NO_QUERY = "❌ No query embeddings available. Please detect/process an image first."
+NO_DATABASE = "❌ No database loaded. Please create or load a database first."
+
+
+def _item(payload, point_id, score=None):
+    """What a report says of one stored region: ``{"filename", "image_source", "bbox", "id"}``, then ``"score"`` if given."""
+    item = {"filename": payload.get("filename", "Unknown"), "image_source": payload.get("image_source", ""),
+            "bbox": payload.get("bbox"), "id": point_id}
+    if score is not None:
+        item["score"] = score
+    return item
+
+
+def _listing(items):
+    """One numbered line per scored item."""
+    return "".join(f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
+                   for n, it in enumerate(items))
+
+
+def _no_hits(what, threshold=None):
+    """The report of an empty result: "❌ No <what>", and the threshold that cut it if there was one."""
+    return f"❌ No {what}" + (f" above threshold {threshold}" if threshold is not None else "")
+
+
 class SimpleReverso:
     """Simplified visual investigation system (MI355X-native hot path)."""
     # names of the databases create_database calls of this instance are building right now (two UI threads may overlap):
@@ -539,11 +563,18 @@ class SimpleReverso:
         payload filter (filters.Filter or its dict form) restricting the search to the points it selects.  ``group_by``
         (a payload key, e.g. ``"image_source"``): at most ``max_results`` distinct values of it, each by its best region
         (a region-mode database holds several rows per image; without it one image can fill every place)."""
-        if not self.region_embeddings:
-            return "❌ No query embeddings available. Please detect/process an image first.", []
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready(need_query=True):
+            return err, []
         return self._search_with_query(self.region_embeddings[0], similarity_threshold, max_results, query_filter, group_by)
+
+    def _not_ready(self, need_query=False):
+        """What a search says instead of starting -- no query embedding (asked first, where a method needs one) or no
+        database -- or None."""
+        if need_query and not self.region_embeddings:
+            return NO_QUERY
+        if not self.vector_db or not self.current_database:
+            return NO_DATABASE
+        return None
 
     def _search_with_query(self, query, similarity_threshold, max_results, query_filter, group_by):
         """The search and the result formatting of :meth:`search_similar` for a query vector (an image region's or a
@@ -560,8 +591,7 @@ class SimpleReverso:
                 hits = self.vector_db.search(query, limit=int(max_results), score_threshold=score_threshold,
                                              query_filter=query_filter)
         if not hits:
-            return ("❌ No similar regions found" +
-                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
+            return _no_hits("similar regions found", similarity_threshold), []
         text = f"🎯 Found {len(hits)} similar regions:\n\n"
 
         def thumbnail(r):
@@ -646,8 +676,8 @@ class SimpleReverso:
     def search_by_text(self, text, similarity_threshold=None, max_results=5, query_filter=None, group_by=None):
         """:meth:`search_similar` with a prompt as the query: the same results and strings.  No default threshold: the
         text-image cosines of a CLIP model lie far below the 0.7 that suits image-image scores."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         try:
             query = self.embed_text([text] if isinstance(text, str) else text)[0].cpu()
         except Exception as e:
@@ -664,10 +694,8 @@ class SimpleReverso:
         the ranks in the text lists are untouched.  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox",
         "id", "score", "ranks", "scores"}`` best first: list 0 is the image, lists 1.. the prompts; ``ranks[j]`` is the
         region's rank in list j (0: not among its candidates), ``scores[j]`` its cosine against that query.  No thumbnails."""
-        if not self.region_embeddings:
-            return "❌ No query embeddings available. Please detect/process an image first.", []
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready(need_query=True):
+            return err, []
         try:
             prompts = self.embed_text([text] if isinstance(text, str) else text)
         except Exception as e:
@@ -680,9 +708,8 @@ class SimpleReverso:
                                                fusion=fusion, weights=[float(image_weight)] + [float(text_weight)] * n_text,
                                                prefetch_thresholds=thresholds, query_filter=query_filter)
         if not hits:
-            return "❌ No regions found for this picture and text", []
-        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
-                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score, "ranks": r.ranks, "scores": r.scores} for r in hits]
+            return _no_hits("regions found for this picture and text"), []
+        items = [dict(_item(r.payload, r.id, r.score), ranks=r.ranks, scores=r.scores) for r in hits]
         out = f"🎯 Found {len(items)} regions for the picture and the text ({fusion}):\n\n"
         for n, it in enumerate(items):
             out += f"{n + 1}. {it['filename']}  fused {it['score']:.4f}  ranks {it['ranks']}  (Source: {it['image_source']})\n"
@@ -693,8 +720,8 @@ class SimpleReverso:
         of the prompts ``labels`` -- the exact assignment of ``Gallery.kmeans(max_iter=0)`` with the prompts' embeddings as
         centroids.  Returns ``(text, out)``: per label ``{"label", "count", "members": [{"filename", "image_source", "bbox",
         "id", "score"}]}`` with its ``members`` best-scoring regions, in the order of ``labels``."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         labels = [labels] if isinstance(labels, str) else list(labels)
         if not labels:
             return "❌ Please provide at least one label", []
@@ -710,10 +737,7 @@ class SimpleReverso:
                     rows = np.nonzero(lab == j)[0]
                     best = rows[np.lexsort((rows, -sc[rows]))][:int(members)]        # score desc, row asc
                     out.append({"label": name, "count": int(rows.size),
-                                "members": [{"filename": db.payloads[r].get("filename", "Unknown"),
-                                             "image_source": db.payloads[r].get("image_source", ""),
-                                             "bbox": db.payloads[r].get("bbox"), "id": db.ids[r], "score": float(sc[r])}
-                                            for r in best.tolist()]})
+                                "members": [_item(db.payloads[r], db.ids[r], float(sc[r])) for r in best.tolist()]})
         except Exception as e:
             return f"❌ Error labelling the database: {str(e)}", []
         total = sum(o["count"] for o in out)
@@ -729,10 +753,8 @@ class SimpleReverso:
         regions of its best score among the group's regions (late-interaction MaxSim; up to 64 query regions).
         ``similarity_threshold`` cuts that SUM (it lies in [-n, n] for n query regions).  Returns ``(text, items)``: items
         ``{"image": the group's value, "score", "regions": [{"bbox", "score", "id", "filename"} per query region]}`` best first."""
-        if not self.region_embeddings:
-            return "❌ No query embeddings available. Please detect/process an image first.", []
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready(need_query=True):
+            return err, []
         queries = torch.stack([torch.as_tensor(e, dtype=torch.float32).reshape(-1) for e in self.region_embeddings])
         if queries.shape[0] > 64:
             return f"❌ {queries.shape[0]} query regions: a multi-region search takes at most 64.", []
@@ -741,8 +763,7 @@ class SimpleReverso:
                                                     score_threshold=None if similarity_threshold is None else float(similarity_threshold),
                                                     query_filter=query_filter)
         if not res:
-            return ("❌ No images found for these regions" +
-                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
+            return _no_hits("images found for these regions", similarity_threshold), []
         items = [{"image": r.value, "score": r.score,
                   "regions": [{"bbox": h.payload.get("bbox"), "score": h.score, "id": h.id,
                                "filename": h.payload.get("filename", "Unknown")} for h in r.hits]} for r in res]
@@ -758,21 +779,16 @@ class SimpleReverso:
         ``similarity_threshold`` against the first region embedding (``query_filter``: only the points a Qdrant-style payload
         filter selects).  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox", "id", "score"}`` best first.
         No thumbnails: the list can hold thousands of hits."""
-        if not self.region_embeddings:
-            return "❌ No query embeddings available. Please detect/process an image first.", []
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready(need_query=True):
+            return err, []
         query = self.region_embeddings[0]
         with self._lock:
             hits = self.vector_db.search_range(query, float(similarity_threshold), query_filter=query_filter)
         if not hits:
-            return f"❌ No similar regions found above threshold {similarity_threshold}", []
-        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
-                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+            return _no_hits("similar regions found", similarity_threshold), []
+        items = [_item(r.payload, r.id, r.score) for r in hits]
         text = f"🎯 Found {len(items)} similar regions:\n\n"
-        for n, it in enumerate(items):
-            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
-        return text, items
+        return text + _listing(items), items
 
     def search_by_examples(self, positive, negative=(), similarity_threshold=None, max_results=5, query_filter=None):
         """Relevance feedback: "more like these, and not like those".  Each example is the ``id`` of a stored region (as
@@ -780,28 +796,14 @@ class SimpleReverso:
         path: embedded whole through the loaded model).  A region's score is its best score against a positive example
         when that beats its best score against a negative one, else minus the square of the latter; examples given by id
         are not returned.  Returns ``(text, items)``, items ``{"filename", "image_source", "bbox", "id", "score"}`` best first."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
 
-        def resolve(examples):
-            if isinstance(examples, (str, bytes)) or torch.is_tensor(examples) or isinstance(examples, (np.ndarray, Image.Image)):
-                examples = [examples]
-            out, images, slots = [], [], []
-            for e in examples or ():
-                is_id = isinstance(e, str) and not os.path.exists(e)
-                is_vec = (torch.is_tensor(e) or isinstance(e, np.ndarray)) and np.ndim(e) == 1
-                if is_id or is_vec:
-                    out.append(e)
-                else:
-                    slots.append(len(out))
-                    out.append(None)
-                    images.append(pp.to_pil(Image.open(e).convert("RGB") if isinstance(e, str) else e))
-            if images:
-                for slot, v in zip(slots, self._embed_pils(images)):
-                    out[slot] = v
-            return out
+        def examples(given):
+            single = isinstance(given, (str, bytes)) or torch.is_tensor(given) or isinstance(given, (np.ndarray, Image.Image))
+            return self._resolve_examples([given] if single else given or ())
 
-        pos, neg = resolve(positive), resolve(negative)
+        pos, neg = examples(positive), examples(negative)
         if not pos:
             return "❌ No positive examples given. Please pick at least one result or image.", []
         try:
@@ -812,14 +814,28 @@ class SimpleReverso:
         except KeyError as e:
             return f"❌ {e.args[0]}", []
         if not hits:
-            return ("❌ No regions found for these examples" +
-                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
-        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
-                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+            return _no_hits("regions found for these examples", similarity_threshold), []
+        items = [_item(r.payload, r.id, r.score) for r in hits]
         text = f"🎯 Found {len(items)} regions like the {len(pos)} positive and unlike the {len(neg)} negative examples:\n\n"
-        for n, it in enumerate(items):
-            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
-        return text, items
+        return text + _listing(items), items
+
+    def _resolve_examples(self, examples):
+        """Examples as the store takes them: an ``id`` or a vector stays, every image (PIL image, array or path) becomes
+        its embedding -- all images in one batch."""
+        out, images, slots = [], [], []
+        for e in examples:
+            is_id = isinstance(e, str) and not os.path.exists(e)
+            is_vec = (torch.is_tensor(e) or isinstance(e, np.ndarray)) and np.ndim(e) == 1
+            if is_id or is_vec:
+                out.append(e)
+            else:
+                slots.append(len(out))
+                out.append(None)
+                images.append(pp.to_pil(Image.open(e).convert("RGB") if isinstance(e, str) else e))
+        if images:
+            for slot, v in zip(slots, self._embed_pils(images)):
+                out[slot] = v
+        return out
 
     def search_by_context(self, target, pairs, similarity_threshold=None, max_results=5, query_filter=None):
         """Discovery: matches for ``target`` under judgements of the form "this is the kind of thing I mean, that is not".
@@ -828,31 +844,14 @@ class SimpleReverso:
         pairs it lies on the positive side of, then by its similarity to the target; ``target=None`` returns the regions
         that satisfy the pairs (score 0: all of them).  Regions given by id are not returned.  Returns ``(text, items)``,
         items ``{"filename", "image_source", "bbox", "id", "score"}`` best first."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         pairs = list(pairs or ())
         if any(not isinstance(p, (tuple, list)) or len(p) != 2 for p in pairs):
             return "❌ Every context entry must be a (positive, negative) pair.", []
         if target is None and not pairs:
             return "❌ No target and no context pairs given. Please pick a target or at least one pair.", []
-
-        def resolve(examples):
-            out, images, slots = [], [], []
-            for e in examples:
-                is_id = isinstance(e, str) and not os.path.exists(e)
-                is_vec = (torch.is_tensor(e) or isinstance(e, np.ndarray)) and np.ndim(e) == 1
-                if is_id or is_vec:
-                    out.append(e)
-                else:
-                    slots.append(len(out))
-                    out.append(None)
-                    images.append(pp.to_pil(Image.open(e).convert("RGB") if isinstance(e, str) else e))
-            if images:
-                for slot, v in zip(slots, self._embed_pils(images)):
-                    out[slot] = v
-            return out
-
-        flat = resolve([e for pair in pairs for e in pair] + ([] if target is None else [target]))
+        flat = self._resolve_examples([e for pair in pairs for e in pair] + ([] if target is None else [target]))
         context = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(pairs))]
         try:
             with self._lock:
@@ -862,15 +861,11 @@ class SimpleReverso:
         except KeyError as e:
             return f"❌ {e.args[0]}", []
         if not hits:
-            return ("❌ No regions found for this context" +
-                    (f" above threshold {similarity_threshold}" if similarity_threshold is not None else "")), []
-        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
-                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+            return _no_hits("regions found for this context", similarity_threshold), []
+        items = [_item(r.payload, r.id, r.score) for r in hits]
         text = (f"🎯 Found {len(items)} regions for the {'target' if target is not None else 'context'} under "
                 f"{len(pairs)} context pairs:\n\n")
-        for n, it in enumerate(items):
-            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
-        return text, items
+        return text + _listing(items), items
 
     def search_similar_diverse(self, similarity_threshold=0.7, max_results=5, diversity=0.5, candidates_limit=None,
                                query_filter=None):
@@ -880,23 +875,18 @@ class SimpleReverso:
         the regions already picked (``diversity`` 0: the plain search, 1: as different as possible).  A database built from
         video frames or region crops otherwise answers with copies of one frame.  Returns ``(text, items)``, items
         ``{"filename", "image_source", "bbox", "id", "score"}`` in pick order.  No thumbnails."""
-        if not self.region_embeddings:
-            return "❌ No query embeddings available. Please detect/process an image first.", []
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready(need_query=True):
+            return err, []
         query = self.region_embeddings[0]
         with self._lock:
             hits = self.vector_db.search_mmr(query, limit=int(max_results), diversity=float(diversity),
                                              candidates_limit=candidates_limit, score_threshold=float(similarity_threshold),
                                              query_filter=query_filter)
         if not hits:
-            return f"❌ No similar regions found above threshold {similarity_threshold}", []
-        items = [{"filename": r.payload.get("filename", "Unknown"), "image_source": r.payload.get("image_source", ""),
-                  "bbox": r.payload.get("bbox"), "id": r.id, "score": r.score} for r in hits]
+            return _no_hits("similar regions found", similarity_threshold), []
+        items = [_item(r.payload, r.id, r.score) for r in hits]
         text = f"🎯 Found {len(items)} similar regions (diversity {float(diversity):g}):\n\n"
-        for n, it in enumerate(items):
-            text += f"{n + 1}. {it['filename']}  score {it['score']:.3f}  (Source: {it['image_source']})\n"
-        return text, items
+        return text + _listing(items), items
 
     def find_duplicates(self, similarity_threshold=0.95, query_filter=None):
         """Groups of near-duplicate regions in the loaded database: every stored region whose vector scores at least
@@ -905,8 +895,8 @@ class SimpleReverso:
         ``(text, groups)``: ``groups`` is a list of groups, each a list of ``{"filename", "image_source", "bbox", "id"}`` in
         storage order.  The default 0.95 is a guess: no trained checkpoint has been run here (parity
         unpinned), so what score separates copies from look-alikes is not measured."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         with self._lock:
             db = self.vector_db
             rows = db.duplicate_row_groups(float(similarity_threshold), query_filter=query_filter)
@@ -915,14 +905,7 @@ class SimpleReverso:
     @staticmethod
     def _duplicates_report(db, row_groups, similarity_threshold):
         """``(text, groups)`` of :meth:`find_duplicates` for groups given as lists of rows (the caller holds the lock)."""
-        out = []
-        for grp in row_groups:
-            members = []
-            for r in grp:
-                payload = db.payloads[r]
-                members.append({"filename": payload.get("filename", "Unknown"), "image_source": payload.get("image_source", ""),
-                                "bbox": payload.get("bbox"), "id": db.ids[r]})
-            out.append(members)
+        out = [[_item(db.payloads[r], db.ids[r]) for r in grp] for grp in row_groups]
         if not out:
             return f"No near-duplicates found at similarity threshold {similarity_threshold}", []
         text = f"🎯 Found {len(out)} groups of near-duplicates:\n\n"
@@ -938,8 +921,8 @@ class SimpleReverso:
         ``(text, groups)`` format, found without listing the pairs, so a group of tens of thousands of regions (the frames
         of a static shot) is returned where :meth:`find_duplicates` is refused.  ``largest_first`` orders the groups by
         (size descending, first region ascending) instead of by their first region."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         with self._lock:
             db = self.vector_db
             rows = db.duplicate_row_clusters(float(similarity_threshold), query_filter=query_filter)
@@ -954,8 +937,8 @@ class SimpleReverso:
         Qdrant-style payload filter selects.  Returns ``(text, graph)``: ``graph`` has one entry per region, in storage
         order: ``{"filename", "image_source", "bbox", "id", "neighbors": [{"filename", "image_source", "id", "score"}]}``,
         neighbours best first."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         try:
             with self._lock:
                 db = self.vector_db
@@ -963,11 +946,7 @@ class SimpleReverso:
                 payload_of = {i: p for i, p in zip(db.ids, db.payloads)}
         except Exception as e:
             return f"❌ Error building the similarity graph: {str(e)}", []
-        out = []
-        for i in g.ids:
-            p = payload_of[i]
-            out.append({"filename": p.get("filename", "Unknown"), "image_source": p.get("image_source", ""), "bbox": p.get("bbox"),
-                        "id": i, "neighbors": []})
+        out = [dict(_item(payload_of[i], i), neighbors=[]) for i in g.ids]
         for a, b, s in zip(g.offsets_row.tolist(), g.offsets_col.tolist(), g.scores.tolist()):
             nb = out[b]
             out[a]["neighbors"].append({"filename": nb["filename"], "image_source": nb["image_source"], "id": nb["id"],
@@ -985,8 +964,8 @@ class SimpleReverso:
         partitioned into ``n_themes`` themes by exact spherical k-means (``GalleryStore.themes``), largest first.  Returns
         ``(text, themes)``: each theme is ``{"size", "ids", "representative": {"filename", "image_source", "bbox", "id",
         "score"}}``, the representative being the member closest to the theme's centre."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first.", []
+        if err := self._not_ready():
+            return err, []
         try:
             with self._lock:
                 db = self.vector_db
@@ -995,13 +974,9 @@ class SimpleReverso:
                 themes = db.themes(int(n_themes), max_iter=int(max_iter), seed=int(seed), query_filter=query_filter)
         except Exception as e:
             return f"❌ Error summarizing the database: {str(e)}", []
-        out = []
-        for t in themes:
-            p = t.representative_payload
-            out.append({"size": t.size, "ids": t.ids,
-                        "representative": {"filename": p.get("filename", "Unknown"), "image_source": p.get("image_source", ""),
-                                           "bbox": p.get("bbox"), "id": t.representative_id,
-                                           "score": float(t.representative_score)}})
+        out = [{"size": t.size, "ids": t.ids,
+                "representative": _item(t.representative_payload, t.representative_id, float(t.representative_score))}
+               for t in themes]
         if not out:
             return "⚠️ No regions to summarize", []
         total = sum(t["size"] for t in out)
@@ -1016,8 +991,8 @@ class SimpleReverso:
         given: regions that meet both).  The database behind the reference does this with ``delete(points_selector=...)``;
         here the rows move on the device and the database directory gets one ``delete`` line (``GalleryStore.delete``).
         Returns a status string with the number of regions removed."""
-        if not self.vector_db or not self.current_database:
-            return "❌ No database loaded. Please create or load a database first."
+        if err := self._not_ready():
+            return err
         if isinstance(image_sources, str):
             image_sources = [image_sources]
         image_sources = list(image_sources or [])

@@ -32,6 +32,30 @@ def _require_cuda(t, name, device=None):
         raise _lib.RevoError(f"{name} is on {t.device} but the handle is bound to {device}")
 
 
+def _f32(t, name, device=None, host_ok=False):
+    """A caller's tensor as the ABI reads it: checked to be on ``device`` (a host tensor passes with ``host_ok``), fp32,
+    contiguous."""
+    if t.is_cuda or not host_ok:
+        _require_cuda(t, name, device)
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _rows(t, name, dim, device, form="n", host_ok=False, one_row=True):
+    """A caller's vectors as fp32 contiguous rows ``[n, dim]`` for a handle on ``device`` (:func:`_f32`); a single vector
+    ``[dim]`` is one row where the method takes that (``one_row``).  ``form`` is how the message names the row count."""
+    t = _f32(t, name, device, host_ok)
+    if one_row and t.dim() == 1:
+        t = t[None]
+    if t.dim() != 2 or t.shape[1] != dim:
+        raise ValueError(f"{name} must be [{form}, {dim}], got {tuple(t.shape)}")
+    return t
+
+
+def _threshold(score_threshold):
+    """``(has_threshold, threshold)`` as the ABI takes an optional score threshold: 0.0 is a threshold, None is none."""
+    return (0, 0.0) if score_threshold is None else (1, float(score_threshold))
+
+
 def _as_device(device):
     d = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
     return torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
@@ -54,6 +78,21 @@ def _tensor_array(state_dict, names):
 class _Handle:
     """A handle of the library held by ``self._h`` in ``self._lib``, destroyed by the entry point ``_destroy`` names."""
     _destroy = None
+
+    @contextlib.contextmanager
+    def _frame(self):
+        """Inside: the handle's lock is held and its device is the current one."""
+        with self._lock, torch.cuda.device(self.device):
+            yield
+
+    def _call(self, name, *args):
+        """The library's entry point ``name`` with this handle first; a status other than 0 raises, naming it."""
+        _lib.check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _chunks(self, n):
+        """``(start, end)`` of ``n`` inputs in forwards of at most ``max_batch``."""
+        for s in range(0, n, self.max_batch):
+            yield s, min(n, s + self.max_batch)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -157,12 +196,10 @@ class VitEngine(_Handle):
         B = images.shape[0]
         if out is None:
             out = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            for s in range(0, B, self.max_batch):
-                e = min(B, s + self.max_batch)
-                _lib.check(self._lib.revo_vit_forward(self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(out[s:e]),
-                                                      int(bool(normalize)), st), "revo_vit_forward")
+            for s, e in self._chunks(B):
+                self._call("revo_vit_forward", _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(out[s:e]), int(bool(normalize)), st)
         return out
 
     def embed_regions(self, images, region_image, token_bits, normalize=True, with_global=True):
@@ -198,10 +235,9 @@ class VitEngine(_Handle):
                     torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device))
         out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
         out_r = torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            for s in range(0, B, self.max_batch):
-                e = min(B, s + self.max_batch)
+            for s, e in self._chunks(B):
                 whole = s == 0 and e == B
                 sel = None if whole else torch.nonzero((ri >= s) & (ri < e)).reshape(-1)
                 n = R if whole else int(sel.shape[0])
@@ -210,10 +246,9 @@ class VitEngine(_Handle):
                 idx = (ri if whole else ri[sel] - s).to(torch.int32).contiguous()
                 cb = bits if whole else bits[sel.to(bits.device)].contiguous()
                 dst = out_r if whole else torch.empty((n, cfg.out_dim), dtype=torch.float32, device=images.device)
-                _lib.check(self._lib.revo_vit_forward_regions(
-                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(idx) if n else None, _lib.ptr(cb) if n else None,
-                    int(cb.is_cuda), n, _lib.ptr(out_g[s:e]) if with_global else None, _lib.ptr(dst) if n else None,
-                    int(bool(normalize)), st), "revo_vit_forward_regions")
+                self._call("revo_vit_forward_regions", _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(idx) if n else None,
+                           _lib.ptr(cb) if n else None, int(cb.is_cuda), n, _lib.ptr(out_g[s:e]) if with_global else None,
+                           _lib.ptr(dst) if n else None, int(bool(normalize)), st)
                 if not whole and n:
                     out_r.index_copy_(0, sel.to(out_r.device), dst)
         return out_g, out_r
@@ -228,13 +263,11 @@ class VitEngine(_Handle):
         B = images.shape[0]
         out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
         out_t = torch.empty((B, cfg.seq, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            for s in range(0, B, self.max_batch):
-                e = min(B, s + self.max_batch)
-                _lib.check(self._lib.revo_vit_forward_tokens(
-                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(out_g[s:e]) if with_global else None,
-                    _lib.ptr(out_t[s:e]), int(bool(normalize)), st), "revo_vit_forward_tokens")
+            for s, e in self._chunks(B):
+                self._call("revo_vit_forward_tokens", _lib.ptr(images[s:e]), kind, e - s,
+                           _lib.ptr(out_g[s:e]) if with_global else None, _lib.ptr(out_t[s:e]), int(bool(normalize)), st)
         return out_g, out_t
 
     def detect(self, images, prompts, thresholds=None, n_background=0, min_cells=1, max_regions=50, with_vectors=True,
@@ -249,10 +282,7 @@ class VitEngine(_Handle):
         import numpy as np
         images, kind = self._images(images)
         cfg = self.cfg
-        _require_cuda(prompts, "prompts", self.device)
-        pr = prompts.detach().to(torch.float32).contiguous()
-        if pr.dim() != 2 or pr.shape[1] != cfg.out_dim:
-            raise ValueError(f"prompts must be [P, {cfg.out_dim}], got {tuple(pr.shape)}")
+        pr = _rows(prompts, "prompts", cfg.out_dim, self.device, "P", one_row=False)
         P = pr.shape[0]
         if thresholds is None:
             thr = np.full(P, -np.inf, dtype=np.float32)
@@ -264,15 +294,13 @@ class VitEngine(_Handle):
         dev = images.device
         parts = []
         out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=dev) if with_global else None
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            for s in range(0, B, self.max_batch):
-                e = min(B, s + self.max_batch)
+            for s, e in self._chunks(B):
                 n = C.c_int64()
-                _lib.check(self._lib.revo_vit_detect(
-                    self._h, _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(pr), P, C.c_void_p(thr.ctypes.data), int(n_background),
-                    int(min_cells), int(max_regions), _lib.ptr(out_g[s:e]) if with_global else None, int(bool(with_vectors)),
-                    int(bool(normalize)), C.byref(n), st), "revo_vit_detect")
+                self._call("revo_vit_detect", _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(pr), P, C.c_void_p(thr.ctypes.data),
+                           int(n_background), int(min_cells), int(max_regions), _lib.ptr(out_g[s:e]) if with_global else None,
+                           int(bool(with_vectors)), int(bool(normalize)), C.byref(n), st)
                 n = int(n.value)
                 d = Detections(
                     image=torch.empty((n,), dtype=torch.int32, device=dev), prompt=torch.empty((n,), dtype=torch.int32, device=dev),
@@ -281,14 +309,12 @@ class VitEngine(_Handle):
                     bits=torch.empty((n, words), dtype=torch.int32, device=dev),
                     vectors=torch.empty((n, cfg.out_dim), dtype=torch.float32, device=dev) if with_vectors else None)
                 if n:
-                    _lib.check(self._lib.revo_vit_detect_read(
-                        self._h, 0, n, _lib.ptr(d.image), _lib.ptr(d.prompt), _lib.ptr(d.boxes), _lib.ptr(d.cells),
-                        _lib.ptr(d.confidence), _lib.ptr(d.bits), _lib.ptr(d.vectors), 1), "revo_vit_detect_read")
+                    self._call("revo_vit_detect_read", 0, n, _lib.ptr(d.image), _lib.ptr(d.prompt), _lib.ptr(d.boxes),
+                               _lib.ptr(d.cells), _lib.ptr(d.confidence), _lib.ptr(d.bits), _lib.ptr(d.vectors), 1)
                 if with_maps:
                     d.scores = torch.empty((e - s, P, G2), dtype=torch.float32, device=dev)
                     d.labels = torch.empty((e - s, G2), dtype=torch.int32, device=dev)
-                    _lib.check(self._lib.revo_vit_detect_maps(self._h, _lib.ptr(d.scores), _lib.ptr(d.labels), 1),
-                               "revo_vit_detect_maps")
+                    self._call("revo_vit_detect_maps", _lib.ptr(d.scores), _lib.ptr(d.labels), 1)
                 d.image += s
                 parts.append(d)
         if len(parts) == 1:
@@ -304,8 +330,8 @@ class VitEngine(_Handle):
         rows whose statistics the consuming GEMMs merged since the last reset, how many of them had |mean| / std above
         ``ratio`` (and above four times it) -- the regime in which the fold's rounding error exceeds the LayerNorm kernel's."""
         out = (C.c_double * 4)()
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self._lib.revo_vit_stats(self._h, out, int(bool(reset)), _lib.current_stream()), "revo_vit_stats")
+        with self._frame():
+            self._call("revo_vit_stats", out, int(bool(reset)), _lib.current_stream())
         return {"rows": int(out[0]), "rows_above_ratio": int(out[1]), "rows_above_4x_ratio": int(out[2]), "ratio": float(out[3])}
 
     # -- parity-test hook -----------------------------------------------------
@@ -317,13 +343,12 @@ class VitEngine(_Handle):
         assert B <= self.max_batch
         x = torch.empty((B, self.cfg.seq, self.cfg.width), dtype=torch.float32, device=images.device)
         dummy = torch.empty((B, self.cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            _lib.check(self._lib.revo_vit_set_debug_layers(self._h, int(n_layers)))
+            self._call("revo_vit_set_debug_layers", int(n_layers))
             try:
-                _lib.check(self._lib.revo_vit_forward(self._h, _lib.ptr(images), kind, B, _lib.ptr(dummy), 0, st),
-                           "revo_vit_forward")
-                _lib.check(self._lib.revo_vit_read_residual(self._h, B, _lib.ptr(x), st))
+                self._call("revo_vit_forward", _lib.ptr(images), kind, B, _lib.ptr(dummy), 0, st)
+                self._call("revo_vit_read_residual", B, _lib.ptr(x), st)
             finally:
                 self._lib.revo_vit_set_debug_layers(self._h, -1)
         return x
@@ -342,10 +367,10 @@ class VitEngine(_Handle):
         emb = self.embed(images)
         lnp = torch.empty((B, cfg.seq, cfg.width), dtype=torch.float32, device=self.device)
         pooled = torch.empty((B, cfg.width), dtype=torch.float32, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            _lib.check(self._lib.revo_vit_read_tap(self._h, 1, B, _lib.ptr(lnp), st), "revo_vit_read_tap")
-            _lib.check(self._lib.revo_vit_read_tap(self._h, 2, B, _lib.ptr(pooled), st), "revo_vit_read_tap")
+            self._call("revo_vit_read_tap", 1, B, _lib.ptr(lnp), st)
+            self._call("revo_vit_read_tap", 2, B, _lib.ptr(pooled), st)
         out.update(ln_post=lnp, pooled=pooled, embedding=emb)
         return out
 
@@ -409,13 +434,11 @@ class TextEngine(_Handle):
         if out is None:
             out = torch.empty((n, self.cfg.out_dim), dtype=torch.float32, device=self.device)
         _require_cuda(out, "out", self.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            for s in range(0, n, self.max_batch):
-                e = min(n, s + self.max_batch)
+            for s, e in self._chunks(n):
                 part = t[s:e]
-                _lib.check(self._lib.revo_text_forward(self._h, C.c_void_p(part.ctypes.data), e - s, L, _lib.ptr(out[s:e]),
-                                                       int(bool(normalize)), st), "revo_text_forward")
+                self._call("revo_text_forward", C.c_void_p(part.ctypes.data), e - s, L, _lib.ptr(out[s:e]), int(bool(normalize)), st)
         return out
 
     def embed(self, texts, normalize=True, trim=True):
@@ -437,13 +460,12 @@ class TextEngine(_Handle):
         assert 1 <= n <= self.max_batch
         x = torch.empty((n, L, self.cfg.width), dtype=torch.float32, device=self.device)
         dummy = torch.empty((n, self.cfg.out_dim), dtype=torch.float32, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             st = _lib.current_stream()
-            _lib.check(self._lib.revo_text_set_debug_layers(self._h, int(n_layers)))
+            self._call("revo_text_set_debug_layers", int(n_layers))
             try:
-                _lib.check(self._lib.revo_text_forward(self._h, C.c_void_p(t.ctypes.data), n, L, _lib.ptr(dummy), 0, st),
-                           "revo_text_forward")
-                _lib.check(self._lib.revo_text_read_residual(self._h, n, _lib.ptr(x), st))
+                self._call("revo_text_forward", C.c_void_p(t.ctypes.data), n, L, _lib.ptr(dummy), 0, st)
+                self._call("revo_text_read_residual", n, _lib.ptr(x), st)
             finally:
                 self._lib.revo_text_set_debug_layers(self._h, -1)
         return x
@@ -475,23 +497,18 @@ class Gallery(_Handle):
         return int(self._lib.revo_gallery_size(self._h))
 
     def clear(self):
-        _lib.check(self._lib.revo_gallery_clear(self._h))
+        self._call("revo_gallery_clear")
 
     def add(self, vectors, normalize=True):
         """Append fp32 rows [n, dim] (device or host tensor).  Rows are normalised
         at insert like qdrant's COSINE collections (core_system.py:600-603)."""
-        v = vectors.detach().to(torch.float32).contiguous()
-        if v.dim() != 2 or v.shape[1] != self.dim:
-            raise ValueError(f"vectors must be [n, {self.dim}], got {tuple(v.shape)}")
-        if v.is_cuda:
-            _require_cuda(v, "vectors", self.device)
+        v = _rows(vectors, "vectors", self.dim, self.device, host_ok=True, one_row=False)
         start = len(self)
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             # a device source is read by kernels on torch's current stream: its memory is not reused before they have
             # run (the caching allocator is stream-ordered), so nothing waits here -- an ingest appends batch after
             # batch without a host round trip; a host source is staged and synchronised inside the call
-            _lib.check(self._lib.revo_gallery_append(self._h, _lib.ptr(v), v.shape[0], int(bool(normalize)),
-                                                     int(v.is_cuda), _lib.current_stream()), "revo_gallery_append")
+            self._call("revo_gallery_append", _lib.ptr(v), v.shape[0], int(bool(normalize)), int(v.is_cuda), _lib.current_stream())
         return start
 
     ADD_UNIQUE_MAX = 16384                        # rows of one revo_gallery_append_unique call (DEDUP_MAX_BATCH, kernels.h)
@@ -502,21 +519,16 @@ class Gallery(_Handle):
         ``(rows int64 [n], scores fp32 [n], kept bool [n])`` on the device: a kept row's new row index and -inf, a dropped
         row's representative (the first such row) and its score.  The gallery needs room for every row of a call, kept or
         not; inputs above ``ADD_UNIQUE_MAX`` rows go in consecutive calls, which gives the same result.  Synchronous."""
-        v = vectors.detach().to(torch.float32).contiguous()
-        if v.dim() != 2 or v.shape[1] != self.dim:
-            raise ValueError(f"vectors must be [n, {self.dim}], got {tuple(v.shape)}")
-        if v.is_cuda:
-            _require_cuda(v, "vectors", self.device)
+        v = _rows(vectors, "vectors", self.dim, self.device, host_ok=True, one_row=False)
         n = int(v.shape[0])
         rows = torch.empty((n,), dtype=torch.int64, device=self.device)
         scores = torch.empty((n,), dtype=torch.float32, device=self.device)
         kept = C.c_int64()
-        with self._lock, torch.cuda.device(self.device):
+        with self._frame():
             for a in range(0, n, self.ADD_UNIQUE_MAX):
                 b = min(n, a + self.ADD_UNIQUE_MAX)
-                _lib.check(self._lib.revo_gallery_append_unique(
-                    self._h, _lib.ptr(v[a:b]), b - a, int(bool(normalize)), int(v.is_cuda), float(threshold), _lib.ptr(rows[a:b]),
-                    _lib.ptr(scores[a:b]), 1, C.byref(kept), _lib.current_stream()), "revo_gallery_append_unique")
+                self._call("revo_gallery_append_unique", _lib.ptr(v[a:b]), b - a, int(bool(normalize)), int(v.is_cuda),
+                           float(threshold), _lib.ptr(rows[a:b]), _lib.ptr(scores[a:b]), 1, C.byref(kept), _lib.current_stream())
         return rows, scores, torch.isinf(scores) & (scores < 0)
 
     def remove(self, rows):
@@ -549,9 +561,8 @@ class Gallery(_Handle):
             raise ValueError(f"rows must be bool [{n}], a packed int32 bitmap [{words}] or int64 indices, got {rows.dtype} "
                              f"{tuple(rows.shape)}")
         removed = C.c_int64()
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self._lib.revo_gallery_remove(self._h, _lib.ptr(bits), n, int(bits.is_cuda), C.byref(removed),
-                                                     _lib.current_stream()), "revo_gallery_remove")
+        with self._frame():
+            self._call("revo_gallery_remove", _lib.ptr(bits), n, int(bits.is_cuda), C.byref(removed), _lib.current_stream())
         return int(removed.value)
 
     def update(self, rows, vectors, normalize=True):
@@ -559,29 +570,27 @@ class Gallery(_Handle):
         have written it (include/revo.h, EDIT).  ``rows``: int64 indices (tensor or list), each inside the gallery and given
         once.  A filter or group ids stay valid: no row moves."""
         idx = torch.as_tensor(rows, dtype=torch.int64).reshape(-1).cpu().contiguous()
-        v = vectors.detach().to(torch.float32).contiguous()
-        if v.dim() != 2 or v.shape[1] != self.dim or v.shape[0] != idx.shape[0]:
+        v = _rows(vectors, "vectors", self.dim, self.device, idx.shape[0], host_ok=True, one_row=False)
+        if v.shape[0] != idx.shape[0]:
             raise ValueError(f"vectors must be [{idx.shape[0]}, {self.dim}] (one per row index), got {tuple(v.shape)}")
-        if v.is_cuda:
-            _require_cuda(v, "vectors", self.device)
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self._lib.revo_gallery_update(self._h, _lib.ptr(idx), _lib.ptr(v), idx.shape[0], int(bool(normalize)),
-                                                     int(v.is_cuda), _lib.current_stream()), "revo_gallery_update")
+        with self._frame():
+            self._call("revo_gallery_update", _lib.ptr(idx), _lib.ptr(v), idx.shape[0], int(bool(normalize)), int(v.is_cuda),
+                       _lib.current_stream())
 
     def read(self, start=0, n=None):
         n = len(self) - start if n is None else n
         out = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             torch.cuda.current_stream().synchronize()
-            _lib.check(self._lib.revo_gallery_read(self._h, start, n, _lib.ptr(out), 1), "revo_gallery_read")
+            self._call("revo_gallery_read", start, n, _lib.ptr(out), 1)
         return out
 
     def cert_stats(self):
         """The certificate's maxima as the searches read them: ``(G, Eg)`` with ``G >= ||g||`` and ``Eg >= ||bf16(g) - g||``
         for every row now present (include/revo.h, revo_op_gallery_cert_stats).  Synchronous."""
         out = (C.c_float * 2)()
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self._lib.revo_op_gallery_cert_stats(self._h, out, _lib.current_stream()), "revo_op_gallery_cert_stats")
+        with self._frame():
+            self._call("revo_op_gallery_cert_stats", out, _lib.current_stream())
         return float(out[0]), float(out[1])
 
     def allow_bits(self, allow):
@@ -603,19 +612,29 @@ class Gallery(_Handle):
         return allow.contiguous()
 
     @contextlib.contextmanager
-    def _filter(self, allow):
-        """Inside: the handle's searches see only the rows ``allow`` selects (revo_search_set_filter); the filter is
-        cleared again on the way out.  The caller holds the handle's lock."""
-        if allow is None:
-            yield
-            return
-        bits = self.allow_bits(allow)
-        _lib.check(self._lib.revo_search_set_filter(self._h, _lib.ptr(bits), len(self), 1, _lib.current_stream()),
-                   "revo_search_set_filter")
-        try:
-            yield
-        finally:
-            self._lib.revo_search_set_filter(self._h, None, 0, 0, None)
+    def _frame(self, allow=None, groups=None):
+        """Inside: the lock is held and the device current (:meth:`_Handle._frame`); then the handle's searches see only
+        the rows ``allow`` selects (revo_search_set_filter) and its grouped searches the group ids ``groups``
+        (revo_search_set_groups).  Both are cleared again on the way out."""
+        with super()._frame():
+            try:
+                if allow is not None:
+                    bits = self.allow_bits(allow)
+                    self._call("revo_search_set_filter", _lib.ptr(bits), len(self), 1, _lib.current_stream())
+                if groups is not None:
+                    n = len(self)
+                    _require_cuda(groups, "groups", self.device)
+                    if groups.dtype != torch.int32 or groups.dim() != 1 or groups.shape[0] != n:
+                        raise ValueError(f"groups must be int32 [{n}] (one group id per gallery row, -1 = none), got "
+                                         f"{groups.dtype} {tuple(groups.shape)}")
+                    groups = groups.contiguous() if n else torch.full((1,), -1, dtype=torch.int32, device=self.device)   # (non-null)
+                    self._call("revo_search_set_groups", _lib.ptr(groups), n, 1, _lib.current_stream())
+                yield
+            finally:
+                if groups is not None:
+                    self._lib.revo_search_set_groups(self._h, None, 0, 0, None)
+                if allow is not None:
+                    self._lib.revo_search_set_filter(self._h, None, 0, 0, None)
 
     def search(self, queries, k=5, score_threshold=None, index_offset=0, allow=None):
         """queries: fp32 [Q, dim] device tensor.  Returns (scores [Q,k] fp32,
@@ -624,23 +643,16 @@ class Gallery(_Handle):
         core_system.py:659-664).  ``allow`` (device tensor, bool [len] or a packed int32 bitmap): search only those
         rows -- exactly the result an unfiltered search of a gallery holding just the allowed rows would give.  k <= 1024
         (51 and up: include/revo.h, LARGE K)."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device, "Q")
         Q = q.shape[0]
         scores = torch.empty((Q, k), dtype=torch.float32, device=q.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
         counts = torch.empty((Q,), dtype=torch.int32, device=q.device)
         # k <= 50: the certified scan; 51 <= k <= 1024: the large-k path (include/revo.h, LARGE K), same result contract
         fn = "revo_search_topk" if k <= 50 else "revo_search_topk_large"
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(getattr(self._lib, fn)(
-                self._h, _lib.ptr(q), Q, int(k), int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), fn)
+        with self._frame(allow):
+            self._call(fn, _lib.ptr(q), Q, int(k), *_threshold(score_threshold), int(index_offset),
+                       _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream())
         return scores, idx, counts
 
     def pairs(self, threshold, allow=None):
@@ -649,14 +661,12 @@ class Gallery(_Handle):
         fp32)`` device tensors ordered by ``(i, j)``, exactly what an exhaustive fp32 scoring of every pair would give.
         Synchronous (the kernels read the candidate count between their passes)."""
         n = C.c_int64()
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_gallery_pairs(self._h, float(threshold), C.byref(n), _lib.current_stream()),
-                       "revo_gallery_pairs")
+        with self._frame(allow):
+            self._call("revo_gallery_pairs", float(threshold), C.byref(n), _lib.current_stream())
             n = int(n.value)
             pairs = torch.empty((n, 2), dtype=torch.int64, device=self.device)
             scores = torch.empty((n,), dtype=torch.float32, device=self.device)
-            _lib.check(self._lib.revo_gallery_pairs_read(self._h, 0, n, _lib.ptr(pairs), _lib.ptr(scores), 1),
-                       "revo_gallery_pairs_read")
+            self._call("revo_gallery_pairs_read", 0, n, _lib.ptr(pairs), _lib.ptr(scores), 1)
         return pairs, scores
 
     def clusters(self, threshold, allow=None):
@@ -667,14 +677,12 @@ class Gallery(_Handle):
         at least two rows; clusters ordered by their lowest row) is ``members[offsets[c]:offsets[c + 1]]``, ascending.
         Synchronous."""
         nc, nm = C.c_int64(), C.c_int64()
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_gallery_clusters(self._h, float(threshold), C.byref(nc), C.byref(nm),
-                                                       _lib.current_stream()), "revo_gallery_clusters")
+        with self._frame(allow):
+            self._call("revo_gallery_clusters", float(threshold), C.byref(nc), C.byref(nm), _lib.current_stream())
             labels = torch.empty((len(self),), dtype=torch.int64, device=self.device)
             offsets = torch.empty((int(nc.value) + 1,), dtype=torch.int64, device=self.device)
             members = torch.empty((int(nm.value),), dtype=torch.int64, device=self.device)
-            _lib.check(self._lib.revo_gallery_clusters_read(self._h, _lib.ptr(labels), _lib.ptr(offsets), _lib.ptr(members), 1),
-                       "revo_gallery_clusters_read")
+            self._call("revo_gallery_clusters_read", _lib.ptr(labels), _lib.ptr(offsets), _lib.ptr(members), 1)
         return labels, offsets, members
 
     def knn(self, k, score_threshold=None, allow=None):
@@ -684,16 +692,13 @@ class Gallery(_Handle):
         ``counts``; a row ``allow`` excludes has count 0 and is nobody's neighbour.  A score has the bits :meth:`pairs`
         gives the same two rows; a row is never its own neighbour, identical rows at other indices are.  Synchronous."""
         n = C.c_int64()
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_gallery_knn(self._h, int(k), int(score_threshold is not None),
-                                                  float(score_threshold if score_threshold is not None else 0.0), C.byref(n),
-                                                  _lib.current_stream()), "revo_gallery_knn")
+        with self._frame(allow):
+            self._call("revo_gallery_knn", int(k), *_threshold(score_threshold), C.byref(n), _lib.current_stream())
             n = int(n.value)
             scores = torch.empty((n, int(k)), dtype=torch.float32, device=self.device)
             idx = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
             counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-            _lib.check(self._lib.revo_gallery_knn_read(self._h, 0, n, _lib.ptr(idx), _lib.ptr(scores), _lib.ptr(counts), 1),
-                       "revo_gallery_knn_read")
+            self._call("revo_gallery_knn_read", 0, n, _lib.ptr(idx), _lib.ptr(scores), _lib.ptr(counts), 1)
         return scores, idx, counts
 
     def kmeans(self, centroids, max_iter=10, normalize=True, allow=None):
@@ -705,25 +710,21 @@ class Gallery(_Handle):
         int64, n_iter, converged)``, all tensors on the device; the labels are the exact assignment against the returned
         centroids, a row ``allow`` excludes has label -1 and score -inf.  Labels and scores are what
         ``search(self.read(), k=1)`` gives on a gallery of the returned centroids.  Synchronous."""
-        _require_cuda(centroids, "centroids", self.device)
-        c = centroids.detach().to(torch.float32).contiguous()
-        if c.dim() != 2 or c.shape[1] != self.dim or c.shape[0] < 1:
+        c = _rows(centroids, "centroids", self.dim, self.device, "C", one_row=False)
+        if c.shape[0] < 1:
             raise ValueError(f"centroids must be [C, {self.dim}] with C >= 1, got {tuple(c.shape)}")
         n_c = int(c.shape[0])
         n, it, conv = C.c_int64(), C.c_int32(), C.c_int32()
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_gallery_kmeans(self._h, _lib.ptr(c), n_c, int(bool(normalize)), 1, int(max_iter),
-                                                     C.byref(it), C.byref(conv), C.byref(n), _lib.current_stream()),
-                       "revo_gallery_kmeans")
+        with self._frame(allow):
+            self._call("revo_gallery_kmeans", _lib.ptr(c), n_c, int(bool(normalize)), 1, int(max_iter), C.byref(it),
+                       C.byref(conv), C.byref(n), _lib.current_stream())
             n = int(n.value)
             out = torch.empty((n_c, self.dim), dtype=torch.float32, device=self.device)
             sizes = torch.empty((n_c,), dtype=torch.int64, device=self.device)
             labels = torch.empty((n,), dtype=torch.int32, device=self.device)
             scores = torch.empty((n,), dtype=torch.float32, device=self.device)
-            _lib.check(self._lib.revo_gallery_kmeans_centroids(self._h, _lib.ptr(out), _lib.ptr(sizes), 1),
-                       "revo_gallery_kmeans_centroids")
-            _lib.check(self._lib.revo_gallery_kmeans_read(self._h, 0, n, _lib.ptr(labels), _lib.ptr(scores), 1),
-                       "revo_gallery_kmeans_read")
+            self._call("revo_gallery_kmeans_centroids", _lib.ptr(out), _lib.ptr(sizes), 1)
+            self._call("revo_gallery_kmeans_read", 0, n, _lib.ptr(labels), _lib.ptr(scores), 1)
         return out, labels, scores, sizes, int(it.value), bool(conv.value)
 
     def search_range(self, queries, score_threshold, index_offset=0, allow=None):
@@ -731,23 +732,17 @@ class Gallery(_Handle):
         fp32 score reaches ``score_threshold`` -- the reference's threshold without its ``limit``.  Returns ``(offsets [Q + 1]
         int64, indices [n] int64, scores [n] fp32)`` device tensors: query q's results are ``offsets[q] .. offsets[q + 1]``,
         best first (score desc, index asc), with the bits :meth:`search` returns.  Synchronous."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device, "Q")
         Q = q.shape[0]
         n = C.c_int64()
         offsets = torch.empty((Q + 1,), dtype=torch.int64, device=self.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_range(self._h, _lib.ptr(q), Q, float(score_threshold), int(index_offset),
-                                                   C.byref(n), _lib.current_stream()), "revo_search_range")
+        with self._frame(allow):
+            self._call("revo_search_range", _lib.ptr(q), Q, float(score_threshold), int(index_offset), C.byref(n),
+                       _lib.current_stream())
             n = int(n.value)
             idx = torch.empty((n,), dtype=torch.int64, device=self.device)
             scores = torch.empty((n,), dtype=torch.float32, device=self.device)
-            _lib.check(self._lib.revo_search_range_read(self._h, _lib.ptr(offsets), 0, n, _lib.ptr(idx), _lib.ptr(scores), 1),
-                       "revo_search_range_read")
+            self._call("revo_search_range_read", _lib.ptr(offsets), 0, n, _lib.ptr(idx), _lib.ptr(scores), 1)
         return offsets, idx, scores
 
     def recommend(self, positive, negative=None, k=5, score_threshold=None, index_offset=0, allow=None):
@@ -757,26 +752,17 @@ class Gallery(_Handle):
         (allowed by ``allow``, as in :meth:`search`) as ``(scores [k] fp32, indices [k] int64, count)`` device tensors
         (``count`` a 0-d int32), best first, padded with -inf / -1 -- exactly what scoring every row that way in fp32 and
         sorting gives.  Synchronous."""
-        def rows(t, name):
-            _require_cuda(t, name, self.device)
-            t = t.detach().to(torch.float32).contiguous()
-            if t.dim() == 1:
-                t = t[None]
-            if t.dim() != 2 or t.shape[1] != self.dim:
-                raise ValueError(f"{name} must be [n, {self.dim}], got {tuple(t.shape)}")
-            return t
-        pos = rows(positive, "positive")
-        neg = rows(negative, "negative") if negative is not None and negative.numel() > 0 else None
+        pos = _rows(positive, "positive", self.dim, self.device)
+        neg = _rows(negative, "negative", self.dim, self.device) if negative is not None and negative.numel() > 0 else None
         ex = pos if neg is None else torch.cat([pos, neg]).contiguous()
         k = int(k)
         scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
         idx = torch.empty((max(k, 1),), dtype=torch.int64, device=self.device)
         counts = torch.empty((1,), dtype=torch.int32, device=self.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_recommend(
-                self._h, _lib.ptr(ex), pos.shape[0], 0 if neg is None else neg.shape[0], k, int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_recommend")
+        with self._frame(allow):
+            self._call("revo_search_recommend", _lib.ptr(ex), pos.shape[0], 0 if neg is None else neg.shape[0], k,
+                       *_threshold(score_threshold), int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts),
+                       _lib.current_stream())
         return scores, idx, counts[0]
 
     def discover(self, target, positives, negatives, k=5, score_threshold=None, index_offset=0, allow=None):
@@ -789,34 +775,23 @@ class Gallery(_Handle):
         Returns the best ``k <= 1024`` rows (allowed by ``allow``, as in :meth:`search`) as ``(scores [k] fp32, indices [k]
         int64, count)`` device tensors, best first, padded with -inf / -1 -- exactly what scoring every row that way in
         fp32 and sorting gives.  Synchronous."""
-        def rows(t, name):
-            _require_cuda(t, name, self.device)
-            t = t.detach().to(torch.float32).contiguous()
-            if t.dim() == 1:
-                t = t[None]
-            if t.dim() != 2 or t.shape[1] != self.dim:
-                raise ValueError(f"{name} must be [n, {self.dim}], got {tuple(t.shape)}")
-            return t
-        pos = rows(positives, "positives") if positives is not None and positives.numel() > 0 else None
-        neg = rows(negatives, "negatives") if negatives is not None and negatives.numel() > 0 else None
+        pos = _rows(positives, "positives", self.dim, self.device) if positives is not None and positives.numel() > 0 else None
+        neg = _rows(negatives, "negatives", self.dim, self.device) if negatives is not None and negatives.numel() > 0 else None
         n = 0 if pos is None else pos.shape[0]
         if n != (0 if neg is None else neg.shape[0]):
             raise ValueError("discover: positives and negatives must hold the same number of rows (one of each per pair)")
         tgt = None
         if target is not None:
-            tgt = rows(target, "target")
+            tgt = _rows(target, "target", self.dim, self.device)
             if tgt.shape[0] != 1:
                 raise ValueError(f"target must be one vector of {self.dim} elements, got {tuple(target.shape)}")
         k = int(k)
         scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
         idx = torch.empty((max(k, 1),), dtype=torch.int64, device=self.device)
         counts = torch.empty((1,), dtype=torch.int32, device=self.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_discover(
-                self._h, None if tgt is None else _lib.ptr(tgt), None if pos is None else _lib.ptr(pos),
-                None if neg is None else _lib.ptr(neg), n, k, int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_discover")
+        with self._frame(allow):
+            self._call("revo_search_discover", _lib.ptr(tgt), _lib.ptr(pos), _lib.ptr(neg), n, k, *_threshold(score_threshold),
+                       int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream())
         return scores, idx, counts[0]
 
     def search_maxsim(self, queries, groups, k=5, score_threshold=None, index_offset=0, allow=None, with_parts=False):
@@ -828,24 +803,16 @@ class Gallery(_Handle):
         what scoring every group that way in fp32 and sorting gives.  ``with_parts``: also ``part_scores [k, n]`` fp32 (the
         best score per query vector) and ``part_rows [k, n]`` int64 (``index_offset`` + the lowest row attaining it),
         padded with -inf / -1.  Synchronous."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.dim() != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [n, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device)
         n, k = q.shape[0], int(k)
         scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
         gids = torch.empty((max(k, 1),), dtype=torch.int32, device=self.device)
         counts = torch.empty((1,), dtype=torch.int32, device=self.device)
         ps = torch.empty((max(k, 1), max(n, 1)), dtype=torch.float32, device=self.device) if with_parts else None
         pr = torch.empty((max(k, 1), max(n, 1)), dtype=torch.int64, device=self.device) if with_parts else None
-        with self._lock, torch.cuda.device(self.device), self._filter(allow), self._groups(groups):
-            _lib.check(self._lib.revo_search_maxsim(
-                self._h, _lib.ptr(q), n, k, int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(gids), _lib.ptr(counts), _lib.ptr(ps), _lib.ptr(pr), _lib.current_stream()),
-                "revo_search_maxsim")
+        with self._frame(allow, groups):
+            self._call("revo_search_maxsim", _lib.ptr(q), n, k, *_threshold(score_threshold), int(index_offset), _lib.ptr(scores),
+                       _lib.ptr(gids), _lib.ptr(counts), _lib.ptr(ps), _lib.ptr(pr), _lib.current_stream())
         return (scores, gids, counts[0], ps, pr) if with_parts else (scores, gids, counts[0])
 
     def search_mmr(self, queries, k=5, candidates=None, diversity=0.5, score_threshold=None, index_offset=0, allow=None):
@@ -857,12 +824,7 @@ class Gallery(_Handle):
         (``scores``: the rows' plain search scores; ``mmr_values``: the value each row was picked with), padded with
         -inf / -inf / -1.  Exact: the candidates are those of the exhaustive fp32 search, every similarity has the bits
         :meth:`pairs` reports, the selection is the fp32 arithmetic the header states.  Asynchronous like :meth:`search`."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device, "Q")
         k = int(k)
         candidates = min(1024, max(k, 100)) if candidates is None else int(candidates)
         Q = q.shape[0]
@@ -870,11 +832,9 @@ class Gallery(_Handle):
         values = torch.empty((Q, max(k, 1)), dtype=torch.float32, device=q.device)
         idx = torch.empty((Q, max(k, 1)), dtype=torch.int64, device=q.device)
         counts = torch.empty((Q,), dtype=torch.int32, device=q.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_mmr(
-                self._h, _lib.ptr(q), Q, k, candidates, float(diversity), int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset),
-                _lib.ptr(scores), _lib.ptr(values), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()), "revo_search_mmr")
+        with self._frame(allow):
+            self._call("revo_search_mmr", _lib.ptr(q), Q, k, candidates, float(diversity), *_threshold(score_threshold),
+                       int(index_offset), _lib.ptr(scores), _lib.ptr(values), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream())
         return scores, values, idx, counts
 
     def search_fusion(self, queries, k=5, limit=100, method="rrf", rrf_k=60.0, weights=None, list_thresholds=None,
@@ -888,8 +848,7 @@ class Gallery(_Handle):
         indices [n, k] int64, counts [n] int32)``, then ``ranks [n, k, m] int32`` (1-based position in list j, 0 = not in
         it) if ``with_ranks`` and ``list_scores [n, k, m] fp32`` (the row's exact score against every one of the m queries,
         member or not) if ``with_list_scores``; padding -inf / -1 / 0 / -inf.  Exact and asynchronous like :meth:`search`."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
+        q = _f32(queries, "queries", self.device)
         if q.dim() == 2:
             q = q[None]
         if q.dim() != 3 or q.shape[2] != self.dim:
@@ -902,30 +861,11 @@ class Gallery(_Handle):
         counts = torch.empty((n,), dtype=torch.int32, device=q.device)
         ranks = torch.empty((n, max(k, 1), m), dtype=torch.int32, device=q.device) if with_ranks else None
         ls = torch.empty((n, max(k, 1), m), dtype=torch.float32, device=q.device) if with_list_scores else None
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_fusion(
-                self._h, _lib.ptr(q), n, m, int(limit), _fusion_method(method), float(rrf_k), w, t, k,
-                int(score_threshold is not None), float(score_threshold if score_threshold is not None else 0.0),
-                int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.ptr(ranks), _lib.ptr(ls),
-                _lib.current_stream()), "revo_search_fusion")
+        with self._frame(allow):
+            self._call("revo_search_fusion", _lib.ptr(q), n, m, int(limit), _fusion_method(method), float(rrf_k), w, t, k,
+                       *_threshold(score_threshold), int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts),
+                       _lib.ptr(ranks), _lib.ptr(ls), _lib.current_stream())
         return (scores, idx, counts) + ((ranks,) if with_ranks else ()) + ((ls,) if with_list_scores else ())
-
-    @contextlib.contextmanager
-    def _groups(self, groups):
-        """Inside: the handle's grouped searches see these group ids (revo_search_set_groups); cleared on the way out.
-        The caller holds the handle's lock."""
-        n = len(self)
-        _require_cuda(groups, "groups", self.device)
-        if groups.dtype != torch.int32 or groups.dim() != 1 or groups.shape[0] != n:
-            raise ValueError(f"groups must be int32 [{n}] (one group id per gallery row, -1 = none), got {groups.dtype} "
-                             f"{tuple(groups.shape)}")
-        groups = groups.contiguous() if n else torch.full((1,), -1, dtype=torch.int32, device=self.device)   # (non-null)
-        _lib.check(self._lib.revo_search_set_groups(self._h, _lib.ptr(groups), n, 1, _lib.current_stream()),
-                   "revo_search_set_groups")
-        try:
-            yield
-        finally:
-            self._lib.revo_search_set_groups(self._h, None, 0, 0, None)
 
     def search_groups(self, queries, groups, limit=5, group_size=1, score_threshold=None, index_offset=0, allow=None):
         """The best ``limit`` groups of rows for each query (Qdrant's ``search_groups``; include/revo.h, GROUPED).
@@ -934,24 +874,16 @@ class Gallery(_Handle):
         exhaustive fp32 scoring of the rows ``allow`` selects (see :meth:`search`).  Returns (scores ``[Q, limit,
         group_size]`` fp32, indices (same, int64), hit_counts ``[Q, limit]`` int32, group_ids ``[Q, limit]`` int32,
         group_counts ``[Q]`` int32), padded with -inf / -1 / 0 / -1."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device, "Q")
         Q, L, S = q.shape[0], int(limit), int(group_size)
         scores = torch.empty((Q, L, S), dtype=torch.float32, device=q.device)
         idx = torch.empty((Q, L, S), dtype=torch.int64, device=q.device)
         hits = torch.empty((Q, L), dtype=torch.int32, device=q.device)
         gids = torch.empty((Q, L), dtype=torch.int32, device=q.device)
         ngroups = torch.empty((Q,), dtype=torch.int32, device=q.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow), self._groups(groups):
-            _lib.check(self._lib.revo_search_groups(
-                self._h, _lib.ptr(q), Q, L, S, int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset), _lib.ptr(scores),
-                _lib.ptr(idx), _lib.ptr(hits), _lib.ptr(gids), _lib.ptr(ngroups), _lib.current_stream()),
-                "revo_search_groups")
+        with self._frame(allow, groups):
+            self._call("revo_search_groups", _lib.ptr(q), Q, L, S, *_threshold(score_threshold), int(index_offset),
+                       _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(hits), _lib.ptr(gids), _lib.ptr(ngroups), _lib.current_stream())
         return scores, idx, hits, gids, ngroups
 
     # -- the exactness certificate (include/revo.h, "EXACTNESS") ------------------------------------------
@@ -964,14 +896,13 @@ class Gallery(_Handle):
         if not self.experiments:
             raise _lib.RevoError("set_search_mode is a parity-test hook of librevo_exp.so: create the gallery with "
                                  "experiments=True (the product library's searches are always certified exact)")
-        _lib.check(self._lib.revo_search_set_mode(self._h, self.MODES[mode] if isinstance(mode, str) else int(mode)),
-                   "revo_search_set_mode")
+        self._call("revo_search_set_mode", self.MODES[mode] if isinstance(mode, str) else int(mode))
 
     def search_stats(self):
         """Counters of the last search on this handle (synchronises the current stream)."""
         out = (C.c_int32 * 8)()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.revo_search_stats(self._h, out, _lib.current_stream()), "revo_search_stats")
+            self._call("revo_search_stats", out, _lib.current_stream())
         return {"uncertified": int(out[0]), "bruteforced": int(out[1]), "checked": int(out[2]), "collected_rows": int(out[3]),
                 "from_segments": int(out[4]), "grouped_fallback": int(out[5]), "large_k_fallback": int(out[6]),
                 "join_passes": int(out[7])}
@@ -979,29 +910,23 @@ class Gallery(_Handle):
     def set_total_rows(self, total_rows):
         """This handle holds ONE SHARD of a row-sharded gallery of ``total_rows`` rows (0: forget): its two-phase scans
         start from an estimate of the whole gallery's admission level (include/revo.h, revo_search_set_total_rows)."""
-        _lib.check(self._lib.revo_search_set_total_rows(self._h, int(total_rows)), "revo_search_set_total_rows")
+        self._call("revo_search_set_total_rows", int(total_rows))
         self._total_rows = int(total_rows)
 
     def search_plan(self, n_queries, k=5):
         """How a search would run (reporting): dict with the scan form, the pre-pass rows, slices and ksel."""
         out = (C.c_int64 * 4)()
-        _lib.check(self._lib.revo_search_plan(self._h, int(n_queries), int(k), out), "revo_search_plan")
+        self._call("revo_search_plan", int(n_queries), int(k), out)
         return {"scan256": bool(out[0]), "prepass_rows": int(out[1]), "slices": int(out[2]), "ksel": int(out[3])}
 
     # -- the same search in two phases (row-sharded gallery; see sharded.py and include/revo.h) --------------
     def search_candidates(self, queries, k=5, top_m=8, allow=None):
         """Phase 1: scan this shard, keep the candidates in the handle.  Returns int32 ``[Q, top_m]``: the bit
         patterns of the order-preserving uint32 scan scores of each query's best ``top_m`` candidates."""
-        _require_cuda(queries, "queries", self.device)
-        q = queries.detach().to(torch.float32).contiguous()
-        if q.dim() == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = _rows(queries, "queries", self.dim, self.device, "Q")
         bounds = torch.empty((q.shape[0], int(top_m)), dtype=torch.int32, device=q.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_candidates(self._h, _lib.ptr(q), q.shape[0], int(k), int(top_m),
-                                                        _lib.ptr(bounds), _lib.current_stream()), "revo_search_candidates")
+        with self._frame(allow):
+            self._call("revo_search_candidates", _lib.ptr(q), q.shape[0], int(k), int(top_m), _lib.ptr(bounds), _lib.current_stream())
         return bounds
 
     def search_finish(self, n_queries, k, all_bounds=None, score_threshold=None, index_offset=0, out_packed=None, allow=None):
@@ -1029,12 +954,9 @@ class Gallery(_Handle):
             parts, top_m = int(all_bounds.shape[0]), int(all_bounds.shape[2])
             if all_bounds.dtype != torch.int32 or all_bounds.shape[1] != Q:
                 raise ValueError("all_bounds must be int32 [parts, Q, top_m]")
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_finish(
-                self._h, Q, k, int(score_threshold is not None),
-                float(score_threshold if score_threshold is not None else 0.0), int(index_offset), _lib.ptr(all_bounds),
-                parts, top_m, _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.ptr(cert), _lib.current_stream()),
-                "revo_search_finish")
+        with self._frame(allow):
+            self._call("revo_search_finish", Q, k, *_threshold(score_threshold), int(index_offset), _lib.ptr(all_bounds), parts,
+                       top_m, _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.ptr(cert), _lib.current_stream())
         return scores, idx, counts
 
     def search_exact(self, q_idx, need, k, index_offset=0, out_packed=None, allow=None):
@@ -1053,10 +975,9 @@ class Gallery(_Handle):
             scores = torch.empty((n, k), dtype=torch.float32, device=self.device)
             idx = torch.empty((n, k), dtype=torch.int64, device=self.device)
         counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-        with self._lock, torch.cuda.device(self.device), self._filter(allow):
-            _lib.check(self._lib.revo_search_exact(self._h, n, _lib.ptr(q_idx.contiguous()), _lib.ptr(need.contiguous()), k, 0,
-                                                   0.0, int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts),
-                                                   _lib.current_stream()), "revo_search_exact")
+        with self._frame(allow):
+            self._call("revo_search_exact", n, _lib.ptr(q_idx.contiguous()), _lib.ptr(need.contiguous()), k, 0, 0.0,
+                       int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream())
         return scores, idx, counts
 
 
@@ -1093,8 +1014,7 @@ def merge_topk_packed(packed, parts, n_queries, k, score_threshold=None, certify
                torch.empty((max(Q, 1),), dtype=torch.float32, device=packed.device))
     lib = _lib.load()
     with torch.cuda.device(packed.device):
-        _lib.check(lib.revo_topk_merge_packed(_lib.ptr(packed), int(parts), Q, k, int(score_threshold is not None),
-                                              float(score_threshold if score_threshold is not None else 0.0),
+        _lib.check(lib.revo_topk_merge_packed(_lib.ptr(packed), int(parts), Q, k, *_threshold(score_threshold),
                                               _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts),
                                               _lib.ptr(unc[0]) if unc else None, _lib.ptr(unc[1]) if unc else None,
                                               _lib.ptr(unc[2]) if unc else None, _lib.current_stream()),
@@ -1114,8 +1034,7 @@ def merge_topk(part_scores, part_indices, k, score_threshold=None):
     counts = torch.empty((Q,), dtype=torch.int32, device=ps.device)
     lib = _lib.load()
     with torch.cuda.device(ps.device):
-        _lib.check(lib.revo_topk_merge(_lib.ptr(ps), _lib.ptr(pi), P, Q, k, int(score_threshold is not None),
-                                       float(score_threshold if score_threshold is not None else 0.0),
+        _lib.check(lib.revo_topk_merge(_lib.ptr(ps), _lib.ptr(pi), P, Q, k, *_threshold(score_threshold),
                                        _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream()),
                    "revo_topk_merge")
     return scores, idx, counts
@@ -1148,10 +1067,9 @@ def fuse_topk(scores, indices, counts, k=5, method="rrf", rrf_k=60.0, weights=No
     int64 ``[n, m, C]``, ``counts`` int32 ``[n, m]``, device tensors -- e.g. the merged lists of a row-sharded search.  The
     arithmetic, order and outputs of :meth:`Gallery.search_fusion`: returns ``(scores [n, k], indices [n, k], counts [n])``
     and ``ranks [n, k, m]`` if ``with_ranks``."""
-    _require_cuda(scores, "scores")
+    s = _f32(scores, "scores")
     _require_cuda(indices, "indices", scores.device)
     _require_cuda(counts, "counts", scores.device)
-    s = scores.detach().to(torch.float32).contiguous()
     i = indices.detach().to(torch.int64).contiguous()
     c = counts.detach().to(torch.int32).contiguous()
     if s.dim() != 3 or i.shape != s.shape or tuple(c.shape) != tuple(s.shape[:2]):
@@ -1167,8 +1085,7 @@ def fuse_topk(scores, indices, counts, k=5, method="rrf", rrf_k=60.0, weights=No
     lib = _lib.load()
     with torch.cuda.device(s.device):
         _lib.check(lib.revo_topk_fuse(_lib.ptr(s), _lib.ptr(i), _lib.ptr(c), n, m, limit, _fusion_method(method), float(rrf_k),
-                                      w, t, k, int(score_threshold is not None),
-                                      float(score_threshold if score_threshold is not None else 0.0), _lib.ptr(out_s),
+                                      w, t, k, *_threshold(score_threshold), _lib.ptr(out_s),
                                       _lib.ptr(out_i), _lib.ptr(out_c), _lib.ptr(ranks), _lib.current_stream()),
                    "revo_topk_fuse")
     return (out_s, out_i, out_c, ranks) if with_ranks else (out_s, out_i, out_c)

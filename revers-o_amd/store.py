@@ -572,6 +572,10 @@ class GalleryStore:
             self._filter_cache = (key, bits)
         return self._filter_cache[1]
 
+    def _points(self, scores, rows):
+        """The hits of a result: host lists of scores and of the rows that have them."""
+        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(scores, rows)]
+
     def search(self, query_vector, limit, score_threshold=None, query_filter=None):
         """One query, qdrant-style result list (core_system.py:659-664).  ``query_filter`` (Qdrant's ``Filter`` shape, see
         filters.py, or its dict form): only points it selects are searched -- exactly, in the kernels, not by dropping hits."""
@@ -581,7 +585,7 @@ class GalleryStore:
         s, i, c = self.gallery.search(q.to(dev), k=int(limit), score_threshold=score_threshold, allow=allow)
         n = int(c[0])
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
-        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
+        return self._points(s, i)
 
     def search_mmr(self, query_vector, limit, diversity=0.5, candidates_limit=None, score_threshold=None, query_filter=None):
         """One query, diverse results (Qdrant's ``Mmr(diversity, candidates_limit)`` re-ranking of a nearest-neighbour query):
@@ -595,7 +599,7 @@ class GalleryStore:
                                              diversity=float(diversity), score_threshold=score_threshold, allow=allow)
         n = int(c[0])
         s, i = s[0, :n].tolist(), i[0, :n].tolist()
-        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s, i)]
+        return self._points(s, i)
 
     def search_range_batch(self, query_vectors, score_threshold, query_filter=None):
         """Every point (selected by ``query_filter``, if given) whose vector scores at least ``score_threshold`` against each
@@ -608,8 +612,7 @@ class GalleryStore:
         allow = self._allow_bits(query_filter) if query_filter is not None else None
         off, idx, sc = self.gallery.search_range(q.to(self.gallery.device), float(score_threshold), allow=allow)
         off, idx, sc = off.tolist(), idx.tolist(), sc.tolist()
-        return [[ScoredPoint(self.ids[j], float(s), self.payloads[j]) for j, s in zip(idx[off[r]:off[r + 1]], sc[off[r]:off[r + 1]])]
-                for r in range(len(off) - 1)]
+        return [self._points(sc[off[r]:off[r + 1]], idx[off[r]:off[r + 1]]) for r in range(len(off) - 1)]
 
     def search_range(self, query_vector, score_threshold, query_filter=None):
         """One query: every point (selected by ``query_filter``, if given) scoring at least ``score_threshold``, best first --
@@ -671,7 +674,7 @@ class GalleryStore:
             s, i, c = self.gallery.recommend(pos, neg if neg.shape[0] else None, k=int(limit), score_threshold=score_threshold,
                                              allow=allow)
             n = int(c)
-        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
+        return self._points(s[:n].tolist(), i[:n].tolist())
 
     def discover(self, target=None, context=(), limit=5, score_threshold=None, query_filter=None):
         """Discovery search in Qdrant's shape: ``context`` is a list of ``(positive, negative)`` pairs and ``target`` the
@@ -696,7 +699,7 @@ class GalleryStore:
         s, i, c = self.gallery.discover(None if tgt is None else tgt[0], pos, neg, k=int(limit), score_threshold=score_threshold,
                                         allow=allow)
         n = int(c)
-        return [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[:n].tolist(), i[:n].tolist())]
+        return self._points(s[:n].tolist(), i[:n].tolist())
 
     def query_fusion(self, prefetch, limit=5, prefetch_limit=100, fusion="rrf", rrf_k=60.0, weights=None, prefetch_thresholds=None,
                      score_threshold=None, query_filter=None):
@@ -747,8 +750,7 @@ class GalleryStore:
         s, i, hc, gid = s[0].tolist(), i[0].tolist(), hc[0].tolist(), gid[0].tolist()
         out = []
         for r in range(int(gc[0])):
-            hits = [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(s[r][:hc[r]], i[r][:hc[r]])]
-            out.append(PointGroup(values[gid[r]], hits))
+            out.append(PointGroup(values[gid[r]], self._points(s[r][:hc[r]], i[r][:hc[r]])))
         return GroupsResult(out)
 
     def search_multivector(self, query_vectors, group_by, limit=5, score_threshold=None, query_filter=None):
@@ -767,9 +769,7 @@ class GalleryStore:
                                                        score_threshold=score_threshold, allow=allow, with_parts=True)
         n = int(c)
         s, gid, ps, pr = s[:n].tolist(), gid[:n].tolist(), ps[:n].tolist(), pr[:n].tolist()
-        return [MultiVectorResult(values[gid[r]], float(s[r]),
-                                  [ScoredPoint(self.ids[j], float(sc), self.payloads[j]) for sc, j in zip(ps[r], pr[r])])
-                for r in range(n)]
+        return [MultiVectorResult(values[gid[r]], float(s[r]), self._points(ps[r], pr[r])) for r in range(n)]
 
     def _pairs(self, score_threshold, query_filter):
         allow = self._allow_bits(query_filter) if query_filter is not None else None

@@ -1087,3 +1087,53 @@ def test_two_phase_state_survives_pairs_and_clusters_and_is_dropped_by_every_oth
         with pytest.raises(_lib.RevoError, match="no matching revo_search_candidates call"):
             G.search_finish(Q, k)
     G.close()
+
+
+# ---- what a caller may hand in as queries ---------------------------------------------------------------------------
+def _query_forms(G, groups):
+    """name -> the search as a function of the query tensor alone, for the five searches that take ``[Q, dim]`` queries"""
+    return {"search": lambda q: G.search(q, k=5),
+            "search_range": lambda q: G.search_range(q, 0.1),
+            "search_mmr": lambda q: G.search_mmr(q, k=5),
+            "search_groups": lambda q: G.search_groups(q, groups, limit=5),
+            "search_candidates": lambda q: (G.search_candidates(q, k=5),)}
+
+
+@pytest.fixture(scope="module")
+def small_gallery(dev):
+    g = torch.Generator().manual_seed(64128)
+    rows = torch.randn(100, 64, generator=g).to(dev)
+    G = engine.Gallery(64, 128, device=0)
+    G.add(rows)
+    groups = (torch.arange(100, device=dev) // 4).to(torch.int32)
+    yield G, groups, torch.randn(3, 64, generator=g).to(dev)
+    G.close()
+
+
+@pytest.mark.parametrize("name", ["search", "search_range", "search_mmr", "search_groups", "search_candidates"])
+def test_queries_that_are_not_rows_of_the_gallery_width_are_rejected(dev, small_gallery, name):
+    """A query tensor is ``[n, dim]`` or ``[dim]``.  ``[3, 64, 2]`` has the right second extent and twice the floats: read as
+    ``3 * 64`` floats it would give well-formed wrong results, so it must not reach the library."""
+    from reverso_amd import _lib
+    G, groups, q = small_gallery
+    run = _query_forms(G, groups)[name]
+    with pytest.raises(ValueError, match="queries"):
+        run(torch.stack([q, q], dim=2))                      # [3, 64, 2]
+    with pytest.raises(ValueError, match="queries"):
+        run(q[:, :32].contiguous())                          # [3, 32]
+    with pytest.raises(_lib.RevoError, match="queries"):
+        run(q.cpu())
+    one, row = run(q[0]), run(q[0][None])                    # [64] is the one row [1, 64]
+    assert len(one) == len(row)
+    for a, b in zip(one, row):
+        assert a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b)
+
+
+def test_a_failed_call_names_its_entry_point(dev):
+    """Every status check carries the entry point's name: ``clear()`` on a closed handle (a null handle is refused before
+    the device is touched) says which call failed."""
+    from reverso_amd import _lib
+    G = engine.Gallery(64, 128, device=0)
+    G.close()
+    with pytest.raises(_lib.RevoError, match="revo_gallery_clear"):
+        G.clear()
