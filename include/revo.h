@@ -146,7 +146,8 @@ int32_t revo_vit_detect_maps(revo_vit* vit, float* scores, int32_t* labels, int3
  * a trained checkpoint this is the number to look at first if embeddings drift: out4 = { rows the consuming GEMMs merged
  * statistics for since the last reset (each row of each folded LayerNorm of each forward, counted once; rows that a
  * separate leftover-row kernel takes -- none at the headline shapes -- are not sampled), of those: rows with |mean| * rstd > out4[3], rows with |mean| * rstd > 4 *
- * out4[3], the ratio that counts as large (8) }.  Synchronises `stream`; reset != 0 clears the counters. */
+ * out4[3], the ratio that counts as large (8) }.  The counters are read, and with reset != 0 cleared, ON `stream` -- behind the
+ * forwards already enqueued there, ahead of the next -- and the call returns when `stream` has drained. */
 int32_t revo_vit_stats(revo_vit* vit, double* out4, int32_t reset, void* stream);
 
 /* ---- TEXT: the text tower of the same CLIP checkpoint (the reference loads it at core_system.py:181 and never calls it):
@@ -178,12 +179,19 @@ int32_t revo_text_forward(revo_text* text, const int32_t* tokens, int32_t batch,
 int32_t revo_gallery_create(int32_t dim, int64_t capacity, int32_t device, int32_t keep_f32, revo_gallery** out);
 int32_t revo_gallery_destroy(revo_gallery* g);
 /* vecs: [n, dim] fp32, host (src_on_device = 0) or device memory.  normalize != 0
- * L2-normalises each row at insert, as qdrant does for Distance.COSINE. */
+ * L2-normalises each row at insert, as qdrant does for Distance.COSINE.  A device source is read by a kernel enqueued on
+ * `stream` (no host round trip); a host source is staged in chunks and the call waits for `stream` before it returns (the
+ * caller may free it on return). */
 int32_t revo_gallery_append(revo_gallery* g, const float* vecs, int64_t n, int32_t normalize, int32_t src_on_device,
                             void* stream);
 int64_t revo_gallery_size(const revo_gallery* g);
+/* Empties the gallery.  Takes no stream and touches no device memory: the certificate's row maxima are reset on the stream of
+ * the next append, ahead of its kernel, so the caller orders a clear exactly as it orders that append (appends still pending
+ * on another stream need an event first, as for any two calls on one handle). */
 int32_t revo_gallery_clear(revo_gallery* g);
-/* copy rows [start, start+n) of the fp32 master copy to dst (host or device); needs keep_f32 */
+/* copy rows [start, start+n) of the fp32 master copy to dst (host or device); needs keep_f32.  Takes no stream: the caller must
+ * first have waited for the streams of the appends, updates and removes that wrote those rows; the copy runs on the default
+ * stream and has completed when the call returns. */
 int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst, int32_t dst_on_device);
 
 /* ---- EDIT: rows leave and change in place (the points-delete and the replacing upsert of the database behind the
@@ -207,7 +215,8 @@ int32_t revo_gallery_read(revo_gallery* g, int64_t start, int64_t n, float* dst,
  * revo_gallery_update overwrites row row_idx[i] (HOST array of n entries) with vecs[i] ([n, dim] fp32, host or device)
  * exactly as an append would have written it: the same normalisation arithmetic, fp32 master, bf16 row, and the row's share
  * merged into the certificate's maxima (which therefore also stay upper bounds).  An index outside [0, size) or a repeated
- * index gives status -2 before the device is touched; n = 0 does nothing.  Enqueued on `stream` like an append.
+ * index gives status -2 before the device is touched; n = 0 does nothing.  Enqueued on `stream` like an append, behind one
+ * wait for `stream`: the host index array has been read when the call returns.
  * Both invalidate a held pairs, clusters and range result (their _read gives -2, as after an append) and the two-phase candidate
  * state.  A remove that removes at least one row also drops the multi-vector search's index, and a filter or group ids set
  * for the old size fail the next search with the message an append gives (set them again); an update leaves filter, group
@@ -331,7 +340,10 @@ int32_t revo_search_topk_large(revo_gallery* g, const float* queries, int32_t n_
  * gives status -2, the count in revo_last_error().  revo_search_stats after it: slot 3 = candidate pairs re-scored in fp32,
  * slot 7 = join passes run (1, or 2 when the candidate workspace had to grow), every other slot 0.
  * revo_gallery_pairs_read copies result entries [start, start + n) to pairs ([n][2] int64) and scores ([n] fp32), host or
- * device memory (dst_on_device).  A result stays valid until the next revo_gallery_pairs call or a change of the gallery's
+ * device memory (dst_on_device).  Like every _read entry point (_pairs, _clusters, _knn, _kmeans and its _centroids, _range,
+ * revo_vit_detect_read and _maps) it takes no stream: the result it copies is complete, because the call that computed it is
+ * SYNCHRONOUS; the copy runs on the default stream and has completed when the call returns, so a device destination may then
+ * be used on any stream.  A result stays valid until the next revo_gallery_pairs call or a change of the gallery's
  * rows: after an append or a clear, or with no result, it gives status -2, as does a range past the result. */
 int32_t revo_gallery_pairs(revo_gallery* g, float threshold, int64_t* n_pairs, void* stream);
 int32_t revo_gallery_pairs_read(revo_gallery* g, int64_t start, int64_t n, int64_t* pairs, float* scores,

@@ -108,8 +108,10 @@ extern "C" int32_t revo_search_set_groups(revo_gallery* g, const int32_t* group_
 
 extern "C" int32_t revo_gallery_clear(revo_gallery* g) {
     REVO_REQUIRE(g, "null handle");
-    REVO_ON_DEVICE(g->device);
-    REVO_HIP_CHECK(hipMemset(g->gstat.p, 0, 8));      // the row maxima of the certificate start over with the rows
+    // The row maxima of the certificate start over with the rows -- on the stream of the next write, ahead of its kernel
+    // (gallery_write_rows): a reset issued from here would run on no stream of the caller's and could overtake an append that
+    // is still pending, or land behind the next one.  No device memory is touched.
+    g->gstat_reset = true;
     g->size = 0;
     g->drop_results(); g->maxsim.rows = -1;
     return 0;
@@ -122,6 +124,10 @@ int gallery_write_rows(revo_gallery* g, const float* vecs, int64_t n, int32_t no
                        const long long* map, const char* prof, hipStream_t st) {
     const int D = g->D;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (D * 4));
+    if (g->gstat_reset && n > 0) {                        // the first rows after revo_gallery_clear
+        REVO_HIP_CHECK(hipMemsetAsync(g->gstat.p, 0, 8, st));
+        g->gstat_reset = false;
+    }
     for (int64_t done = 0; done < n; done += chunk_rows) {
         const int64_t m = std::min(chunk_rows, n - done);
         const float* src = vecs + done * D;
@@ -171,7 +177,8 @@ extern "C" int32_t revo_op_gallery_cert_stats(revo_gallery* g, float* out, void*
     API_BEGIN
     REVO_REQUIRE(g && out, "op_gallery_cert_stats: null argument");
     REVO_ON_DEVICE(g->device);
-    REVO_HIP_CHECK(hipMemcpyAsync(out, g->gstat.p, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (g->gstat_reset) out[0] = out[1] = 0.f;            // cleared, nothing written since: the reset is still to be enqueued
+    else REVO_HIP_CHECK(hipMemcpyAsync(out, g->gstat.p, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
     REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
     API_END

@@ -134,6 +134,7 @@ struct __attribute__((visibility("default"))) revo_gallery {   // (the C ABI nam
     // exactness certificate (kernels.h): per-query rounding norms of the last search's queries, running maxima over the
     // gallery's rows, the fallback workspace (xbuf, sized with q_cap; its layout is xw) and the handle's mode
     DeviceBuffer<float> qstat; DeviceBuffer<uint32_t> gstat;
+    bool gstat_reset = false;      // revo_gallery_clear: the next gallery_write_rows zeroes gstat on its stream, ahead of its kernel
     DeviceBuffer<> xbuf; revo::ExactWs xw{};
     int mode = 0;
     const uint32_t* seed_bounds = nullptr;   // experiment build only (revo_debug_seed_bounds): admission bounds from outside
@@ -188,9 +189,12 @@ inline int require_threshold(int has_thr, float thr, const char* who) {
     REVO_REQUIRE(!has_thr || !std::isnan(thr), std::string(who) + ": threshold is NaN");
     return 0;
 }
-// `count` elements of a result held in the handle, to the caller's host or device array (a _read entry point; synchronous)
+// `count` elements of a result held in the handle, to the caller's host or device array (a _read entry point; synchronous: a
+// device-to-device hipMemcpy may return before the default stream has run it, and the caller's stream is not ordered behind
+// that one, so the copy is waited for here)
 template <class T> int copy_out(void* dst, const T* src, size_t count, int dst_on_device) {
     REVO_HIP_CHECK(hipMemcpy(dst, src, count * sizeof(T), dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (dst_on_device) REVO_HIP_CHECK(hipStreamSynchronize(nullptr));
     return 0;
 }
 

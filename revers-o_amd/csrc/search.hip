@@ -522,8 +522,8 @@ extern "C" int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* strea
     REVO_ON_DEVICE(g->device);
     using namespace revo;
     int c[CTR_SLOTS];
+    REVO_HIP_CHECK(hipMemcpyAsync(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream));   // on `stream`, like revo_vit_stats
     REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    REVO_HIP_CHECK(hipMemcpy(c, g->xw.ctr, sizeof(c), hipMemcpyDeviceToHost));
     out8[0] = c[CTR_UNCERTIFIED] + c[CTR_MODE3_FAILED] + c[CTR_FROM_SEGS]; out8[1] = c[CTR_BRUTEFORCE];
     out8[2] = c[CTR_CHECKED]; out8[3] = c[CTR_COLLECTED]; out8[4] = c[CTR_FROM_SEGS]; out8[5] = c[CTR_GROUPED];
     out8[6] = c[CTR_LARGE_FALLBACK]; out8[7] = c[CTR_PAIR_PASSES];

@@ -217,9 +217,11 @@ extern "C" int32_t revo_vit_stats(revo_vit* vit, double* out4, int32_t reset, vo
     REVO_REQUIRE(vit && out4, "vit_stats: null argument");
     REVO_ON_DEVICE(vit->device);
     unsigned long long c[4] = {0, 0, 0, 0};
-    REVO_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    REVO_HIP_CHECK(hipMemcpy(c, vit->ln_tele, sizeof(c), hipMemcpyDeviceToHost));
-    if (reset) REVO_HIP_CHECK(hipMemset(vit->ln_tele, 0, sizeof(c)));
+    // read and reset ON `stream`, behind the forwards that count and ahead of the next one, then the documented wait
+    hipStream_t st = (hipStream_t)stream;
+    REVO_HIP_CHECK(hipMemcpyAsync(c, vit->ln_tele, sizeof(c), hipMemcpyDeviceToHost, st));
+    if (reset) REVO_HIP_CHECK(hipMemsetAsync(vit->ln_tele, 0, sizeof(c), st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));
     out4[0] = (double)c[0]; out4[1] = (double)c[1]; out4[2] = (double)c[2]; out4[3] = (double)revo::LNC_TELE_RATIO;
     return 0;
     API_END
@@ -563,6 +565,7 @@ extern "C" int32_t revo_vit_detect(revo_vit* v, const void* images, int32_t imag
 template <class T> static int detect_copy(void* dst, const T* src, size_t count, int dst_on_device) {
     if (!dst || count == 0) return 0;
     REVO_HIP_CHECK(hipMemcpy(dst, src, count * sizeof(T), dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    if (dst_on_device) REVO_HIP_CHECK(hipStreamSynchronize(nullptr));   // (complete on return, whatever stream the caller is on)
     return 0;
 }
 
