@@ -545,6 +545,39 @@ int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t n_
 int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
                              int32_t n_pairs, int32_t k, int32_t has_threshold, float threshold, int64_t index_offset,
                              float* scores, int64_t* indices, int32_t* counts, void* stream);
+/* ---- boosted search: "images like this one, but prefer those taken near this date / near this place / from trusted sources"
+ * (the score-boosting query of the vector database the reference sits on, over EVERY allowed row instead of a prefetched
+ * candidate list)
+ * BOOSTED.  query: [dim] fp32 on the device, ONE query, normalised like every query.  mult / bias: [rows] fp32 on the device,
+ * one entry per gallery row in row order; either may be NULL.  For a gallery row r, with s(r) the fp32 score of the query
+ * against row r (the one fma chain of EXACTNESS: the bits every search returns), m = mult[r] (NULL: 1), b = bias[r] (NULL: 0),
+ *   final(r) = fmaf(m, s(r), b)     ONE correctly rounded fused multiply-add
+ * With both arrays NULL final = s with no operation at all: the call is revo_search_topk_large for one query, bit for bit.
+ * The result is the best k (1 <= k <= 1024) rows the handle's filter allows (revo_search_set_filter, with its lifecycle)
+ * that have s(r) >= min_similarity when has_min_similarity (a cut on the SIMILARITY, not on the boosted score) and
+ * final(r) >= threshold when has_threshold, ordered by (final desc, row index asc).  Outputs, padding and index_offset as
+ * revo_search_recommend: scores [k] (final), indices [k], counts [1]; similarities [k] carries s(r) of every hit (padding
+ * -inf).  EXACT: the rows, their order and both score arrays are those of computing final for every allowed row and sorting;
+ * two calls give identical bytes.  How: RECOMMEND's plan.  With a a row's bf16 scan score and e the query's rounding bound,
+ * s lies in [lo, hi] = [a - e, a + e] moved outward by their own rounding; a correctly rounded fma is monotone in each
+ * argument and m >= 0, so final lies in [fmaf(m, lo, b), fmaf(m, hi, b)] with no further widening.  A row can pass the
+ * minimum similarity only if hi reaches it and certainly passes if lo does.  tau = the k-th largest lower bound over the
+ * sample rows that certainly pass (raised to the threshold) is a level k rows reach, for ANY sample: here 256-row tiles
+ * strided evenly over the gallery (boosts that grow with the row index, as timestamps do, leave no good row in a prefix).
+ * One MFMA pass keeps every allowed row that can pass and whose upper bound reaches tau; those rows are re-scored in fp32
+ * and sorted on the device.  No certificate can fail and there is no fallback.
+ * DOMAIN.  On every allowed row mult must be finite and >= 0 and bias finite.  The pass reads both for every allowed row
+ * and counts the rows outside the domain: the call then returns status -2 with that count in revo_last_error() and the
+ * outputs are not to be used -- never a wrong answer.  Rows the filter does not allow are not inspected.
+ * SYNCHRONOUS on `stream`, like revo_search_recommend.  Needs the fp32 master rows (keep_f32 = 0: status -2).  A null handle,
+ * query or output pointer, k outside 1..1024, a NaN threshold or a NaN min_similarity give status -2 before the device is
+ * touched.  An empty gallery, or a filter that allows no row: counts = 0, all padding.  revo_search_stats after it: slot 3 =
+ * candidate rows re-scored in fp32, slot 7 as for RECOMMEND, every other slot 0.  A pairs or a range result held by the
+ * handle stays valid. */
+int32_t revo_search_boosted(revo_gallery* g, const float* query, const float* mult, const float* bias, int32_t k,
+                            int32_t has_threshold, float threshold, int32_t has_min_similarity, float min_similarity,
+                            int64_t index_offset, float* scores, float* similarities, int64_t* indices, int32_t* counts,
+                            void* stream);
 /* ---- multi-vector search: "which images contain ALL of what this image shows?" -- a point is a set of vectors (the rows of
  * one group), a query is a set of vectors, the score is late-interaction MaxSim (the multi-vector comparator of the vector
  * database the reference sits on)
@@ -751,7 +784,7 @@ int32_t revo_search_exact(revo_gallery* g, int32_t n, const int32_t* q_idx, cons
  * that took the exhaustive fallback (0 after every other search), revo_gallery_pairs: join passes, revo_search_range:
  * candidate passes (0 after every other search) }.  After revo_search_topk_large slot 3 counts the rows of the bands it
  * re-scored and slots 0, 1, 2, 4, 5 are 0; after revo_gallery_pairs see PAIRS, after revo_gallery_clusters see CLUSTERS, after revo_search_range see RANGE,
- * after revo_search_recommend see RECOMMEND, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM, after
+ * after revo_search_recommend see RECOMMEND, after revo_search_boosted see BOOSTED, after revo_search_mmr see MMR, after revo_search_maxsim see MAXSIM, after
  * revo_gallery_knn see KNN, after revo_gallery_kmeans see KMEANS. */
 int32_t revo_search_stats(revo_gallery* g, int32_t* out8, void* stream);
 /* merge `parts` result sets laid out [parts, n_queries, k] (the all-gathered per-shard

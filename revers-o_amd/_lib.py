@@ -77,6 +77,7 @@ SIGNATURES = {
     "revo_search_range": (_i32, [_p, _p, _i32, _f32, _i64, C.POINTER(C.c_int64), _p]),
     "revo_search_range_read": (_i32, [_p, _p, _i64, _i64, _p, _p, _i32]),
     "revo_search_recommend": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
+    "revo_search_boosted": (_i32, [_p, _p, _p, _p, _i32, _i32, _f32, _i32, _f32, _i64, _p, _p, _p, _p, _p]),
     "revo_search_discover": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p]),
     "revo_search_maxsim": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i64, _p, _p, _p, _p, _p, _p]),
     "revo_search_mmr": (_i32, [_p, _p, _i32, _i32, _i32, _f32, _i32, _f32, _i64, _p, _p, _p, _p, _p]),

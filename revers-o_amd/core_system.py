@@ -557,6 +557,28 @@ class SimpleReverso:
                 "skip_duplicates": self.skip_duplicates}      # (an older manifest has no such key: the same as None)
 
     # ---------------------------------------------------------------- search --
+    def search_similar_boosted(self, formula, similarity_threshold=0.7, max_results=5, query_filter=None):
+        """:meth:`search_similar` with the ranking rescored by ``formula`` over ``$score`` and the stored payloads (boost.py:
+        "like this region, but prefer images taken near this date / place").  ``similarity_threshold`` is what the
+        reference's slider means: a cut on the plain similarity (None: none), not on the boosted score; every stored region
+        that passes it (and ``query_filter``) competes, not a prefetched short list.  Returns ``(text, items)``, items
+        ``{"filename", "image_source", "bbox", "id", "score", "similarity"}``, best boosted score first.  No thumbnails."""
+        if err := self._not_ready(need_query=True):
+            return err, []
+        query = self.region_embeddings[0]
+        min_similarity = None if similarity_threshold is None else float(similarity_threshold)
+        try:
+            with self._lock:
+                hits = self.vector_db.search_boosted(query, int(max_results), formula, min_similarity=min_similarity,
+                                                     query_filter=query_filter)
+        except ValueError as e:
+            return f"❌ {e.args[0]}", []
+        if not hits:
+            return _no_hits("similar regions found", similarity_threshold), []
+        items = [dict(_item(r.payload, r.id, r.score), similarity=r.similarity) for r in hits]
+        text = f"🎯 Found {len(items)} similar regions (boosted):\n\n"
+        return text + _listing(items), items
+
     def search_similar(self, similarity_threshold=0.7, max_results=5, query_filter=None, group_by=None):
         """core_system.py:650-717: first region embedding as the query, limit + score
         threshold, results best first with the same text and thumbnail formatting.  ``query_filter``: a Qdrant-style

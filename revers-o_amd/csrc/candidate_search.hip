@@ -1,5 +1,5 @@
 // C ABI of the searches on the candidate pipeline (include/revo.h): pairs, clusters, kNN, k-means, range,
-// recommend, discover, MaxSim, MMR and the hybrid queries (fusion), with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
+// recommend, discover, boosted, MaxSim, MMR and the hybrid queries (fusion), with their _read entry points.  The handle: gallery_internal.h; the certified top-k: search.hip.
 #include <algorithm>
 #include <vector>
 
@@ -739,16 +739,28 @@ extern "C" int32_t revo_search_range_read(revo_gallery* g, int64_t* offsets, int
     API_END
 }
 
-// ---- search by examples: one host skeleton under revo_search_recommend (recommend.hip) and
-// revo_search_discover (discover.hip, section 4m).  name: "recommend" / "discover" (messages search_<name>, profile classes
-// <name>_sample, _pass, _rescore, _sort); tile_rows: the rows the example tile takes in the handle; n_examples: the example rows
-// that size the sample; pa: the pass's arguments (RecommendPassArgs / DiscoverPassArgs) with the search's own fields set -- the
-// skeleton sets those the two share.  normalise() fills the example tile, pass(pa, sample, st) launches the sample or the
-// candidate pass, rescore(cand, n, b, kept, out_keys, out_scores) the fp32 re-score.
-template <class PassArgs, class Normalise, class Rescore>
+// ---- search by examples: one host skeleton under revo_search_recommend (recommend.hip),
+// revo_search_discover (discover.hip, section 4m) and revo_search_boosted (boost.hip, section 4z).  name: "recommend" / "discover" /
+// "boosted" (messages search_<name>, profile classes <name>_sample, _pass, _rescore, _sort); tile_rows: the rows the example tile
+// takes in the handle; n_examples: the example rows
+// that size the sample; pa: the pass's arguments (RecommendPassArgs / DiscoverPassArgs / BoostPassArgs) with the search's own
+// fields set -- the skeleton sets those they share.  normalise() fills the example tile, pass(pa, sample, st) launches the sample
+// or the candidate pass, rescore(cand, n, b, kept, out_keys, out_scores) the fp32 re-score.  ext: what a search adds to these
+// steps -- ExamplesPlain, as it is, for recommend and discover.
+struct ExamplesPlain {
+    void carve(Layout&, long) {}                                            // arrays behind the workspace's own, for N rows
+    template <class PassArgs> void sample(PassArgs& pa, long n_s, long) const { pa.N = n_s; }   // the sample: the first n_s rows
+    int after_pass(const unsigned long long (&)[4]) const { return 0; }     // the candidate pass's counters, read and synchronised
+    int emit(const uint64_t* sk, const float* sv, long n, int k, int b, long index_offset, float* scores, long long* indices,
+             int* counts, hipStream_t st) const {
+        return revo::launch_recommend_emit(sk, sv, n, k, b, index_offset, scores, indices, counts, st);
+    }
+};
+template <class PassArgs, class Normalise, class Rescore, class Ext>
 static int search_by_examples(revo_gallery* g, const char* name, int tile_rows, int n_examples, PassArgs pa, int k, int has_thr,
                               float thr, long index_offset, float* scores, long long* indices, int* counts, const uint32_t* allow,
-                              hipStream_t st, Normalise&& normalise, int (*pass)(const PassArgs&, int, hipStream_t), Rescore&& rescore) {
+                              hipStream_t st, Normalise&& normalise, int (*pass)(const PassArgs&, int, hipStream_t), Rescore&& rescore,
+                              Ext&& ext) {
     using namespace revo;
     const long N = g->size;
     const int D = g->D;
@@ -760,13 +772,13 @@ static int search_by_examples(revo_gallery* g, const char* name, int tile_rows, 
         REVO_HIP_CHECK(hipStreamSynchronize(st));
         return 0;
     }
-    // the sample: the rows revo_search_topk_large's sample pass covers (none in a small gallery: tau = -inf or the threshold)
+    // the sample: as many rows as revo_search_topk_large's sample pass covers (none in a small gallery: tau = -inf or the threshold)
     const long n_s = large_sample_rows(n_examples, N, k);
     // candidates are rows (32-bit indices in the key array), at most N: sized once; counter [2] = allowed rows the pass met
     long cap = 0;
     CandidateWs ws{g->pbuf, cap};
     float *tau = nullptr, *lb = nullptr;
-    CHECK_RC(ws.carve(N, st, [&](Layout& l) { tau = l.take<float>(1); lb = l.take<float>(n_s > 0 ? n_s : 1); }));
+    CHECK_RC(ws.carve(N, st, [&](Layout& l) { tau = l.take<float>(1); lb = l.take<float>(n_s > 0 ? n_s : 1); ext.carve(l, N); }));
     uint32_t* cand = (uint32_t*)ws.cand;
     { ProfScope ps("search_prep", st);
       CHECK_RC(normalise()); }
@@ -774,7 +786,7 @@ static int search_by_examples(revo_gallery* g, const char* name, int tile_rows, 
     pa.qstat = g->qstat.p; pa.gstat = g->gstat.p; pa.allow = allow;
     CHECK_RC(ws.join_until_it_fits(st, [&]() -> int {
         { ProfScope ps((cls + "_sample").c_str(), st);
-          if (n_s > 0) { pa.N = n_s; pa.lb_out = lb; CHECK_RC(pass(pa, 1, st)); }
+          if (n_s > 0) { pa.N = N; ext.sample(pa, n_s, N); pa.lb_out = lb; CHECK_RC(pass(pa, 1, st)); }
           CHECK_RC(launch_recommend_level(lb, (int)n_s, k, has_thr, thr, tau, st)); }
         ProfScope ps((cls + "_pass").c_str(), st);
         pa.N = N; pa.lb_out = nullptr; pa.tau = tau; pa.cnt = ws.cnt; pa.rows = cand; pa.cap = N;
@@ -783,11 +795,12 @@ static int search_by_examples(revo_gallery* g, const char* name, int tile_rows, 
         REVO_REQUIRE(n_cand <= (unsigned long long)N, who + ": more candidates than rows");
         return 0;
     }, (who + ": the candidate count changed between two passes").c_str()));
+    CHECK_RC(ext.after_pass(ws.h));
     const int b = row_index_bits(N);
     { ProfScope ps((cls + "_rescore").c_str(), st);
       CHECK_RC(rescore(cand, (long)ws.n_cand, b, ws.cnt + 1, ws.kept_k, ws.kept_v)); }
     CHECK_RC(ws.sort_kept((cls + "_sort").c_str(), 32 + b, st));
-    CHECK_RC(launch_recommend_emit(ws.sk, ws.sv, (long)ws.n_kept, k, b, index_offset, scores, indices, counts, st));
+    CHECK_RC(ext.emit(ws.sk, ws.sv, (long)ws.n_kept, k, b, index_offset, scores, indices, counts, st));
     return publish_candidate_stats(g->xw.ctr, ws.n_cand, ws.h[2] > 0 ? 1 : 0, st);   // (no allowed row: no candidate pass counted)
 }
 extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples, int32_t P, int32_t Nn, int32_t k, int32_t has_thr,
@@ -813,7 +826,7 @@ extern "C" int32_t revo_search_recommend(revo_gallery* g, const float* examples,
         return launch_recommend_rescore(cand, n, g->qf.p, D, P, Nn, g->gf.p, D, D, has_thr, thr, b, kept, out_keys, out_scores, st);
     };
     return search_by_examples(g, "recommend", E, E, pa, k, has_thr, thr, index_offset, scores, (long long*)indices, counts, allow, st,
-                              normalise, launch_recommend_pass, rescore);
+                              normalise, launch_recommend_pass, rescore, ExamplesPlain{});
     API_END
 }
 extern "C" int32_t revo_search_discover(revo_gallery* g, const float* target, const float* positives, const float* negatives,
@@ -854,7 +867,60 @@ extern "C" int32_t revo_search_discover(revo_gallery* g, const float* target, co
                                        out_scores, st);
     };
     return search_by_examples(g, "discover", rows, 2 * n_pairs + has_target, pa, k, has_thr, thr, index_offset, scores,
-                              (long long*)indices, counts, allow, st, normalise, launch_discover_pass, rescore);
+                              (long long*)indices, counts, allow, st, normalise, launch_discover_pass, rescore, ExamplesPlain{});
+    API_END
+}
+
+// ---- boosted search (include/revo.h revo_search_boosted; boost.hip): the third user of the skeleton
+namespace {
+// what the boosted search adds: the similarities by row behind the workspace, the strided sample, the domain check of mult and
+// bias (the candidate pass counted the allowed rows outside it), the emit that also delivers the similarities
+struct ExamplesBoosted {
+    float* sim = nullptr;
+    float* similarities = nullptr;
+    void carve(Layout& l, long N) { sim = l.take<float>(N); }
+    void sample(revo::BoostPassArgs& pa, long n_s, long N) const { pa.N = N; pa.n_sample = n_s; }
+    int after_pass(const unsigned long long (&h)[4]) const {
+        REVO_REQUIRE(h[3] == 0, "search_boosted: " + std::to_string(h[3]) + " allowed rows have a mult that is negative or not "
+                                "finite, or a bias that is not finite");
+        return 0;
+    }
+    int emit(const uint64_t* sk, const float* sv, long n, int k, int b, long index_offset, float* scores, long long* indices,
+             int* counts, hipStream_t st) const {
+        return revo::launch_boost_emit(sk, sv, n, k, b, index_offset, sim, scores, similarities, indices, counts, st);
+    }
+};
+}  // namespace
+extern "C" int32_t revo_search_boosted(revo_gallery* g, const float* query, const float* mult, const float* bias, int32_t k,
+                                       int32_t has_thr, float thr, int32_t has_min, float min_sim, int64_t index_offset,
+                                       float* scores, float* similarities, int64_t* indices, int32_t* counts, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(g && query && scores && similarities && indices && counts, "search_boosted: null argument");
+    REVO_REQUIRE(k >= 1 && k <= revo::LARGE_K_MAX, "search_boosted: k must be in [1, 1024]");
+    CHECK_RC(require_threshold(has_thr, thr, "search_boosted"));
+    REVO_REQUIRE(!has_min || !std::isnan(min_sim), "search_boosted: min_similarity is NaN");
+    CHECK_RC(require_f32_rows(g, "search_boosted"));
+    const uint32_t* allow; CHECK_RC(search_filter(g, &allow));
+    REVO_ON_DEVICE(g->device);
+    hipStream_t st = (hipStream_t)stream;
+    using namespace revo;
+    const int D = g->D;
+    BoostPassArgs pa{};
+    pa.mult = mult; pa.bias = bias; pa.has_min = has_min ? 1 : 0; pa.min_sim = min_sim;
+    ExamplesBoosted ext;
+    ext.similarities = similarities;
+    // (an empty gallery: the skeleton pads scores, indices and counts; the similarities' padding goes in front of it)
+    if (g->size == 0) CHECK_RC(launch_topk_fill_empty(similarities, (long long*)indices, counts, 1, k, st));
+    auto normalise = [&]() -> int { return launch_l2norm_rows(query, D, g->qf.p, D, g->qb.p, D, 1, D, st, 1, g->qstat.p); };
+    auto rescore = [&](const uint32_t* cand, long n, int b, unsigned long long* kept, uint64_t* out_keys, float* out_scores) -> int {
+        BoostRescoreArgs ra{};
+        ra.cand = cand; ra.n = n; ra.Qf = g->qf.p; ra.Gf = g->gf.p; ra.ldg = D; ra.D = D; ra.mult = mult; ra.bias = bias;
+        ra.has_min = pa.has_min; ra.min_sim = min_sim; ra.has_thr = has_thr ? 1 : 0; ra.thr = thr; ra.b = b;
+        ra.kept = kept; ra.out_keys = out_keys; ra.out_scores = out_scores; ra.sim = ext.sim;
+        return launch_boost_rescore(ra, st);
+    };
+    return search_by_examples(g, "boosted", 1, 1, pa, k, has_thr, thr, index_offset, scores, (long long*)indices, counts, allow, st,
+                              normalise, launch_boost_pass, rescore, ext);
     API_END
 }
 

@@ -705,6 +705,42 @@ int launch_discover_pass(const DiscoverPassArgs& a, int sample, hipStream_t st);
 int launch_discover_rescore(const uint32_t* cand, long n, const float* Qf, long ldq, int half, int n_pairs, int has_target,
                             const float* Gf, long ldg, int D, int has_thr, float thr, int b, unsigned long long* kept,
                             uint64_t* out_keys, float* out_scores, hipStream_t st);
+// ---- boosted search (revo_search_boosted; boost.hip): the recommend search's plan (its level kernel as it
+// is) for one query whose fp32 score s is rescored per row, final = fmaf(mult[r], s, bias[r]); the sample is strided
+struct BoostPassArgs {
+    const bf16_t* Qb; long ldq;   // the bf16 query row
+    const bf16_t* Gb; long ldg;   // the gallery's bf16 rows
+    long N; int D;                // the gallery's rows (both passes)
+    const float* qstat;           // [2] the query's rounding norms (launch_l2norm_rows row_stats)
+    const uint32_t* gstat;        // [2] the gallery's running maxima (max ||g||, max ||gb - g||), fp32 bit patterns
+    const uint32_t* allow;        // optional allow-bitmap, padded to whole 256-row tiles
+    const float* mult;            // [N] row multipliers, null: 1
+    const float* bias;            // [N] row biases, null: 0
+    int has_min; float min_sim;   // the cut on the similarity
+    long n_sample;                // sample pass: its rows, a multiple of 256: tile i of it is gallery tile floor(i T / S)
+    const float* tau;             // candidate pass: [1] the level (device)
+    unsigned long long* cnt;      // candidate pass: [0] candidates found (counts past cap), [2] allowed rows met, [3] allowed rows
+                                  // whose mult is negative or not finite or whose bias is not finite
+    uint32_t* rows; long cap;     // candidate pass: [cap] candidate rows
+    float* lb_out;                // sample pass: [n_sample] lower bound of the final score by sample position (-inf: not allowed,
+                                  // past the gallery's end, or not certainly at or above min_sim)
+};
+int launch_boost_pass(const BoostPassArgs& a, int sample, hipStream_t st);
+// s and final of candidate rows [0, n) against the fp32 query row Qf; those passing both cuts appended to out_keys
+// ((~order-preserving final bits << b) | row) / out_scores (final), count in *kept; sim[row] = s of every kept row
+struct BoostRescoreArgs {
+    const uint32_t* cand; long n;
+    const float* Qf; const float* Gf; long ldg; int D;
+    const float* mult; const float* bias;
+    int has_min; float min_sim; int has_thr; float thr;
+    int b;
+    unsigned long long* kept; uint64_t* out_keys; float* out_scores;
+    float* sim;                   // [N]
+};
+int launch_boost_rescore(const BoostRescoreArgs& a, hipStream_t st);
+// launch_recommend_emit, and sims[i] = sim[row of entry i] (-inf in the padding)
+int launch_boost_emit(const uint64_t* keys, const float* vals, long n, int k, int b, long idx_offset, const float* sim,
+                      float* scores, float* sims, long long* idx, int* counts, hipStream_t st);
 // ---- multi-vector search (revo_search_maxsim; maxsim.hip): late-interaction MaxSim of up to 64 query
 // vectors over the groups of the gallery's rows; the recommend search's pass form with a storing epilogue, bounds per group
 constexpr int MAXSIM_MAX_VECTORS = 64;       // the query vectors of a tile column live in one wave (the 64-row form of the tile)

@@ -794,6 +794,40 @@ class Gallery(_Handle):
                        int(index_offset), _lib.ptr(scores), _lib.ptr(idx), _lib.ptr(counts), _lib.current_stream())
         return scores, idx, counts[0]
 
+    def search_boosted(self, query, mult=None, bias=None, k=5, score_threshold=None, min_similarity=None, index_offset=0,
+                       allow=None):
+        """Boosted search (include/revo.h, BOOSTED): ``query`` one fp32 ``[dim]`` device vector; ``mult`` and ``bias`` fp32
+        ``[len]`` device tensors, one entry per gallery row, or None (1 / 0).  A row's final score is
+        ``fma(mult[r], s(r), bias[r])``, one correctly rounded operation, with ``s`` the similarity :meth:`search` returns.
+        Returns the best ``k <= 1024`` rows (allowed by ``allow``, as in :meth:`search`) with ``s >= min_similarity`` and
+        ``final >= score_threshold`` where given, as ``(scores [k] fp32, similarities [k] fp32, indices [k] int64, count)``
+        device tensors (``count`` a 0-d int32), best final score first, padded with -inf / -inf / -1 -- exactly what computing
+        the final score of every row and sorting gives.  On every allowed row ``mult`` must be finite and >= 0 and ``bias``
+        finite: the call raises otherwise.  Synchronous."""
+        q = _rows(query, "query", self.dim, self.device)
+        if q.shape[0] != 1:
+            raise ValueError(f"query must be one vector of {self.dim} elements, got {tuple(query.shape)}")
+        n = len(self)
+
+        def per_row(t, name):
+            if t is None:
+                return None
+            _require_cuda(t, name, self.device)
+            if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n:
+                raise ValueError(f"{name} must be fp32 [{n}] (one entry per gallery row), got {t.dtype} {tuple(t.shape)}")
+            return t.contiguous() if n else None
+        m, b = per_row(mult, "mult"), per_row(bias, "bias")
+        k = int(k)
+        scores = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
+        sims = torch.empty((max(k, 1),), dtype=torch.float32, device=self.device)
+        idx = torch.empty((max(k, 1),), dtype=torch.int64, device=self.device)
+        counts = torch.empty((1,), dtype=torch.int32, device=self.device)
+        with self._frame(allow):
+            self._call("revo_search_boosted", _lib.ptr(q), _lib.ptr(m), _lib.ptr(b), k, *_threshold(score_threshold),
+                       *_threshold(min_similarity), int(index_offset), _lib.ptr(scores), _lib.ptr(sims), _lib.ptr(idx),
+                       _lib.ptr(counts), _lib.current_stream())
+        return scores, sims, idx, counts[0]
+
     def search_maxsim(self, queries, groups, k=5, score_threshold=None, index_offset=0, allow=None, with_parts=False):
         """Multi-vector search (include/revo.h, MAXSIM): ``queries`` fp32 ``[n, dim]`` device tensor, ``1 <= n <= 64``;
         ``groups`` int32 ``[len]`` device tensor, the group of every row (-1 = none), as in :meth:`search_groups`.  A

@@ -29,6 +29,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import boost as _boost
 from . import filters as _filters
 from .engine import Gallery
 
@@ -184,6 +185,12 @@ class ScoredPoint:
     id: str
     score: float
     payload: dict
+
+
+@dataclass
+class BoostedPoint(ScoredPoint):
+    """One hit of :meth:`GalleryStore.search_boosted`: ``score`` is the boosted score, ``similarity`` the plain search score."""
+    similarity: float = 0.0
 
 
 @dataclass
@@ -372,6 +379,9 @@ def average_vector_query(positive, negative=None):
 
 
 class GalleryStore:
+    _mutations = 0           # counts every upsert, delete, update and set_payload (the key of search_boosted's cache)
+    _boost_cache = None      # ((formula key, filter key, _mutations), device mult, device bias) of the last boosted search
+
     def __init__(self, dim, device=0, capacity=65536, collection="simple_reverso", path=None, _fresh=True, build_info=None):
         """``build_info``: what the vectors were made from and how (source folder, model, region mode, ...), written into
         the manifest header; a resume compares it (core_system.create_database) so that rows of different builds never mix."""
@@ -459,6 +469,8 @@ class GalleryStore:
         if files:
             self._files_pending.extend(files)
         self.complete = False
+        self._mutations += 1
+        self._boost_cache = None
         return report
 
     # -- changes of stored points (include/revo.h, EDIT): on the device in place, on disk one manifest line each ------
@@ -470,7 +482,8 @@ class GalleryStore:
     def _points_changed(self):
         """ids / payloads changed under the caches built from them"""
         self._pindex = _filters.PayloadIndex()
-        self._filter_cache = self._group_cache = self._id_rows = None
+        self._filter_cache = self._group_cache = self._id_rows = self._boost_cache = None
+        self._mutations += 1
         self.complete = False
 
     def _log_op(self, line):
@@ -700,6 +713,32 @@ class GalleryStore:
                                         allow=allow)
         n = int(c)
         return self._points(s[:n].tolist(), i[:n].tolist())
+
+    def search_boosted(self, query_vector, limit, formula, score_threshold=None, min_similarity=None, query_filter=None,
+                       defaults=None):
+        """One query rescored by a formula over ``$score`` and the points' payloads (the database's score-boosting query;
+        boost.py has the formula's shape): "like this, but prefer the ones taken near this date".  The formula must be
+        affine in ``$score`` with a coefficient >= 0 on every point searched; it then is ``M * $score + B`` per point, and
+        the device search (include/revo.h, BOOSTED) ranks EVERY point ``query_filter`` selects by it -- no prefetched
+        candidate list a late winner could be missing from.  ``min_similarity`` cuts on the plain score, ``score_threshold``
+        on the boosted one; ``defaults`` gives payload keys a value where a point lacks them.  Returns
+        :class:`BoostedPoint` s, best boosted score first, ``limit <= 1024``.  The per-point arrays are cached on the device
+        per (formula, filter, state of the store): any upsert, delete, update or ``set_payload`` drops them."""
+        q = torch.as_tensor(query_vector, dtype=torch.float32).reshape(-1)
+        dev = self.gallery.device
+        allow = self._allow_bits(query_filter) if query_filter is not None else None
+        key = (_boost.formula_key(formula, defaults), _filters.filter_key(query_filter) if query_filter is not None else None,
+               self._mutations)
+        if self._boost_cache is None or self._boost_cache[0] != key:
+            mask = self.filter_mask(query_filter) if query_filter is not None else None
+            m, b = _boost.compile_formula(formula, self.payloads, defaults=defaults, allowed=mask)
+            self._boost_cache = (key, torch.from_numpy(m).to(dev), torch.from_numpy(b).to(dev))
+        _, m, b = self._boost_cache
+        s, sim, i, c = self.gallery.search_boosted(q.to(dev), m, b, k=int(limit), score_threshold=score_threshold,
+                                                   min_similarity=min_similarity, allow=allow)
+        n = int(c)
+        return [BoostedPoint(self.ids[j], float(sc), self.payloads[j], float(sm))
+                for sc, sm, j in zip(s[:n].tolist(), sim[:n].tolist(), i[:n].tolist())]
 
     def query_fusion(self, prefetch, limit=5, prefetch_limit=100, fusion="rrf", rrf_k=60.0, weights=None, prefetch_thresholds=None,
                      score_threshold=None, query_filter=None):
