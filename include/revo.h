@@ -65,7 +65,31 @@ int32_t revo_vit_destroy(revo_vit* vit);
  * the device; normalize != 0 applies embedding / embedding.norm() (core_system.py:447). */
 int32_t revo_vit_forward(revo_vit* vit, const void* images, int32_t image_dtype, int32_t batch, float* out,
                          int32_t normalize, void* stream);
+/* The tokens per image of the ACTIVE grid (GRIDS below): gh * gw + use_cls; natively g * g + use_cls.  -1 for a null handle. */
 int32_t revo_vit_seq_len(const revo_vit* vit);
+/* GRIDS: native-aspect embedding -- the forward on a rectangular token grid.  g = image_size /
+ * patch_size is the native side, P the patch side.  revo_vit_set_grid(vit, gh, gw, stream) makes every forward that follows on
+ * the handle (revo_vit_forward, _forward_regions, _forward_tokens) take images [batch, 3, gh * P, gw * P] and run on S' = gh *
+ * gw + use_cls tokens per image: patch (gy, gx) is token use_cls + gy * gw + gx, the class token, if any, token 0.  The token
+ * budget is the native one, gh * gw <= g * g, so every workspace of the handle already fits and a forward costs at most what
+ * the native one costs; any such (gh, gw) is accepted.  The shape holds until the next revo_vit_set_grid; (0, 0) or (g, g)
+ * restores the native grid.  What changes with the grid, and nothing else does:
+ *   positions  the class row of visual.positional_embedding is kept; its g x g patch rows are resampled to gh x gw by bilinear
+ *              interpolation with half-pixel centres: source coordinate (o + 0.5) * g / g_out - 0.5 clamped below at 0, the
+ *              upper neighbour clamped at g - 1 (F.interpolate(mode = "bilinear", align_corners = False), no antialiasing).
+ *              Coordinates and the four weights in fp64, each weight rounded once to fp32, then one fp32 fma chain w00 p00 +
+ *              w01 p01 + w10 p10 + w11 p11 in that order: within 6 * 2^-24 * max|corner| of the same formula in fp64.
+ *   RoPE       the table revo_vit_create builds, with gx = c % gw, gy = c / gw of cell c and integer coordinates gx + use_cls,
+ *              gy + use_cls: not rescaled to the native range.  Host fp64, each cos and sin rounded once.
+ * Both are [UPSTREAM-RECALL], like the rest of the tower.  At (g, g) the native tables are used themselves.  A shape's tables
+ * are built by the first revo_vit_set_grid that names it (a kernel and a copy on `stream`, which the call waits for) and kept:
+ * the handle holds at most 64 shapes, the native one included, and refuses a 65th.  The result for an image depends on its
+ * grid and on nothing else the caller did before.  Bitmaps of revo_vit_forward_regions have ceil(S' / 32) words per region
+ * under a grid, revo_vit_forward_tokens writes batch * S' rows.  revo_vit_detect runs on the native grid only (its component
+ * kernel walks a g x g map) and is refused under another with a message that names the grid; setting another grid ends the
+ * life of a detect result.  Status -2 before the device is touched: a null handle, a non-positive side (other than (0, 0)),
+ * gh * gw > g * g, a band of more than 65535 pixels (gh * P or gw * P), a 65th shape. */
+int32_t revo_vit_set_grid(revo_vit* vit, int32_t grid_h, int32_t grid_w, void* stream);
 /* REGIONS: a vector per region for one forward per image (masked attention pooling).
  * One body forward of the batch, ln_post and the pool's logits once; then for region r of image region_image[r] the head of
  * revo_vit_forward with its softmax restricted to the tokens the region's bitmap allows: region_bits [n_regions][ceil(S / 32)]
@@ -938,6 +962,9 @@ int64_t revo_debug_gemm_plan(int32_t epi, int32_t m, int32_t n, int32_t k, int64
                              int32_t offers, int32_t rope_seq, int32_t rope_head_dim, int32_t rope_cols, int64_t* out, int32_t cap);
 /* 1 if a forward of `batch` images keeps the residual stream in two bf16 planes between its folded GEMMs (reporting) */
 int32_t revo_debug_stream_in_planes(const revo_vit* vit, int32_t batch);
+/* The tables of the ACTIVE grid shape (GRIDS), device to device on `stream`: pos_dst [S'][width] fp32, rope_dst [S'][head_dim /
+ * 2][2] fp32 (cos, sin) -- for the tests that hold them to the fp64 formulas. */
+int32_t revo_vit_read_grid_tables(revo_vit* vit, float* pos_dst, float* rope_dst, void* stream);
 /* copies bytes of the handle's search workspace to host_dst (host_dst NULL: returns the workspace size) */
 int64_t revo_debug_read_workspace(revo_gallery* g, int64_t offset, int64_t bytes, void* host_dst);
 /* experiment: bounds = device array [Q] of order-preserving u32 scan scores (the format revo_search_candidates publishes)
@@ -1083,6 +1110,11 @@ typedef struct revo_crop_job {
     int32_t x0, y0, x1, y1;  /* crop box, half-open [x0, x1) x [y0, y1); the whole image = 0, 0, width, height */
 } revo_crop_job;
 int32_t revo_preprocess_crop_resize(const revo_crop_job* jobs, int32_t n, int32_t out_size, uint8_t* out, void* stream);
+/* The same to out_h x out_w: out [n, 3, out_h, out_w], bit-identical to Image.crop(box).resize((out_w, out_h), Image.BILINEAR)
+ * -- the input of a forward under revo_vit_set_grid(gh, gw) with out_h = gh * P, out_w = gw * P.  The entry above is this one
+ * with out_h = out_w = out_size.  Each of out_h, out_w in 1..4096 (status -2 before the device is touched). */
+int32_t revo_preprocess_crop_resize_hw(const revo_crop_job* jobs, int32_t n, int32_t out_h, int32_t out_w, uint8_t* out,
+                                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ SIGNATURES = {
     "revo_vit_detect_read": (_i32, [_p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i32]),
     "revo_vit_detect_maps": (_i32, [_p, _p, _p, _i32]),
     "revo_vit_seq_len": (_i32, [_p]),
+    "revo_vit_set_grid": (_i32, [_p, _i32, _i32, _p]),
     "revo_vit_stats": (_i32, [_p, C.POINTER(C.c_double), _i32, _p]),
     "revo_text_create": (_i32, [C.POINTER(TextCfg), C.POINTER(Tensor), _i32, _i32, _i32, C.POINTER(_p)]),
     "revo_text_destroy": (_i32, [_p]),
@@ -129,6 +130,7 @@ SIGNATURES = {
     "revo_prof_reset": (_i32, []),
     "revo_prof_report": (_i32, [C.c_char_p, _i32]),
     "revo_preprocess_crop_resize": (_i32, [C.POINTER(CropJob), _i32, _i32, _p, _p]),
+    "revo_preprocess_crop_resize_hw": (_i32, [C.POINTER(CropJob), _i32, _i32, _i32, _p, _p]),
     "revo_probe_mfma": (_i32, [_p, _i64, _p, _i32, _i32, _p]),
     "revo_probe_mfma_flops": (_i64, [_i32, _i32]),
     "revo_probe_copy": (_i32, [_p, _p, _i64, _p]),
@@ -139,6 +141,7 @@ EXPERIMENT_SIGNATURES = {
     "revo_vit_set_debug_layers": (_i32, [_p, _i32]),
     "revo_vit_read_residual": (_i32, [_p, _i32, _p, _p]),
     "revo_vit_read_tap": (_i32, [_p, _i32, _i32, _p, _p]),
+    "revo_vit_read_grid_tables": (_i32, [_p, _p, _p, _p]),
     "revo_text_set_debug_layers": (_i32, [_p, _i32]),
     "revo_text_read_residual": (_i32, [_p, _i32, _p, _p]),
     "revo_search_set_mode": (_i32, [_p, _i32]),

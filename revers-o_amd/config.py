@@ -127,6 +127,39 @@ def get_config(name: str = DEFAULT_VARIANT) -> PEConfig:
     return VARIANTS[name]
 
 
+def aspect_grids(cfg, max_ratio: float = 4.0):
+    """The menu of token grids ``(gh, gw)`` of a tower for native-aspect embedding: every shape within
+    the native token budget ``G * G`` that is maximal both ways -- ``gw == G * G // gh`` and ``gh == G * G // gw`` -- with
+    ``max(gh, gw) / min(gh, gw) <= max_ratio``, by ascending ``gh``.  ``(G, G)`` is always in it."""
+    G2 = int(cfg.grid) ** 2
+    if not float(max_ratio) >= 1.0:
+        raise ValueError("aspect_grids: max_ratio must be at least 1")
+    out = []
+    for gh in range(1, G2 + 1):
+        gw = G2 // gh
+        if gw >= 1 and G2 // gw == gh and max(gh, gw) <= float(max_ratio) * min(gh, gw):
+            out.append((gh, gw))
+    return out
+
+
+def aspect_grid(cfg, height, width, max_ratio: float = 4.0, grids=None):
+    """The grid an image of ``height x width`` pixels is embedded on: the entry of ``grids`` (default: the menu
+    :func:`aspect_grids`) that minimises ``|ln(gw / gh) - ln(width / height)|``; ties go to more cells, then to the smaller
+    ``gh``.  (The logarithms are taken per side and subtracted, so a shape and its transpose are exactly as far from a
+    square image, and a transposed image gets the transposed grid.)"""
+    import math
+    height, width = int(height), int(width)
+    if height <= 0 or width <= 0:
+        raise ValueError("aspect_grid: height and width must be positive")
+    if grids is None:
+        grids = aspect_grids(cfg, max_ratio)
+    if not grids:
+        raise ValueError("aspect_grid: no grids to choose from")
+    want = math.log(width) - math.log(height)
+    return min(((int(gh), int(gw)) for gh, gw in grids),
+               key=lambda g: (abs((math.log(g[1]) - math.log(g[0])) - want), -g[0] * g[1], g[0]))
+
+
 def available_configs():
     """Mirror of ``pe.CLIP.available_configs()`` (core_system.py:173)."""
     return [n for n in VARIANTS if n.startswith("PE-Core")]

@@ -34,7 +34,7 @@ from . import ingest
 from . import preprocess as pp
 from . import regions as rg
 from . import store as st
-from .config import DEFAULT_VARIANT, TEXT_VARIANTS, available_configs, get_config, get_text_config
+from .config import DEFAULT_VARIANT, TEXT_VARIANTS, aspect_grid, available_configs, get_config, get_text_config
 from .engine import TextEngine, VitEngine
 from .ingest import BUILDING, uuid4 as _uuid4
 from .tokenizer import ClipTokenizer
@@ -133,11 +133,23 @@ class SimpleReverso:
     # list_databases / load_database leave those build directories alone meanwhile.  Guarded by _building_lock.
     _building_lock = threading.Lock()
     _building_names = frozenset()      # (per-instance set from __init__ on)
+    aspect, aspect_max_ratio = "squash", 4.0      # (set by __init__; the defaults are the reference's behaviour)
 
     def __init__(self, model_name=DEFAULT_VARIANT, checkpoint=None, device=0, db_root=DB_ROOT, max_batch=64,
                  detector=None, decode_workers=None, synthetic_seed=0, region_mode="global", device_resize=False,
-                 checkpoint_interval_s=30.0, skip_duplicates=None, detect_threshold=None, background_prompts=()):
+                 checkpoint_interval_s=30.0, skip_duplicates=None, detect_threshold=None, background_prompts=(),
+                 aspect="squash", aspect_max_ratio=4.0):
         print("🚀 Initializing Simple Revers-o...")
+        if aspect not in ("squash", "keep"):
+            raise ValueError("aspect must be 'squash' (every image resized to the model's square: the reference's behaviour, "
+                             "core_system.py:200) or 'keep' (embedded on the token grid nearest its own aspect ratio)")
+        if not float(aspect_max_ratio) >= 1.0:
+            raise ValueError("aspect_max_ratio must be at least 1")
+        # "keep": native-aspect embedding -- a query, a stored frame and a region crop are resized,
+        # without crop, to the grid of the tower's menu (config.aspect_grids) nearest their own aspect ratio and embedded on
+        # it; the token budget stays the native one.  The prompt detector keeps running on the squashed native image: only the
+        # vectors follow the aspect.  A database holds vectors of ONE mode (its build info names it).
+        self.aspect, self.aspect_max_ratio = aspect, float(aspect_max_ratio)
         if region_mode not in ("global", "crop", "pool"):
             raise ValueError("region_mode must be 'global' (the reference's behaviour, core_system.py:406), 'crop' or 'pool'")
         # "crop": every region is cropped to its box on the device and embedded on its own -- the
@@ -227,6 +239,10 @@ class SimpleReverso:
                     self.vector_db.close()
                 self.vector_db = st.GalleryStore.load(db_path, device=self.device.index or 0)
                 self.current_database = self.vector_db.collection
+                built = (self.vector_db.build_info or {}).get("aspect", "squash")
+            if built != self.aspect:
+                return (f"✅ Loaded database: {database_name}\n⚠️ It was built with aspect='{built}' and this system embeds "
+                        f"queries with aspect='{self.aspect}': their vectors are not made the same way")
             return f"✅ Loaded database: {database_name}"
         except Exception as e:
             return f"❌ Error loading database: {str(e)}"
@@ -366,8 +382,50 @@ class SimpleReverso:
         return kept, metas
 
     # ----------------------------------------------------------------- embed --
+    def _grid_of(self, width, height):
+        """aspect="keep": the token grid of a ``width x height`` image or crop (config.aspect_grid over the tower's menu)"""
+        return aspect_grid(self.pe_model.cfg, height, width, self.aspect_max_ratio)
+
+    def _embed_by_grid(self, frames, boxes, bits=None, grids=None, to_host=True):
+        """aspect="keep", the one place a batch is split by grid: device frames (uint8 ``[H, W, 3]``) and jobs ``boxes``
+        (``(frame_index, x0, y0, x1, y1)``, or None for every frame whole), each embedded on the grid of its box's aspect
+        ratio (``grids``: per job, where the caller already chose them).  The jobs are grouped by grid; per group one
+        crop + resize launch and one forward of the group's jobs, and the vectors are scattered back: fp32 ``[n, D]`` in job
+        order.  With ``bits`` (pool mode: per job the token bitmaps of its regions ON ITS GRID) the forward is
+        ``embed_regions`` and the result one row per region, jobs in order, regions in theirs."""
+        cfg = self.pe_model.cfg
+        if boxes is None:
+            boxes = [(i, 0, 0, f.shape[1], f.shape[0]) for i, f in enumerate(frames)]
+        if grids is None:
+            grids = [self._grid_of(b[3] - b[1], b[4] - b[2]) for b in boxes]
+        counts = [1] * len(boxes) if bits is None else [len(b) for b in bits]
+        starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        out = torch.empty((int(starts[-1]), cfg.out_dim), dtype=torch.float32, device=self.device)
+        groups = {}
+        for i, g in enumerate(grids):
+            if counts[i]:
+                groups.setdefault(tuple(g), []).append(i)
+        P = cfg.patch_size
+        with self._lock, torch.cuda.device(self.device):
+            for (gh, gw), idx in groups.items():
+                u8 = pp.crop_resize_device(frames, [boxes[i] for i in idx], (gh * P, gw * P))
+                if bits is None:
+                    emb = self.pe_model.embed(u8, grid=(gh, gw))
+                else:
+                    ri = np.concatenate([np.full(counts[i], j, dtype=np.int64) for j, i in enumerate(idx)])
+                    _, emb = self.pe_model.embed_regions(u8, ri, np.concatenate([bits[i] for i in idx]), with_global=False,
+                                                         grid=(gh, gw))
+                rows = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in idx])
+                out.index_copy_(0, torch.from_numpy(rows).to(self.device), emb)
+        return out.cpu() if to_host else out
+
+    def _device_frames(self, pils):
+        return [torch.from_numpy(np.array(pp.to_pil(im), dtype=np.uint8)).to(self.device, non_blocking=True) for im in pils]
+
     def _embed_pils(self, pils):
         """list of PIL images -> fp32 CPU tensor [n, D] (L2-normalised)."""
+        if self.aspect == "keep":
+            return self._embed_by_grid(self._device_frames(pils), None)
         u8 = self._frames_u8(pils)
         with self._lock:
             emb = self.pe_model.embed(u8)
@@ -395,6 +453,8 @@ class SimpleReverso:
                 boxes.append((fi,) + pp.clamp_box((x0, y0, x1, y1), pil.width, pil.height))
         if not boxes:
             return torch.empty((0, self.pe_model.cfg.out_dim), device=None if to_host else self.device)
+        if self.aspect == "keep":                  # every crop on the grid of its own box
+            return self._embed_by_grid(frames, boxes, to_host=to_host)
         with self._lock:
             u8 = pp.crop_resize_device(frames, boxes, self.pe_model.cfg.image_size)
             emb = self.pe_model.embed(u8)
@@ -404,24 +464,24 @@ class SimpleReverso:
         """One vector per region of one image (see _embed_regions_batch)."""
         return self._embed_regions_batch([(pil, metas)])
 
-    def _pool_bits(self, regions, kept):
+    def _pool_bits(self, regions, kept, grid=None):
         """pool mode: the token bitmap of every kept region (uint32 [len(kept), words]).  A processed mask is pooled over
         the tokens it covers (regions.token_masks; binarised as _region_metadata does); a region without a mask gets every
         token, class token included -- its image's global vector bit for bit, the reference's own fallback
-        (core_system.py:367-389)."""
+        (core_system.py:367-389).  ``grid``: the token grid the image is embedded on (aspect="keep"; None: the native one)."""
         cfg = self.pe_model.cfg
-        out = np.zeros((len(kept), rg.words_per_region(cfg)), dtype=np.uint32)
+        out = np.zeros((len(kept), rg.words_per_region(cfg, grid)), dtype=np.uint32)
         by_shape = {}                                  # masks of one shape (the usual case: the image's) share the cell tables
         for j, i in enumerate(kept):
             mask = regions.mask[i] if getattr(regions, "mask", None) is not None and i < len(regions.mask) else None
             if mask is None:
-                out[j] = rg.full_mask(cfg, include_cls=True)
+                out[j] = rg.full_mask(cfg, include_cls=True, grid=grid)
                 continue
             m = np.asarray(mask)
             m = (m > 0.5) if np.issubdtype(m.dtype, np.floating) else (m.astype(np.uint8) != 0)
             by_shape.setdefault(m.shape, []).append((j, m))
         for (h, w), items in by_shape.items():
-            out[[j for j, _ in items]] = rg.token_masks(cfg, [m for _, m in items], w, h)
+            out[[j for j, _ in items]] = rg.token_masks(cfg, [m for _, m in items], w, h, grid=grid)
         return out
 
     def _embed_pool_batch(self, u8, bits_per_image, to_host=True):
@@ -458,6 +518,10 @@ class SimpleReverso:
         elif self.region_mode == "pool":
             if not kept:
                 embeddings = []
+            elif self.aspect == "keep":            # the image's own grid; the masks' tokens on that grid
+                grid = self._grid_of(pil.width, pil.height)
+                embeddings = list(self._embed_by_grid(self._device_frames([pil]), None, grids=[grid],
+                                                      bits=[self._pool_bits(self.detected_regions, kept, grid)]))
             else:
                 embeddings = list(self._embed_pool_batch(self._frames_u8([pil]), [self._pool_bits(self.detected_regions, kept)]))
         else:
@@ -513,6 +577,13 @@ class SimpleReverso:
             if progress_callback:
                 progress_callback(msg, None)
             return msg
+        if self.aspect == "keep" and not self.device_resize:
+            # the frames of a batch have different grids: they go up as decoded and are resized on the device, group by group
+            msg = ("❌ aspect='keep' builds a database through the device resize: create the system with device_resize=True "
+                   "(the host-resize route stages one square row per file)")
+            if progress_callback:
+                progress_callback(msg, None)
+            return msg
         log_status = ingest.StatusLog(progress_callback)
         os.makedirs(self.db_root, exist_ok=True)
         processed_files = set()
@@ -526,6 +597,8 @@ class SimpleReverso:
             try:
                 header = st.read_manifest(os.path.join(build_path, st.MANIFEST))[0]
                 diff = [k for k in build_info if header.get("build", {}).get(k) != build_info[k]]
+                if header.get("build", {}).get("aspect", "squash") != self.aspect and "aspect" not in diff:
+                    diff.append("aspect")
                 if header.get("dim") != self.pe_model.cfg.out_dim:
                     diff.append("dim")
                 if diff:
@@ -551,10 +624,13 @@ class SimpleReverso:
 
     def _build_info(self, folder_path, use_direct_pe, include_subfolders):
         """What a collection is made from and how: written into the build's manifest header, compared on resume."""
-        return {"folder_path": os.path.abspath(folder_path), "model": self.pe_model.cfg.name,
+        info = {"folder_path": os.path.abspath(folder_path), "model": self.pe_model.cfg.name,
                 "use_ls": bool(self.pe_model.cfg.use_ls), "region_mode": self.region_mode,
                 "use_direct_pe": bool(use_direct_pe), "include_subfolders": bool(include_subfolders),
                 "skip_duplicates": self.skip_duplicates}      # (an older manifest has no such key: the same as None)
+        if self.aspect != "squash":                           # (no key: "squash", what every older manifest is)
+            info.update(aspect=self.aspect, aspect_max_ratio=self.aspect_max_ratio)
+        return info
 
     # ---------------------------------------------------------------- search --
     def search_similar_boosted(self, formula, similarity_threshold=0.7, max_results=5, query_filter=None):

@@ -395,19 +395,20 @@ int launch_planes_to_f32(const bf16_t* hi, const bf16_t* lo, long ldp, float* x,
 // embedded tokens feed all 24 blocks: their rounding was a fifth of the residual stream's final error.)
 // Each thread produces 8 consecutive k of one patch row (one 16-byte store per part).
 template <bool U8>
-__global__ __launch_bounds__(256) void patchify_kernel(const void* __restrict__ images, int B, int img, int P, int G,
-                                                       bf16_t* __restrict__ out, long Kp) {
+// (the image is img_h x img_w pixels = gh x gw patches: a rectangle under revo_vit_set_grid, the square otherwise)
+__global__ __launch_bounds__(256) void patchify_kernel(const void* __restrict__ images, int B, int img_h, int img_w, int P,
+                                                       int gh, int gw, bf16_t* __restrict__ out, long Kp) {
     constexpr int PARTS = U8 ? 2 : 3;
     const long ld = Kp * PARTS;
     const int chunks = (int)(Kp >> 3);
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = (long)B * G * G * chunks;
+    const long total = (long)B * gh * gw * chunks;
     if (gid >= total) return;
     const int c8 = (int)(gid % chunks);
     const long prow = gid / chunks;
-    const int gx = (int)(prow % G);
-    const int gy = (int)((prow / G) % G);
-    const int b = (int)(prow / ((long)G * G));
+    const int gx = (int)(prow % gw);
+    const int gy = (int)((prow / gw) % gh);
+    const int b = (int)(prow / ((long)gh * gw));
     const int PP = P * P, Kreal = 3 * PP;
     float v[8];
 #pragma unroll
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const void* __restrict__ 
         if (k < Kreal) {
             const int c = k / PP, rem = k - c * PP;
             const int py = rem / P, px = rem - py * P;
-            const long off = (((long)b * 3 + c) * img + (gy * P + py)) * img + (gx * P + px);
+            const long off = (((long)b * 3 + c) * img_h + (gy * P + py)) * img_w + (gx * P + px);
             if (U8) f = 2.0f * (float)((const uint8_t*)images)[off] - 255.0f;
             else f = ((const float*)images)[off] * 255.0f;
         }
@@ -445,32 +446,32 @@ __global__ __launch_bounds__(256) void patchify_kernel(const void* __restrict__ 
     }
 }
 
-// u8 images, one workgroup per band of G patches (image b, patch row gy): the band's 3 x P pixel rows are contiguous runs of
-// `img` bytes -- loaded with 16-byte loads into LDS (the gather form above reads every pixel with a byte load of its own, 37
+// u8 images, one workgroup per band of gw patches (image b, patch row gy): the band's 3 x P pixel rows are contiguous runs of
+// `img_w` bytes -- loaded with 16-byte loads into LDS (the gather form above reads every pixel with a byte load of its own, 37
 // cache lines per wave instruction: 56-62 us at batch 64 for 22 MB in, 94 MB out) -- then every thread builds 8-value chunks
 // of patch rows from LDS bytes through a table of the k -> (channel, py, px) offsets (no divisions per element).
-// The values are the exact integers 2 v - 255: the same bytes as the gather form.  img % 16 == 0, 16-byte aligned images.
-__global__ __launch_bounds__(256) void patchify_band_u8_kernel(const uint8_t* __restrict__ images, int img, int P, int G,
-                                                               bf16_t* __restrict__ out, long Kp) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t pband[];       // [3 P][img] bytes, then int koff[Kreal]
-    const int b = blockIdx.x / G, gy = blockIdx.x - b * G;
-    const int PP = P * P, Kreal = 3 * PP, rows = 3 * P, v16 = img >> 4;
-    int* koff = (int*)(pband + (((long)rows * img + 15) & ~15l));
+// The values are the exact integers 2 v - 255: the same bytes as the gather form.  img_w % 16 == 0, 16-byte aligned images.
+__global__ __launch_bounds__(256) void patchify_band_u8_kernel(const uint8_t* __restrict__ images, int img_h, int img_w, int P,
+                                                               int gh, int gw, bf16_t* __restrict__ out, long Kp) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t pband[];       // [3 P][img_w] bytes, then int koff[Kreal]
+    const int b = blockIdx.x / gh, gy = blockIdx.x - b * gh;
+    const int PP = P * P, Kreal = 3 * PP, rows = 3 * P, v16 = img_w >> 4;
+    int* koff = (int*)(pband + (((long)rows * img_w + 15) & ~15l));
     for (int i = threadIdx.x; i < rows * v16; i += 256) {
         const int r = i / v16, q = i - r * v16;
         const int c = r / P, py = r - c * P;
-        const uint8_t* src = images + (((long)b * 3 + c) * img + (gy * P + py)) * img;
-        *(uint4*)(pband + (long)r * img + q * 16) = *(const uint4*)(src + q * 16);
+        const uint8_t* src = images + (((long)b * 3 + c) * img_h + (gy * P + py)) * img_w;
+        *(uint4*)(pband + (long)r * img_w + q * 16) = *(const uint4*)(src + q * 16);
     }
     for (int k = threadIdx.x; k < Kreal; k += 256) {
         const int c = k / PP, rem = k - c * PP;
         const int py = rem / P, px = rem - py * P;
-        koff[k] = (c * P + py) * img + px;
+        koff[k] = (c * P + py) * img_w + px;
     }
     __syncthreads();
     const int chunks = (int)(Kp >> 3);
     const long ld = Kp * 2;
-    for (int it = threadIdx.x; it < G * chunks; it += 256) {
+    for (int it = threadIdx.x; it < gw * chunks; it += 256) {
         const int gx = it / chunks, c8 = it - gx * chunks;
         float v[8];
 #pragma unroll
@@ -483,32 +484,34 @@ __global__ __launch_bounds__(256) void patchify_band_u8_kernel(const uint8_t* __
         o.y = pack_bf16x2(v[2], v[3]);
         o.z = pack_bf16x2(v[4], v[5]);
         o.w = pack_bf16x2(v[6], v[7]);
-        bf16_t* dst = out + ((long)(b * G + gy) * G + gx) * ld + c8 * 8;
+        bf16_t* dst = out + (((long)b * gh + gy) * gw + gx) * ld + c8 * 8;
         *(uint4*)dst = o;
         *(uint4*)(dst + Kp) = o;
     }
 }
 
-// out rows: [B*G*G][parts * Kp] with parts = 2 (u8) or 3 (f32); see the kernel
-int launch_patchify(const void* images, int is_u8, int B, int img, int P, bf16_t* out, long Kp, hipStream_t st) {
-    REVO_REQUIRE(img % P == 0, "patchify: image size must be a multiple of the patch size");
+// out rows: [B*gh*gw][parts * Kp] with parts = 2 (u8) or 3 (f32); see the kernel
+int launch_patchify(const void* images, int is_u8, int B, int img_h, int img_w, int P, bf16_t* out, long Kp, hipStream_t st) {
+    REVO_REQUIRE(P > 0 && img_h > 0 && img_w > 0 && img_h % P == 0 && img_w % P == 0,
+                 "patchify: image size must be a multiple of the patch size");
     REVO_REQUIRE(Kp % 8 == 0 && Kp >= 3 * P * P, "patchify: bad part width");
-    const int G = img / P;
-    const long total = (long)B * G * G * (Kp / 8);
+    const int gh = img_h / P, gw = img_w / P;
+    const long total = (long)B * gh * gw * (Kp / 8);
     if (total <= 0) return 0;
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    const size_t band_lds = (((size_t)3 * P * img + 15) & ~(size_t)15) + (size_t)3 * P * P * 4;
-    bool band = is_u8 && img % 16 == 0 && (((uintptr_t)images) & 15) == 0 && band_lds <= 64 * 1024 && B * G >= 64;
+    const size_t band_lds = (((size_t)3 * P * img_w + 15) & ~(size_t)15) + (size_t)3 * P * P * 4;
+    bool band = is_u8 && img_w % 16 == 0 && (((uintptr_t)images) & 15) == 0 && band_lds <= 64 * 1024 && (long)B * gh >= 64;
 #ifdef REVO_EXPERIMENTS
     if (getenv("REVO_PATCHIFY_GATHER")) band = false;      // parity of the two forms (tests)
 #endif
     if (band) {
-        hipLaunchKernelGGL(patchify_band_u8_kernel, dim3((unsigned)(B * G)), block, band_lds, st, (const uint8_t*)images, img, P, G, out, Kp);
+        hipLaunchKernelGGL(patchify_band_u8_kernel, dim3((unsigned)(B * gh)), block, band_lds, st, (const uint8_t*)images, img_h, img_w,
+                           P, gh, gw, out, Kp);
         REVO_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (is_u8) hipLaunchKernelGGL((patchify_kernel<true>), grid, block, 0, st, images, B, img, P, G, out, Kp);
-    else hipLaunchKernelGGL((patchify_kernel<false>), grid, block, 0, st, images, B, img, P, G, out, Kp);
+    if (is_u8) hipLaunchKernelGGL((patchify_kernel<true>), grid, block, 0, st, images, B, img_h, img_w, P, gh, gw, out, Kp);
+    else hipLaunchKernelGGL((patchify_kernel<false>), grid, block, 0, st, images, B, img_h, img_w, P, gh, gw, out, Kp);
     REVO_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -520,6 +523,46 @@ __global__ void cls_rows_kernel(float* x, long ldx, const float* cls, const floa
     const int b = i / W, c = i - b * W;
     x[(long)b * S * ldx + c] = cls[c] + pos[c];
 }
+// ------------------------------------------------- position resample ----
+// The G x G patch rows of the position table resampled to gh x gw (revo_vit_set_grid; once per grid and handle): bilinear with
+// half-pixel centres, the source coordinate (o + 0.5) G / g_out - 0.5 clamped below at 0 and the upper neighbour at G - 1
+// (torch's F.interpolate(mode="bilinear", align_corners=False), no antialiasing).  Coordinates and the four weights in fp64,
+// each weight rounded once to fp32, then ONE fp32 fma chain w00 p00 + w01 p01 + w10 p10 + w11 p11 in that order: five
+// roundings, |err| <= 6 * 2^-24 * max|corner| against the same formula in fp64.  The class row, if any, is copied.
+__global__ __launch_bounds__(256) void pos_resample_kernel(const float* __restrict__ src, int G, int cls, int gh, int gw, int W,
+                                                           float* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)(gh * gw + cls) * W;
+    if (gid >= total) return;
+    const int c = (int)(gid % W);
+    const int s = (int)(gid / W);
+    if (s < cls) { dst[gid] = src[gid]; return; }
+    const int g = s - cls, oy = g / gw, ox = g - oy * gw;
+    double sy = ((double)oy + 0.5) * (double)G / (double)gh - 0.5;
+    double sx = ((double)ox + 0.5) * (double)G / (double)gw - 0.5;
+    if (sy < 0.0) sy = 0.0;
+    if (sx < 0.0) sx = 0.0;
+    int y0 = (int)sy, x0 = (int)sx;
+    if (y0 > G - 1) y0 = G - 1;
+    if (x0 > G - 1) x0 = G - 1;
+    const int y1 = y0 + 1 < G ? y0 + 1 : G - 1, x1 = x0 + 1 < G ? x0 + 1 : G - 1;
+    const double ly = sy - (double)y0, lx = sx - (double)x0;
+    const float w00 = (float)((1.0 - ly) * (1.0 - lx)), w01 = (float)((1.0 - ly) * lx);
+    const float w10 = (float)(ly * (1.0 - lx)), w11 = (float)(ly * lx);
+    const float* p = src + (long)cls * W + c;
+    const float p00 = p[((long)y0 * G + x0) * W], p01 = p[((long)y0 * G + x1) * W];
+    const float p10 = p[((long)y1 * G + x0) * W], p11 = p[((long)y1 * G + x1) * W];
+    dst[gid] = __builtin_fmaf(w11, p11, __builtin_fmaf(w10, p10, __builtin_fmaf(w01, p01, w00 * p00)));
+}
+int launch_pos_resample(const float* src, int G, int cls, int gh, int gw, int W, float* dst, hipStream_t st) {
+    REVO_REQUIRE(src && dst && G >= 1 && gh >= 1 && gw >= 1 && W >= 1 && (cls == 0 || cls == 1), "pos_resample: bad arguments");
+    const long total = ((long)gh * gw + cls) * W;
+    hipLaunchKernelGGL(pos_resample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, G, cls, gh, gw, W, dst);
+    REVO_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_cls_rows(float* x, long ldx, const float* cls, const float* pos, int B, int S, int W, hipStream_t st) {
     const int n = B * W;
     if (n <= 0) return 0;

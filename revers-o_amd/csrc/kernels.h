@@ -135,7 +135,10 @@ int launch_fold_ln_linear(const float* w, const float* gamma, const float* beta,
 // images NCHW (u8 pixel values; f32: already normalised to [-1, 1]) -> im2col matrix for the split-precision patch GEMM:
 // rows [B*G*G][parts * Kp] bf16, k = c*P*P + py*P + px zero padded to Kp, parts = 2 (u8: the exact integers 2v - 255,
 // twice) or 3 (f32: hi | hi | lo of 255 x); the weights carry the 1/255 (elementwise.hip, head.hip split_hi_lo_hi)
-int launch_patchify(const void* images, int is_u8, int B, int img, int P, bf16_t* out, long Kp, hipStream_t st);
+// (img_h x img_w pixels = gh x gw patches of P x P)
+int launch_patchify(const void* images, int is_u8, int B, int img_h, int img_w, int P, bf16_t* out, long Kp, hipStream_t st);
+// position table [cls + G*G][W] -> [cls + gh*gw][W], bilinear with half-pixel centres (elementwise.hip)
+int launch_pos_resample(const float* src, int G, int cls, int gh, int gw, int W, float* dst, hipStream_t st);
 // ---- the attention-pool head in fp32 (head.hip)
 int launch_probe_qk(const float* q, const float* Wk, const float* bk, int W, int heads, float* qk, float* ck, hipStream_t st);
 // u [B][H][W] = softmax-weighted sums of the fp32 ln_post rows x; the logits [B][H][S] of the probe come from the

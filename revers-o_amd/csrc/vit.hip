@@ -44,6 +44,14 @@ struct revo_vit : TowerCore {
     float *pln_w = nullptr, *pln_b = nullptr, *w_pfc1 = nullptr, *b_pfc1 = nullptr, *w_pfc2 = nullptr, *b_pfc2 = nullptr,
           *w_projT = nullptr;
     float2* rope_cs = nullptr;
+    // grid shapes (revo_vit_set_grid): the token grid a forward runs on, with its position and rotary tables, built on first
+    // use.  Entry 0 is the native G x G grid and aliases pos / rope_cs above; S and G2 above stay the native (largest) sizes
+    // every workspace is allocated for, and the forwards read the ACTIVE shape (shape()) where they need the call's.
+    struct GridShape { int gh, gw, S, G2; float* pos; float2* rope_cs; };
+    static constexpr int MAX_SHAPES = 64;
+    std::vector<GridShape> shapes;
+    int active = 0;
+    const GridShape& shape() const { return shapes[active]; }
     // workspace beside the body's
     bf16_t* patches = nullptr;
     float *pool_logits = nullptr, *pool_u = nullptr, *pool_att = nullptr, *pool_o = nullptr, *pool_h = nullptr,
@@ -68,6 +76,30 @@ struct revo_vit : TowerCore {
     } det;
     ~revo_vit() { if (det.r_vec) (void)hipFree(det.r_vec); }
 };
+
+// 2-D rope table of a gh x gw grid: [S][hd/2] (cos, sin); x-axis pairs first, then y-axis; cls row unrotated.  Integer
+// coordinates gx + cls, gy + cls whatever the grid: not rescaled to the native range.
+static std::vector<float2> rope_table(const revo_vit_cfg& c, int hd, int gh, int gw) {
+    const int d = hd / 2, nf = d / 2;
+    const int start = c.use_cls ? 1 : 0;
+    const int S = gh * gw + start;
+    std::vector<float2> cs((size_t)S * (hd / 2));
+    for (int s = 0; s < S; ++s) {
+        for (int pi = 0; pi < hd / 2; ++pi) {
+            double ang = 0.0;
+            if (!(c.use_cls && s == 0)) {
+                const int g = s - start;
+                const int gy = g / gw, gx = g % gw;
+                const bool xaxis = pi < nf;
+                const int f = xaxis ? pi : pi - nf;
+                const double freq = 1.0 / pow((double)c.rope_theta, (double)(2 * f) / (double)d);
+                ang = (double)((xaxis ? gx : gy) + start) * freq;
+            }
+            cs[(size_t)s * (hd / 2) + pi] = make_float2((float)cos(ang), (float)sin(ang));
+        }
+    }
+    return cs;
+}
 
 extern "C" int32_t revo_vit_create(const revo_vit_cfg* cfg, const revo_tensor* weights, int32_t n_weights,
                                    int32_t device, int32_t max_batch, revo_vit** out) {
@@ -165,27 +197,13 @@ extern "C" int32_t revo_vit_create(const revo_vit_cfg* cfg, const revo_tensor* w
     }
     CHECK_RC(upload_projT(v.get(), wm, sg, "visual.proj", D, &v->w_projT));
 
-    // 2-D rope table: [S][hd/2] (cos, sin); x-axis pairs first, then y-axis; cls row unrotated
+    // 2-D rope table of the native grid, and the native shape: entry 0 of the grid cache
     {
-        const int hd = v->hd, d = hd / 2, nf = d / 2;
-        std::vector<float2> cs((size_t)S * (hd / 2));
-        const int start = c.use_cls ? 1 : 0;
-        for (int s = 0; s < S; ++s) {
-            for (int pi = 0; pi < hd / 2; ++pi) {
-                double ang = 0.0;
-                if (!(c.use_cls && s == 0)) {
-                    const int g = s - (c.use_cls ? 1 : 0);
-                    const int gy = g / G, gx = g % G;
-                    const bool xaxis = pi < nf;
-                    const int f = xaxis ? pi : pi - nf;
-                    const double freq = 1.0 / pow((double)c.rope_theta, (double)(2 * f) / (double)d);
-                    ang = (double)((xaxis ? gx : gy) + start) * freq;
-                }
-                cs[(size_t)s * (hd / 2) + pi] = make_float2((float)cos(ang), (float)sin(ang));
-            }
-        }
+        const std::vector<float2> cs = rope_table(c, v->hd, G, G);
         CHECK_RC(v->dalloc(&v->rope_cs, cs.size()));
         REVO_HIP_CHECK(hipMemcpy(v->rope_cs, cs.data(), cs.size() * sizeof(float2), hipMemcpyHostToDevice));
+        v->shapes.reserve(revo_vit::MAX_SHAPES);
+        v->shapes.push_back({G, G, v->S, v->G2, v->pos, v->rope_cs});
     }
 
     // workspace for max_batch images
@@ -211,7 +229,46 @@ extern "C" int32_t revo_vit_destroy(revo_vit* vit) {
     return 0;
     API_END
 }
-extern "C" int32_t revo_vit_seq_len(const revo_vit* vit) { return vit ? vit->S : -1; }
+extern "C" int32_t revo_vit_seq_len(const revo_vit* vit) { return vit ? vit->shape().S : -1; }
+
+// The grid of the forwards that follow (include/revo.h GRIDS).  Everything that can be refused is refused before the device is
+// touched; a shape's tables are built on `stream` by the first call that names it and kept for the life of the handle.
+extern "C" int32_t revo_vit_set_grid(revo_vit* v, int32_t grid_h, int32_t grid_w, void* stream) {
+    API_BEGIN
+    REVO_REQUIRE(v, "vit_set_grid: null handle");
+    const revo_vit_cfg& c = v->cfg;
+    const int P = c.patch_size, G = c.image_size / P, cls = c.use_cls ? 1 : 0;
+    if (grid_h == 0 && grid_w == 0) grid_h = grid_w = G;
+    const std::string name = "(" + std::to_string(grid_h) + ", " + std::to_string(grid_w) + ")";
+    REVO_REQUIRE(grid_h >= 1 && grid_w >= 1, "vit_set_grid: grid " + name + " must have positive sides ((0, 0) restores the native grid)");
+    REVO_REQUIRE((int64_t)grid_h * grid_w <= (int64_t)v->G2, "vit_set_grid: grid " + name + " has more than the native " +
+                 std::to_string(G) + " * " + std::to_string(G) + " = " + std::to_string(v->G2) + " cells");
+    REVO_REQUIRE((int64_t)grid_h * P <= 65535 && (int64_t)grid_w * P <= 65535,
+                 "vit_set_grid: grid " + name + " makes a band of more than 65535 pixels");
+    for (size_t i = 0; i < v->shapes.size(); ++i)
+        if (v->shapes[i].gh == grid_h && v->shapes[i].gw == grid_w) {
+            if ((int)i != v->active) v->det.valid = false;        // a detect result belongs to the grid it was made on
+            v->active = (int)i;
+            return 0;
+        }
+    REVO_REQUIRE((int)v->shapes.size() < revo_vit::MAX_SHAPES, "vit_set_grid: the handle already holds " +
+                 std::to_string(revo_vit::MAX_SHAPES) + " grid shapes; grid " + name + " would be one more");
+    REVO_ON_DEVICE(v->device);
+    hipStream_t st = (hipStream_t)stream;
+    revo_vit::GridShape sh{grid_h, grid_w, grid_h * grid_w + cls, grid_h * grid_w, nullptr, nullptr};
+    const std::vector<float2> cs = rope_table(c, v->hd, grid_h, grid_w);
+    CHECK_RC(v->dalloc(&sh.pos, (size_t)sh.S * c.width));
+    CHECK_RC(v->dalloc(&sh.rope_cs, cs.size()));
+    CHECK_RC(revo::launch_pos_resample(v->pos, G, cls, grid_h, grid_w, c.width, sh.pos, st));
+    REVO_HIP_CHECK(hipMemcpyAsync(sh.rope_cs, cs.data(), cs.size() * sizeof(float2), hipMemcpyHostToDevice, st));
+    REVO_HIP_CHECK(hipStreamSynchronize(st));                     // (cs is this frame's; once per grid and handle)
+    v->shapes.push_back(sh);
+    v->active = (int)v->shapes.size() - 1;
+    v->det.valid = false;
+    return 0;
+    API_END
+}
+
 extern "C" int32_t revo_vit_stats(revo_vit* vit, double* out4, int32_t reset, void* stream) {
     API_BEGIN
     REVO_REQUIRE(vit && out4, "vit_stats: null argument");
@@ -235,7 +292,7 @@ extern "C" int32_t revo_vit_set_debug_layers(revo_vit* vit, int32_t n) {
 extern "C" int32_t revo_vit_read_residual(revo_vit* vit, int32_t batch, float* dst, void* stream) {
     REVO_REQUIRE(vit && dst && batch >= 1 && batch <= vit->max_batch, "read_residual: bad arguments");
     REVO_ON_DEVICE(vit->device);
-    REVO_HIP_CHECK(hipMemcpyAsync(dst, vit->x, (size_t)batch * vit->S * vit->cfg.width * 4, hipMemcpyDeviceToDevice,
+    REVO_HIP_CHECK(hipMemcpyAsync(dst, vit->x, (size_t)batch * vit->shape().S * vit->cfg.width * 4, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream));
     return 0;
 }
@@ -243,7 +300,7 @@ extern "C" int32_t revo_vit_read_residual(revo_vit* vit, int32_t batch, float* d
 extern "C" int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch, void* dst, void* stream) {
     REVO_REQUIRE(vit && dst && batch >= 1 && batch <= vit->max_batch, "read_tap: bad arguments");
     REVO_ON_DEVICE(vit->device);
-    const size_t rows = (size_t)batch * vit->S, W = vit->cfg.width;
+    const size_t rows = (size_t)batch * vit->shape().S, W = vit->cfg.width;
     const void* src = nullptr;
     size_t bytes = 0;
     switch (which) {
@@ -256,7 +313,17 @@ extern "C" int32_t revo_vit_read_tap(revo_vit* vit, int32_t which, int32_t batch
     return 0;
 }
 // whether the forward keeps the residual stream in planes for this many rows of this tower (reporting / tests)
-extern "C" int32_t revo_debug_stream_in_planes(const revo_vit* v, int32_t batch) { return v && stream_in_planes(*v, batch * v->S); }
+extern "C" int32_t revo_debug_stream_in_planes(const revo_vit* v, int32_t batch) { return v && stream_in_planes(*v, batch * v->shape().S); }
+// the active grid shape's tables: pos [S'][W] fp32 and rope [S'][head_dim / 2] (cos, sin) fp32 pairs (tests)
+extern "C" int32_t revo_vit_read_grid_tables(revo_vit* vit, float* pos_dst, float* rope_dst, void* stream) {
+    REVO_REQUIRE(vit && pos_dst && rope_dst, "read_grid_tables: null argument");
+    REVO_ON_DEVICE(vit->device);
+    const revo_vit::GridShape& sh = vit->shape();
+    REVO_HIP_CHECK(hipMemcpyAsync(pos_dst, sh.pos, (size_t)sh.S * vit->cfg.width * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    REVO_HIP_CHECK(hipMemcpyAsync(rope_dst, sh.rope_cs, (size_t)sh.S * (vit->hd / 2) * sizeof(float2), hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream));
+    return 0;
+}
 #endif
 
 // The head behind the pooled rows u [R][pool_heads][W]: value and output projection, the pool's LayerNorm and MLP, proj, L2 --
@@ -291,7 +358,8 @@ static int pool_head_tail(revo_vit* v, int R, const float* u, long u_ld, long u_
 static int vit_forward(revo_vit* v, const void* images, int32_t image_dtype, int B, float* out, int32_t normalize,
                        hipStream_t st, bool with_head = true) {
     const revo_vit_cfg& c = v->cfg;
-    const int W = c.width, S = v->S, PH = c.pool_heads;
+    const revo_vit::GridShape& sh = v->shape();        // the call's grid: gh x gw patches, S tokens per image
+    const int W = c.width, S = sh.S, PH = c.pool_heads;
     const int rows = B * S;
     using namespace revo;
     v->det.valid = false;                 // a detect result lives until the next forward of any kind
@@ -300,13 +368,14 @@ static int vit_forward(revo_vit* v, const void* images, int32_t image_dtype, int
         // exact integers for u8 images -- or as hi | hi | lo; the weight rows are hi | lo | hi of w / 255), position add, cls row
         const int parts = image_dtype == 1 ? 2 : 3;
         { ProfScope ps("patchify", st);
-          CHECK_RC(launch_patchify(images, image_dtype == 1, B, c.image_size, c.patch_size, v->patches, v->Kp, st)); }
+          CHECK_RC(launch_patchify(images, image_dtype == 1, B, sh.gh * c.patch_size, sh.gw * c.patch_size, c.patch_size, v->patches,
+                                   v->Kp, st)); }
         GemmArgs a{};
-        a.A = v->patches; a.lda = (long)parts * v->Kp; a.B = v->w_patch; a.ldb = 3l * v->Kp; a.M = B * v->G2; a.N = W;
+        a.A = v->patches; a.lda = (long)parts * v->Kp; a.B = v->w_patch; a.ldb = 3l * v->Kp; a.M = B * sh.G2; a.N = W;
         a.K = parts * v->Kp;
-        a.C = v->x; a.ldc = W; a.pos = v->pos; a.S = S; a.G2 = v->G2; a.cls = c.use_cls ? 1 : 0;
+        a.C = v->x; a.ldc = W; a.pos = sh.pos; a.S = S; a.G2 = sh.G2; a.cls = c.use_cls ? 1 : 0;
         { ProfScope ps("gemm_patch", st); CHECK_RC(launch_gemm(EPI_PATCH, a, st)); }
-        if (c.use_cls) { ProfScope ps("elementwise", st); CHECK_RC(launch_cls_rows(v->x, W, v->cls, v->pos, B, S, W, st)); }
+        if (c.use_cls) { ProfScope ps("elementwise", st); CHECK_RC(launch_cls_rows(v->x, W, v->cls, sh.pos, B, S, W, st)); }
     }
     if (v->debug_layers == -2) return 0;   // parity hook: the embedded tokens (patch embed + position + class token), before ln_pre
     { ProfScope ps("layernorm", st);
@@ -317,7 +386,7 @@ static int vit_forward(revo_vit* v, const void* images, int32_t image_dtype, int
     CHECK_RC(body_blocks(
         *v, "vit_forward", rows, v->debug_layers < 0 ? c.layers : std::min(v->debug_layers, c.layers), st,
         [&](GemmArgs& a) {
-            a.rope_cs = v->rope_cs; a.rope_S = S; a.rope_hd = v->hd; a.rope_cols = 2 * W;
+            a.rope_cs = sh.rope_cs; a.rope_S = S; a.rope_hd = v->hd; a.rope_cols = 2 * W;
             return (int)EPI_BF16_ROPE;
         },
         [&]() { return launch_attention_ex(v->qkv, 3 * W, v->att, W, B, S, c.heads, v->hd, c.use_cls, st); }));
@@ -393,7 +462,7 @@ extern "C" int32_t revo_vit_forward_regions(revo_vit* v, const void* images, int
     CHECK_RC(vit_forward(v, images, image_dtype, batch, out_global, normalize, st, out_global != nullptr));
     if (n_regions == 0 || v->debug_layers != -1) return 0;
     const revo_vit_cfg& c = v->cfg;
-    const int W = c.width, D = c.out_dim, S = v->S, PH = c.pool_heads;
+    const int W = c.width, D = c.out_dim, S = v->shape().S, PH = c.pool_heads;     // (the workspace is sized for the native S)
     const size_t words = ((size_t)S + 31) / 32;
     uint32_t* pin = (uint32_t*)v->rg_pin.p;
     for (int64_t s0 = 0; s0 < n_regions; s0 += REGION_STAGE) {
@@ -450,7 +519,7 @@ extern "C" int32_t revo_vit_forward_tokens(revo_vit* v, const void* images, int3
     CHECK_RC(vit_forward(v, images, image_dtype, batch, out_global, normalize, st, out_global != nullptr));
     if (v->debug_layers != -1) return 0;
     ProfScope ps("token_head", st);
-    return token_head(v, (long)batch * v->S, out_tokens, normalize, st);
+    return token_head(v, (long)batch * v->shape().S, out_tokens, normalize, st);
     API_END
 }
 
@@ -491,6 +560,8 @@ extern "C" int32_t revo_vit_detect(revo_vit* v, const void* images, int32_t imag
     REVO_REQUIRE(n_prompts >= 1 && n_prompts <= revo::DETECT_MAX_PROMPTS, "vit_detect: n_prompts must be in [1, 64]");
     REVO_REQUIRE(n_background >= 0 && n_background < n_prompts, "vit_detect: n_background must be in [0, n_prompts)");
     REVO_REQUIRE(min_cells >= 1, "vit_detect: min_cells must be at least 1");
+    REVO_REQUIRE(v->active == 0, "vit_detect: the handle is set to grid (" + std::to_string(v->shape().gh) + ", " +
+                 std::to_string(v->shape().gw) + "); text-prompted regions run on the native grid only (revo_vit_set_grid(0, 0))");
     REVO_REQUIRE(v->G2 <= revo::DETECT_MAX_CELLS, "vit_detect: a grid of more than 1024 cells is not supported");
     REVO_REQUIRE(max_regions >= 1 && max_regions <= v->G2, "vit_detect: max_regions must be in [1, g * g = " + std::to_string(v->G2) + "]");
     for (int32_t p = 0; p < n_prompts; ++p)

@@ -171,12 +171,40 @@ class VitEngine(_Handle):
         sd = synth_weights(cfg, seed=seed, device=dev, **kw)
         return cls(cfg, sd, device=device, max_batch=max_batch, experiments=experiments)
 
-    def _images(self, images):
-        """``images`` validated for a forward: contiguous, and its ``image_dtype``."""
+    def _grid(self, grid):
+        """``grid=None | (gh, gw)`` -> ``(gh, gw, S)``: the token grid of a call (include/revo.h, GRIDS) and its tokens per
+        image.  ``None`` is the tower's native ``g x g``; any shape within its ``g * g`` cells is accepted
+        (``config.aspect_grid`` chooses one for an image)."""
+        g = self.cfg.grid
+        if grid is None:
+            gh = gw = g
+        else:
+            gh, gw = (int(v) for v in grid)
+            if gh < 1 or gw < 1 or gh * gw > g * g:
+                raise ValueError(f"grid must be (gh, gw) with positive sides and gh * gw <= {g} * {g}, got {tuple(grid)!r}")
+        return gh, gw, gh * gw + (1 if self.cfg.use_cls else 0)
+
+    @contextlib.contextmanager
+    def _grid_frame(self, grid):
+        """:meth:`_frame` with the handle set to ``grid`` inside -- yields the stream -- and back to native on the way out,
+        whatever happened: a call without ``grid`` always runs native."""
+        gh, gw, _ = self._grid(grid)
+        with self._frame():
+            st = _lib.current_stream()
+            self._call("revo_vit_set_grid", gh, gw, st)
+            try:
+                yield st
+            finally:
+                self._lib.revo_vit_set_grid(self._h, 0, 0, st)
+
+    def _images(self, images, grid=None):
+        """``images`` validated for a forward on ``grid``: contiguous, and its ``image_dtype``."""
         _require_cuda(images, "images", self.device)
-        n = self.cfg.image_size
-        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != n or images.shape[3] != n:
-            raise ValueError(f"images must be [B,3,{n},{n}], got {tuple(images.shape)}")
+        gh, gw, _ = self._grid(grid)
+        h, w = gh * self.cfg.patch_size, gw * self.cfg.patch_size
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != h or images.shape[3] != w:
+            raise ValueError(f"images must be [B,3,{h},{w}]" + (f" for grid ({gh}, {gw})" if grid is not None else "") +
+                             f", got {tuple(images.shape)}")
         if images.dtype == torch.uint8:
             kind = IMAGE_U8
         elif images.dtype == torch.float32:
@@ -186,34 +214,37 @@ class VitEngine(_Handle):
         return images.contiguous(), kind
 
     # -- the embed entry point ------------------------------------------------
-    def embed(self, images, normalize=True, out=None):
+    def embed(self, images, normalize=True, out=None, grid=None):
         """images: uint8 or float32 ``[B,3,H,W]`` device tensor at the model
         resolution (float input already normalised to [-1,1], i.e. what
         ``self.preprocess`` yields at core_system.py:439).  Returns fp32
-        ``[B, out_dim]`` on the device, L2-normalised (core_system.py:447)."""
-        images, kind = self._images(images)
+        ``[B, out_dim]`` on the device, L2-normalised (core_system.py:447).
+        ``grid=(gh, gw)``: native-aspect embedding (include/revo.h, GRIDS) -- the images are
+        ``[B,3,gh * patch,gw * patch]`` and the forward runs on that token grid."""
+        images, kind = self._images(images, grid)
         cfg = self.cfg
         B = images.shape[0]
         if out is None:
             out = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._frame():
-            st = _lib.current_stream()
+        with self._grid_frame(grid) as st:
             for s, e in self._chunks(B):
                 self._call("revo_vit_forward", _lib.ptr(images[s:e]), kind, e - s, _lib.ptr(out[s:e]), int(bool(normalize)), st)
         return out
 
-    def embed_regions(self, images, region_image, token_bits, normalize=True, with_global=True):
+    def embed_regions(self, images, region_image, token_bits, normalize=True, with_global=True, grid=None):
         """A vector per region for one forward per image (include/revo.h, REGIONS): region ``r`` is pooled over the tokens
         of image ``region_image[r]`` that ``token_bits[r]`` allows (``regions.token_masks``: ``[R, ceil(S / 32)]`` as a
         uint32 / int32 numpy array, or an int32 torch tensor on the host or on this device).  ``images`` as in
         :meth:`embed`.  Returns ``(global, regions)``: fp32 ``[B, out_dim]`` (exactly :meth:`embed`'s rows; ``None``
         without ``with_global``) and fp32 ``[R, out_dim]`` in the caller's order.  A region that allows every token has
         its image's global vector bit for bit, one that allows none is all zeros.  Batches above ``max_batch`` are split
-        and every region goes with its image."""
+        and every region goes with its image.  Under ``grid=(gh, gw)`` the bitmaps are those of that grid
+        (``regions.token_masks(..., grid=grid)``)."""
         import numpy as np
-        images, kind = self._images(images)
+        images, kind = self._images(images, grid)
         cfg = self.cfg
-        B, words = images.shape[0], (cfg.seq + 31) // 32
+        seq = self._grid(grid)[2]
+        B, words = images.shape[0], (seq + 31) // 32
         ri = torch.as_tensor(np.asarray(region_image.cpu() if isinstance(region_image, torch.Tensor) else region_image,
                                         dtype=np.int64).reshape(-1))
         R = ri.shape[0]
@@ -228,15 +259,14 @@ class VitEngine(_Handle):
         else:
             bits = torch.from_numpy(np.ascontiguousarray(np.asarray(token_bits)).astype(np.uint32, copy=False).view(np.int32))
         if bits.dim() != 2 or bits.shape[0] != R or bits.shape[1] != words:
-            raise ValueError(f"token_bits must be [{R}, {words}] (one bitmap of ceil({cfg.seq} / 32) words per region), "
+            raise ValueError(f"token_bits must be [{R}, {words}] (one bitmap of ceil({seq} / 32) words per region), "
                              f"got {tuple(bits.shape)}")
         if B == 0 or (R == 0 and not with_global):
             return (torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None,
                     torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device))
         out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
         out_r = torch.empty((R, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._frame():
-            st = _lib.current_stream()
+        with self._grid_frame(grid) as st:
             for s, e in self._chunks(B):
                 whole = s == 0 and e == B
                 sel = None if whole else torch.nonzero((ri >= s) & (ri < e)).reshape(-1)
@@ -253,18 +283,18 @@ class VitEngine(_Handle):
                     out_r.index_copy_(0, sel.to(out_r.device), dst)
         return out_g, out_r
 
-    def embed_tokens(self, images, normalize=True, with_global=True):
+    def embed_tokens(self, images, normalize=True, with_global=True, grid=None):
         """A vector per token from one forward per image (include/revo.h, TOKENS): returns ``(global, tokens)``, fp32
         ``[B, out_dim]`` (exactly :meth:`embed`'s rows; ``None`` without ``with_global``) and fp32 ``[B, S, out_dim]``.
         Token ``s`` of image ``b`` has, bit for bit, the vector :meth:`embed_regions` gives the region that allows token ``s``
-        alone.  Token 0 is the class token on towers that have one; patch ``(gy, gx)`` is token ``use_cls + gy * g + gx``."""
-        images, kind = self._images(images)
+        alone.  Token 0 is the class token on towers that have one; patch ``(gy, gx)`` is token ``use_cls + gy * g + gx``
+        (``use_cls + gy * gw + gx`` and ``S = gh * gw + use_cls`` under ``grid=(gh, gw)``)."""
+        images, kind = self._images(images, grid)
         cfg = self.cfg
         B = images.shape[0]
         out_g = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=images.device) if with_global else None
-        out_t = torch.empty((B, cfg.seq, cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._frame():
-            st = _lib.current_stream()
+        out_t = torch.empty((B, self._grid(grid)[2], cfg.out_dim), dtype=torch.float32, device=images.device)
+        with self._grid_frame(grid) as st:
             for s, e in self._chunks(B):
                 self._call("revo_vit_forward_tokens", _lib.ptr(images[s:e]), kind, e - s,
                            _lib.ptr(out_g[s:e]) if with_global else None, _lib.ptr(out_t[s:e]), int(bool(normalize)), st)
@@ -335,16 +365,15 @@ class VitEngine(_Handle):
         return {"rows": int(out[0]), "rows_above_ratio": int(out[1]), "rows_above_4x_ratio": int(out[2]), "ratio": float(out[3])}
 
     # -- parity-test hook -----------------------------------------------------
-    def residual_after(self, images, n_layers):
+    def residual_after(self, images, n_layers, grid=None):
         """fp32 residual stream [B, S, W] after ln_pre and the first n blocks."""
         _need_hooks(self, "residual_after")
-        images, kind = self._images(images)
+        images, kind = self._images(images, grid)
         B = images.shape[0]
         assert B <= self.max_batch
-        x = torch.empty((B, self.cfg.seq, self.cfg.width), dtype=torch.float32, device=images.device)
+        x = torch.empty((B, self._grid(grid)[2], self.cfg.width), dtype=torch.float32, device=images.device)
         dummy = torch.empty((B, self.cfg.out_dim), dtype=torch.float32, device=images.device)
-        with self._frame():
-            st = _lib.current_stream()
+        with self._grid_frame(grid) as st:
             self._call("revo_vit_set_debug_layers", int(n_layers))
             try:
                 self._call("revo_vit_forward", _lib.ptr(images), kind, B, _lib.ptr(dummy), 0, st)
@@ -354,7 +383,7 @@ class VitEngine(_Handle):
         return x
 
 
-    def taps(self, images):
+    def taps(self, images, grid=None):
         """Parity-test hook: intermediate activations of one forward as fp32 CPU-comparable tensors:
         ``embed`` [B,S,W] (patch embed + position + class token, before ln_pre), ``ln_post`` [B,S,W] (fp32: the head
         works in fp32), ``pooled`` [B,W] (attention-pool output before proj) and the ``embedding`` [B,D]."""
@@ -363,12 +392,11 @@ class VitEngine(_Handle):
         B = images.shape[0]
         assert B <= self.max_batch
         cfg = self.cfg
-        out = {"embed": self.residual_after(images, -2)}
-        emb = self.embed(images)
-        lnp = torch.empty((B, cfg.seq, cfg.width), dtype=torch.float32, device=self.device)
+        out = {"embed": self.residual_after(images, -2, grid=grid)}
+        emb = self.embed(images, grid=grid)
+        lnp = torch.empty((B, self._grid(grid)[2], cfg.width), dtype=torch.float32, device=self.device)
         pooled = torch.empty((B, cfg.width), dtype=torch.float32, device=self.device)
-        with self._frame():
-            st = _lib.current_stream()
+        with self._grid_frame(grid) as st:          # (the rows of the forward just run: the tap's size follows the grid)
             self._call("revo_vit_read_tap", 1, B, _lib.ptr(lnp), st)
             self._call("revo_vit_read_tap", 2, B, _lib.ptr(pooled), st)
         out.update(ln_post=lnp, pooled=pooled, embedding=emb)

@@ -334,7 +334,9 @@ class IngestRun:
                 continue
             n_reg = sr.detect_regions(im, self.text_prompt)
             kept, metas = sr._region_metadata(im, sr.detected_regions) if n_reg else ([], [])
-            det.append((n_reg, metas, sr._pool_bits(sr.detected_regions, kept) if self.mode.pool and metas else None))
+            # (aspect="keep": the frame is embedded on the grid of its own aspect ratio, and its masks' tokens are that grid's)
+            grid = sr._grid_of(im.width, im.height) if sr.aspect == "keep" else None
+            det.append((n_reg, metas, sr._pool_bits(sr.detected_regions, kept, grid) if self.mode.pool and metas else None, grid))
         return det
 
     def launch(self, it, results):
@@ -362,8 +364,13 @@ class IngestRun:
                         with sr._lock:
                             with self.slot_frames(it, handles) as frames:
                                 pass                    # (the event goes directly behind the copy)
-                            u8 = pp.crop_resize_device(frames, None, size)
-                    dev_emb = sr._embed_pool_batch(u8, [det[j][2] for j in idx], to_host=False)
+                            if sr.aspect != "keep":
+                                u8 = pp.crop_resize_device(frames, None, size)
+                    if sr.aspect == "keep":             # one resize and one embed_regions per grid of the batch's frames
+                        dev_emb = sr._embed_by_grid(frames, None, bits=[det[j][2] for j in idx], grids=[det[j][3] for j in idx],
+                                                    to_host=False)
+                    else:
+                        dev_emb = sr._embed_pool_batch(u8, [det[j][2] for j in idx], to_host=False)
         elif good:
             with sr._lock, torch.cuda.device(sr.device):
                 if mode.pipelined:
@@ -377,7 +384,10 @@ class IngestRun:
                     # device resize: the decoded frames go up as they are, one crop + resize launch, one forward
                     with self.slot_frames(it, good) as frames:
                         pass
-                    dev_emb = sr.pe_model.embed(pp.crop_resize_device(frames, None, size))
+                    if sr.aspect == "keep":             # one resize and one forward per grid of the batch's frames
+                        dev_emb = sr._embed_by_grid(frames, None, to_host=False)
+                    else:
+                        dev_emb = sr.pe_model.embed(pp.crop_resize_device(frames, None, size))
         return Batch(start, paths, pils, dev_emb, start + self.B >= len(self.files), det)
 
     def settle(self, batch):

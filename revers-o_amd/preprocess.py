@@ -26,18 +26,28 @@ def to_pil(image):
     return image.convert("RGB")
 
 
+def _hw(size):
+    """size: an int (a square) or (height, width) -> (height, width)"""
+    if isinstance(size, (tuple, list)):
+        h, w = size
+        return int(h), int(w)
+    return int(size), int(size)
+
+
 def resize_u8(image, size):
-    """PIL RGB -> uint8 tensor [3, size, size] (bilinear squash, no crop)."""
+    """PIL RGB -> uint8 tensor [3, height, width] (bilinear resize, no crop); ``size`` is an int -- the square -- or
+    ``(height, width)``, the pixels of a token grid (``grid_h * patch, grid_w * patch``)."""
+    h, w = _hw(size)
     im = to_pil(image)
-    if im.size != (size, size):
-        im = im.resize((size, size), Image.BILINEAR)
+    if im.size != (w, h):
+        im = im.resize((w, h), Image.BILINEAR)
     arr = np.asarray(im, dtype=np.uint8)            # HWC
     return torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)))
 
 
 def batch_u8(images, size, pin=False):
-    """list of images -> uint8 [B, 3, size, size] host tensor."""
-    out = torch.empty((len(images), 3, size, size), dtype=torch.uint8)
+    """list of images -> uint8 [B, 3, height, width] host tensor (``size``: an int or ``(height, width)``)."""
+    out = torch.empty((len(images), 3, *_hw(size)), dtype=torch.uint8)
     if pin:
         out = out.pin_memory()
     for i, im in enumerate(images):
@@ -56,8 +66,9 @@ def crop_resize_device(frames, boxes, size, out=None):
     frames: one uint8 ``[H, W, 3]`` device tensor, or a list of them (sizes may differ).
     boxes:  sequence of ``(frame_index, x0, y0, x1, y1)`` (half-open pixel boxes), or
             ``None`` for one full-frame job per frame.
-    Returns uint8 ``[n, 3, size, size]`` on the device, equal to what
-    ``Image.fromarray(frame).crop(box).resize((size, size), Image.BILINEAR)`` gives
+    size:   an int -- the square -- or ``(height, width)``.
+    Returns uint8 ``[n, 3, height, width]`` on the device, equal to what
+    ``Image.fromarray(frame).crop(box).resize((width, height), Image.BILINEAR)`` gives
     (core_system.py:439 applied to the crop of :687-690)."""
     from . import _lib
     if isinstance(frames, torch.Tensor):
@@ -75,8 +86,9 @@ def crop_resize_device(frames, boxes, size, out=None):
     if boxes is None:
         boxes = [(i, 0, 0, f.shape[1], f.shape[0]) for i, f in enumerate(frames)]
     n = len(boxes)
+    oh, ow = _hw(size)
     if out is None:
-        out = torch.empty((n, 3, size, size), dtype=torch.uint8, device=dev)
+        out = torch.empty((n, 3, oh, ow), dtype=torch.uint8, device=dev)
     if n == 0:
         return out
     jobs = (_lib.CropJob * n)()
@@ -87,8 +99,12 @@ def crop_resize_device(frames, boxes, size, out=None):
         j.x0, j.y0, j.x1, j.y1 = int(x0), int(y0), int(x1), int(y1)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        _lib.check(lib.revo_preprocess_crop_resize(jobs, n, int(size), _lib.ptr(out), _lib.current_stream()),
-                   "revo_preprocess_crop_resize")
+        if oh == ow:
+            _lib.check(lib.revo_preprocess_crop_resize(jobs, n, oh, _lib.ptr(out), _lib.current_stream()),
+                       "revo_preprocess_crop_resize")
+        else:
+            _lib.check(lib.revo_preprocess_crop_resize_hw(jobs, n, oh, ow, _lib.ptr(out), _lib.current_stream()),
+                       "revo_preprocess_crop_resize_hw")
     return out
 
 

@@ -14,7 +14,11 @@ never gives an empty bitmap.  A region without a pixel raises ``ValueError``.  T
 (token 0 is the class token on towers that have one; ``include_cls`` adds it to every region).
 
 A box ``(x0, y0, x1, y1)`` stands for its rectangle: the pixels whose centre ``(px + 0.5, py + 0.5)`` lies in
-``[x0, x1) x [y0, y1)``, clipped to the image."""
+``[x0, x1) x [y0, y1)``, clipped to the image.
+
+Under a rectangular token grid (``grid=(gh, gw)``: native-aspect embedding) the same rule holds with
+``gw`` columns and ``gh`` rows: the cell is ``(px * gw // width, py * gh // height)``, the token ``use_cls + gy * gw + gx``,
+``S = gh * gw + use_cls``.  ``grid=None`` is the tower's native ``g x g``."""
 import math
 
 import numpy as np
@@ -22,14 +26,25 @@ import numpy as np
 __all__ = ["token_masks", "full_mask", "words_per_region", "cell_masks", "cell_boxes"]
 
 
-def words_per_region(cfg):
-    return (cfg.seq + 31) // 32
+def _grid(cfg, grid):
+    """grid=None | (gh, gw) -> (gh, gw, S)"""
+    if grid is None:
+        gh = gw = int(cfg.grid)
+    else:
+        gh, gw = (int(v) for v in grid)
+        if gh < 1 or gw < 1:
+            raise ValueError(f"grid must be (gh, gw) with positive sides, got {grid!r}")
+    return gh, gw, gh * gw + (1 if cfg.use_cls else 0)
 
 
-def full_mask(cfg, include_cls=True):
+def words_per_region(cfg, grid=None):
+    return (_grid(cfg, grid)[2] + 31) // 32
+
+
+def full_mask(cfg, include_cls=True, grid=None):
     """``uint32 [ceil(S / 32)]`` allowing every patch token, and the class token with ``include_cls`` (then the region's
     vector is the image's global vector, bit for bit)."""
-    allow = np.ones(cfg.seq, dtype=bool)
+    allow = np.ones(_grid(cfg, grid)[2], dtype=bool)
     if cfg.use_cls and not include_cls:
         allow[0] = False
     return _pack(allow[None])[0]
@@ -63,27 +78,28 @@ def _is_box(region):
     return a.ndim == 1 and a.shape[0] == 4
 
 
-def token_masks(cfg, regions, width, height, min_cover=0.5, include_cls=False):
+def token_masks(cfg, regions, width, height, min_cover=0.5, include_cls=False, grid=None):
     """regions: a sequence of boolean pixel masks ``[height, width]`` and / or boxes ``(x0, y0, x1, y1)`` in source pixels
     of a ``width x height`` image.  Returns ``uint32 [R, ceil(S / 32)]`` for the tower ``cfg`` (module docstring)."""
-    width, height, g = int(width), int(height), int(cfg.grid)
+    width, height = int(width), int(height)
+    gh, gw, seq = _grid(cfg, grid)
     if width <= 0 or height <= 0:
         raise ValueError("token_masks: width and height must be positive")
     if not 0.0 <= float(min_cover) <= 1.0:
         raise ValueError("token_masks: min_cover must be in [0, 1]")
     first = 1 if cfg.use_cls else 0
-    cx, nx = _axis_cells(width, g)
-    cy, ny = _axis_cells(height, g)
+    cx, nx = _axis_cells(width, gw)
+    cy, ny = _axis_cells(height, gh)
     cell_pixels = np.outer(ny, nx)                                    # [gy, gx]
     contiguous = bool((nx > 0).all() and (ny > 0).all())
     x_start, y_start = np.cumsum(nx) - nx, np.cumsum(ny) - ny       # first pixel of every cell
-    allow = np.zeros((len(regions), cfg.seq), dtype=bool)
+    allow = np.zeros((len(regions), seq), dtype=bool)
     for r, region in enumerate(regions):
         if _is_box(region):
             x0, y0, x1, y1 = (float(v) for v in np.asarray(region, dtype=np.float64))
             xa, xb = _box_range(x0, x1, width)
             ya, yb = _box_range(y0, y1, height)
-            count = np.outer(np.bincount(cy[ya:yb], minlength=g), np.bincount(cx[xa:xb], minlength=g)).astype(np.int64)
+            count = np.outer(np.bincount(cy[ya:yb], minlength=gh), np.bincount(cx[xa:xb], minlength=gw)).astype(np.int64)
         else:
             m = np.asarray(region)
             if m.shape != (height, width):
@@ -94,7 +110,7 @@ def token_masks(cfg, regions, width, height, min_cover=0.5, include_cls=False):
                 count = np.add.reduceat(np.add.reduceat(m.view(np.uint8), x_start, axis=1, dtype=np.int32), y_start,
                                         axis=0).astype(np.int64)
             else:               # fewer pixels than cells along an axis: some cells are empty
-                count = np.bincount((cy[:, None] * g + cx[None, :])[m], minlength=g * g).astype(np.int64).reshape(g, g)
+                count = np.bincount((cy[:, None] * gw + cx[None, :])[m], minlength=gh * gw).astype(np.int64).reshape(gh, gw)
         if count.sum() == 0:
             raise ValueError(f"token_masks: region {r} holds no pixel of the image")
         ok = (count > 0) & (count.astype(np.float64) >= float(min_cover) * cell_pixels.astype(np.float64))
@@ -108,44 +124,49 @@ def token_masks(cfg, regions, width, height, min_cover=0.5, include_cls=False):
     return _pack(allow)
 
 
-def _unpack_cells(cfg, bits):
-    """uint32 [R, ceil(S / 32)] -> bool [R, g, g]: the patch-token bits (the class token's bit is dropped)"""
-    g, first = int(cfg.grid), 1 if cfg.use_cls else 0
+def _unpack_cells(cfg, bits, grid=None):
+    """uint32 [R, ceil(S / 32)] -> bool [R, gh, gw]: the patch-token bits (the class token's bit is dropped)"""
+    gh, gw, _ = _grid(cfg, grid)
+    first = 1 if cfg.use_cls else 0
     b = np.ascontiguousarray(np.asarray(bits))
     b = b.view(np.uint32) if b.dtype == np.int32 else b.astype(np.uint32, copy=False)
-    if b.ndim != 2 or b.shape[1] != words_per_region(cfg):
-        raise ValueError(f"bits must be [R, {words_per_region(cfg)}], got {b.shape}")
+    if b.ndim != 2 or b.shape[1] != words_per_region(cfg, grid):
+        raise ValueError(f"bits must be [R, {words_per_region(cfg, grid)}], got {b.shape}")
     allow = ((b[:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)).astype(bool).reshape(b.shape[0], -1)
-    return allow[:, first:first + g * g].reshape(b.shape[0], g, g)
+    return allow[:, first:first + gh * gw].reshape(b.shape[0], gh, gw)
 
 
-def cell_masks(cfg, bits, width, height):
+def cell_masks(cfg, bits, width, height, grid=None):
     """The inverse of :func:`token_masks`' pixel -> cell rule: token bitmaps ``uint32 [R, ceil(S / 32)]`` (a detection's
     ``bits``; int32 words are reinterpreted) -> boolean pixel masks ``[R, height, width]`` of a ``width x height`` source
     image.  Pixel ``(px, py)`` is set iff cell ``(px * g // width, py * g // height)`` is; the class token's bit is ignored.
     For ``width, height >= g`` every cell holds a pixel and ``token_masks(cfg, cell_masks(cfg, bits, w, h), w, h) == bits``
     (patch bits).  When an axis has fewer pixels than cells, the cells no pixel maps to vanish: the mask cannot show them,
     and a region made only of such cells gives an empty mask."""
-    width, height, g = int(width), int(height), int(cfg.grid)
+    width, height = int(width), int(height)
+    gh, gw, _ = _grid(cfg, grid)
     if width <= 0 or height <= 0:
         raise ValueError("cell_masks: width and height must be positive")
-    cells = _unpack_cells(cfg, bits)
-    cx, _ = _axis_cells(width, g)
-    cy, _ = _axis_cells(height, g)
+    cells = _unpack_cells(cfg, bits, grid)
+    cx, _ = _axis_cells(width, gw)
+    cy, _ = _axis_cells(height, gh)
     return cells[:, cy[:, None], cx[None, :]]
 
 
-def cell_boxes(cfg, boxes, width, height):
+def cell_boxes(cfg, boxes, width, height, grid=None):
     """Inclusive cell boxes ``[R, 4]`` (gx0, gy0, gx1, gy1: a detection's ``boxes``) -> source-pixel ``xyxy`` ``int64 [R, 4]``
     by the same integer map: ``x0`` is the first pixel of column ``gx0``, ``x1`` one past the last pixel of column ``gx1``
     (half-open, like the full-frame box ``[0, 0, width, height]``), so the box encloses :func:`cell_masks`' pixels.  Pixel
     ``px`` lies in column ``gx`` iff ``ceil(gx * width / g) <= px < ceil((gx + 1) * width / g)``.  When an axis has fewer
     pixels than cells a box of cells without a pixel is empty (``x1 == x0``)."""
-    width, height, g = int(width), int(height), int(cfg.grid)
+    width, height = int(width), int(height)
+    gh, gw, _ = _grid(cfg, grid)
     if width <= 0 or height <= 0:
         raise ValueError("cell_boxes: width and height must be positive")
     b = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
-    if b.size and (b.min() < 0 or b.max() >= g or (b[:, 0] > b[:, 2]).any() or (b[:, 1] > b[:, 3]).any()):
-        raise ValueError(f"cell_boxes: boxes must be inclusive cell ranges inside the {g} x {g} grid")
-    start = lambda c, n: -((-c * n) // g)                     # ceil(c * n / g): the first pixel of cell c
-    return np.stack([start(b[:, 0], width), start(b[:, 1], height), start(b[:, 2] + 1, width), start(b[:, 3] + 1, height)], axis=1)
+    if b.size and (b.min() < 0 or b[:, [0, 2]].max() >= gw or b[:, [1, 3]].max() >= gh or (b[:, 0] > b[:, 2]).any()
+                   or (b[:, 1] > b[:, 3]).any()):
+        raise ValueError(f"cell_boxes: boxes must be inclusive cell ranges inside the {gh} x {gw} grid")
+    start = lambda c, n, g: -((-c * n) // g)                  # ceil(c * n / g): the first pixel of cell c
+    return np.stack([start(b[:, 0], width, gw), start(b[:, 1], height, gh), start(b[:, 2] + 1, width, gw),
+                     start(b[:, 3] + 1, height, gh)], axis=1)
